@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 PCIE_LONE_STREAM_GBS = 57.0   # H2D of large pinned pieces on one stream, measured on these boxes (profiles/r03/pcie_probe.txt)
 W_IMG, H_IMG = 640, 480
 TUM_CAM = np.array([517.3, 516.5, 318.6, 255.3])
@@ -377,34 +378,31 @@ def cpu_baseline(frames, mapper=False, threads=1, ref_flags=False):
     return tracked / wall, tracked, wall
 
 
-def hw_queues_leg(args, n_queues):
-    """The resident leg once more in a CHILD process whose HIP runtime multiplexes the farm's streams onto `n_queues` hardware queues
-    (GPU_MAX_HW_QUEUES; the runtime's default is 4, the farm has 16 groups = 16 streams).  With 16 queues up to sixteen kernels share the chip:
-    the farm is 3-5 % faster on most boxes of the pool (profiles/r06/ab_round6.txt) and every dispatch lasts longer, so the per-kernel durations the
-    `roofline` block divides by stop describing a kernel — which is why `value` and `roofline` stay on the runtime's default and this figure is
-    reported beside them (value_hw_queues_16).  Started before this process touches the GPU, like the latency legs; skipped under a profiler."""
-    import subprocess
-    preload = " ".join(os.environ.get(k, "") for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_FORCE_LOAD", "HSA_TOOLS_LIB"))
-    if "rocprof" in preload.lower():
-        return None
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--texture", args.texture, "--distortion", args.distortion,
-           "--steps", str(args.steps), "--warmup", str(args.warmup), "--seqs", str(args.user_seqs), "--groups", str(args.groups), "--threads", str(args.threads),
-           "--workers", str(args.workers), "--fibers", str(args.fibers), "--cpu-frames", "0", "--host-steps", "0", "--sustained-frames", "0",
-           "--latency-frames", "0", "--lost-mix-steps", "0", "--hw-queues-leg", "0"]
-    try:
-        r = subprocess.run(cmd, env=dict(os.environ, GPU_MAX_HW_QUEUES=str(n_queues)), capture_output=True, text=True, timeout=900)
-        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
-        if r.returncode != 0 or not line:
-            sys.stderr.write("bench.py: hardware-queues leg failed (rc %d): %s\n" % (r.returncode, r.stderr[-400:]))
-            return None
-        d = json.loads(line[-1])
-    except (subprocess.SubprocessError, ValueError) as e:
-        sys.stderr.write("bench.py: hardware-queues leg failed: %s\n" % e)
-        return None
-    return {"value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "steps": d["steps"], "gpu_max_hw_queues": n_queues,
-            "note": "the same resident leg (same sequences, steps and farm shape) in a child process with GPU_MAX_HW_QUEUES=%d: the farm's 16 streams on "
-                    "16 hardware queues instead of the runtime's 4; not `value`: with sixteen kernels sharing the chip a dispatch's duration no longer "
-                    "describes its kernel, so the roofline block is measured on the runtime's default" % n_queues}
+def dump_outputs(dirname, stats, K, B, my_seqs, rank, dist=None):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST step - one tracker.FrameStats record per sequence (the
+    pose as the 7 doubles (qw,qx,qy,qz,tx,ty,tz) and every counter) - as DIR/<field>.npy in float64, rows in global sequence order
+    (DIR/sequence.npy names them).  Ranks send theirs to rank 0.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rows."""
+    last = stats[(K - 1) * B:K * B]
+    rows = {"sequence": np.asarray(my_seqs, np.float64)}
+    for name, _ in last[0]._fields_:
+        if name == "pose":
+            rows[name] = np.array([list(r.pose) for r in last], np.float64).reshape(B, 7)
+        else:
+            rows[name] = np.array([getattr(r, name) for r in last], np.float64)
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, rows)
+        if rank != 0:
+            return
+        rows = {k: np.concatenate([p[k] for p in parts]) for k in rows}
+    order = np.argsort(rows["sequence"], kind="stable")
+    n = len(order)
+    row_bytes = sum(v[0].nbytes for v in rows.values())
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        order = order[np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in rows.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v[order]))
 
 
 def latency_legs(wl, texture, n_frames, mapper=False, dist=None):
@@ -660,7 +658,7 @@ def main():
                     help="S-A: the metric configuration (640x480); S-B: EuRoC geometry 752x480, four chunks; S-C: 1280x960, 4000 features")
     ap.add_argument("--texture", choices=sorted(TEXTURES), default="plane",
                     help="plane: value noise, a FAST corner on every second tested pixel (rounds 1-4); camera: piecewise-smooth shading + soft-edged "
-                         "shapes, 2-5 k FAST keypoints per 640x480 frame (a few % of the pixels, like a camera frame)")
+                         "shapes, 2-5 k FAST keypoints per 640x480 frame (a few %% of the pixels, like a camera frame)")
     ap.add_argument("--distortion", choices=sorted(DISTORTIONS), default="none",
                     help="the camera's lens (the cfg file's Camera.d1..d5): the synthetic frames are rendered THROUGH that lens and every leg undistorts "
                          "them first, as main.cc:133 does (Camera::UndistortImage: a remap from a per-camera map cached on the device)")
@@ -688,9 +686,9 @@ def main():
                          "(its own baseline), then this many steps in which 5 %% of the trackers are blinded (a featureless frame) for 5 frames every 50 "
                          "frames: they go TRACKING_BAD x3, relocalise over their keyframes inside the tabled step and rejoin; reported as value_lost_mix "
                          "and lost_mix; 0 = skip; default 100 for S-A / S-B on one GPU")
-    ap.add_argument("--hw-queues-leg", type=int, default=-1,
-                    help="hardware queues of the extra HW-QUEUES leg (the resident leg again in a child process with GPU_MAX_HW_QUEUES set to this; "
-                         "reported as value_hw_queues_16): 0 = skip; default 16 for S-A / S-B on one GPU when the caller has not set GPU_MAX_HW_QUEUES")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed for every sequence (pose and counters) as DIR/<name>.npy "
+                         "(float64; a seeded sample of the sequences above 64 MB)")
     ap.add_argument("--host-steps", type=int, default=-1,
                     help="steps of the second, HOST-FED leg (frames in pinned host memory, uploaded inside the step, as SDVL::HandleFrame(const cv::Mat&) "
                          "receives them): reported as value_host_fed next to the HBM-resident value; 0 = skip; "
@@ -704,7 +702,6 @@ def main():
     TEXTURE = TEXTURES[args.texture]
     global PROFILE_TAG
     PROFILE_TAG = "%s_%s" % (args.workload.lower().replace("-", ""), args.texture) + ("_" + args.distortion if args.distortion != "none" else "")
-    args.user_seqs = args.seqs   # what the caller asked for (0 = the workload's choices): handed on to the hardware-queues leg's child
     seq_choices = [args.seqs] if args.seqs > 0 else list(wl["seqs"])
     args.seqs = seq_choices[0]
     if args.cpu_frames < 0:
@@ -740,9 +737,6 @@ def main():
     latency = None
     if world == 1 and args.latency_frames > 2:
         latency = latency_legs(wl, args.texture, args.latency_frames, args.mapper, DISTORTION)   # child processes, before this one touches the GPU
-    if args.hw_queues_leg < 0:
-        args.hw_queues_leg = 16 if (world == 1 and args.workload in ("S-A", "S-B") and not args.mapper and "GPU_MAX_HW_QUEUES" not in os.environ) else 0
-    hw_queues = hw_queues_leg(args, args.hw_queues_leg) if (world == 1 and args.hw_queues_leg > 0) else None
     # (GPU_MAX_HW_QUEUES: the farm's 16 groups are 16 HIP streams and the runtime multiplexes a process's streams onto 4 hardware queues by
     #  default.  16 queues gave +5 % over three alternating pairs on one box (profiles/r05/ab_round5.txt) and nothing on the next
     #  (ab_queues_by_steps.txt: within the run-to-run spread at 10 / 20 / 40 / 80 steps), while every dispatch gets 2-10 x longer because
@@ -944,6 +938,8 @@ def main():
         n_lk += st.lk_iters
 
     tracked_all, elapsed_max = shard.reduce_throughput(tracked, elapsed, dist if distributed else None, "cuda")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stats, K, B, my_seqs, rank, dist if distributed else None)
 
     # ---- second leg, HOST-FED: the same trackers continue, but their next frames come from pinned HOST memory and every group
     # uploads them on its own stream inside the step — what SDVL::HandleFrame(const cv::Mat&) receives (sdvl.cc:55-59).  This is
@@ -1323,7 +1319,6 @@ def main():
             "value_host_fed": host_fed["value"] if host_fed else None, "host_fed": host_fed,
             "value_sustained": sustained["value"] if sustained else None, "sustained": sustained,
             "value_lost_mix": lost_mix["value"] if lost_mix else None, "lost_mix": lost_mix,
-            "value_hw_queues_16": hw_queues["value"] if hw_queues else None, "hw_queues": hw_queues,
             "config": {"workload": "%s: synthetic %s %dx%d mono, textured plane z=2m, %d independent sequences per GPU, "
                                    "one tracked frame per sequence per step%s" % (args.workload, {"S-A": "TUM fr1-like", "S-B": "EuRoC MH_01-like (config_euroc.cfg)", "S-C": "roofline case"}[args.workload], W_IMG, H_IMG, B, "; map = reference mapper run inside the step (sequential mode)" if args.mapper else ""),
                        "input": "hbm_resident (frames rendered into HBM before the timed region; the host-fed rate is value_host_fed)",

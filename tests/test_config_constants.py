@@ -1,6 +1,6 @@
 """The constants the tests, the bench and the host layer carry are the reference's: every value in tracker.TUM_OVERRIDES and
-oraclelib.*_CAM / *_DIST equals what host/config.cc parses out of the reference's own configuration files.  Runs only where
-/root/reference exists (the build container); the GPU box has no reference tree and skips it."""
+oraclelib.*_CAM / *_DIST equals what host/config.cc parses out of the reference's own configuration files (stored under tests/golden/reference_config by
+tests/golden/make_reference_fixtures.py)."""
 import ctypes as C
 import importlib
 import os
@@ -10,8 +10,7 @@ import pytest
 
 import oraclelib as ol
 
-REF = "/root/reference/config"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_config")
 
 
 def snapshot(cfg):

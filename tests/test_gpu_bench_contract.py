@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -80,13 +81,9 @@ def check(d, steps=4, warmup=1, mapper=False):
     if lm is not None:
         assert d["value_lost_mix"] == lm["value"] > 0 and lm["steps"] == 20 and lm["undisturbed_value"] > 0
         assert lm["frames_on_the_host_driven_path"] == 0 and lm["blinded_tracker_frames"] == 10 and lm["relocalized"] == 2, lm
-    # round 6: the resident leg again on 16 hardware queues (a child process with GPU_MAX_HW_QUEUES=16), reported beside `value`, never as it
-    hq = d["hw_queues"]
-    if not mapper:
-        assert hq is not None and d["value_hw_queues_16"] == hq["value"] > 0 and hq["gpu_max_hw_queues"] == 16 and hq["steps"] == steps
-        assert d["config"]["gpu_max_hw_queues"].startswith("runtime default")   # `value` itself was measured on the runtime's default
-    else:
-        assert hq is None and d["value_hw_queues_16"] is None
+    # no leg of the line changes the hardware queues: every figure is measured on the caller's setting, and the line reports it
+    assert "hw_queues" not in d and "value_hw_queues_16" not in d
+    assert d["config"]["gpu_max_hw_queues"] == os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)")
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "tracked frames/s" and "sample" in c
     assert 0 < c["one_core"] <= c["value"] * 1.05   # the all-core figure is at least the one-core figure
@@ -145,3 +142,23 @@ def test_bench_line_contract_s_c():
     assert d["metric"].startswith("tracked frames/sec (1280x960") and d["config"]["workload"].startswith("S-C") and d["config"]["sequences_per_gpu"] == 16
     assert d["value"] > 0 and d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0
     assert d["config"]["features_per_frame"] > 400 and d["config"]["matches_per_frame"] > 400     # really the 1000-match configuration
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's per-sequence records (pose and counters) as float64 .npy files, in sequence order"""
+    d = run_bench("--steps", "3", "--sustained-frames", "0", "--latency-frames", "0", "--lost-mix-steps", "0", "--host-steps", "0",
+                  "--cpu-frames", "0", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert "pose.npy" in files and "quality.npy" in files and "matches.npy" in files and "sequence.npy" in files
+    total = 0
+    for name in files:
+        a = np.load(tmp_path / name)
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 32, (name, a.dtype, a.shape)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "sequence.npy"), np.arange(32))
+    pose = np.load(tmp_path / "pose.npy")
+    assert pose.shape == (32, 7) and np.all(np.isfinite(pose))
+    assert np.allclose(np.linalg.norm(pose[:, :4], axis=1), 1.0, atol=1e-6)     # unit quaternions
+    assert np.all(np.load(tmp_path / "quality.npy") != 2) and np.all(np.load(tmp_path / "matches.npy") > 0)

@@ -1,18 +1,17 @@
 """The one piece of reference DATA the product and the oracle share: the 256 x 4 ORB sampling table
-(`/root/reference/extra/orb_detector.cc:62-319`), carried as `orb_pattern_31.inc` on both sides.  Both sides read the same text,
-so a wrong integer would be invisible to every parity test — here the table is parsed out of the reference source again, by a
-parser of its own, and compared integer by integer; the circular-patch row ends `umax_` (orb_detector.cc:325-348) are
-recomputed from the reference's formula and compared with the constants the kernels carry.  Runs only where /root/reference
-exists (the build container); the GPU box has no reference tree and skips it."""
+(the reference's extra/orb_detector.cc:62-319), carried as `orb_pattern_31.inc` on both sides.  Both sides read the same text,
+so a wrong integer would be invisible to every parity test — here the table as parsed out of the reference source again, by a
+parser of its own (tests/golden/make_reference_fixtures.py -> tests/golden/reference_orb.npz), is compared integer by integer;
+the circular-patch row ends `umax_` (orb_detector.cc:325-348) are recomputed from the reference's formula and compared with
+the constants the kernels carry."""
 import math
 import os
 import re
 
-import pytest
+import numpy as np
 
-REF = "/root/reference/extra/orb_detector.cc"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isfile(REF), reason="reference tree not present (GPU box)")
+REF = np.load(os.path.join(ROOT, "tests", "golden", "reference_orb.npz"))
 
 
 def inc_numbers(path):
@@ -20,20 +19,8 @@ def inc_numbers(path):
     return [int(t) for t in text.replace("\n", " ").split(",") if t.strip()]
 
 
-def reference_table():
-    lines = open(REF).read().splitlines()
-    start = next(i for i, l in enumerate(lines) if "bit_pattern_31_[256*4]" in l)
-    nums = []
-    for l in lines[start + 1:]:
-        if l.strip().startswith("};"):
-            break
-        body = l.split("/*")[0]          # every row ends in a /*mean (...), correlation (...)*/ comment
-        nums += [int(t) for t in body.split(",") if t.strip()]
-    return start + 1, nums
-
-
 def test_orb_table_equals_the_reference_source():
-    first_line, ref = reference_table()
+    first_line, ref = int(REF["first_line"]), REF["bit_pattern_31"].tolist()
     assert first_line == 62 and len(ref) == 1024          # declared at orb_detector.cc:62, closed at :319: 256 rows of {x0, y0, x1, y1}
     assert all(-15 <= v <= 15 for v in ref)                # inside the 31 x 31 patch
     prod = inc_numbers(os.path.join(ROOT, "slam-sdvl_amd", "csrc", "orb_pattern_31.inc"))
@@ -52,12 +39,10 @@ def cv_round(x):
 
 
 def test_umax_equals_the_reference_formula():
-    src = open(REF).read()
-    # the statements being restated are the ones the reference has (orb_detector.cc:325-348)
-    for stmt in ("int HALF_PATCH_SIZE = Config::ORBSize()/2;", "vmax = cvFloor(HALF_PATCH_SIZE * sqrt(2.f) / 2 + 1);",
-                 "int vmin = cvCeil(HALF_PATCH_SIZE * sqrt(2.f) / 2);", "umax_[v] = cvRound(sqrt(hp2 - v * v));",
-                 "while (umax_[v0] == umax_[v0 + 1])", "umax_[v] = v0;"):
-        assert stmt in src, stmt
+    # the statements being restated are the ones the reference has (make_reference_fixtures.UMAX_STATEMENTS: every one found in
+    # orb_detector.cc:325-348)
+    lines = REF["umax_lines"].tolist()
+    assert len(lines) == 6 and all(325 <= n <= 348 for n in lines), lines
     half = 31 // 2                                         # ORBSize 31 (config.cc:84)
     s2 = float.fromhex("0x1.6a09e6p+0")                    # sqrt(2.f) as a float
     vmax = math.floor(half * s2 / 2 + 1)
