@@ -448,6 +448,25 @@ int sdvl_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride,
 int sdvl_frames_upload_undistorted(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride,
                                    int src_on_device, const sdvl_camera *cam, const sdvl_distortion *dist);
 
+/* ---- input stage, first half: cv::cvtColor(frame, *img, CV_RGB2GRAY) on every camera frame (video_source.cc:59-81, :63) ----
+ * Y = (c0 w0 + c1 w1 + c2 w2 + 8192) >> 14, OpenCV's 8-bit luma (R 4899, G 9617, B 1868; restated from OpenCV, not pinned by the
+ * reference tree).  RGB / RGBA put the R weight on byte 0 (CV_RGB2GRAY), BGR / BGRA on byte 2 (CV_BGR2GRAY); byte 3 of a 4-channel
+ * pixel is ignored.  cv::VideoCapture delivers BGR bytes and video_source.cc:63 converts them with CV_RGB2GRAY: SDVL_RGB8 on those
+ * bytes is what main.cc computes; SDVL_BGR8 is the luma of the true colours.  Strides are in bytes.  SDVL_GRAY8 behaves exactly like
+ * the gray entries (a copy; sdvl_frames_upload / sdvl_frames_upload_undistorted).  SDVL_ERR_INVALID (with a message) for an unknown
+ * format, a source stride below width x channels, null pointers or in-place conversion. */
+enum sdvl_pixel_format { SDVL_GRAY8 = 0, SDVL_RGB8 = 1, SDVL_BGR8 = 2, SDVL_RGBA8 = 3, SDVL_BGRA8 = 4 };
+
+/* n interleaved colour images src[i] (host pointers — pinned ones are read in place, pageable ones are staged — or device pointers
+ * if src_on_device) -> n gray images dst_dev[i] (device).  Up to 16384 pixels a side.  Asynchronous on the context's stream. */
+int sdvl_convert_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int width, int height, int format,
+                      void *const *dst_dev, int dst_stride);
+/* the fused form video_source.cc:63 + main.cc:133 need: colour camera images -> level 0 of the frames = undistort(gray(raw)), the
+ * conversion first (main.cc:128-137).  cam / dist null, or dist->d[0] == 0 (camera.cc:46): no lens, gray straight into level 0.
+ * Follow with sdvl_pyramid_build. */
+int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
+                             int format, const sdvl_camera *cam, const sdvl_distortion *dist);
+
 /* ---- pose from matches: FeatureAlign::SelectInliers + OptimizePose (feature_align.cc:73-82,152-243,258-283,341-431) --
  * One job per frame.  obs[] are the frame's matched features in found order: ax, ay = feature bearing x/z, y/z
  * (feature_align.cc:268), p = 3D point position, inv_cov = 1 / (1 << level).  The reference draws rand() % size once

@@ -22,6 +22,9 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libsdvl_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "host", "libsdvl_host.so")
 
+# enum sdvl_pixel_format
+SDVL_GRAY8, SDVL_RGB8, SDVL_BGR8, SDVL_RGBA8, SDVL_BGRA8 = 0, 1, 2, 3, 4
+
 MAX_LEVELS = 8
 MAX_CORNERS = 6144
 
@@ -126,7 +129,7 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
@@ -595,6 +598,36 @@ class Context:
         finally:
             self.device_free(buf)
         return [out[i].copy() for i in range(n)]
+
+    def convert_gray(self, imgs, fmt):
+        """cv::cvtColor(img, CV_*2GRAY) on the device for a batch of host colour images (numpy u8 [h, w, 3 or 4]; fmt = SDVL_* value)
+        -> numpy gray images"""
+        n = len(imgs)
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        h, w, ch = imgs[0].shape
+        src = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
+        buf = self.device_malloc(n * w * h)
+        try:
+            dst = (C.c_void_p * n)(*[buf + i * w * h for i in range(n)])
+            self.lib.sdvl_convert_gray.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+            self._check(self.lib.sdvl_convert_gray(self.h, n, src, w * ch, 0, w, h, int(fmt), dst, w))
+            out = self.device_download(buf, n * w * h).reshape(n, h, w)
+        finally:
+            self.device_free(buf)
+        return [out[i].copy() for i in range(n)]
+
+    def upload_color(self, frames, imgs, fmt, cam=None, dist=None):
+        """host colour images (numpy u8 [h, w, 3 or 4]) -> level 0 of `frames` = undistort(gray(img)) (no lens without cam / dist);
+        follow with pyramid_build"""
+        n = len(imgs)
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        h, w, ch = imgs[0].shape
+        src = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
+        arr = (C.c_void_p * n)(*[f.h for f in frames])
+        d = Distortion((C.c_double * 5)(*[float(x) for x in dist])) if dist is not None else None
+        self.lib.sdvl_frames_upload_color.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_frames_upload_color(self.h, n, arr, src, w * ch, 0, int(fmt), C.byref(cam) if cam is not None else None,
+                                                      C.byref(d) if d is not None else None))
 
     # ---- synthetic frames in HBM
     def device_malloc(self, nbytes):

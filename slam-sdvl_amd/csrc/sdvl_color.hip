@@ -1,0 +1,243 @@
+// sdvl_color.hip — K0 input stage, first half: cv::cvtColor(frame, img, CV_RGB2GRAY) on every camera frame (video_source.cc:63), on the
+// device, fused into the frames' upload.  The second half, Camera::UndistortImage (main.cc:133), follows it unchanged (sdvl_undistort.hip):
+// undistort(gray(raw)), the order of main.cc:128-137.
+//
+// The arithmetic is OpenCV's 8-bit fixed-point luma (restated from OpenCV's source, not from the reference tree: unpinned there, like
+// cv::pyrDown and cv::FAST):  Y = (c0 w0 + c1 w1 + c2 w2 + 2^13) >> 14  with R 4899, G 9617, B 1868 (sum 2^14: gray maps to itself).
+// CV_RGB2GRAY weights byte 0 with R, CV_BGR2GRAY byte 2; 4-channel pixels use the same weights and ignore byte 3.  The order is uniform
+// per launch (two kernel arguments), never decided per pixel.
+//
+// to_gray_kernel reads the colour bytes where they lie — pinned host memory through its device address, or HBM — so colour crosses the
+// link once and no colour copy is staged in HBM (pageable sources are: hipMemcpy2DAsync into the context's scratch first).  Dense and
+// aligned images: a lane converts 16 pixels from three (RGB) or four (RGBA) dwordx4 loads and writes them with ONE dwordx4 store (byte
+// stores cost up to ~12x per byte); padded rows whose starts stay 16-byte aligned take the same path row by row; anything else (odd
+// strides, odd widths, unaligned sources) goes row by row with byte accesses.  HBM-bound: (C + 1) W H bytes per frame.
+#include <vector>
+
+#include "sdvl_internal.h"
+
+namespace {
+
+enum { kScalar = 0, kRows16 = 1, kFlat16 = 2 };
+
+struct GrayJob {
+  const uint8_t *src;  // device-visible address of the colour image
+  uint8_t *dst;        // gray output
+  long long sstride;   // bytes between source rows (per job: a staged copy is tight, a source read in place keeps the caller's pitch)
+  int mode;            // kScalar / kRows16 / kFlat16
+  int pad_;
+};
+
+constexpr int kW1 = 9617;          // G
+constexpr int kWR = 4899, kWB = 1868;
+constexpr int kMaxChunks = 1024;   // workgroups per image at most (a 4096 x 4096 image: four 16-pixel units per lane)
+constexpr int kMaxSide = 16384;
+
+int channels_of(int format) {
+  switch (format) {
+    case SDVL_GRAY8: return 1;
+    case SDVL_RGB8: case SDVL_BGR8: return 3;
+    case SDVL_RGBA8: case SDVL_BGRA8: return 4;
+    default: return 0;
+  }
+}
+
+template <int C>
+__device__ __forceinline__ uint32_t byte_at(const uint32_t *dw, int k) { return (dw[k >> 2] >> (8 * (k & 3))) & 255u; }
+
+// one workgroup = 256 lanes of one image (blockIdx.y); w0 / w2: the weights of bytes 0 and 2 of a pixel
+template <int C>
+__global__ __launch_bounds__(256) void to_gray_kernel(const GrayJob *__restrict__ jobs, int width, int height, int dstride, int w0, int w2) {
+  const GrayJob job = jobs[blockIdx.y];
+  if (job.mode != kScalar) {
+    // (global address space: global_load / global_store with a scalar base instead of flat accesses)
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4 *gsrc_t;
+    typedef __attribute__((address_space(1))) u32x4 *gdst_t;
+    const bool flat = job.mode == kFlat16;
+    const int upr = flat ? static_cast<int>((static_cast<long long>(width) * height) >> 4) : width >> 4;  // 16-pixel units per row
+    const long long units = flat ? upr : static_cast<long long>(upr) * height;
+    for (long long u = blockIdx.x * 256 + threadIdx.x; u < units; u += 256LL * gridDim.x) {
+      const int r = flat ? 0 : static_cast<int>(u / upr), c = static_cast<int>(u - static_cast<long long>(r) * upr);
+      const gsrc_t s = (gsrc_t)(job.src + r * job.sstride + static_cast<long long>(c) * 16 * C);
+      u32x4 a[C];
+#pragma unroll
+      for (int k = 0; k < C; k++) a[k] = __builtin_nontemporal_load(s + k);
+      uint32_t dw[4 * C];
+#pragma unroll
+      for (int k = 0; k < C; k++) {
+        dw[4 * k] = a[k].x; dw[4 * k + 1] = a[k].y; dw[4 * k + 2] = a[k].z; dw[4 * k + 3] = a[k].w;
+      }
+      uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int p = 0; p < 16; p++) {
+        const uint32_t y = (byte_at<C>(dw, C * p) * w0 + byte_at<C>(dw, C * p + 1) * kW1 + byte_at<C>(dw, C * p + 2) * w2 + 8192u) >> 14;
+        o[p >> 2] |= y << (8 * (p & 3));
+      }
+      u32x4 v;
+      v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
+      *(gdst_t)(job.dst + static_cast<long long>(r) * dstride + static_cast<long long>(c) * 16) = v;
+    }
+    return;
+  }
+  // odd strides, odd widths, unaligned sources: row by row, a pixel per lane
+  for (int r = blockIdx.x; r < height; r += gridDim.x) {
+    const uint8_t *s = job.src + r * job.sstride;
+    uint8_t *d = job.dst + static_cast<long long>(r) * dstride;
+    for (int x = threadIdx.x; x < width; x += 256) {
+      const uint8_t *px = s + x * C;
+      d[x] = static_cast<uint8_t>((px[0] * w0 + px[1] * kW1 + px[2] * w2 + 8192) >> 14);
+    }
+  }
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// n colour images -> n gray images (device, row stride dst_stride), on ctx->stream.  dst == nullptr: the gray images go to the front of
+// the context's scratch (row stride w, 256-byte aligned) and `scratch_dst` receives where; staged copies of pageable sources follow them.
+int run_to_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int w, int h, int format,
+                uint8_t *const *dst, int dst_stride, std::vector<uint8_t *> *scratch_dst) {
+  const int C = channels_of(format);
+  const size_t row_bytes = static_cast<size_t>(w) * C, img_bytes = row_bytes * h;
+  SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
+  std::vector<const uint8_t *> srcs(n);
+  std::vector<long long> strides(n, src_stride);
+  std::vector<int> staged;
+  for (int i = 0; i < n; i++) {
+    if (src_on_device) {
+      srcs[i] = static_cast<const uint8_t *>(src[i]);
+      continue;
+    }
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, src[i]) == hipSuccess && (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice) &&
+        attr.devicePointer) {  // pinned host memory (or HBM): read in place over the link
+      srcs[i] = static_cast<const uint8_t *>(attr.devicePointer);
+    } else {
+      (void)hipGetLastError();  // an unregistered pointer is not an error here
+      staged.push_back(i);
+    }
+  }
+  const size_t gray_pitch = (static_cast<size_t>(w) * h + 255) / 256 * 256, pitch = (img_bytes + 255) / 256 * 256;
+  const size_t scratch_off = dst ? 0 : gray_pitch * n;
+  if (scratch_off + pitch * staged.size() > 0) {
+    int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, scratch_off + pitch * staged.size(), false);
+    if (rc) return rc;
+  }
+  if (!dst) {
+    scratch_dst->resize(n);
+    for (int i = 0; i < n; i++) (*scratch_dst)[i] = static_cast<uint8_t *>(ctx->d_work) + gray_pitch * i;
+    dst = scratch_dst->data();
+    dst_stride = w;
+  }
+  if (!staged.empty()) {  // pageable: a tight copy in the context's scratch first
+    for (size_t k = 0; k < staged.size(); k++) {
+      const int i = staged[k];
+      uint8_t *d = static_cast<uint8_t *>(ctx->d_work) + scratch_off + pitch * k;
+      SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(d, row_bytes, src[i], src_stride, row_bytes, h, hipMemcpyHostToDevice, ctx->stream));
+      srcs[i] = d;
+      strides[i] = static_cast<long long>(row_bytes);
+    }
+  }
+  const size_t jb = (sizeof(GrayJob) * n + 255) / 256 * 256;
+  void *hs = nullptr, *dsx = nullptr;
+  int rc = sdvl_stage_alloc(ctx, jb, &hs, &dsx);
+  if (rc) return rc;
+  GrayJob *hj = static_cast<GrayJob *>(hs);
+  const bool dense_px = ((static_cast<size_t>(w) * h) & 15u) == 0;
+  for (int i = 0; i < n; i++) {
+    int mode = kScalar;
+    if (aligned16(srcs[i]) && aligned16(dst[i])) {
+      if (strides[i] == static_cast<long long>(row_bytes) && dst_stride == w && dense_px) mode = kFlat16;
+      else if ((w & 15) == 0 && (strides[i] & 15) == 0 && (dst_stride & 15) == 0) mode = kRows16;
+    }
+    hj[i] = GrayJob{srcs[i], dst[i], strides[i], mode, 0};
+  }
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, jb));
+  const bool bgr = format == SDVL_BGR8 || format == SDVL_BGRA8;
+  const int w0 = bgr ? kWB : kWR, w2 = bgr ? kWR : kWB;
+  const long long units = (static_cast<long long>(w) * h) >> 4;
+  const int gx = static_cast<int>(std::max(1LL, std::min<long long>((units + 255) / 256, kMaxChunks)));
+  constexpr int kMaxJobsPerLaunch = 32768;  // (grid y)
+  for (int i0 = 0; i0 < n; i0 += kMaxJobsPerLaunch) {
+    const int m = std::min(kMaxJobsPerLaunch, n - i0);
+    const GrayJob *jobs = static_cast<const GrayJob *>(dsx) + i0;
+    if (C == 3) SDVL_LAUNCH(ctx, "to_gray", to_gray_kernel<3>, dim3(gx, m), dim3(256), jobs, w, h, dst_stride, w0, w2);
+    else SDVL_LAUNCH(ctx, "to_gray", to_gray_kernel<4>, dim3(gx, m), dim3(256), jobs, w, h, dst_stride, w0, w2);
+  }
+  SDVL_HIP_CHECK(ctx, hipGetLastError());
+  return SDVL_OK;
+}
+
+// the frame records of an upload (what sdvl_frames_upload does to a frame besides the pixels)
+void frame_takes_new_image(sdvl_frame *f) {
+  f->v.level[0] = f->own_level0;
+  f->hdr_stale = 1;
+  f->v.n_corners = 0;
+  f->desc_valid = 0;
+  f->bins_valid = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdvl_convert_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int width, int height, int format,
+                      void *const *dst_dev, int dst_stride) {
+  if (!ctx) return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, n >= 0 && (n == 0 || (src && dst_dev)), "sdvl_convert_gray: null image list");
+  const int C = channels_of(format);
+  SDVL_REQUIRE(ctx, C > 0, "sdvl_convert_gray: unknown pixel format");
+  SDVL_REQUIRE(ctx, width >= 1 && height >= 1 && width <= kMaxSide && height <= kMaxSide, "sdvl_convert_gray: image size out of range (1 .. 16384 a side)");
+  SDVL_REQUIRE(ctx, static_cast<long long>(src_stride) >= static_cast<long long>(width) * C, "sdvl_convert_gray: source stride smaller than width x channels");
+  SDVL_REQUIRE(ctx, dst_stride >= width, "sdvl_convert_gray: destination stride smaller than width");
+  for (int i = 0; i < n; i++) SDVL_REQUIRE(ctx, src[i] && dst_dev[i] && src[i] != dst_dev[i], "sdvl_convert_gray: null image or in-place conversion");
+  if (n == 0) return SDVL_OK;
+  if (format == SDVL_GRAY8) {  // the gray entries' copy (sdvl_undistort without a lens)
+    SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
+    for (int i = 0; i < n; i++)
+      SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(dst_dev[i], dst_stride, src[i], src_stride, width, height,
+                                           src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    return SDVL_OK;
+  }
+  return run_to_gray(ctx, n, src, src_stride, src_on_device, width, height, format, reinterpret_cast<uint8_t *const *>(dst_dev), dst_stride, nullptr);
+}
+
+int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
+                             int format, const sdvl_camera *cam, const sdvl_distortion *dist) {
+  if (!ctx) return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, n >= 0 && (n == 0 || (frames && src)), "sdvl_frames_upload_color: null frame or image list");
+  const int C = channels_of(format);
+  SDVL_REQUIRE(ctx, C > 0, "sdvl_frames_upload_color: unknown pixel format");
+  SDVL_REQUIRE(ctx, (cam == nullptr) == (dist == nullptr), "sdvl_frames_upload_color: pass both cam and dist, or neither");
+  if (n == 0) return SDVL_OK;
+  SDVL_REQUIRE(ctx, frames[0] != nullptr, "sdvl_frames_upload_color: null frame or image");
+  const int w = frames[0]->width, h = frames[0]->height;
+  for (int i = 0; i < n; i++) {
+    SDVL_REQUIRE(ctx, frames[i] && src[i], "sdvl_frames_upload_color: null frame or image");
+    SDVL_REQUIRE(ctx, frames[i]->width == w && frames[i]->height == h, "sdvl_frames_upload_color: frames of one call share a size");
+    SDVL_REQUIRE(ctx, src[i] != frames[i]->own_level0, "sdvl_frames_upload_color: in-place conversion");
+  }
+  SDVL_REQUIRE(ctx, static_cast<long long>(src_stride) >= static_cast<long long>(w) * C, "sdvl_frames_upload_color: source stride smaller than width x channels");
+  const bool lens = dist && dist->d[0] != 0.0;  // Camera::SetDistortions tests d0 only (camera.cc:46)
+  if (format == SDVL_GRAY8) {  // exactly the gray producers
+    if (lens) return sdvl_frames_upload_undistorted(ctx, n, frames, src, src_stride, src_on_device, cam, dist);
+    return sdvl_frames_upload(ctx, n, frames, reinterpret_cast<const uint8_t *const *>(src), src_stride);
+  }
+  SDVL_REQUIRE(ctx, w <= kMaxSide && h <= kMaxSide, "sdvl_frames_upload_color: image size out of range");
+  if (!lens) {  // gray straight into the frames' level 0
+    std::vector<uint8_t *> dst(n);
+    for (int i = 0; i < n; i++) dst[i] = frames[i]->own_level0;
+    const int rc = run_to_gray(ctx, n, src, src_stride, src_on_device, w, h, format, dst.data(), w, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) frame_takes_new_image(frames[i]);
+    return SDVL_OK;
+  }
+  // with a lens: gray into the scratch the remap reads raw sources from, then the unchanged remap writes level 0
+  std::vector<uint8_t *> gray;
+  const int rc = run_to_gray(ctx, n, src, src_stride, src_on_device, w, h, format, nullptr, w, &gray);
+  if (rc) return rc;
+  std::vector<const void *> gsrc(gray.begin(), gray.end());
+  return sdvl_frames_upload_undistorted(ctx, n, frames, gsrc.data(), w, 1, cam, dist);
+}
+
+}  // extern "C"

@@ -39,6 +39,7 @@ struct Batch {
   std::vector<std::unique_ptr<SDVL>> trackers;
   std::unique_ptr<SDVLBatch> batch;
   bool raw_input = false;  // sdvlh_batch_set_distortion: the images of a step are RAW camera frames (Image::raw)
+  int format = PIX_GRAY8;  // sdvlh_batch_set_color: the pixel format of the images of a step (row strides in bytes)
   int w, h;
   std::string err;
 };
@@ -120,6 +121,20 @@ int sdvlh_batch_set_distortion(void *bp, const double *dist5) {
   return 0;
 }
 
+// The images of every later step are COLOUR camera frames of `format` (enum sdvl_pixel_format; row strides in bytes): cv::cvtColor
+// (video_source.cc:63) runs on the device inside the step, fused into the frames' upload, before the undistortion of a lens.  SDVL_RGB8
+// is what main.cc computes on cv::VideoCapture's bytes; SDVL_GRAY8 (0) turns it off again.
+int sdvlh_batch_set_color(void *bp, int format) {
+  Batch *b = static_cast<Batch *>(bp);
+  if (!b) return -1;
+  if (format < PIX_GRAY8 || format > PIX_BGRA8) {
+    g_err = "sdvlh_batch_set_color: unknown pixel format " + std::to_string(format);
+    return -1;
+  }
+  b->format = format;
+  return 0;
+}
+
 // map mode of the batches created AFTER the call: 0 = plane map stub (every keyframe seeded from the scene plane),
 // 1 = the reference's mapper in sequential mode (map.cc; the first keyframe is still bootstrapped from the plane)
 void sdvlh_set_mapper(int on) { g_use_mapper = on != 0; }
@@ -145,8 +160,10 @@ void sdvlh_batch_destroy(void *bp) {
 static int step(Batch *b, std::vector<Image> &imgs, sdvlh_frame_stats *out) {
   try {
     std::vector<FrameStats> st(imgs.size());
-    if (b->raw_input)
-      for (Image &im : imgs) im.raw = true;
+    for (Image &im : imgs) {
+      im.raw = im.raw || b->raw_input;
+      im.format = b->format;
+    }
     b->batch->HandleFrames(imgs, st.data());
     for (size_t i = 0; i < imgs.size(); i++) {
       const FrameStats &s = st[i];
@@ -253,8 +270,10 @@ int sdvlh_batch_set_next_device(void *bp, const void *const *dev_imgs, int strid
     std::vector<Image> v;
     if (dev_imgs)
       for (size_t i = 0; i < b->trackers.size(); i++) v.push_back(Image::WrapDevice(dev_imgs[i], b->w, b->h, stride, true));
-    if (b->raw_input)
-      for (Image &im : v) im.raw = true;
+    for (Image &im : v) {
+      im.raw = im.raw || b->raw_input;
+      im.format = b->format;
+    }
     b->batch->SetNextImages(v);
     return 0;
   } catch (const std::exception &e) {
@@ -302,6 +321,7 @@ struct Farm {
   std::vector<char> busy;
   bool failed = false;
 
+  int format = PIX_GRAY8;     // sdvlh_farm_set_color
   int fibers_per_worker = 1;  // > 1: a worker interleaves that many group-steps, switching at every GPU wait
   bool host_input = false;    // the frame pointers of a run are HOST pointers (pinned): every step uploads its frames
   // host input travels ahead: while a group computes step s, its copy stream carries the images of the next steps into the free
@@ -748,6 +768,16 @@ void sdvlh_farm_set_host_input(void *fp, int on) {
     }
 }
 // (the feed itself is created by the first host-fed run)
+// every group's frames are colour camera frames of `format` (sdvlh_batch_set_color).  Colour frames must be resident in HBM: the host
+// input and its input ring (sdvl_feed_*, sdvl_ctx_prefetch_images) carry gray images only, and sdvlh_farm_run refuses the combination.
+int sdvlh_farm_set_color(void *fp, int format) {
+  Farm *f = static_cast<Farm *>(fp);
+  if (!f) return -1;
+  for (void *b : f->batches)
+    if (sdvlh_batch_set_color(b, format) != 0) return -1;
+  f->format = format;
+  return 0;
+}
 // the input ring of host-fed runs on (default) / off (every step uploads its own frames on its own stream before it computes)
 void sdvlh_farm_set_input_ring(void *fp, int on) { static_cast<Farm *>(fp)->input_ring = on != 0; }
 
@@ -887,6 +917,10 @@ void ProfStop() {
 int sdvlh_farm_run(void *fp, int n_steps, const void *const *dev_frames, int stride, sdvlh_frame_stats *out, int workers) {
   Farm *f = static_cast<Farm *>(fp);
   const int W = workers > 0 ? (workers < f->G ? workers : f->G) : f->G;
+  if (f->host_input && f->format != PIX_GRAY8) {
+    g_err = "sdvlh_farm_run: colour frames need frames resident in HBM; the host input and its input ring carry gray images only";
+    return -1;
+  }
   {
     std::lock_guard<std::mutex> lk(f->m);
     f->n_steps = n_steps; f->stride = stride; f->dev_frames = dev_frames; f->out = out;

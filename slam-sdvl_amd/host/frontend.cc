@@ -433,8 +433,37 @@ void BuildFrames(const vector<Frame *> &frames, const vector<sdvl_frame *> &devs
     un_f[kind].clear();
     un_i[kind].clear();
   };
+  // COLOUR camera images (Image::format): level 0 = cv::cvtColor(image, CV_*2GRAY) (video_source.cc:63), then Camera::UndistortImage if
+  // the image is raw and the camera has a lens — one conversion launch per (format, row pitch, source kind, lens); the frame always owns
+  // the converted gray (a colour image is never aliased as level 0)
+  vector<sdvl_frame *> co_f;
+  vector<const void *> co_i;
+  int co_key[4] = {0, 0, 0, 0};  // format, step, source on the device, lens
+  const Camera *co_cam = nullptr;
+  auto flush_color = [&]() {
+    if (co_f.empty()) return;
+    const Camera *cam = co_cam;
+    const sdvl_camera c = cam->abi();
+    const sdvl_distortion d = cam->distortion();
+    dev->Check(sdvl_frames_upload_color(dev->ctx(), static_cast<int>(co_f.size()), co_f.data(), co_i.data(), co_key[1], co_key[2], co_key[0],
+                                        co_key[3] ? &c : nullptr, co_key[3] ? &d : nullptr),
+               "sdvl_frames_upload_color");
+    co_f.clear();
+    co_i.clear();
+  };
   for (int i = 0; i < n; i++) {
     frames[i]->SetImageTransient(false);
+    if (imgs[i].color()) {
+      const int key[4] = {imgs[i].format, imgs[i].step, imgs[i].dev_src ? 1 : 0, imgs[i].raw && frames[i]->GetCamera()->HasDistortion() ? 1 : 0};
+      if (!co_f.empty() && (key[0] != co_key[0] || key[1] != co_key[1] || key[2] != co_key[2] || key[3] != co_key[3] ||
+                            frames[i]->GetCamera() != co_cam))
+        flush_color();
+      for (int k = 0; k < 4; k++) co_key[k] = key[k];
+      co_cam = frames[i]->GetCamera();
+      co_f.push_back(devs[i]);
+      co_i.push_back(imgs[i].dev_src ? imgs[i].dev_src : static_cast<const void *>(imgs[i].data));
+      continue;
+    }
     if (imgs[i].raw && frames[i]->GetCamera()->HasDistortion()) {
       const int kind = imgs[i].dev_src ? 1 : 0;
       if (!un_f[kind].empty() && (imgs[i].step != un_step[kind] || frames[i]->GetCamera() != frames[0]->GetCamera())) flush_raw(kind);
@@ -457,6 +486,7 @@ void BuildFrames(const vector<Frame *> &frames, const vector<sdvl_frame *> &devs
   flush();
   flush_raw(0);
   flush_raw(1);
+  flush_color();
   dev->Check(sdvl_pyramid_build(dev->ctx(), n, devs.data()), "sdvl_pyramid_build");
   if (!corners) return;
   // FastDetector::DetectPyramid on the device (FAST + quota + retainBest in libstdc++ order); nothing returns to the host

@@ -40,7 +40,8 @@ void Camera::SetDistortions(double d0, double d1, double d2, double d3, double d
   has_distortion_ = !(d_[0] == 0.0);
 }
 
-// camera.cc:100-105
+// camera.cc:100-105.  (an addition) A colour image (Image::format) is converted first, then undistorted — cv::cvtColor (video_source.cc:63)
+// and then UndistortImage, the order of main.cc:128-137: the result is the undistorted GRAY image.
 void Camera::UndistortImage(const Image &in, Image *out) const {
   Device *dev = Device::Current();
   if (!dev) throw std::runtime_error("Camera::UndistortImage: no sdvl::Device bound to this thread");
@@ -52,7 +53,20 @@ void Camera::UndistortImage(const Image &in, Image *out) const {
   const void *src = in.dev_src ? in.dev_src : static_cast<const void *>(in.data);
   const sdvl_camera cam = abi();
   const sdvl_distortion dist = distortion();  // d0 == 0 -> plain copy, like in.clone()
-  dev->Check(sdvl_undistort(ctx, 1, &src, in.step, in.dev_src ? 1 : 0, w, h, &cam, &dist, &buf, w), "sdvl_undistort");
+  if (in.color()) {
+    if (!HasDistortion()) {
+      dev->Check(sdvl_convert_gray(ctx, 1, &src, in.step, in.dev_src ? 1 : 0, w, h, in.format, &buf, w), "sdvl_convert_gray");
+    } else {
+      void *gray = nullptr;
+      dev->Check(sdvl_device_malloc(ctx, static_cast<int64_t>(w) * h, &gray), "sdvl_device_malloc");
+      std::shared_ptr<void> keep(gray, [ctx](void *p) { sdvl_device_free(ctx, p); });  // (sdvl_device_free waits for the stream)
+      dev->Check(sdvl_convert_gray(ctx, 1, &src, in.step, in.dev_src ? 1 : 0, w, h, in.format, &gray, w), "sdvl_convert_gray");
+      const void *gsrc = gray;
+      dev->Check(sdvl_undistort(ctx, 1, &gsrc, w, 1, w, h, &cam, &dist, &buf, w), "sdvl_undistort");
+    }
+  } else {
+    dev->Check(sdvl_undistort(ctx, 1, &src, in.step, in.dev_src ? 1 : 0, w, h, &cam, &dist, &buf, w), "sdvl_undistort");
+  }
   *out = Image::WrapDevice(buf, w, h, w, false);
   out->dev_owner = owner;
 }

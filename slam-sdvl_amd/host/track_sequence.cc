@@ -3,7 +3,8 @@
 // view" of the drop-in: nothing here knows about HIP; the classes are the reference's (Camera, Config, SDVL, Map).
 //
 //   track_sequence --synthetic N [--seed S]                      N frames of the S-A scene, rendered on the host
-//   track_sequence --list frames.txt                             one binary PGM (P5, 8 bit) path per line, e.g. a TUM / EuRoC list
+//   track_sequence --list frames.txt                             one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB: converted to gray on the
+//                                                                device, SDVL_RGB8) path per line, e.g. a TUM / EuRoC list
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper]
 //   round 5 (bench.py's latency legs):  [--texture plane|camera]  [--trackers N]  N cameras = N host threads, each with its own Device
 //            (= HIP stream), Camera, Map and SDVL, all fed the same frames;  [--batch]  with --trackers N: the N cameras step together through
@@ -41,10 +42,13 @@ using namespace sdvl;
 
 namespace {
 
-bool ReadPGM(const std::string &path, int *w, int *h, std::vector<uint8_t> *px) {
+// binary PGM (P5: gray) or PPM (P6: RGB byte order), 8 bit; *format = PIX_GRAY8 / PIX_RGB8
+bool ReadPNM(const std::string &path, int *w, int *h, std::vector<uint8_t> *px, int *format) {
   std::ifstream f(path, std::ios::binary);
   std::string magic;
-  if (!(f >> magic) || magic != "P5") return false;
+  if (!(f >> magic) || (magic != "P5" && magic != "P6")) return false;
+  const int channels = magic == "P6" ? 3 : 1;
+  *format = magic == "P6" ? PIX_RGB8 : PIX_GRAY8;
   int vals[3], n = 0;
   while (n < 3) {  // width, height, maxval with '#' comments in between
     f >> std::ws;
@@ -56,7 +60,7 @@ bool ReadPGM(const std::string &path, int *w, int *h, std::vector<uint8_t> *px) 
   f.get();  // the single whitespace byte after maxval
   *w = vals[0];
   *h = vals[1];
-  px->resize(static_cast<size_t>(vals[0]) * vals[1]);
+  px->resize(static_cast<size_t>(vals[0]) * vals[1] * channels);
   f.read(reinterpret_cast<char *>(px->data()), static_cast<std::streamsize>(px->size()));
   return static_cast<size_t>(f.gcount()) == px->size();
 }
@@ -202,6 +206,7 @@ int main(int argc, char **argv) {
         }
         for (int k = 0; k < n_frames; k++) {
           uint8_t *data = px.data();
+          int format = PIX_GRAY8;
           if (pool) {
             data = pool + frame_bytes * k;
           } else if (n_synth > 0) {
@@ -209,14 +214,13 @@ int main(int argc, char **argv) {
             sdvl_synth_render_host(&v, W, H, px.data(), W);
           } else {
             int w = 0, h = 0;
-            if (!ReadPGM(files[k], &w, &h, &px) || w != W || h != H) {
-              me.err = "cannot read " + files[k] + " as a binary PGM of the configured size";
+            if (!ReadPNM(files[k], &w, &h, &px, &format) || w != W || h != H) {
+              me.err = "cannot read " + files[k] + " as a binary PGM / PPM of the configured size";
               return;
             }
             data = px.data();
           }
-          Image img;
-          img.data = data; img.cols = W; img.rows = H; img.step = W;
+          Image img = Image::Wrap(data, W, H, format == PIX_RGB8 ? 3 * W : W, format);  // a P6 frame: cvtColor on the device (video_source.cc:63)
           Image imgu;
           if (lookahead && pool && ahead_valid) {
             imgu = ahead;                                          // undistorted one iteration ago
@@ -292,9 +296,9 @@ int main(int argc, char **argv) {
             uint8_t *data = px.data();
             if (pool) data = pool + frame_bytes * k;
             else if (n_synth > 0) { const sdvl_synth_view v = view_of(k); sdvl_synth_render_host(&v, W, H, px.data(), W); }
-            else { int w = 0, h = 0; if (!ReadPGM(files[k], &w, &h, &px) || w != W || h != H) { me.err = "cannot read " + files[k]; return; } data = px.data(); }
-            Image img;
-            img.data = data; img.cols = W; img.rows = H; img.step = W;
+            int format = PIX_GRAY8;
+            if (!pool && n_synth == 0) { int w = 0, h = 0; if (!ReadPNM(files[k], &w, &h, &px, &format) || w != W || h != H) { me.err = "cannot read " + files[k]; return; } data = px.data(); }
+            Image img = Image::Wrap(data, W, H, format == PIX_RGB8 ? 3 * W : W, format);
             std::vector<Image> imgs(n_trackers);
             for (int i = 0; i < n_trackers; i++) camera.UndistortImage(img, &imgs[i]);  // every camera its own frame in HBM (main.cc:133, outside the window)
             const auto t0 = std::chrono::steady_clock::now();

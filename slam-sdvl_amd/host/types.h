@@ -66,13 +66,33 @@ typedef Vec<double, 6> Vector6d;
 enum { CV_8UC1 = 0 };  // the only cv::Mat type the tracking front-end sees (frame.cc:38-41 converts to grey)
 #endif
 
+// Pixel layout of an Image (= enum sdvl_pixel_format of include/sdvl_hip.h).  A colour image is a RAW camera frame: the Frame built from it
+// takes cv::cvtColor(frame, img, CV_*2GRAY) (video_source.cc:63) as its image, converted on the device inside the upload.
+enum PixelFormat { PIX_GRAY8 = 0, PIX_RGB8 = 1, PIX_BGR8 = 2, PIX_RGBA8 = 3, PIX_BGRA8 = 4 };
+enum { SDVL_CV_8UC3 = 16, SDVL_CV_8UC4 = 24 };  // the cv::Mat type codes of 8-bit 3- and 4-channel images (CV_8UC3, CV_8UC4)
+
 struct Image {
   const uint8_t *data = nullptr;
-  int cols = 0, rows = 0, step = 0;
+  int cols = 0, rows = 0, step = 0;  // step: bytes between rows
+  // colour images default to the REFERENCE's order: the R weight on byte 0 (CV_RGB2GRAY, video_source.cc:63 — applied there to the BGR
+  // bytes of cv::VideoCapture, so this reproduces main.cc bit for bit); bgr() picks CV_BGR2GRAY, the luma of the true colours of BGR bytes
+  int format = PIX_GRAY8;
   Image() {}
-  // cv::Mat(rows, cols, type, data, step): a header over caller-owned pixels
-  Image(int rows_, int cols_, int /*type*/, const void *pixels, size_t step_ = 0)
-      : data(static_cast<const uint8_t *>(pixels)), cols(cols_), rows(rows_), step(step_ ? static_cast<int>(step_) : cols_) {}
+  // cv::Mat(rows, cols, type, data, step): a header over caller-owned pixels; type CV_8UC3 / CV_8UC4 = a colour frame
+  Image(int rows_, int cols_, int type, const void *pixels, size_t step_ = 0)
+      : data(static_cast<const uint8_t *>(pixels)), cols(cols_), rows(rows_),
+        format(type == SDVL_CV_8UC3 ? PIX_RGB8 : type == SDVL_CV_8UC4 ? PIX_RGBA8 : PIX_GRAY8) {
+    step = step_ ? static_cast<int>(step_) : cols_ * channels();
+  }
+  int channels() const { return format == PIX_GRAY8 ? 1 : (format == PIX_RGB8 || format == PIX_BGR8) ? 3 : 4; }
+  bool color() const { return format != PIX_GRAY8; }
+  // the same pixels, converted as CV_BGR2GRAY (the R weight on byte 2); a gray image stays as it is
+  Image bgr() const {
+    Image r = *this;
+    if (format == PIX_RGB8) r.format = PIX_BGR8;
+    if (format == PIX_RGBA8) r.format = PIX_BGRA8;
+    return r;
+  }
   sdvl_frame *dev = nullptr;
   int level = 0;
   std::shared_ptr<std::vector<uint8_t>> owner;  // keeps a host copy alive (cv::Mat ref-count analogue)
@@ -80,18 +100,22 @@ struct Image {
   Image clone() const {
     Image r = *this;
     if (data) {
-      r.owner = std::make_shared<std::vector<uint8_t>>(static_cast<size_t>(cols) * rows);
+      const int row = cols * channels();
+      r.owner = std::make_shared<std::vector<uint8_t>>(static_cast<size_t>(row) * rows);
       for (int y = 0; y < rows; y++)
-        for (int x = 0; x < cols; x++) (*r.owner)[static_cast<size_t>(y) * cols + x] = data[static_cast<size_t>(y) * step + x];
+        for (int x = 0; x < row; x++) (*r.owner)[static_cast<size_t>(y) * row + x] = data[static_cast<size_t>(y) * step + x];
       r.data = r.owner->data();
-      r.step = cols;
+      r.step = row;
     }
     return r;
   }
 #ifdef SDVL_HAVE_OPENCV
-  // a cv::Mat frame as the reference passes it (CV_8UC1, main.cc:128-138): a header over its pixels, the Mat kept alive
+  // a cv::Mat frame as the reference passes it (CV_8UC1, main.cc:128-138): a header over its pixels, the Mat kept alive.  A 3- or
+  // 4-channel Mat (type 16 = CV_8UC3, 24 = CV_8UC4) is a colour frame in the reference's order (see `format`).
   Image(const cv::Mat &m) {
-    if (!m.empty() && m.type() == CV_8UC1) {
+    const int t = m.empty() ? -1 : m.type();
+    if (t == CV_8UC1 || t == SDVL_CV_8UC3 || t == SDVL_CV_8UC4) {
+      format = t == SDVL_CV_8UC3 ? PIX_RGB8 : t == SDVL_CV_8UC4 ? PIX_RGBA8 : PIX_GRAY8;
       auto keep = std::make_shared<cv::Mat>(m);
       mat_owner = keep;
       data = keep->data;
@@ -101,7 +125,10 @@ struct Image {
     }
   }
   // the host mirror as a cv::Mat header (GetPyramid() users: homography_init.cc:196, ui/drawimage.cc); empty while only the HBM copy exists
-  operator cv::Mat() const { return data ? cv::Mat(rows, cols, CV_8UC1, const_cast<uint8_t *>(data), static_cast<size_t>(step)) : cv::Mat(); }
+  operator cv::Mat() const {
+    const int t = channels() == 1 ? CV_8UC1 : channels() == 3 ? SDVL_CV_8UC3 : SDVL_CV_8UC4;
+    return data ? cv::Mat(rows, cols, t, const_cast<uint8_t *>(data), static_cast<size_t>(step)) : cv::Mat();
+  }
   std::shared_ptr<void> mat_owner;
 #endif
   static Image Wrap(const uint8_t *p, int w, int h, int stride) {
@@ -122,6 +149,18 @@ struct Image {
   static Image WrapDevice(const void *dev_ptr, int w, int h, int stride, bool borrow_storage = false, bool transient_storage = false) {
     Image r;
     r.dev_src = dev_ptr; r.cols = w; r.rows = h; r.step = stride; r.borrow = borrow_storage; r.transient = borrow_storage && transient_storage;
+    return r;
+  }
+  // the same with a pixel format: a colour image (host or HBM, row stride in bytes) is converted into the Frame's own level 0 — never
+  // aliased, so borrow / transient do not apply to it
+  static Image Wrap(const uint8_t *p, int w, int h, int stride, int pixel_format) {
+    Image r = Wrap(p, w, h, stride);
+    r.format = pixel_format;
+    return r;
+  }
+  static Image WrapDeviceFormat(const void *dev_ptr, int w, int h, int stride, int pixel_format, bool borrow_storage) {
+    Image r = WrapDevice(dev_ptr, w, h, stride, borrow_storage);
+    r.format = pixel_format;
     return r;
   }
 };

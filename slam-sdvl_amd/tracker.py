@@ -120,11 +120,25 @@ class HostDevice:
             self.h = None
 
 
+# enum sdvl_pixel_format (include/sdvl_hip.h) and the bytes per pixel of each
+PIXEL_FORMATS = {"gray": 0, "rgb": 1, "bgr": 2, "rgba": 3, "bgra": 4}
+PIXEL_CHANNELS = {0: 1, 1: 3, 2: 3, 3: 4, 4: 4}
+
+
+def pixel_format(fmt):
+    """a pixel format name or SDVL_* value -> the SDVL_* value"""
+    code = PIXEL_FORMATS.get(fmt.lower()) if isinstance(fmt, str) else int(fmt)
+    if code not in PIXEL_CHANNELS:
+        raise ValueError("unknown pixel format %r (one of %s)" % (fmt, ", ".join(PIXEL_FORMATS)))
+    return code
+
+
 class TrackerBatch:
     def __init__(self, dev, B, w, h, cam4, plane4=(0, 0, 1, 2.0), first_poses=None, host_threads=1):
         self.lib = dev.lib
         self.dev = dev
         self.B, self.w, self.h_img = B, w, h
+        self.channels = 1   # set_color
         cam4 = np.ascontiguousarray(cam4, np.float64)
         plane4 = np.ascontiguousarray(plane4, np.float64)
         if first_poses is None:
@@ -138,13 +152,13 @@ class TrackerBatch:
     def step_host(self, imgs):
         imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
         ptrs = (C.c_void_p * self.B)(*[im.ctypes.data for im in imgs])
-        if self.lib.sdvlh_batch_step_host(self.h, ptrs, self.w, self._stats) != 0:
+        if self.lib.sdvlh_batch_step_host(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
 
     def step_device(self, dev_ptrs):
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs])
-        if self.lib.sdvlh_batch_step_device(self.h, ptrs, self.w, self._stats) != 0:
+        if self.lib.sdvlh_batch_step_device(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
 
@@ -153,7 +167,7 @@ class TrackerBatch:
         are queued behind the coming step's search / pose chain (SDVLBatch::SetNextImages).  The buffers must keep their CONTENT until that
         call: the look-ahead is recognised by device address alone.  It belongs to the one coming step and is dropped if that step cannot use it"""
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs]) if dev_ptrs is not None else None
-        if self.lib.sdvlh_batch_set_next_device(self.h, ptrs, self.w) != 0:
+        if self.lib.sdvlh_batch_set_next_device(self.h, ptrs, self.w * self.channels) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
 
     def set_distortion(self, dist5):
@@ -164,11 +178,21 @@ class TrackerBatch:
         if self.lib.sdvlh_batch_set_distortion(self.h, d.ctypes.data) != 0:
             raise RuntimeError("sdvlh_batch_set_distortion")
 
+    def set_color(self, fmt):
+        """the images of every later step are COLOUR camera frames (h x w x channels, interleaved) of pixel format `fmt` ("gray", "rgb",
+        "bgr", "rgba", "bgra" or the SDVL_* value): cv::cvtColor (video_source.cc:63) runs on the device inside the step, before the
+        undistortion of set_distortion.  "rgb" puts the R weight on byte 0 — what main.cc computes on cv::VideoCapture's BGR bytes"""
+        code = pixel_format(fmt)
+        self.lib.sdvlh_batch_set_color.argtypes = [C.c_void_p, C.c_int]
+        if self.lib.sdvlh_batch_set_color(self.h, code) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        self.channels = PIXEL_CHANNELS[code]
+
     def step_device_transient(self, dev_ptrs):
         """frames in HBM that stay valid for THIS step only (a slot of an input ring): aliased while tracked, frames that become
         keyframes take a copy at the end of the step"""
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs])
-        if self.lib.sdvlh_batch_step_device_transient(self.h, ptrs, self.w, self._stats) != 0:
+        if self.lib.sdvlh_batch_step_device_transient(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
 
@@ -204,6 +228,7 @@ class TrackerFarm:
     def __init__(self, gpu, G, Bg, w, h, cam4, plane4=(0, 0, 1, 2.0), first_poses=None, host_threads_per_group=1):
         self.lib = load_host_library()
         self.G, self.Bg, self.w, self.h_img = G, Bg, w, h
+        self.channels = 1   # set_color
         n = G * Bg
         cam4 = np.ascontiguousarray(cam4, np.float64)
         plane4 = np.ascontiguousarray(plane4, np.float64)
@@ -240,6 +265,15 @@ class TrackerFarm:
             if self.lib.sdvlh_batch_set_distortion(self.lib.sdvlh_farm_batch(self.h, g), d.ctypes.data) != 0:
                 raise RuntimeError("sdvlh_batch_set_distortion")
 
+    def set_color(self, fmt):
+        """every group's frames are COLOUR camera frames of `fmt` (TrackerBatch.set_color).  They must be resident in HBM: run() refuses
+        colour frames together with set_host_input (the host input and its input ring carry gray images only)"""
+        code = pixel_format(fmt)
+        self.lib.sdvlh_farm_set_color.argtypes = [C.c_void_p, C.c_int]
+        if self.lib.sdvlh_farm_set_color(self.h, code) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        self.channels = PIXEL_CHANNELS[code]
+
     def set_fibers(self, n):
         """n > 1: every worker thread interleaves n group-steps, switching at GPU waits (use G = n * workers groups)"""
         self.lib.sdvlh_farm_set_fibers.argtypes = [C.c_void_p, C.c_int]
@@ -265,7 +299,7 @@ class TrackerFarm:
         if out is None:
             out = self.alloc_stats(n_steps)
         assert len(out) >= n_steps * self.G * self.Bg
-        if self.lib.sdvlh_farm_run(self.h, n_steps, dev_frames.ctypes.data, self.w, out, int(workers)) != 0:
+        if self.lib.sdvlh_farm_run(self.h, n_steps, dev_frames.ctypes.data, self.w * self.channels, out, int(workers)) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return out
 
