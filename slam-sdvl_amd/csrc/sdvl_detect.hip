@@ -1527,7 +1527,6 @@ int64_t sdvl_detect_scratch_bytes(int width, int height, const sdvl_detect_param
   return static_cast<int64_t>(detect_slot_layout(total, p->max_fast_levels).bytes);
 }
 
-// SDVL_FAST_INT_SCORES=1: the dense path's epilogue on integer scores (round 3's form; A/B measurements, tests)
 // the share (of 64) of a cell's probed pixels that must pass the compass test for the cell to take the dense path
 // (SDVL_FAST_DENSE_NUM: 0 = every cell dense, 64 = every cell through the candidate list; A/B and the sweep of profiles/r05)
 static int fast_cells_dense_num() {

@@ -146,12 +146,10 @@ __device__ bool converge_pose_small(const sdvl_pose_obs *obs, const int *idx, in
   return true;
 }
 
-// Round 3: two launches.  pose_hypotheses_kernel converges the draws, one LANE per draw (a dependent FP64 chain of ~105 us; at ~180
-// VGPRs per lane its waves are few and narrow: 64-thread workgroups, two per frame for 100 draws), and
-// pose_supporters_kernel counts every draw's supporters over all matches with one wave per (draw, 256 matches) — 100 x 1000 pairs
-// per frame in configuration C took 250 of the 370 us when the two waves of the first kernel walked them alone.
+// pose_hypotheses_kernel converges the draws, one LANE per draw (a dependent FP64 chain of ~105 us; at ~180 VGPRs per lane its
+// waves are few and narrow: 64-thread workgroups).  It converges the first kHypDraws draws; pose_refine converges the rest on demand
+// and counts every draw's supporters as its replay of the RANSAC loop reaches the draw.
 constexpr int kHypDraws = 64;     // draws of one workgroup = lanes of its wave
-constexpr int kSupChunk = 256;    // matches one supporter wave tests against its draw (4 per lane)
 
 __global__ __launch_bounds__(kHypDraws) void pose_hypotheses_kernel(const PoseJobDev *__restrict__ jobs, const sdvl_pose_obs *__restrict__ obs_all,
                                                                     const int32_t *__restrict__ rand_idx, sdvl_pose_params prm,
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(kHypDraws) void pose_hypotheses_kernel(const PoseJo
   HypResult &dst = hyp[static_cast<size_t>(blockIdx.y) * prm.max_ransac_its + h];
   for (int k = 0; k < 7; k++) dst.se3[k] = r.se3[k];
   dst.ok = r.ok;
-  dst.supporters = 0;  // pose_supporters_kernel adds to it
+  dst.supporters = 0;  // counted by pose_refine (lazy supporters)
 }
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -197,7 +195,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // swap predicated, and a wave runs until its SLOWEST draw has converged); here lanes 0..npts-1 take one point each, lanes 0..27 add the
 // points' normal-equation terms IN POINT ORDER (the rounding of the sequential loop, feature_align.cc:370-400), the solve and the SE3
 // update run uniformly (scalar pivot branches), the wave leaves as soon as ITS draw has converged — and counts the draw's supporters
-// over all matches itself (feature_align.cc:190, 245-283: an integer sum), so pose_supporters_kernel is not launched behind this form.
+// over all matches itself (feature_align.cc:190, 245-283: an integer sum), so pose_refine finds them counted.
 // Same operations on the same operands in the same order as converge_pose_small: the draws' results are bit-identical.
 struct HypWaveLds {
   double terms[8][29];
@@ -336,36 +334,6 @@ __global__ __launch_bounds__(64) void pose_hypotheses_wave_kernel(const PoseJobD
     dst.ok = ok;
     dst.supporters = supporters;
   }
-}
-
-// CheckReprojectionError of every draw over every match (feature_align.cc:190, 245-283).  blockIdx.x = draw, blockIdx.y = chunk of
-// kSupChunk matches, blockIdx.z = frame; a supporter count is an integer sum, so its order is free: one add per wave.
-__global__ __launch_bounds__(64) void pose_supporters_kernel(const PoseJobDev *__restrict__ jobs, const sdvl_pose_obs *__restrict__ obs_all,
-                                                             sdvl_pose_params prm, HypResult *__restrict__ hyp) {
-  const PoseJobDev &job = jobs[blockIdx.z];
-  const int size = job.n_obs;
-  const int q0 = static_cast<int>(blockIdx.y) * kSupChunk;
-  if (q0 >= size) return;
-  HypResult &H = hyp[static_cast<size_t>(blockIdx.z) * prm.max_ransac_its + blockIdx.x];
-  if (!H.ok) return;
-  const Rigid se3 = se3_from7(H.se3);
-  const M3 R = se3_rot(se3);
-  const sdvl_pose_obs *obs = obs_all + job.obs_begin;
-  const int lane = threadIdx.x;
-  int mine = 0;
-#pragma unroll
-  for (int u = 0; u < kSupChunk / 64; u++) {
-    const int q = q0 + u * 64 + lane;
-    if (q < size) {
-      double ex, ey;
-      V3 pos;
-      reproj_error(obs[q], R, se3.t, &ex, &ey, &pos);
-      mine += sqrt(ex * ex + ey * ey) <= prm.inlier_threshold ? 1 : 0;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if (lane == 0 && mine > 0) atomicAdd(&H.supporters, mine);
 }
 
 // ---------------------------------------------------------------------------------------------- refinement (wave each)
@@ -654,8 +622,8 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
   double best7[7] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (lazy_supporters) {
     // Round 6: the supporters of a draw are counted HERE, when the replay reaches the draw — the reference stops drawing once the budget is
-    // met (typically after 5-10 of the 100 draws when nine matches in ten are inliers), and so does this loop: pose_supporters_kernel
-    // tested every draw against every match (24 k of a tracked frame's 694 k instructions) for counts nobody read.  Lane h holds draw
+    // met (typically after 5-10 of the 100 draws when nine matches in ten are inliers), and so does this loop: rounds 3-5 tested every
+    // draw against every match in a launch of its own (24 k of a tracked frame's 694 k instructions) for counts nobody read.  Lane h holds draw
     // base + h; the loop takes a draw's pose out of it with readlane and counts over the matches in rounds of 64 (an integer sum).
     for (int base = 0; base < prm.max_ransac_its && it < nits; base += 64) {
       const int h = base + lane;
@@ -788,7 +756,6 @@ int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseJobDev *d_jobs
                              int batch_size) {
   if (max_obs < 1) max_obs = 1;
   if (max_obs > kMaxObs) max_obs = kMaxObs;
-  const bool all_supporters = getenv("SDVL_POSE_ALL_SUPPORTERS") != nullptr;  // (read per call: the test flips it inside one process)
   int hyp_ready = p->max_ransac_its;
   // one wave per draw pays while every wave finds a SIMD of its own: a lone camera (100 waves), not configuration C's groups of 16
   // (1600 waves per launch, four groups at a time: 46.3 k tracked frames/s with the lane form against 41.3 k, two alternating pairs)
@@ -798,7 +765,7 @@ int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseJobDev *d_jobs
     SDVL_LAUNCH(ctx, "pose_hypotheses", pose_hypotheses_wave_kernel, dim3(p->max_ransac_its, n_jobs), dim3(64), d_jobs, d_obs, d_rand, *p,
                 static_cast<HypResult *>(d_hyp));
   } else {
-    hyp_ready = all_supporters ? p->max_ransac_its : std::min(p->max_ransac_its, kHypDraws);  // the first wave of draws; the rest on demand (pose_refine)
+    hyp_ready = std::min(p->max_ransac_its, kHypDraws);  // the first wave of draws; the rest on demand (pose_refine)
     {
       hipEvent_t ev_a = nullptr, ev_b = nullptr;
       sdvl_timer_events(ctx, "pose_hypotheses", &ev_a, &ev_b);
@@ -806,13 +773,9 @@ int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseJobDev *d_jobs
       hipExtLaunchKernelGGL(pose_hypotheses_kernel, dim3((hyp_ready + kHypDraws - 1) / kHypDraws, n_jobs), dim3(kHypDraws), cache_bytes, ctx->stream, ev_a, ev_b,
                             0, d_jobs, d_obs, d_rand, *p, static_cast<HypResult *>(d_hyp));
     }
-    // the supporters: counted by pose_refine as its replay of the RANSAC loop reaches a draw; SDVL_POSE_ALL_SUPPORTERS=1 (A/B and test):
-    // every draw against every match in a launch of its own, as in rounds 3-5
-    if (all_supporters)
-      SDVL_LAUNCH(ctx, "pose_supporters", pose_supporters_kernel, dim3(p->max_ransac_its, (max_obs + kSupChunk - 1) / kSupChunk, n_jobs), dim3(64), d_jobs, d_obs, *p,
-                  static_cast<HypResult *>(d_hyp));
+    // the supporters: counted by pose_refine as its replay of the RANSAC loop reaches a draw
   }
-  const int lazy = (!wave_form && !all_supporters) ? 1 : 0;
+  const int lazy = !wave_form ? 1 : 0;
   // a frame of the metric configuration has <= 200 observations: one wave (three waves with 59 KB of LDS wait longer for a CU among the
   // other streams' kernels than they save: 2.4 -> 3.9 ms of dispatch time per step); configuration C's ~850: wave 0 + two helpers
   // Round 5: a small batch (a lone camera) takes the helper waves too — nobody else wants the CU

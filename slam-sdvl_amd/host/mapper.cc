@@ -297,14 +297,15 @@ bool MapperMap::BeginUpdate() {
 
 // Map::UpdateCandidates, map.cc:402-498, one pass = the `pass_`-th occurrence of every point in the list.  Points do not
 // interact, so processing the list occurrence by occurrence leaves every point in the state the sequential loop does.
-static int g_device_filter = -1;  // -1: not decided yet (environment)
+static std::atomic<int> g_device_filter{-1};  // -1: the environment decides (read once); worker threads read it while a setter may write
 void MapperMap::SetDeviceFilter(bool on) { g_device_filter = on ? 1 : 0; }
 bool MapperMap::DeviceFilter() {
-  if (g_device_filter < 0) {
+  static const int env = [] {
     const char *e = std::getenv("SDVL_HOST_DEPTH_FILTER");
-    g_device_filter = (e && e[0] == '1') ? 0 : 1;
-  }
-  return g_device_filter != 0;
+    return (e && e[0] == '1') ? 0 : 1;
+  }();
+  const int v = g_device_filter;
+  return (v < 0 ? env : v) != 0;
 }
 
 sdvl_depth_params MapperMap::FilterParams() const {

@@ -169,6 +169,16 @@ class SDVL {
  private:
   friend class SDVLBatch;
   void CalcTrackingQuality(int matches, int attempts);
+  // the per-frame logic of HandleFrame (sdvl.cc:55-130) that every form of SDVLBatch's step shares
+  void SetMotionModel();
+  void GetMotionModel();
+  void ResetMotionModel();
+  void SaveFirstFrame(FrameStats &st);
+  int TrackingDecision();
+  void StartRelocalizing();
+  void Relocalized(const std::shared_ptr<Frame> &kf, FrameStats &st);
+  void LinkFeatures();
+  void SaveKeyframe(FrameStats &st);
   std::unique_ptr<Device> own_device_;  // SDVL(Camera*) on a thread without a Device
   std::unique_ptr<Map> own_map_;        // SDVL(Camera*): the reference's `Map map_` member
   Camera *camera_;
@@ -187,7 +197,6 @@ class SDVL {
   bool relocalize_pending_ = false;
   // Round 5: HandleFrame() steps through a batch of one that LIVES with the tracker, so a lone camera gets the device-resident
   // tracking tables too — a tracked frame is one submission and one wait instead of the host-driven stage-by-stage form
-  // (SDVL_HANDLEFRAME_ONE_SHOT=1: a fresh batch per call, rounds 1-4)
   std::unique_ptr<SDVLBatch> self_batch_;
   std::vector<Image> next_image_;  // SetNextImage: handed to the batch by the HandleFrame call it belongs to
   void SyncSelfBatch();
@@ -239,7 +248,7 @@ class SDVLBatch {
   // also set by SDVL_POSE_HOST=1 in the environment.  Both produce the same decisions (tests/test_gpu_tracker.py).
   static void SetDevicePose(bool on);
   static bool DevicePose();
-  // Device-resident tracking tables (default for a persistent batch on one host thread): last_frame's features and points
+  // Device-resident tracking tables (the default): last_frame's features and points
   // stay in HBM, a step is ONE submission and ONE wait, the host keeps rand(), the motion model and the keyframe logic.
   // Off (SDVL_NO_TRACK_TABLES=1 or SetTrackTables(false)): the host assembles every request as before.  Same results.
   static void SetTrackTables(bool on);
@@ -281,7 +290,6 @@ class SDVLBatch {
   unsigned long long reloc_epoch_ = 0;  // 0: no store yet
   void RelocAlign(const std::vector<sdvl_align_job> &jobs, const sdvl_align_params &ap, std::vector<sdvl_align_result> *res);
   int track_cells_ = 0, track_cap_ = 0;
-  bool persistent_ = true;  // SDVL::HandleFrame's one-shot batches never build tables
   friend class SDVL;
   std::vector<sdvl_track_job> tr_jobs_;
   std::vector<uint16_t> tr_rank_;

@@ -416,21 +416,81 @@ void SDVL::CalcTrackingQuality(int matches, int attempts) {
   tracking_quality_ = TRACKING_INSUFFICIENT;
 }
 
+// sdvl.cc:278-281
+void SDVL::SetMotionModel() { current_frame_->SetPose(SE3::Exp(vel_) * last_frame_->GetPose()); }
+
+// sdvl.cc:266-276
+void SDVL::GetMotionModel() {
+  const SE3 mov = current_frame_->GetPose() * last_frame_->GetPose().Inverse();
+  const Vector6d vel = SE3::Log(mov);
+  for (int c = 0; c < 6; c++) vel_[c] = 0.9 * (0.5 * vel[c] + 0.5 * vel_[c]);
+}
+
+// sdvl.h:85
+void SDVL::ResetMotionModel() {
+  for (int k = 0; k < 6; k++) vel_[k] = 0.0;
+}
+
+// bootstrap replacement (SaveFirstFrame/SaveSecondFrame are out of scope): first frame = keyframe at first_pose
+void SDVL::SaveFirstFrame(FrameStats &st) {
+  current_frame_->SetPose(first_pose_);
+  current_frame_->SetKeyframe();
+  map_->AddKeyframe(current_frame_, false);  // like SaveFirstFrame / SaveSecondFrame (sdvl.cc:144,165): not queued
+  pending_kf_ = current_frame_;              // seeded from the scene plane in the mapping stage
+  last_frame_ = current_frame_;
+  last_kf_ = current_frame_;
+  state_ = STATE_RUNNING;
+  track_.valid = false;
+  st.state = 0;
+  st.keyframe = 1;
+}
+
+// sdvl.cc:97-100: CalcTrackingQuality, then NeedKeyframe.  0 = tracking lost, 1 = ordinary frame, 2 = new keyframe
+int SDVL::TrackingDecision() {
+  CalcTrackingQuality(matches_, attempts_);
+  if (tracking_quality_ == TRACKING_BAD) return 0;
+  return (tracking_quality_ == TRACKING_GOOD && map_->NeedKeyframe(current_frame_, matches_)) ? 2 : 1;
+}
+
+// sdvl.cc:77-80: relocalisation starts (lost_frames_ >= 3)
+void SDVL::StartRelocalizing() {
+  map_->SetRelocalizing(true);
+  ResetMotionModel();
+}
+
+// sdvl.cc:84-85: relocalised onto keyframe kf
+void SDVL::Relocalized(const shared_ptr<Frame> &kf, FrameStats &st) {
+  map_->SetRelocalizing(false);
+  last_kf_ = kf;
+  last_frame_ = kf;
+  track_.valid = false;  // the table follows last_frame_
+  st.relocalized = 1;
+}
+
+// sdvl.cc:101-106: the points learn of their observations in the new keyframe
+void SDVL::LinkFeatures() {
+  vector<shared_ptr<Feature>> &features = current_frame_->GetFeatures();
+  for (auto it = features.begin(); it != features.end(); it++)
+    if (Point *p = (*it)->GetPointRaw()) p->AddFeature(*it);
+}
+
+// sdvl.cc:108-114: the frame becomes a keyframe
+void SDVL::SaveKeyframe(FrameStats &st) {
+  current_frame_->SetKeyframe();
+  map_->AddKeyframe(current_frame_);
+  last_kf_ = current_frame_;
+  map_->LimitKeyframes(current_frame_);
+  if (!dynamic_cast<MapperMap *>(map_)) pending_kf_ = current_frame_;  // plane map stub: seed every keyframe
+  st.keyframe = 1;
+}
+
 void SDVL::SetNextImage(const Image &next) {
   next_image_.assign(1, next);
 }
 
 bool SDVL::HandleFrame(const Image &img) {
   std::unique_lock<std::mutex> lock(map_->GetMutex());  // the mapper thread of threaded mode stays out meanwhile
-  static const bool one_shot = std::getenv("SDVL_HANDLEFRAME_ONE_SHOT") != nullptr;
   FrameStats st;
-  if (one_shot) {  // rounds 1-4: a one-call batch, no device-resident tables, every stage driven from the host
-    next_image_.clear();
-    SDVLBatch one(Device::Current(), {this}, 1);
-    one.persistent_ = false;
-    one.HandleFrames({img}, &st);
-    return true;
-  }
   Device *dev = Device::Current();
   if (!self_batch_ || self_batch_->dev_ != dev) {  // first call, or the caller moved to another Device (= stream)
     if (self_batch_) self_batch_->SyncHostState();
@@ -445,7 +505,7 @@ bool SDVL::HandleFrame(const Image &img) {
     self_batch_->HandleFrames({img}, &st);
   } catch (...) {
     // a step that failed half way leaves the set's tables and its own bookkeeping in an unknown state: the next call starts with a
-    // fresh batch and rebuilds the table from the host objects (what the one-shot form did after every call)
+    // fresh batch and rebuilds the table from the host objects
     self_batch_.reset();
     track_.valid = false;
     throw;
@@ -590,23 +650,26 @@ void SDVLBatch::ParallelFor(int n, const std::function<void(int)> &fn) {
   g_pool_of(g_pool_slot, threads_)->For(n, fn);
 }
 
-static int g_device_pose = -1;  // -1: not decided yet (environment)
 void SDVLBatch::SetNextImages(const vector<Image> &next) { next_imgs_ = next; }
 
+// process-wide switches: worker threads read them while a setter may write; -1 = the environment decides (read once)
+static std::atomic<int> g_device_pose{-1};
 void SDVLBatch::SetDevicePose(bool on) { g_device_pose = on ? 1 : 0; }
 bool SDVLBatch::DevicePose() {
-  if (g_device_pose < 0) {
+  static const int env = [] {
     const char *e = std::getenv("SDVL_POSE_HOST");
-    g_device_pose = (e && e[0] == '1') ? 0 : 1;
-  }
-  return g_device_pose != 0;
+    return (e && e[0] == '1') ? 0 : 1;
+  }();
+  const int v = g_device_pose;
+  return (v < 0 ? env : v) != 0;
 }
 
-static int g_track_tables = -1;  // -1: not decided yet (environment)
+static std::atomic<int> g_track_tables{-1};
 void SDVLBatch::SetTrackTables(bool on) { g_track_tables = on ? 1 : 0; }
 bool SDVLBatch::TrackTables() {
-  if (g_track_tables < 0) g_track_tables = std::getenv("SDVL_NO_TRACK_TABLES") ? 0 : 1;
-  return g_track_tables != 0;
+  static const int env = std::getenv("SDVL_NO_TRACK_TABLES") ? 0 : 1;
+  const int v = g_track_tables;
+  return (v < 0 ? env : v) != 0;
 }
 
 // The counters the device advanced (Promote / Unpromote / SetLastFrame / status) reach the Point objects.
@@ -851,9 +914,8 @@ void SDVLBatch::RelocalizeLost(const vector<int> &lost, FrameStats *stats, vecto
   vector<char> stale(L, 0);
   for (int q = 0; q < L; q++) {
     SDVL &t = *trk_[lost[q]];
-    SyncStats(t);                   // the Point objects Reproject reads catch up with the device's counters
-    t.map_->SetRelocalizing(true);  // sdvl.cc:80
-    for (int k = 0; k < 6; k++) t.vel_[k] = 0.0;
+    SyncStats(t);  // the Point objects Reproject reads catch up with the device's counters
+    t.StartRelocalizing();
     SDVL::RelocCache &rc = t.reloc_;
     stale[q] = (!reloc_store_ || rc.owner != this || rc.epoch != reloc_epoch_ || rc.version != t.map_->Version()) ? 1 : 0;
   }
@@ -1014,12 +1076,7 @@ void SDVLBatch::RelocalizeLost(const vector<int> &lost, FrameStats *stats, vecto
       t.matches_ = t.feature_align_.GetMatches();
       t.attempts_ = t.feature_align_.GetAttempts();
       if (t.matches_ >= Config::MinMatches()) {
-        const shared_ptr<Frame> cframe = t.reloc_.kfs[cursor[q] - first[q]];
-        t.map_->SetRelocalizing(false);  // sdvl.cc:84
-        t.last_kf_ = cframe;
-        t.last_frame_ = cframe;
-        t.track_.valid = false;  // the table follows last_frame_
-        stats[lost[q]].relocalized = 1;
+        t.Relocalized(t.reloc_.kfs[cursor[q] - first[q]], stats[lost[q]]);
         (*found)[q] = 1;
         open_[q] = 0;
       } else {
@@ -1043,22 +1100,16 @@ int SDVLBatch::TrackOnHost(SDVL &t, FrameStats *st) {
   t.feature_align_.OptimizePose(t.current_frame_);
   st->inliers = t.feature_align_.GetInliers();
   st->outliers = t.feature_align_.GetOutliers();
-  {  // GetMotionModel, sdvl.cc:266-276
-    const SE3 mov = t.current_frame_->GetPose() * t.last_frame_->GetPose().Inverse();
-    const Vector6d vel = SE3::Log(mov);
-    for (int c = 0; c < 6; c++) t.vel_[c] = 0.9 * (0.5 * vel[c] + 0.5 * t.vel_[c]);
-  }
-  t.CalcTrackingQuality(t.matches_, t.attempts_);
+  t.GetMotionModel();
   t.track_.valid = false;  // this frame's features live on the host
-  if (t.tracking_quality_ == SDVL::TRACKING_BAD) return 0;
-  return (t.tracking_quality_ == SDVL::TRACKING_GOOD && t.map_->NeedKeyframe(t.current_frame_, t.matches_)) ? 2 : 1;
+  return t.TrackingDecision();
 }
 
 // One step of B trackers on the device-resident tables: ONE submission (alignment, detection, reprojection, search, match
 // selection, pose, table update) and ONE wait.  The host keeps what only it can do: rand() (cell shuffle, RANSAC draws), the
 // motion model, tracking quality, the keyframe decision and everything a keyframe sets off.
 bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats) {
-  if (!persistent_ || !TrackTables() || !DevicePose() || Config::MaxRansacPoints() > 8) return false;
+  if (!TrackTables() || !DevicePose() || Config::MaxRansacPoints() > 8) return false;
   const int B = static_cast<int>(trk_.size());
   for (int i = 0; i < B; i++) {
     SDVL &t = *trk_[i];
@@ -1127,23 +1178,13 @@ bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats
     t.current_frame_ = frames[i];
     t.current_frame_->SetID(t.frame_counter_++);
     if (t.state_ != SDVL::STATE_RUNNING) {
-      // bootstrap replacement (SaveFirstFrame/SaveSecondFrame are out of scope): first frame = keyframe at first_pose
-      t.current_frame_->SetPose(t.first_pose_);
-      t.current_frame_->SetKeyframe();
-      t.map_->AddKeyframe(t.current_frame_, false);
-      t.pending_kf_ = t.current_frame_;
-      t.last_frame_ = t.current_frame_;
-      t.last_kf_ = t.current_frame_;
-      t.state_ = SDVL::STATE_RUNNING;
-      t.track_.valid = false;
-      st.state = 0;
-      st.keyframe = 1;
+      t.SaveFirstFrame(st);
     } else if (t.lost_frames_ >= 3) {
       st.state = 2;
       lost.push_back(i);  // relocalize = lost_frames_ >= 3, sdvl.cc:73
     } else {
       st.state = 2;
-      t.current_frame_->SetPose(SE3::Exp(t.vel_) * t.last_frame_->GetPose());  // SetMotionModel, sdvl.cc:278-281
+      t.SetMotionModel();
       run.push_back(i);
     }
   }
@@ -1169,7 +1210,7 @@ bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats
       UploadTables(again, &built);
       for (size_t q = 0; q < again.size(); q++) {
         SDVL &t = *trk_[again[q]];
-        t.current_frame_->SetPose(SE3::Exp(t.vel_) * t.last_frame_->GetPose());  // SetMotionModel, sdvl.cc:278-281 (vel_ = 0)
+        t.SetMotionModel();  // (vel_ = 0)
         (built[q] ? run : host_run).push_back(again[q]);
       }
       std::sort(run.begin(), run.end());
@@ -1284,14 +1325,8 @@ bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats
             (*ts.points)[p]->SetDeviceTrashed();  // the row carries the deletion: nothing to rebuild when the trash is emptied
             t.map_->DeletePoint((*ts.points)[p]);
           }
-      {  // GetMotionModel, sdvl.cc:266-276
-        const SE3 mov = t.current_frame_->GetPose() * t.last_frame_->GetPose().Inverse();
-        const Vector6d vel = SE3::Log(mov);
-        for (int c = 0; c < 6; c++) t.vel_[c] = 0.9 * (0.5 * vel[c] + 0.5 * t.vel_[c]);
-      }
-      t.CalcTrackingQuality(t.matches_, t.attempts_);
-      if (t.tracking_quality_ != SDVL::TRACKING_BAD)
-        decision[i] = (t.tracking_quality_ == SDVL::TRACKING_GOOD && t.map_->NeedKeyframe(t.current_frame_, t.matches_)) ? 2 : 1;
+      t.GetMotionModel();
+      decision[i] = static_cast<char>(t.TrackingDecision());
     });
   }
   // (a relocalised tracker whose keyframe no table can hold: the per-object calls, behind the batch's chain on the same stream)
@@ -1343,18 +1378,11 @@ bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats
         } else {
           // the frame becomes part of the map: its features and the points behind them turn into objects
           SyncStats(t);
-          vector<shared_ptr<Feature>> &features = t.current_frame_->GetFeatures();
-          for (auto it = features.begin(); it != features.end(); it++)
-            if (Point *p = (*it)->GetPointRaw()) p->AddFeature(*it);
+          t.LinkFeatures();
           t.track_.valid = false;  // seeding / the mapper add features: the table is rebuilt from the keyframe
         }
         t.current_frame_->ClearSceneDepthHint();  // a keyframe's features lose the points EmptyTrash deletes (map.cc:207-259)
-        t.current_frame_->SetKeyframe();
-        t.map_->AddKeyframe(t.current_frame_);
-        t.last_kf_ = t.current_frame_;
-        t.map_->LimitKeyframes(t.current_frame_);  // sdvl.cc:114
-        if (plane) t.pending_kf_ = t.current_frame_;
-        st.keyframe = 1;
+        t.SaveKeyframe(st);
       } else {
         t.map_->AddFrame(t.current_frame_);
         if (t.current_frame_->HasFlatFeatures()) t.track_.feat_buf ^= 1;  // the matches the step left in the other buffer are last_frame's features now
@@ -1479,16 +1507,7 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
     t.current_frame_ = frames[i];
     t.current_frame_->SetID(t.frame_counter_++);
     if (t.state_ != SDVL::STATE_RUNNING) {
-      // bootstrap replacement (SaveFirstFrame/SaveSecondFrame are out of scope): first frame = keyframe at first_pose
-      t.current_frame_->SetPose(t.first_pose_);
-      t.current_frame_->SetKeyframe();
-      t.map_->AddKeyframe(t.current_frame_, false);  // like SaveFirstFrame / SaveSecondFrame (sdvl.cc:144,165): not queued
-      t.pending_kf_ = t.current_frame_;              // seeded from the scene plane in the mapping stage
-      t.last_frame_ = t.current_frame_;
-      t.last_kf_ = t.current_frame_;
-      t.state_ = SDVL::STATE_RUNNING;
-      st.state = 0;
-      st.keyframe = 1;
+      t.SaveFirstFrame(st);
     } else {
       st.state = 2;
       bool relocalize = t.lost_frames_ >= 3;
@@ -1497,8 +1516,7 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
         // from that keyframe's pose, fast mode) is independent of the others: one launch with |keyframes| jobs.  The
         // keyframe loop then runs in the reference's order (newest first) over the results; Reproject stays sequential
         // because it draws from rand() and stops at the first keyframe that gathers MinMatches.
-        t.map_->SetRelocalizing(true);  // sdvl.cc:80
-        for (int k = 0; k < 6; k++) t.vel_[k] = 0.0;
+        t.StartRelocalizing();
         vector<shared_ptr<Frame>> &kfs = t.map_->GetKeyframes();
         vector<std::pair<shared_ptr<Frame>, shared_ptr<Frame>>> pairs;
         vector<SE3> start, aligned;
@@ -1517,17 +1535,14 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
           t.matches_ = t.feature_align_.GetMatches();
           t.attempts_ = t.feature_align_.GetAttempts();
           if (t.matches_ >= Config::MinMatches()) {
-            t.map_->SetRelocalizing(false);  // sdvl.cc:84
-            t.last_kf_ = cframe;
-            t.last_frame_ = cframe;
+            t.Relocalized(cframe, st);
             relocalize = false;
-            st.relocalized = 1;
             break;
           }
         }
       }
       if (!relocalize) {
-        t.current_frame_->SetPose(SE3::Exp(t.vel_) * t.last_frame_->GetPose());  // SetMotionModel, sdvl.cc:278-281
+        t.SetMotionModel();
         run.push_back(i);
       }
     }
@@ -1572,8 +1587,8 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
       for (int k = 0; k < R; k++) cap += static_cast<int>(trk_[run[k]]->last_frame_->GetFeatures().size());
       sink.ctx = dev_->ctx();
       sink.cap = cap;
-      // unique per DEVICE, not per SDVLBatch: frames remember the slot they got in a batch by its id, and SDVL::HandleFrame
-      // makes a fresh one-tracker SDVLBatch for every frame
+      // unique per DEVICE, not per SDVLBatch: frames remember the slot they got in a batch by its id, and several SDVLBatches
+      // may step on one device
       sink.batch_id = ++dev_->search_batch_counter;
       // search -> match selection -> RANSAC + pose refinement as ONE submission (sdvl_search_run_chain): the device replays
       // the second half of SelectPoints itself, so the pose kernels run while this thread does the same replay for its
@@ -1713,14 +1728,8 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
       }
       st.inliers = t.feature_align_.GetInliers();
       st.outliers = t.feature_align_.GetOutliers();
-      {  // GetMotionModel, sdvl.cc:266-276
-        const SE3 mov = t.current_frame_->GetPose() * t.last_frame_->GetPose().Inverse();
-        const Vector6d vel = SE3::Log(mov);
-        for (int c = 0; c < 6; c++) t.vel_[c] = 0.9 * (0.5 * vel[c] + 0.5 * t.vel_[c]);
-      }
-      t.CalcTrackingQuality(t.matches_, t.attempts_);
-      if (t.tracking_quality_ != SDVL::TRACKING_BAD)
-        decision[k] = (t.tracking_quality_ == SDVL::TRACKING_GOOD && t.map_->NeedKeyframe(t.current_frame_, t.matches_)) ? 2 : 1;
+      t.GetMotionModel();
+      decision[k] = static_cast<char>(t.TrackingDecision());
     });
     // the keyframes are known: queue their FilterCorners inputs (Shi-Tomasi, descriptors, one gather + copy) now; the
     // bookkeeping below (feature lists of the points, keyframe graph, retiring the previous frames) runs meanwhile
@@ -1745,15 +1754,8 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
       FrameStats &st = stats[i];
       if (decision[k] != 0) {
         if (decision[k] == 2) {
-          vector<shared_ptr<Feature>> &features = t.current_frame_->GetFeatures();
-          for (auto it = features.begin(); it != features.end(); it++)
-            if (Point *p = (*it)->GetPointRaw()) p->AddFeature(*it);
-          t.current_frame_->SetKeyframe();
-          t.map_->AddKeyframe(t.current_frame_);
-          t.last_kf_ = t.current_frame_;
-          t.map_->LimitKeyframes(t.current_frame_);  // sdvl.cc:114
-          if (!dynamic_cast<MapperMap *>(t.map_)) t.pending_kf_ = t.current_frame_;  // plane map stub: seed every keyframe
-          st.keyframe = 1;
+          t.LinkFeatures();
+          t.SaveKeyframe(st);
         } else {
           t.map_->AddFrame(t.current_frame_);
         }

@@ -60,7 +60,7 @@ def set_device_pose(on):
 
 
 def set_track_tables(on):
-    """device-resident tracking tables (default for persistent batches) on / off: off = the host assembles every request"""
+    """device-resident tracking tables (default) on / off: off = the host assembles every request"""
     load_host_library().sdvlh_set_track_tables(int(bool(on)))
 
 

@@ -152,11 +152,11 @@ def test_farm_at_bench_size_on_the_camera_texture(trk, sdvl, orc):
     farm.close()
 
 
-@pytest.mark.parametrize("env,extra", [({}, []), ({"SDVL_HANDLEFRAME_ONE_SHOT": "1"}, []), ({}, ["--trackers", "3"]), ({}, ["--lookahead"])])
+@pytest.mark.parametrize("env,extra", [({}, []), ({"SDVL_NO_TRACK_TABLES": "1"}, []), ({}, ["--trackers", "3"]), ({}, ["--lookahead"])])
 def test_one_camera_through_handleframe_on_the_camera_texture(orc, synth, env, extra):
     """host/track_sequence = the loop of main.cc:126-159, one SDVL::HandleFrame call per frame.  Round 5: the call steps through a
-    batch of one that lives with the tracker (device-resident tables, one submission per tracked frame); SDVL_HANDLEFRAME_ONE_SHOT=1
-    keeps rounds 1-4's host-driven form; --trackers 3: three cameras on three host threads and streams; --lookahead: the next frame of the
+    batch of one that lives with the tracker (device-resident tables, one submission per tracked frame); SDVL_NO_TRACK_TABLES=1
+    steps it through the host-driven form; --trackers 3: three cameras on three host threads and streams; --lookahead: the next frame of the
     sequence named one call ahead (SDVL::SetNextImage: its pyramid and corners are built behind the current frame's chain).  All give
     the oracle's answers."""
     exe = os.path.join(ROOT, "slam-sdvl_amd", "host", "track_sequence")

@@ -958,14 +958,10 @@ def test_pose_from_matches_many_draws(ctx, orc):
     assert max(w["n_draws"] for w in wants) > 128   # the later workgroups' draws are really consumed
 
 
-@pytest.mark.parametrize("env", [None, "SDVL_POSE_ALL_SUPPORTERS"])
-def test_pose_from_matches_batch_of_40_on_the_farm_forms(ctx, orc, env, monkeypatch):
+def test_pose_from_matches_batch_of_40_on_the_farm_forms(ctx, orc):
     """More than 32 jobs in one call: the farm's forms of the pose stage — one LANE per draw, the first 64 draws converged by
     pose_hypotheses, the supporters counted by pose_refine as its replay reaches a draw, draws beyond 64 converged there on demand
-    (round 6).  Jobs with few inliers keep drawing past 64; the oracle's n_draws, lists and poses are demanded of every job.
-    SDVL_POSE_ALL_SUPPORTERS=1: rounds 3-5's form (every draw against every match in pose_supporters)."""
-    if env:
-        monkeypatch.setenv(env, "1")
+    (round 6).  Jobs with few inliers keep drawing past 64; the oracle's n_draws, lists and poses are demanded of every job."""
     cam = TUM_CAM
     jobs, wants = [], []
     for j in range(40):

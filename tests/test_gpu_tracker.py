@@ -646,10 +646,9 @@ def test_cpp_example_track_sequence_matches_the_oracle(orc, synth, tmp_path):
     # third run: the tracked step's search without the corner bins (SDVL_TRACK_NO_BINS=1: the views of the current frames lose the
     # bins sdvl_track_align named ahead of the detection, as for frames whose corners were set by hand) — same answers
     # further runs, one per environment switch of the tracking step (README): the host-driven form (round 1's path), the pose stage on
-    # the host, the one-shot batch per HandleFrame call — same answers each time
+    # the host — same answers each time
     for args, env in ((["--synthetic", str(n)], {}), (["--list", str(lst)], {}), (["--synthetic", str(n)], {"SDVL_TRACK_NO_BINS": "1"}),
-                      (["--synthetic", str(n)], {"SDVL_NO_TRACK_TABLES": "1"}), (["--synthetic", str(n)], {"SDVL_POSE_HOST": "1"}),
-                      (["--synthetic", str(n)], {"SDVL_HANDLEFRAME_ONE_SHOT": "1"})):
+                      (["--synthetic", str(n)], {"SDVL_NO_TRACK_TABLES": "1"}), (["--synthetic", str(n)], {"SDVL_POSE_HOST": "1"})):
         r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
         assert r.returncode == 0, r.stderr
         rows = [l.split() for l in r.stdout.strip().splitlines()]
