@@ -6,13 +6,18 @@ grid reprojection with SearchPoint/AlignPatch, RANSAC + pose refinement) over on
 640x480 sequences per GPU (workload S-A of SURVEY §8d, TUM intrinsics / TUM cfg parameters, 5-level pyramid,
 max 200 matches).  All input frames are rendered into HBM before the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W          (N > 1: one rank per GPU - started by torch.distributed.run, or by this
+  python bench.py --gpus N --steps K --warmup W [--full]  (N > 1: one rank per GPU - started by torch.distributed.run, or by this
                                                           file itself when it is launched directly; fewer GPUs than N = error)
 
 Sequences shard across ranks with no data-path collective ("weak" scaling: B sequences per GPU); RCCL is used only
 for the barrier and the throughput reduction.  Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP events
-on the kernel's own stream over the timed region) and `cpu_baseline` (the CPU oracle on one host core and on all usable host cores,
-bounded sample; N = 1 only).
+on the kernel's own stream over the timed region).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  `--full` adds the
+legs beside the headline: `cpu_baseline` (the CPU oracle on one host core and on all usable host cores, bounded sample; N = 1
+only), `latency` (one and 16 cameras through the C++ HandleFrame loop), `host_fed`, `lost_mix` and `sustained`.  Without --full
+these fields are null.  A leg's own option (--cpu-frames, --latency-frames, --host-steps, --lost-mix-steps, --sustained-frames)
+skips it at 0 and runs it at a positive count, with or without --full; left at its default it runs under --full only.
 """
 import argparse
 import ctypes as C
@@ -662,9 +667,12 @@ def main():
     ap.add_argument("--distortion", choices=sorted(DISTORTIONS), default="none",
                     help="the camera's lens (the cfg file's Camera.d1..d5): the synthetic frames are rendered THROUGH that lens and every leg undistorts "
                          "them first, as main.cc:133 does (Camera::UndistortImage: a remap from a per-camera map cached on the device)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the legs beside the headline (cpu_baseline, latency, host_fed, lost_mix, sustained) at their default "
+                         "sizes; a plain run does only the warm-up and timed steps and the legs given a count of their own")
     ap.add_argument("--latency-frames", type=int, default=-1,
                     help="frames of the LATENCY legs (one sequence alone and 16 sequences through the C++ SDVL::HandleFrame loop, host/track_sequence): "
-                         "0 = skip; default 300 for S-A / S-B on one GPU")
+                         "0 = skip; default with --full 300 for S-A / S-B on one GPU")
     ap.add_argument("--seqs", type=int, default=int(os.environ.get("SDVL_BENCH_SEQS", "0")), help="independent sequences per GPU (0 = the workload's)")
     ap.add_argument("--groups", type=int, default=0, help="groups per GPU, each = host thread + HIP stream (0 = auto)")
     ap.add_argument("--threads", type=int, default=0, help="extra host threads inside a group for per-sequence stages (0 = 1)")
@@ -673,27 +681,32 @@ def main():
                     help="group-steps a worker thread interleaves, switching at GPU waits (1 = one at a time)")
     ap.add_argument("--mapper", action="store_true",
                     help="run the reference's mapper (map.cc, sequential mode) inside every step instead of the plane map stub")
-    ap.add_argument("--cpu-frames", type=int, default=-1, help="frames of the CPU baseline sample (0 = skip, -1 = the workload's)")
+    ap.add_argument("--cpu-frames", type=int, default=-1, help="frames of the CPU baseline sample (0 = skip, -1 = the workload's with --full)")
     ap.add_argument("--sustained-frames", type=int, default=-1,
                     help="frames per sequence of the third, SUSTAINED leg: fresh trackers run long sequences (two lengths of SURVEY §8d's S-A: 600 frames) "
                          "host-fed from a pool of distinct sequences, with SDVL.max_keyframes = --sustained-max-keyframes so that the map — and with "
                          "it HBM and host memory — stops growing; reported as value_sustained with the memory in use at the middle and at the end; "
-                         "0 = skip; default 600 for S-A on one GPU")
+                         "0 = skip; default with --full 600 for S-A on one GPU")
     ap.add_argument("--sustained-max-keyframes", type=int, default=48,
                     help="SDVL.max_keyframes of the sustained leg (the reference's cfg files say 1000, its default is 100: config.cc:63); 0 = the workload's")
     ap.add_argument("--lost-mix-steps", type=int, default=-1,
                     help="steps of the LOST-MIX leg (VERDICT r05 #1): a fresh farm on a pool of distinct sequences resident in HBM runs 40 undisturbed steps "
                          "(its own baseline), then this many steps in which 5 %% of the trackers are blinded (a featureless frame) for 5 frames every 50 "
                          "frames: they go TRACKING_BAD x3, relocalise over their keyframes inside the tabled step and rejoin; reported as value_lost_mix "
-                         "and lost_mix; 0 = skip; default 100 for S-A / S-B on one GPU")
+                         "and lost_mix; 0 = skip; default with --full 100 for S-A / S-B on one GPU")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed for every sequence (pose and counters) as DIR/<name>.npy "
                          "(float64; a seeded sample of the sequences above 64 MB)")
     ap.add_argument("--host-steps", type=int, default=-1,
                     help="steps of the second, HOST-FED leg (frames in pinned host memory, uploaded inside the step, as SDVL::HandleFrame(const cv::Mat&) "
                          "receives them): reported as value_host_fed next to the HBM-resident value; 0 = skip; "
-                         "default 16 on one GPU, 8 per rank on several (10 GB of pinned host memory per rank, NUMA-local to its GPU)")
+                         "default with --full 16 on one GPU, 8 per rank on several (10 GB of pinned host memory per rank, NUMA-local to its GPU)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline alone: a leg left at its default (-1) is skipped, one given a count explicitly still runs
+        for opt in ("cpu_frames", "latency_frames", "sustained_frames", "lost_mix_steps", "host_steps"):
+            if getattr(args, opt) < 0:
+                setattr(args, opt, 0)
     global W_IMG, H_IMG, TUM_CAM, FEATS_LABEL, ORACLE_PARAMS, TEXTURE, SEQ_SEED, DISTORTION
     DISTORTION = DISTORTIONS[args.distortion]
     wl = WORKLOADS[args.workload]

@@ -19,7 +19,7 @@ def _env(**kw):
 
 
 def test_launcher_runs_two_ranks_over_gloo():
-    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--seqs", "8"], env=_env(SDVL_BENCH_DRY="1"),
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--seqs", "8", "--full"], env=_env(SDVL_BENCH_DRY="1"),
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -32,7 +32,7 @@ def test_launcher_runs_two_ranks_over_gloo():
     # MAX over ranks: rank 1 sleeps 40 ms, rank 0 20 ms
     assert d["ms_per_step"] * 3 >= 39.0
     assert abs(d["value"] - d["tracked"] / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 0.02
-    # round 4: the N > 1 line carries the DROP-IN figure too — the host-fed leg runs on every rank (8 steps each by default), its
+    # round 4: the N > 1 line carries the DROP-IN figure too — the host-fed leg runs on every rank (8 steps each by default with --full), its
     # tracked frames are summed, its time is the slowest rank's, and the ranks' own link rates come back as min / max
     hf = d["host_fed"]
     assert d["value_host_fed"] == hf["value"] and hf["steps"] == 8 and hf["tracked"] == 2 * 8 * 8
@@ -81,6 +81,17 @@ def _dry(*args):
     out = subprocess.run([sys.executable, BENCH, *args], env=_env(SDVL_BENCH_DRY="1"), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
+
+
+def test_plain_run_leaves_the_legs_out_unless_asked():
+    """a plain run (no --full) measures the headline alone; --full adds the host-fed leg at its default size, and a leg given a count
+    of its own runs at that count either way"""
+    base = ("--gpus", "2", "--steps", "2", "--warmup", "1", "--seqs", "8")
+    plain = _dry(*base)
+    assert plain["host_fed"] is None and plain["value_host_fed"] is None and plain["roofline"]["link"] is None
+    assert _dry(*base, "--full")["host_fed"]["steps"] == 8
+    assert _dry(*base, "--host-steps", "3")["host_fed"]["steps"] == 3
+    assert _dry(*base, "--full", "--host-steps", "0")["host_fed"] is None
 
 
 def test_eight_ranks_s_b_every_rank_tracks_chunk_rank_mod_4():

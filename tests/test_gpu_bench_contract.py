@@ -11,9 +11,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*extra, env=None, want_stderr=False):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--seqs", "32", "--cpu-frames", "12", "--sustained-frames", "40", "--latency-frames", "12",
-                          "--lost-mix-steps", "20", *extra], capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, **(env or {})))
+def run_bench(*extra, env=None, want_stderr=False, full=True):
+    legs = ["--full", "--cpu-frames", "12", "--sustained-frames", "40", "--latency-frames", "12", "--lost-mix-steps", "20"] if full else []
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--seqs", "32", *legs, *extra],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, **(env or {})))
     assert out.returncode == 0, out.stderr[-2000:]
     if want_stderr:
         lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -95,6 +96,20 @@ def test_bench_line_contract():
     check(run_bench())
 
 
+def test_bench_plain_run_measures_the_headline_alone():
+    """without --full the line carries the headline and the timed region's own figures; none of the legs beside it runs"""
+    d = run_bench(full=False)
+    assert d["metric"].startswith("tracked frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8/f32/f64"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["config"]["input"].startswith("hbm_resident")
+    assert d["value"] > 0 and abs(d["value"] - 32 * 4 / (d["ms_per_step"] * 4 / 1e3)) / d["value"] < 0.02   # every frame tracked
+    for k in ("cpu_baseline", "latency", "host_fed", "sustained", "lost_mix", "value_host_fed", "value_sustained", "value_lost_mix",
+              "speedup_vs_cpu_1core", "speedup_vs_cpu_all_cores"):
+        assert d[k] is None, k
+    r = d["roofline"]
+    ms = d["kernel_ms_per_step"]
+    assert r["kernel"] == max(ms, key=ms.get) and r["achieved"] > 0 and "link" not in r
+
+
 def test_bench_line_contract_with_the_drivers_warmup():
     """--warmup 5 as the driver runs it: every dispatch timed over the last three warm-up steps, the roofline's kernel alone after that"""
     d = run_bench("--warmup", "5")
@@ -136,7 +151,7 @@ def test_bench_line_contract_through_a_lens():
 def test_bench_line_contract_s_c():
     """BASELINE config 5's workload (S-C: 1280x960, 4000 features, 1000 matches), 16 sequences"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "S-C", "--seqs", "16", "--steps", "4", "--warmup", "2", "--cpu-frames", "6",
-                          "--host-steps", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--host-steps", "2", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][-1])
     assert d["metric"].startswith("tracked frames/sec (1280x960") and d["config"]["workload"].startswith("S-C") and d["config"]["sequences_per_gpu"] == 16
