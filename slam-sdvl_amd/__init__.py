@@ -216,6 +216,27 @@ class Frame:
 
 
 
+class AlignStore:
+    """sdvl_align_store: alignment feature records kept in HBM (Relocalize aligns every frame against the same keyframes)"""
+
+    def __init__(self, ctx, capacity):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(ctx.lib.sdvl_align_store_create(ctx.h, int(capacity), C.byref(h)))
+        self.h = h
+
+    def write(self, offset, feats, begin=0, end=None):
+        """records [offset, offset + end - begin) of the store <- feats[begin:end] (an AlignFeature array)"""
+        end = len(feats) if end is None else end
+        src = C.byref(feats, begin * C.sizeof(AlignFeature))
+        self.ctx._check(self.ctx.lib.sdvl_align_store_write(self.ctx.h, self.h, int(offset), int(end - begin), src))
+
+    def close(self):
+        if self.h:
+            self.ctx._check(self.ctx.lib.sdvl_align_store_destroy(self.ctx.h, self.h))
+            self.h = None
+
+
 class Distortion(C.Structure):
     _fields_ = [("d", C.c_double * 5)]
 
@@ -430,18 +451,30 @@ class Context:
                                                  _ptr(bi, i32p), _ptr(bd, i32p)))
         return bi, bd
 
-    def image_align(self, jobs, feats, cam, ap):
-        """jobs: list of (ref Frame, cur Frame, feat_begin, feat_end, T7); feats: AlignFeature array"""
-        n = len(jobs)
-        ja = (AlignJob * n)()
+    @staticmethod
+    def _align_jobs(jobs):
+        ja = (AlignJob * len(jobs))()
         for i, (ref, cur, b, e, T) in enumerate(jobs):
             ja[i].ref = ref.h.value
             ja[i].cur = cur.h.value
             ja[i].feat_begin, ja[i].feat_end = b, e
             for k in range(7):
                 ja[i].T[k] = float(T[k])
+        return ja
+
+    def image_align(self, jobs, feats, cam, ap):
+        """jobs: list of (ref Frame, cur Frame, feat_begin, feat_end, T7); feats: AlignFeature array"""
+        n = len(jobs)
         res = (AlignResult * n)()
-        self._check(self.lib.sdvl_image_align(self.h, n, ja, len(feats), feats, C.byref(cam), C.byref(ap), res))
+        self._check(self.lib.sdvl_image_align(self.h, n, self._align_jobs(jobs), len(feats), feats, C.byref(cam), C.byref(ap), res))
+        return res
+
+    def image_align_stored(self, jobs, store, cam, ap):
+        """sdvl_image_align_begin_stored + _end: as image_align, with feat_begin / feat_end naming records of `store` (AlignStore)"""
+        n = len(jobs)
+        res = (AlignResult * n)()
+        self._check(self.lib.sdvl_image_align_begin_stored(self.h, n, self._align_jobs(jobs), store.h, C.byref(cam), C.byref(ap)))
+        self._check(self.lib.sdvl_image_align_end(self.h, n, res))
         return res
 
     def search_points(self, reqs, cam, sp):
