@@ -36,6 +36,8 @@ enum sdvl_status {
 #define SDVL_MAX_CORNERS 6144        /* per frame: num_features plus the ties retainBest keeps (config C: 4000 + ~2 %) */
 #define SDVL_MAX_ALIGN_FEATURES 2048 /* features per image-alignment job */
 #define SDVL_CELL_KP_CAP 176         /* a 32x32 ROI holds at most 13*13 = 169 NMS-surviving corners */
+#define SDVL_MAX_CELL_SIZE 64        /* detection cells of 8 .. 64 px; cells wider than 32 take the wide-tile FAST kernel */
+#define SDVL_MAX_LEVEL_CELLS 8192    /* cells of one detection level (3840x2160 at cell 32: 120 x 68 = 8160) */
 
 typedef struct sdvl_camera { /* camera.h:34-135 pinhole part */
   double width, height, fx, fy, u0, v0;
@@ -220,6 +222,9 @@ int sdvl_frame_download_level(sdvl_ctx *ctx, const sdvl_frame *f, int level, uin
  * are exclusive offsets over the frame's concatenated cells (ncells = sum over levels, see sdvl_fast_num_cells).
  * The quota / retainBest selection (fast_detector.cc:108-151) stays on the host. */
 int sdvl_fast_num_cells(int width, int height, const sdvl_detect_params *p, int *cells_per_level, int *total);
+/* entries of one cell's FAST list for this cell size: SDVL_CELL_KP_CAP up to 32, ceil((c - 6) / 2)^2 beyond (a c x c ROI
+ * tests (c - 6)^2 pixels and no two 8-neighbours both survive the strict 3x3 suppression: 841 at 64); 0 outside 8 .. 64 */
+int sdvl_cell_kp_cap(int cell_size);
 /* bytes of context scratch one frame of a detection batch needs while the batch is in flight (per-cell lists, selection lists) */
 int64_t sdvl_detect_scratch_bytes(int width, int height, const sdvl_detect_params *p);
 int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_detect_params *p, int cap,

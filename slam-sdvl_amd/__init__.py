@@ -126,7 +126,7 @@ ABI_SYMBOLS = [
     "sdvl_ctx_bind_thread", "sdvl_ctx_device", "sdvl_pointer_device", "sdvl_ctx_scratch_device",
     "sdvl_ctx_timing_enable", "sdvl_ctx_timing_only", "sdvl_ctx_timing_get", "sdvl_ctx_timing_reset",
     "sdvl_frame_create", "sdvl_frame_create_many", "sdvl_frame_destroy", "sdvl_frame_upload", "sdvl_frames_upload", "sdvl_ctx_prefetch_images", "sdvl_ctx_prefetch_fence", "sdvl_frame_set_image_device", "sdvl_frame_borrow_image_device",
-    "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_fast_cells",
+    "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
     "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
@@ -345,12 +345,15 @@ class Context:
         arr = (C.c_void_p * len(frames))(*[f.h for f in frames])
         self._check(self.lib.sdvl_frames_own_images(self.h, len(frames), arr))
 
-    def fast_cells(self, frames, dp, cap=16384):
-        """-> list of (keypoints[(x,y,score,level,cell)], cell_offsets) per frame"""
+    def fast_cells(self, frames, dp, cap=None):
+        """-> list of (keypoints[(x,y,score,level,cell)], cell_offsets) per frame.  cap = keypoints per frame; None: as many as
+        the cells can hold (cells x sdvl_cell_kp_cap) — a fixed default refused the denser grids of small cells"""
         n = len(frames)
         cpl = (C.c_int * 4)()
         tot = C.c_int()
         self._check(self.lib.sdvl_fast_num_cells(frames[0].width, frames[0].height, C.byref(dp), cpl, C.byref(tot)))
+        if cap is None:
+            cap = max(1, tot.value * self.lib.sdvl_cell_kp_cap(dp.cell_size))
         kps = (Keypoint * (n * cap))()
         offs = np.zeros((n, tot.value + 1), np.int32)
         arr = (C.c_void_p * n)(*[f.h for f in frames])

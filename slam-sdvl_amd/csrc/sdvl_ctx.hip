@@ -510,7 +510,7 @@ bool frame_layout(int width, int height, int levels, int corner_cap, FrameLayout
   off = align_up(off + static_cast<size_t>(32) * corner_cap, 256);
   L->bin_gw = (width + 31) / 32;
   const int cells = L->bin_gw * ((height + 31) / 32);
-  L->bin_cells = cells <= 4096 ? cells : 0;  // larger grids: no bins, the searches scan the list
+  L->bin_cells = cells <= 4096 ? cells : 0;  // larger grids (3840x2160: 8160 bins): no bins, the searches scan the list — same results
   L->bin_start_off = off;
   off = align_up(off + sizeof(int32_t) * (static_cast<size_t>(L->bin_cells) + 1), 256);
   L->bin_entries_off = off;

@@ -669,9 +669,72 @@ __global__ __launch_bounds__(64) void fast_cells_wave_kernel(const FastJob *__re
 #undef SDVL_MIN2
 #undef SDVL_MAX2
 
+// The wide-tile form for cells of 33 .. 64 px (fast_cells_wave_kernel's lane layout is cut for 32 x 32 ROIs).  One wave per cell as
+// there: the ROI as bytes in LDS (64 rows of 64 bytes), then one ROI row per pass with a lane per pixel: compass pre-test and
+// fast_corner_best into a byte score plane (0 = no corner, uchar like OpenCV's score buffer), a wave fence, and the strict 3x3
+// suppression row by row with ballot / mbcnt ranks — row-major, cv::FAST's scan order.  Every ring and every neighbour of a tested
+// pixel lies inside the ROI, so neither plane needs a border.  8 KB of LDS per cell.
+constexpr int kWideTile = SDVL_MAX_CELL_SIZE;
+constexpr int kWideCellCap = ((kWideTile - 5) / 2) * ((kWideTile - 5) / 2);  // sdvl_cell_kp_cap(64) = 29 * 29 = 841
+
+__global__ __launch_bounds__(64) void fast_cells_wide_kernel(const FastJob *__restrict__ jobs, FastLevels lv, const CellGeo *__restrict__ cells,
+                                                             int kp_cap) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_imgw[kWideTile * kWideTile / 4];
+  __shared__ __attribute__((aligned(16))) uint32_t s_scorew[kWideTile * kWideTile / 4];
+  const FastJob &job = jobs[blockIdx.y];
+  const int total_cells = lv.cell_begin[lv.n_levels];
+  const int gcell = static_cast<int>(blockIdx.x & ~31u) + static_cast<int>(blockIdx.x & 7u) * 4 + static_cast<int>((blockIdx.x >> 3) & 3u);
+  if (gcell >= total_cells) return;
+  const CellGeo geo = cells[gcell];
+  const int lane = threadIdx.x;
+  if ((geo.wh & 0xFFFFu) == 0u) {  // cell swallowed by the margin: cv::FAST is not called (fast_detector.cc:84-92)
+    if (lane == 0) job.cell_counts[gcell] = 0;
+    return;
+  }
+  const int l = geo.level & 0xFF;
+  const int W = job.lw[l];
+  const int x0 = static_cast<int>(geo.xy & 0xFFFFu), y0 = static_cast<int>(geo.xy >> 16);
+  const int rw = static_cast<int>(geo.wh & 0xFFFFu), rh = static_cast<int>(geo.wh >> 16);  // <= 64
+  const uint8_t *img = job.level[l] + static_cast<size_t>(y0) * W + x0;
+  uint8_t *s_img = reinterpret_cast<uint8_t *>(s_imgw);
+  uint8_t *s_score = reinterpret_cast<uint8_t *>(s_scorew);
+  const int t = lv.threshold;
+  for (int z = lane; z < kWideTile * kWideTile / 4; z += 64) s_scorew[z] = 0u;
+  if (lane < rw)
+    for (int r = 0; r < rh; r++) s_img[r * kWideTile + lane] = img[static_cast<size_t>(r) * W + lane];
+  fc_wave_sync();
+  const int x = lane;
+  const bool tested_col = x >= 3 && x < rw - 3;
+  for (int r = 3; r < rh - 3; r++) {
+    if (!tested_col) continue;
+    const uint8_t *p = s_img + r * kWideTile + x;
+    if (!fast_compass_pass(p[0], p[3 * kWideTile], p[3], p[-3 * kWideTile], p[-3], t)) continue;
+    const int best = fast_corner_best(p, kWideTile, t);
+    if (best > t) s_score[r * kWideTile + x] = static_cast<uint8_t>((best - 1) & 0xFF);
+  }
+  fc_wave_sync();
+  uint32_t *out = job.cell_kps + static_cast<size_t>(gcell) * kp_cap;
+  int base = 0;
+  for (int r = 3; r < rh - 3; r++) {
+    bool ok = false;
+    int sc = 0;
+    if (tested_col) {
+      const uint8_t *q = s_score + r * kWideTile + x;
+      constexpr int pb = kWideTile;
+      sc = q[0];
+      ok = sc > q[-1] && sc > q[1] && sc > q[-pb - 1] && sc > q[-pb] && sc > q[-pb + 1] && sc > q[pb - 1] && sc > q[pb] && sc > q[pb + 1];
+    }
+    const unsigned long long m = __ballot(ok);
+    const int pos = base + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0)));
+    if (ok && pos < kp_cap) out[pos] = static_cast<uint32_t>(x0 + x) | (static_cast<uint32_t>(y0 + r) << 12) | (static_cast<uint32_t>(sc) << 24);
+    base += __popcll(m);
+  }
+  if (lane == 0) job.cell_counts[gcell] = min(base, kp_cap);
+}
+
 // one workgroup per frame: exclusive scan of the cell counts, dense gather (cell-major, scan order inside a cell)
 __global__ __launch_bounds__(256) void compact_cells_kernel(const FastJob *__restrict__ jobs, int total_cells, int cap,
-                                                            uint32_t *__restrict__ out_kps, int32_t *__restrict__ out_offsets) {
+                                                            uint32_t *__restrict__ out_kps, int32_t *__restrict__ out_offsets, int cell_cap) {
   __shared__ int s_tot[4];
   __shared__ int s_carry;
   const FastJob job = jobs[blockIdx.x];
@@ -696,7 +759,7 @@ __global__ __launch_bounds__(256) void compact_cells_kernel(const FastJob *__res
     const int excl = base + incl - cnt;
     if (c < total_cells) {
       offs[c] = excl;
-      const uint32_t *src = job.cell_kps + static_cast<size_t>(c) * SDVL_CELL_KP_CAP;
+      const uint32_t *src = job.cell_kps + static_cast<size_t>(c) * cell_cap;
       for (int k = 0; k < cnt; k++)
         if (excl + k < cap) dst[excl + k] = src[k];
     }
@@ -852,8 +915,8 @@ __device__ __forceinline__ int sel_retain_best(uint32_t *v, int len, int n_point
   return len;
 }
 
-constexpr int kSelMaxCells = 2048;  // cells of one level
-constexpr int kSelFts = 4096;       // concatenated selection of one level before the final retainBest
+constexpr int kSelMaxCells = 2048;  // cells of one level in the select_cells form of the default sizes (SDVL_MAX_LEVEL_CELLS beyond)
+constexpr int kSelFts = 4096;       // concatenated selection of one level before the final retainBest (the least spill area per level)
 
 // Round 3: the selection is two launches of NARROW workgroups instead of one 1024-thread workgroup per (frame, level) that held
 // 128 KB of LDS (a whole CU's worth: among the other streams' kernels it waited for a CU to drain, 104 us alone -> 460 us):
@@ -870,13 +933,16 @@ struct SelLevels {
   int not_run[4];      // cells of the level whose ROI the margin swallows: cv::FAST is not called there (fast_detector.cc:84-94)
   int slice_begin[5];  // select_cells: first 8-cell slice of each level among the slices of one frame
   int fts_cap[4];      // select_pack: LDS entries for each level's concatenated list (longer lists go through HBM)
+  int spill_cap[4];    // select_pack: entries of each level's spill area (>= kSelFts; a longer list is a capacity error)
+  int spill_off[4];    // select_pack: word offset of each level's spill area (list + stopper lists: 2 * spill_cap words)
+  int kp_stride;       // entries of one cell's list in the detection scratch (sdvl_cell_kp_cap)
 };
 
 struct SelJob {
   uint32_t *cell_kps;          // detection scratch of the frame's batch slot: per-cell lists, rewritten in place by select_cells
   const int32_t *cell_counts;
   int32_t *cell_newlen;        // [total_cells] length of every cell's list after its retainBest
-  uint32_t *spill;             // [n_levels][2 * kSelFts] words: a level's list + stopper lists when they outgrow the LDS share
+  uint32_t *spill;             // per level 2 * spill_cap words (SelLevels::spill_off): a level's list + stopper lists when they outgrow the LDS share
   int32_t *corner_hdr;         // {count,0,0,0} + corners
   int lw[4], lh[4];
   int32_t *bin_start;          // [bin_cells + 1]
@@ -1183,8 +1249,9 @@ __device__ __forceinline__ int sel_wave_sum(int v) {
 // The quota loop of FastDetector::SelectPixels (fast_detector.cc:108-135) for one level, by one wave.  Every pass hands each cell that
 // still has keypoints left min(left, npercell) more, so after any pass a cell holds min(count, S) with S = the npercell values summed
 // so far, and the loop's two running sums are sum(min(count, S)) and #(count > S): ONE number per level describes the outcome for
-// every cell.  Returns S; cnt = the level's cell counts (bytes, LDS).
-__device__ __forceinline__ int sel_level_quota(const uint8_t *cnt, int ncells, int cells_left, int nfeatures, int lane) {
+// every cell.  Returns S; cnt = the level's cell counts (LDS: bytes, 16-bit words for the wide cells' longer lists).
+template <typename CNT>
+__device__ __forceinline__ int sel_level_quota(const CNT *cnt, int ncells, int cells_left, int nfeatures, int lane) {
   int S = 0, selected = 0;
   while ((nfeatures - selected) > 0 && cells_left > 0) {
     const int rem = nfeatures - selected;
@@ -1201,13 +1268,19 @@ __device__ __forceinline__ int sel_level_quota(const uint8_t *cnt, int ncells, i
   return S;
 }
 
-// one wave per (frame, level, 8 consecutive cells): per-cell retainBest, fast_detector.cc:138-145.  The surviving list replaces the
-// head of the cell's list in the detection scratch, its length goes to cell_newlen.
+// one wave per (frame, level, 64 / G consecutive cells): per-cell retainBest, fast_detector.cc:138-145.  The surviving list replaces the
+// head of the cell's list in the detection scratch, its length goes to cell_newlen.  Forms: <uint8_t, SDVL_CELL_KP_CAP, 2048, 8> for
+// cells <= 32 px and levels of <= 2048 cells (11 KB of LDS); the same with 8192 cells (larger frames: 19 KB); <uint16_t, 841, 8192, 64>
+// for cells of 33 .. 64 px, whose lists (<= sdvl_cell_kp_cap) outgrow byte positions: one cell per wave, 23 KB.
+template <typename CNT, int kCap, int kMaxCells, int G>
 __global__ __launch_bounds__(64) void select_cells_kernel(const SelJob *__restrict__ jobs, SelLevels lv, int n_frames) {
-  __shared__ uint8_t s_cnt[kSelMaxCells];
-  __shared__ uint32_t s_list[kSelCellsPerWave][SDVL_CELL_KP_CAP];
-  __shared__ uint8_t s_glr[kSelCellsPerWave][2 * SDVL_CELL_KP_CAP];  // stopper lists of the lane groups
-  static_assert(SDVL_CELL_KP_CAP <= 255, "cell positions and counts are stored in a byte");
+  constexpr int kCellsPerWave = 64 / G;
+  __shared__ CNT s_cnt[kMaxCells];
+  __shared__ uint32_t s_list[kCellsPerWave][kCap];
+  __shared__ CNT s_glr[kCellsPerWave][2 * kCap];  // stopper lists of the lane groups
+  static_assert(kCap <= static_cast<int>(static_cast<CNT>(~0u)), "cell positions and counts must fit the count type");
+  // the list stride of the detection scratch: a constant in the form of the cells <= 32 px
+  const int stride = kCap == SDVL_CELL_KP_CAP ? SDVL_CELL_KP_CAP : lv.kp_stride;
   // blocks b and b + 8 share an XCD (observed placement, used for speed only): all waves of a frame run on one, so the level's count
   // array and the neighbouring cells' lists come out of one L2
   const int slices = lv.slice_begin[lv.n_levels];
@@ -1224,27 +1297,27 @@ __global__ __launch_bounds__(64) void select_cells_kernel(const SelJob *__restri
   int zeros = 0;
   for (int c = lane; c < ncells; c += 64) {
     const int n = job.cell_counts[cbeg + c];
-    s_cnt[c] = static_cast<uint8_t>(n);
+    s_cnt[c] = static_cast<CNT>(n);
     zeros += n == 0 ? 1 : 0;
   }
   const int nempty = sel_wave_sum(zeros) - lv.not_run[l];
   sel_wave_sync();
-  const int S = sel_level_quota(s_cnt, ncells, ncells - nempty, lv.quota[l], lane);
-  // ---- kSelGroup lanes per cell
-  const int g = lane / kSelGroup, sub = lane % kSelGroup, shift = lane - sub;
-  const int c = (s - lv.slice_begin[l]) * kSelCellsPerWave + g;
+  const int S = sel_level_quota<CNT>(s_cnt, ncells, ncells - nempty, lv.quota[l], lane);
+  // ---- G lanes per cell
+  const int g = lane / G, sub = lane % G, shift = lane - sub;
+  const int c = (s - lv.slice_begin[l]) * kCellsPerWave + g;
   if (c >= ncells) return;
   const int cnt = s_cnt[c];
   const int nsel = min(cnt, S);
   int nl = cnt;
   if (cnt > nsel) {
-    uint32_t *list = job.cell_kps + static_cast<size_t>(cbeg + c) * SDVL_CELL_KP_CAP;
+    uint32_t *list = job.cell_kps + static_cast<size_t>(cbeg + c) * stride;
     uint32_t *v = s_list[g];
-    for (int k = sub; k < cnt; k += kSelGroup) v[k] = list[k];
+    for (int k = sub; k < cnt; k += G) v[k] = list[k];
     sel_wave_sync();
-    nl = group_retain_best<kSelGroup, uint8_t>(v, cnt, nsel, s_glr[g], s_glr[g] + cnt, sub, shift);
+    nl = group_retain_best<G, CNT>(v, cnt, nsel, s_glr[g], s_glr[g] + cnt, sub, shift);
     sel_wave_sync();
-    for (int k = sub; k < nl; k += kSelGroup) list[k] = v[k];
+    for (int k = sub; k < nl; k += G) list[k] = v[k];
   }
   if (sub == 0) job.cell_newlen[cbeg + c] = nl;
 }
@@ -1286,16 +1359,16 @@ __global__ __launch_bounds__(256) void select_pack_kernel(const SelJob *__restri
     }
     const int nfts = __shfl(incl, 63, 64);
     int dst = incl - mine;
-    int n = -1;  // a level of more than kSelFts candidates: reported as a capacity error, as before
-    if (nfts <= kSelFts) {
+    int n = -1;  // a level of more candidates than its spill area holds: reported as a capacity error
+    if (nfts <= lv.spill_cap[l]) {
       const bool fits = nfts <= lv.fts_cap[l];
-      uint32_t *spill = job.spill + static_cast<size_t>(l) * 2 * kSelFts;
+      uint32_t *spill = job.spill + lv.spill_off[l];
       // the gather: every lane copies the heads of its cells' lists
       if (fits) {
         uint32_t *v = lists[l];
         for (int c = c_lo; c < c_hi; c++) {
           const int len = job.cell_newlen[cbeg + c];
-          const uint32_t *src = job.cell_kps + static_cast<size_t>(cbeg + c) * SDVL_CELL_KP_CAP;
+          const uint32_t *src = job.cell_kps + static_cast<size_t>(cbeg + c) * lv.kp_stride;
           for (int k = 0; k < len; k++) v[dst++] = src[k];
         }
         sel_wave_sync();
@@ -1308,14 +1381,14 @@ __global__ __launch_bounds__(256) void select_pack_kernel(const SelJob *__restri
         uint32_t *v = spill;
         for (int c = c_lo; c < c_hi; c++) {
           const int len = job.cell_newlen[cbeg + c];
-          const uint32_t *src = job.cell_kps + static_cast<size_t>(cbeg + c) * SDVL_CELL_KP_CAP;
+          const uint32_t *src = job.cell_kps + static_cast<size_t>(cbeg + c) * lv.kp_stride;
           for (int k = 0; k < len; k++) v[dst++] = src[k];
         }
         sel_wave_sync();
         n = nfts;
         if (nfts > lv.quota[l]) {
-          uint16_t *Ls = reinterpret_cast<uint16_t *>(v + kSelFts);
-          n = group_retain_best<64, uint16_t>(v, nfts, lv.quota[l], Ls, Ls + kSelFts, lane, 0);
+          uint16_t *Ls = reinterpret_cast<uint16_t *>(v + lv.spill_cap[l]);  // (spill_cap <= 65536: positions fit 16 bits)
+          n = group_retain_best<64, uint16_t>(v, nfts, lv.quota[l], Ls, Ls + lv.spill_cap[l], lane, 0);
         }
         sel_wave_sync();
       }
@@ -1333,7 +1406,7 @@ __global__ __launch_bounds__(256) void select_pack_kernel(const SelJob *__restri
   for (int l = 0; l < lv.n_levels; l++) {
     const int raw = s_n[l];
     if (raw < 0) { bad = true; lvl_off[l + 1] = lvl_off[l]; continue; }
-    if (raw & 0x40000000) lists[l] = job.spill + static_cast<size_t>(l) * 2 * kSelFts;
+    if (raw & 0x40000000) lists[l] = job.spill + lv.spill_off[l];
     lvl_off[l + 1] = lvl_off[l] + (raw & 0x3FFFFFFF);
   }
   if (lvl_off[lv.n_levels] > job.corner_cap) bad = true;
@@ -1503,17 +1576,22 @@ int sdvl_fast_num_cells(int width, int height, const sdvl_detect_params *p, int 
 struct DetectSlot {
   size_t counts_off, newlen_off, kps_off, spill_off, bytes;
 };
-static DetectSlot detect_slot_layout(int total_cells, int n_levels) {
+// kp_cap entries per cell list; spill_words for the spill areas of all levels together
+static DetectSlot detect_slot_layout(int total_cells, int kp_cap, size_t spill_words) {
   DetectSlot L;
   size_t off = 0;
   const auto take = [&off](size_t bytes) { const size_t at = off; off = (off + bytes + 255) / 256 * 256; return at; };
   L.counts_off = take(sizeof(int32_t) * (static_cast<size_t>(total_cells) + 1));
   L.newlen_off = take(sizeof(int32_t) * static_cast<size_t>(total_cells));
-  L.kps_off = take(sizeof(uint32_t) * SDVL_CELL_KP_CAP * static_cast<size_t>(total_cells));
-  L.spill_off = take(sizeof(uint32_t) * 2 * kSelFts * static_cast<size_t>(n_levels));
+  L.kps_off = take(sizeof(uint32_t) * static_cast<size_t>(kp_cap) * static_cast<size_t>(total_cells));
+  L.spill_off = take(sizeof(uint32_t) * spill_words);
   L.bytes = off;
   return L;
 }
+
+// entries of a level's spill area: kSelFts as ever for levels of up to 512 cells; beyond, eight per cell (a level's list holds about
+// quota + cells entries, ties on top), at most 65536 so that the stopper lists keep 16-bit positions
+static int sel_spill_cap(int ncells) { return std::max(kSelFts, std::min(65536, (8 * ncells + 63) / 64 * 64)); }
 static int detect_scratch(sdvl_ctx *ctx, int n, const DetectSlot &L, uint8_t **base) {
   const int rc = sdvl_ensure(ctx, &ctx->d_detect, &ctx->d_detect_bytes, L.bytes * static_cast<size_t>(n), false);
   if (rc) return rc;
@@ -1521,10 +1599,21 @@ static int detect_scratch(sdvl_ctx *ctx, int n, const DetectSlot &L, uint8_t **b
   return SDVL_OK;
 }
 
+int sdvl_cell_kp_cap(int cell_size) {
+  if (cell_size < 8 || cell_size > SDVL_MAX_CELL_SIZE) return 0;
+  if (cell_size <= 32) return SDVL_CELL_KP_CAP;
+  const int half = (cell_size - 6 + 1) / 2;  // tested pixels per row, every second one at most survives the suppression
+  return half * half;
+}
+
 int64_t sdvl_detect_scratch_bytes(int width, int height, const sdvl_detect_params *p) {
-  int total = 0;
-  if (sdvl_fast_num_cells(width, height, p, nullptr, &total) != SDVL_OK) return -1;
-  return static_cast<int64_t>(detect_slot_layout(total, p->max_fast_levels).bytes);
+  int total = 0, per_level[4] = {0, 0, 0, 0};
+  if (sdvl_fast_num_cells(width, height, p, per_level, &total) != SDVL_OK) return -1;
+  const int kp_cap = sdvl_cell_kp_cap(p->cell_size);
+  if (kp_cap == 0) return -1;
+  size_t spill_words = 0;
+  for (int l = 0; l < p->max_fast_levels; l++) spill_words += 2 * static_cast<size_t>(sel_spill_cap(per_level[l]));
+  return static_cast<int64_t>(detect_slot_layout(total, kp_cap, spill_words).bytes);
 }
 
 // the share (of 64) of a cell's probed pixels that must pass the compass test for the cell to take the dense path
@@ -1591,9 +1680,10 @@ int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_
                     sdvl_keypoint *out_kps, int32_t *out_cell_offsets) {
   if (!ctx || !p || n < 0 || (n > 0 && (!frames || !out_kps || !out_cell_offsets))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= kTile, "cell_size must be in [8,32]");
+  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= SDVL_MAX_CELL_SIZE, "cell_size must be in [8,64]");
   SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "max_fast_levels must be in [1,4]");
   SDVL_REQUIRE(ctx, p->margin >= 0 && cap > 0, "bad margin / capacity");
+  const int kp_cap = sdvl_cell_kp_cap(p->cell_size);
   const int W = frames[0]->width, H = frames[0]->height;
   FastLevels lv;
   memset(&lv, 0, sizeof(lv));
@@ -1608,13 +1698,15 @@ int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_
     const int w = frames[0]->v.lw[l], h = frames[0]->v.lh[l];
     lv.cell_begin[l] = total_cells;
     lv.wcells[l] = (w + p->cell_size - 1) / p->cell_size;
-    total_cells += lv.wcells[l] * ((h + p->cell_size - 1) / p->cell_size);
+    const int ncells = lv.wcells[l] * ((h + p->cell_size - 1) / p->cell_size);
+    SDVL_REQUIRE(ctx, ncells <= SDVL_MAX_LEVEL_CELLS, "too many cells in one level (8192: at most 3840x2160 at cell 32)");  // (sdvl_keypoint::cell is 16-bit)
+    total_cells += ncells;
   }
   lv.cell_begin[lv.n_levels] = total_cells;
   for (int i = 0; i < n; i++)
     SDVL_REQUIRE(ctx, frames[i] && frames[i]->width == W && frames[i]->height == H && frames[i]->v.levels == frames[0]->v.levels,
                  "frames of one batch must share size and pyramid depth");
-  const DetectSlot slot = detect_slot_layout(total_cells, lv.n_levels);
+  const DetectSlot slot = detect_slot_layout(total_cells, kp_cap, 2 * kSelFts * static_cast<size_t>(lv.n_levels));  // (no selection here)
   uint8_t *scratch = nullptr;
   {
     const int rc_s = detect_scratch(ctx, n, slot, &scratch);
@@ -1647,8 +1739,12 @@ int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_
     const int rc_t = fast_cell_table(ctx, lv, frames[0], &d_cells);
     if (rc_t) return rc_t;
   }
-  SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), static_cast<const FastJob *>(dsx), lv, d_cells);
-  SDVL_LAUNCH(ctx, "compact_cells", compact_cells_kernel, dim3(n), dim3(256), static_cast<const FastJob *>(dsx), total_cells, cap, d_kps, d_offs);
+  if (lv.cell_size <= kTile)
+    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), static_cast<const FastJob *>(dsx), lv, d_cells);
+  else
+    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wide_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), static_cast<const FastJob *>(dsx), lv, d_cells,
+                kp_cap);
+  SDVL_LAUNCH(ctx, "compact_cells", compact_cells_kernel, dim3(n), dim3(256), static_cast<const FastJob *>(dsx), total_cells, cap, d_kps, d_offs, kp_cap);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   int32_t *h_offs = static_cast<int32_t *>(ctx->h_out);
   uint32_t *h_kps = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->h_out) + offs_bytes);
@@ -1694,9 +1790,10 @@ int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_
 int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_detect_params *p, int nfeatures) {
   if (!ctx || !p || n < 0 || (n > 0 && !frames)) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= kTile, "cell_size must be in [8,32]");
+  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= SDVL_MAX_CELL_SIZE, "cell_size must be in [8,64]");
   SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "max_fast_levels must be in [1,4]");
   SDVL_REQUIRE(ctx, p->margin >= 0 && nfeatures >= 0, "bad margin / nfeatures");
+  const int kp_cap = sdvl_cell_kp_cap(p->cell_size);
   const int W = frames[0]->width, H = frames[0]->height;
   FastLevels lv;
   SelLevels sl;
@@ -1713,7 +1810,13 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
   for (int i = 0; i < p->max_fast_levels; i++) { val += factor; factor /= scale; }
   int levelfeatures = static_cast<int>(nfeatures / val);
   int total_cells = 0, n_slices = 0;
-  size_t pack_lds = 0;
+  size_t pack_lds = 0, spill_words = 0;
+  sl.kp_stride = kp_cap;
+  // the select_cells form: level 0 is the largest level
+  const int cells0 = ((frames[0]->v.lw[0] + p->cell_size - 1) / p->cell_size) * ((frames[0]->v.lh[0] + p->cell_size - 1) / p->cell_size);
+  SDVL_REQUIRE(ctx, cells0 <= SDVL_MAX_LEVEL_CELLS, "too many cells in one level for the selection kernel (8192: at most 3840x2160 at cell 32)");
+  const int sel_form = p->cell_size > kTile ? 2 : (cells0 > kSelMaxCells ? 1 : 0);
+  const int sel_cells_per_wave = sel_form == 2 ? 1 : kSelCellsPerWave;
   for (int l = 0; l < lv.n_levels; l++) {
     SDVL_REQUIRE(ctx, l < frames[0]->v.levels, "max_fast_levels exceeds the pyramid depth");
     const int w = frames[0]->v.lw[l], h = frames[0]->v.lh[l];
@@ -1721,7 +1824,6 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
     lv.wcells[l] = sl.wcells[l] = (w + p->cell_size - 1) / p->cell_size;
     sl.hcells[l] = (h + p->cell_size - 1) / p->cell_size;
     const int ncells = sl.wcells[l] * sl.hcells[l];
-    SDVL_REQUIRE(ctx, ncells <= kSelMaxCells, "too many cells in one level for the selection kernel");
     total_cells += ncells;
     sl.quota[l] = levelfeatures;
     levelfeatures = static_cast<int>(levelfeatures / scale);
@@ -1735,18 +1837,21 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
       }
     sl.not_run[l] = not_run;
     sl.slice_begin[l] = n_slices;
-    n_slices += (ncells + kSelCellsPerWave - 1) / kSelCellsPerWave;
+    n_slices += (ncells + sel_cells_per_wave - 1) / sel_cells_per_wave;
     // LDS entries of the level's concatenated list in select_pack: the quota loop selects < quota + cells, ties that the per-cell
     // retainBest keeps come on top (half as many again; a longer list is worked on in HBM)
     sl.fts_cap[l] = std::min(kSelFts, ((sl.quota[l] + ncells) * 3 / 2 + 63) / 64 * 64);
     pack_lds += static_cast<size_t>(sl.fts_cap[l]) * 8;
+    sl.spill_cap[l] = sel_spill_cap(ncells);
+    sl.spill_off[l] = static_cast<int>(spill_words);
+    spill_words += 2 * static_cast<size_t>(sl.spill_cap[l]);
   }
   lv.cell_begin[lv.n_levels] = sl.cell_begin[sl.n_levels] = total_cells;
   sl.slice_begin[sl.n_levels] = n_slices;
   for (int i = 0; i < n; i++)
     SDVL_REQUIRE(ctx, frames[i] && frames[i]->width == W && frames[i]->height == H && frames[i]->v.levels == frames[0]->v.levels,
                  "frames of one batch must share size and pyramid depth");
-  const DetectSlot slot = detect_slot_layout(total_cells, lv.n_levels);
+  const DetectSlot slot = detect_slot_layout(total_cells, kp_cap, spill_words);
   uint8_t *scratch = nullptr;
   {
     const int rc_s = detect_scratch(ctx, n, slot, &scratch);
@@ -1794,8 +1899,17 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
     const int rc_t = fast_cell_table(ctx, lv, frames[0], &d_cells);
     if (rc_t) return rc_t;
   }
-  SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), df, lv, d_cells);
-  SDVL_LAUNCH(ctx, "select_cells", select_cells_kernel, dim3(static_cast<unsigned>((n + 7) / 8 * 8 * n_slices)), dim3(64), ds, sl, n);
+  const dim3 sel_grid(static_cast<unsigned>((n + 7) / 8 * 8 * n_slices));
+  if (sel_form == 2) {
+    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wide_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), df, lv, d_cells, kp_cap);
+    SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint16_t, kWideCellCap, SDVL_MAX_LEVEL_CELLS, 64>), sel_grid, dim3(64), ds, sl, n);
+  } else {
+    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), df, lv, d_cells);
+    if (sel_form == 0)
+      SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint8_t, SDVL_CELL_KP_CAP, kSelMaxCells, kSelGroup>), sel_grid, dim3(64), ds, sl, n);
+    else
+      SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint8_t, SDVL_CELL_KP_CAP, SDVL_MAX_LEVEL_CELLS, kSelGroup>), sel_grid, dim3(64), ds, sl, n);
+  }
   // the counts follow the kernels to the host without anyone waiting for them (see sdvl_frames_corner_counts): the pack kernel
   // writes them into device memory and, when results go direct, into the pinned host array as well
   const bool direct = sdvl_ensure(ctx, &ctx->h_counts, &ctx->h_counts_bytes, sizeof(int32_t) * n, true) == SDVL_OK;

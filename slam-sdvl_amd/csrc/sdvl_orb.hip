@@ -231,14 +231,17 @@ __global__ __launch_bounds__(256) void filter_select_kernel(const FilterJob *__r
 // Round 6: two sizes.  The arrays are static LDS: 60 KB when they are cut for configuration C's 1200 cells and 6144 corners — a
 // workgroup that has to find 60 KB free on one compute unit among the other streams' kernels (fast_cells alone fills 150 of a CU's
 // 160 KB) waits: 132 us per dispatch in the farm against 15 alone.  The metric configuration's 300 cells and ~1000 corners take 16 KB.
+// Beyond the unbinned form's 4096 cells (3840x2160 at cell 32: 8160) a fourth size keeps four slots per cell: such grids hold
+// well under one corner per cell on average, a fuller cell takes the scan as above.  108 KB of LDS, one workgroup per frame.
 constexpr int kBinCells = 2048, kBinSlots = 10;
 constexpr int kBinCellsSmall = 512, kBinCornersSmall = 2048;
+constexpr int kBinCellsLarge = SDVL_MAX_LEVEL_CELLS, kBinSlotsLarge = 4;
 
-template <int kCells, int kCorners>
+template <int kCells, int kCorners, int kSlots = kBinSlots>
 __global__ __launch_bounds__(256) void filter_select_binned_kernel(const FilterJob *__restrict__ jobs, int cell_size, int grid_w, int n_cells,
                                                                    int margin, int min_score, int max_out) {
   __shared__ uint16_t s_cell[kCorners];
-  __shared__ uint16_t s_list[kCells * kBinSlots];
+  __shared__ uint16_t s_list[kCells * kSlots];
   __shared__ int s_cnt[kCells];  // corners of the cell; afterwards the chosen corner or -1
   __shared__ int s_wave[4];
   const FilterJob &job = jobs[blockIdx.x];
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(256) void filter_select_binned_kernel(const FilterJ
       if (pos >= 0 && pos < n_cells && !((job.locked[pos >> 5] >> (pos & 31)) & 1u)) {
         c = static_cast<uint16_t>(pos);
         const int slot = atomicAdd(&s_cnt[pos], 1);
-        if (slot < kBinSlots) s_list[pos * kBinSlots + slot] = static_cast<uint16_t>(i);
+        if (slot < kSlots) s_list[pos * kSlots + slot] = static_cast<uint16_t>(i);
       }
     }
     s_cell[i] = c;
@@ -264,21 +267,21 @@ __global__ __launch_bounds__(256) void filter_select_binned_kernel(const FilterJ
   for (int c = tid; c < n_cells; c += 256) {
     const int cnt = s_cnt[c];
     int best_idx = 0, best = min_score;  // cgrid_ starts as (0, MinFeatureScore), fast_detector.cc:40
-    if (cnt <= kBinSlots) {
-      int idx[kBinSlots];
+    if (cnt <= kSlots) {
+      int idx[kSlots];
 #pragma unroll
-      for (int q = 0; q < kBinSlots; q++) idx[q] = q < cnt ? s_list[c * kBinSlots + q] : 0x7FFFFFFF;
+      for (int q = 0; q < kSlots; q++) idx[q] = q < cnt ? s_list[c * kSlots + q] : 0x7FFFFFFF;
       // list order = ascending corner index: a fixed compare-exchange network over the (at most 10) entries
 #pragma unroll
-      for (int a = 0; a < kBinSlots; a++)
+      for (int a = 0; a < kSlots; a++)
 #pragma unroll
-        for (int b = 0; b + 1 < kBinSlots - a; b++) {
+        for (int b = 0; b + 1 < kSlots - a; b++) {
           const int lo = min(idx[b], idx[b + 1]), hi = max(idx[b], idx[b + 1]);
           idx[b] = lo;
           idx[b + 1] = hi;
         }
 #pragma unroll
-      for (int q = 0; q < kBinSlots; q++) {
+      for (int q = 0; q < kSlots; q++) {
         if (q >= cnt) break;
         const double score = job.scores[idx[q]];
         if (score > best) {
@@ -611,7 +614,7 @@ int sdvl_filter_corners_begin(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, c
   (void)with_desc;  // descriptors of the selected corners always ride along (32 B each)
   const int W = frames[0]->width, H = frames[0]->height;
   const int grid_w = (W + cell_size - 1) / cell_size, grid_h = (H + cell_size - 1) / cell_size, n_cells = grid_w * grid_h;
-  SDVL_REQUIRE(ctx, n_cells <= 4096 && n_cells <= mask_words * 32, "filter grid too large (4096 cells) or lock mask too short");
+  SDVL_REQUIRE(ctx, n_cells <= kBinCellsLarge && n_cells <= mask_words * 32, "filter grid too large (8192 cells) or lock mask too short");
   int ccap = 1;
   for (int i = 0; i < n; i++) {
     SDVL_REQUIRE(ctx, frames[i] && frames[i]->width == W && frames[i]->height == H, "frames of one batch must share their size");
@@ -658,9 +661,12 @@ int sdvl_filter_corners_begin(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, c
   else if (n_cells <= kBinCells)
     SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCells, kFilterMaxCorners>), dim3(n), dim3(256), static_cast<const FilterJob *>(dsx),
                 cell_size, grid_w, n_cells, margin, min_feature_score, max_out);
-  else
+  else if (n_cells <= 4096)
     SDVL_LAUNCH(ctx, "filter_select", filter_select_kernel, dim3(n), dim3(256), static_cast<const FilterJob *>(dsx), cell_size, grid_w, n_cells, margin,
                 min_feature_score, max_out);
+  else
+    SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCellsLarge, kFilterMaxCorners, kBinSlotsLarge>), dim3(n), dim3(256),
+                static_cast<const FilterJob *>(dsx), cell_size, grid_w, n_cells, margin, min_feature_score, max_out);
   SDVL_LAUNCH(ctx, "filter_describe", filter_describe_kernel, xcd_frame_grid(n, std::min(max_out, 512)), dim3(64), static_cast<const FilterJob *>(dsx),
               max_out, n, std::min(max_out, 512));
   SDVL_HIP_CHECK(ctx, hipGetLastError());

@@ -60,7 +60,8 @@ struct SearchPrep {
   int bin_e0[4], bin_pre[4];  // bin_pre[r] = entries of the rows before r + 1 (bin_pre[3] = all of them)
 };
 
-// search regions of up to this many 32-px cells go through the corner bins (their corners: ~3.4 per cell); larger ones scan the whole list
+// search regions of up to this many 32-px cells go through the corner bins (their corners: ~3.4 per cell); larger ones scan the whole list.
+// The bins are 32-px cells of level 0 whatever SDVL.cell_size is; frames of more than 4096 bins have none (sdvl_ctx.hip frame_layout)
 constexpr int kBinRegionCells = 320;
 
 struct ChainFrameDev {

@@ -134,6 +134,7 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
   __syncthreads();
   const Rigid pose = se3_from7(s_pose);
   const M3 R = se3_rot(pose);
+  // the FeatureAlign grid: cell ranks are 16-bit (sdvl_track_create: <= 65535 cells); 3840x2160 at cell 32 has 8160, at 8 px 130 k are refused there
   const int gw = static_cast<int>(ceil(cam.width / cell_size));
   for (int i = tid; i < n_feat; i += static_cast<int>(blockDim.x)) {
     unsigned long long key = ~0ull;

@@ -31,15 +31,52 @@ struct UndistParams {
   int w, h, sstride, dstride;
 };
 
-constexpr int kMapMax = 2044;  // integer parts are stored with 11 bits each (clamped to [-2, size], + 2)
+constexpr int kMapMax = 2044;      // the packed map: integer parts are stored with 11 bits each (clamped to [-2, size], + 2)
+constexpr int kMapMaxWide = 4095;  // the wide map (frames with a side above 2044, up to the frames' own limit): 16 bits each
 
 // map word: a | b << 5 | (clamp(sx, -2, W) + 2) << 10 | (clamp(sy, -2, H) + 2) << 21.  sx <= -2 or sx >= W (likewise sy) puts all four
-// taps outside the image, so the clamp loses nothing.  Row pitch = W rounded up to 4 words; the padding says "outside".
+// taps outside the image, so the clamp loses nothing.  Row pitch = W rounded up to 4 pixels; the padding says "outside".
+// The wide map (kWideMap) keeps two words per pixel: a | b << 5, then (clamp(sx, -2, W) + 2) | (clamp(sy, -2, H) + 2) << 16.
+template <bool kWideMap>
+__device__ __forceinline__ void map_store(uint32_t *map, size_t px, uint32_t a, uint32_t b, uint32_t sxc, uint32_t syc) {
+  if (kWideMap)
+    *reinterpret_cast<uint2 *>(map + 2 * px) = make_uint2(a | b << 5, sxc | syc << 16);
+  else
+    map[px] = a | b << 5 | sxc << 10 | syc << 21;
+}
+
+// the entries of four adjacent pixels (px a multiple of 4): fractions and source positions (sx, sy), -2 .. size
+template <bool kWideMap>
+__device__ __forceinline__ void map_load4(const uint32_t *map, size_t px, uint32_t a[4], uint32_t b[4], int sx[4], int sy[4]) {
+  if (kWideMap) {
+    const uint4 w01 = *reinterpret_cast<const uint4 *>(map + 2 * px), w23 = *reinterpret_cast<const uint4 *>(map + 2 * px + 4);
+    const uint32_t lo[4] = {w01.x, w01.z, w23.x, w23.z}, hi[4] = {w01.y, w01.w, w23.y, w23.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      a[k] = lo[k] & 31u;
+      b[k] = (lo[k] >> 5) & 31u;
+      sx[k] = static_cast<int>(hi[k] & 0xFFFFu) - 2;
+      sy[k] = static_cast<int>(hi[k] >> 16) - 2;
+    }
+  } else {
+    const uint4 words = *reinterpret_cast<const uint4 *>(map + px);
+    const uint32_t wd[4] = {words.x, words.y, words.z, words.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      a[k] = wd[k] & 31u;
+      b[k] = (wd[k] >> 5) & 31u;
+      sx[k] = static_cast<int>((wd[k] >> 10) & 2047u) - 2;
+      sy[k] = static_cast<int>(wd[k] >> 21) - 2;
+    }
+  }
+}
+
+template <bool kWideMap>
 __global__ __launch_bounds__(256) void undistort_map_kernel(const double *__restrict__ xw, const double *__restrict__ yw, UndistParams P, int pitch,
                                                             uint32_t *__restrict__ map) {
   const int j = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
   if (j >= pitch) return;
-  uint32_t word = 0;  // sx = sy = -2: outside
+  uint32_t fa = 0, fb = 0, sxc = 0, syc = 0;  // sx = sy = -2: outside
   if (j < P.w) {
     const double x = xw[j], y = yw[r];
     const double x2 = x * x, y2 = y * y;
@@ -50,11 +87,12 @@ __global__ __launch_bounds__(256) void undistort_map_kernel(const double *__rest
     const double v = P.fy * (y * kr + P.p1 * (r2 + 2 * y2) + P.p2 * _2xy) + P.v0;
     const int iu = __double2int_rn(u * 32), iv = __double2int_rn(v * 32);  // cvRound = round half to even
     const int sx = static_cast<short>(iu >> 5), sy = static_cast<short>(iv >> 5);
-    const int a = iu & 31, b = iv & 31;
-    const int sxc = min(max(sx, -2), P.w) + 2, syc = min(max(sy, -2), P.h) + 2;
-    word = static_cast<uint32_t>(a) | static_cast<uint32_t>(b) << 5 | static_cast<uint32_t>(sxc) << 10 | static_cast<uint32_t>(syc) << 21;
+    fa = static_cast<uint32_t>(iu & 31);
+    fb = static_cast<uint32_t>(iv & 31);
+    sxc = static_cast<uint32_t>(min(max(sx, -2), P.w) + 2);
+    syc = static_cast<uint32_t>(min(max(sy, -2), P.h) + 2);
   }
-  map[static_cast<size_t>(r) * pitch + j] = word;
+  map_store<kWideMap>(map, static_cast<size_t>(r) * pitch + j, fa, fb, sxc, syc);
 }
 
 // The remap proper works on QUADS of adjacent output pixels.  The map moves by about a pixel per pixel, so the source pixels of a quad
@@ -79,21 +117,20 @@ struct QuadRec {
   uint32_t b;    // [0:20) b x 4, [20:24) valid bits of pixel 3
 };
 
+template <bool kWideMap>
 __global__ __launch_bounds__(256) void undistort_quad_kernel(const uint32_t *__restrict__ map, int pitch, UndistParams P, QuadRec *__restrict__ quads) {
   const int qx = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, nq = pitch / 4;
   if (qx >= nq) return;
-  const uint4 words = *reinterpret_cast<const uint4 *>(map + static_cast<size_t>(r) * pitch + 4 * qx);
-  const uint32_t wd[4] = {words.x, words.y, words.z, words.w};
   const int W = P.w, H = P.h, ss = P.sstride;
   int sx[4], sy[4];
+  uint32_t fa[4], fb[4];
+  map_load4<kWideMap>(map, static_cast<size_t>(r) * pitch + 4 * qx, fa, fb, sx, sy);
   uint32_t valid = 0, qa = 0, qb = 0;
   int xlo = 1 << 20, xhi = -(1 << 20), y0 = 1 << 20, y1 = -(1 << 20);
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    sx[k] = static_cast<int>((wd[k] >> 10) & 2047u) - 2;
-    sy[k] = static_cast<int>(wd[k] >> 21) - 2;
-    qa |= (wd[k] & 31u) << (5 * k);
-    qb |= ((wd[k] >> 5) & 31u) << (5 * k);
+    qa |= fa[k] << (5 * k);
+    qb |= fb[k] << (5 * k);
     bool live = false;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -221,6 +258,7 @@ __device__ __forceinline__ void remap_compact(const UndistJob *__restrict__ jobs
   }
 }
 
+template <bool kWideMap>
 __global__ __launch_bounds__(256) void undistort_remap_kernel(const UndistJob *__restrict__ jobs, const uint32_t *__restrict__ map,
                                                               const QuadRec *__restrict__ quads, int pitch, int n, int wide, UndistParams P) {
   // Workgroups are dealt to the eight XCDs round robin by their linear id: the frame group is the FASTEST index, so an XCD (its L2)
@@ -232,7 +270,7 @@ __global__ __launch_bounds__(256) void undistort_remap_kernel(const UndistJob *_
   if (j0 >= P.w || r >= P.h) return;
   const int W = P.w, H = P.h, ss = P.sstride;
   const int f0 = zi * kRemapFrames, nf = min(n - f0, kRemapFrames);
-  const uint32_t drow = static_cast<uint32_t>(r) * P.dstride + j0;  // (images of at most 2044 x 2044: 32 bits)
+  const uint32_t drow = static_cast<uint32_t>(r) * P.dstride + j0;  // (images of at most 4095 x 4095: 32 bits)
   const QuadRec q = quads[static_cast<size_t>(r) * (pitch / 4) + (j0 >> 2)];
   const int npx = min(4, W - j0);
   if (q.sel != ~0u) {
@@ -246,13 +284,14 @@ __global__ __launch_bounds__(256) void undistort_remap_kernel(const UndistJob *_
   }
   // A quad whose live taps do not fit one window: tap by tap from the per-pixel words, the same way — a tap outside the image has
   // weight 0 and an address clamped into the image, decided once per lane.
-  const uint4 words = *reinterpret_cast<const uint4 *>(map + static_cast<size_t>(r) * pitch + j0);
-  const uint32_t wd[4] = {words.x, words.y, words.z, words.w};
+  uint32_t fa[4], fb[4];
+  int psx[4], psy[4];
+  map_load4<kWideMap>(map, static_cast<size_t>(r) * pitch + j0, fa, fb, psx, psy);
   uint32_t off[4][4], wt[4][4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    const uint32_t a = wd[k] & 31u, b = (wd[k] >> 5) & 31u;
-    const int sx = static_cast<int>((wd[k] >> 10) & 2047u) - 2, sy = static_cast<int>(wd[k] >> 21) - 2;
+    const uint32_t a = fa[k], b = fb[k];
+    const int sx = psx[k], sy = psy[k];
     const uint32_t pw[4] = {(32u - b) * (32u - a), (32u - b) * a, b * (32u - a), b * a};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -342,11 +381,12 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
   }
   // ---- the camera's map: built once per (size, intrinsics, distortion) and context
   const int pitch = (w + 3) / 4 * 4;
+  const bool wide_map = w > kMapMax || h > kMapMax;  // integer parts beyond the packed word's 11 bits: two words per pixel
   UndistParams P{cam->fx, cam->fy, cam->u0, cam->v0, dist->d[0], dist->d[1], dist->d[2], dist->d[3], dist->d[4], w, h, src_stride, dst_stride};
   double key[12] = {cam->fx, cam->fy, cam->u0, cam->v0, dist->d[0], dist->d[1], dist->d[2], dist->d[3], dist->d[4], static_cast<double>(w), static_cast<double>(h),
                     static_cast<double>(src_stride)};  // (the quad records hold source offsets)
   if (!ctx->d_undist_map || memcmp(key, ctx->undist_key, sizeof(key)) != 0) {
-    const size_t px_bytes = (sizeof(uint32_t) * static_cast<size_t>(pitch) * h + 255) / 256 * 256;
+    const size_t px_bytes = (sizeof(uint32_t) * (wide_map ? 2 : 1) * static_cast<size_t>(pitch) * h + 255) / 256 * 256;
     const size_t map_bytes = px_bytes + sizeof(QuadRec) * static_cast<size_t>(pitch / 4) * h;
     if (ctx->undist_map_bytes < map_bytes) {
       if (ctx->d_undist_map) {
@@ -369,10 +409,16 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
       return SDVL_ERR_INVALID;
     }
     SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, xb + yb));
-    SDVL_LAUNCH(ctx, "undistort_map", undistort_map_kernel, dim3((pitch + 255) / 256, h), dim3(256), reinterpret_cast<const double *>(d8),
-                reinterpret_cast<const double *>(d8 + xb), P, pitch, static_cast<uint32_t *>(ctx->d_undist_map));
-    SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(ctx->d_undist_map), pitch, P,
-                reinterpret_cast<QuadRec *>(static_cast<uint8_t *>(ctx->d_undist_map) + px_bytes));
+    const double *d_xw = reinterpret_cast<const double *>(d8), *d_yw = reinterpret_cast<const double *>(d8 + xb);
+    uint32_t *d_map = static_cast<uint32_t *>(ctx->d_undist_map);
+    QuadRec *d_quads = reinterpret_cast<QuadRec *>(static_cast<uint8_t *>(ctx->d_undist_map) + px_bytes);
+    if (wide_map) {
+      SDVL_LAUNCH(ctx, "undistort_map", undistort_map_kernel<true>, dim3((pitch + 255) / 256, h), dim3(256), d_xw, d_yw, P, pitch, d_map);
+      SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<true>, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(d_map), pitch, P, d_quads);
+    } else {
+      SDVL_LAUNCH(ctx, "undistort_map", undistort_map_kernel<false>, dim3((pitch + 255) / 256, h), dim3(256), d_xw, d_yw, P, pitch, d_map);
+      SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<false>, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(d_map), pitch, P, d_quads);
+    }
     SDVL_HIP_CHECK(ctx, hipGetLastError());
     ctx->undist_quads = static_cast<uint8_t *>(ctx->d_undist_map) + px_bytes;
     memcpy(ctx->undist_key, key, sizeof(key));
@@ -390,8 +436,13 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
     if (reinterpret_cast<uintptr_t>(dst[i]) & 3u) wide = 0;
   }
   SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, jb));
-  SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel, dim3((n + kRemapFrames - 1) / kRemapFrames, (w + 127) / 128, (h + 7) / 8), dim3(256),
-              static_cast<const UndistJob *>(dsx), static_cast<const uint32_t *>(ctx->d_undist_map), static_cast<const QuadRec *>(ctx->undist_quads), pitch, n, wide, P);
+  const dim3 grid((n + kRemapFrames - 1) / kRemapFrames, (w + 127) / 128, (h + 7) / 8);
+  if (wide_map)
+    SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel<true>, grid, dim3(256), static_cast<const UndistJob *>(dsx), static_cast<const uint32_t *>(ctx->d_undist_map),
+                static_cast<const QuadRec *>(ctx->undist_quads), pitch, n, wide, P);
+  else
+    SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel<false>, grid, dim3(256), static_cast<const UndistJob *>(dsx), static_cast<const uint32_t *>(ctx->d_undist_map),
+                static_cast<const QuadRec *>(ctx->undist_quads), pitch, n, wide, P);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
 }
@@ -404,7 +455,7 @@ int sdvl_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride,
                    const sdvl_camera *cam, const sdvl_distortion *dist, void *const *dst_dev, int dst_stride) {
   if (!ctx || n < 0 || (n > 0 && (!src || !dst_dev)) || !cam || !dist) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, width >= 2 && height >= 2 && width <= kMapMax && height <= kMapMax, "image size out of range (2 .. 2044 a side)");
+  SDVL_REQUIRE(ctx, width >= 2 && height >= 2 && width <= kMapMaxWide && height <= kMapMaxWide, "image size out of range (2 .. 4095 a side)");
   SDVL_REQUIRE(ctx, src_stride >= width && dst_stride >= width, "stride smaller than width");
   for (int i = 0; i < n; i++) SDVL_REQUIRE(ctx, src[i] && dst_dev[i] && src[i] != dst_dev[i], "null image or in-place undistort");
   return run_undistort(ctx, n, src, src_stride, src_on_device, width, height, cam, dist, reinterpret_cast<uint8_t *const *>(dst_dev), dst_stride);
@@ -419,7 +470,7 @@ int sdvl_frames_upload_undistorted(sdvl_ctx *ctx, int n, sdvl_frame *const *fram
     SDVL_REQUIRE(ctx, frames[i] && src[i], "null frame or image");
     SDVL_REQUIRE(ctx, frames[i]->width == frames[0]->width && frames[i]->height == frames[0]->height, "frames of one call share a size");
     SDVL_REQUIRE(ctx, src_stride >= frames[i]->width, "stride smaller than width");
-    SDVL_REQUIRE(ctx, frames[i]->width <= kMapMax && frames[i]->height <= kMapMax, "image size out of range (2 .. 2044 a side)");
+    SDVL_REQUIRE(ctx, frames[i]->width <= kMapMaxWide && frames[i]->height <= kMapMaxWide, "image size out of range (2 .. 4095 a side)");
     frames[i]->v.level[0] = frames[i]->own_level0;
     dst[i] = frames[i]->own_level0;
     frames[i]->hdr_stale = 1;

@@ -929,6 +929,9 @@ void SDVLBatch::RelocalizeLost(const vector<int> &lost, FrameStats *stats, vecto
     vector<shared_ptr<Frame>> &kfs = t.map_->GetKeyframes();
     for (auto it = kfs.rbegin(); it != kfs.rend(); it++) {
       rc.kfs.push_back(*it);
+      // (a keyframe holds its matches plus at most one seed per free grid cell, and the seeds are filtered corners: <= max_matches +
+      // num_features whatever the grid, 1200 with the TUM settings even on 8160 cells; a keyframe beyond SDVL_MAX_ALIGN_FEATURES (2048)
+      // makes the stored alignment report SDVL_ERR_CAPACITY, at any frame size)
       ImageAlign::PackFeatures(**it, &fresh[q]);
       rc.begin.push_back(static_cast<int32_t>(fresh[q].size()));
       double T7[7];
@@ -1136,6 +1139,7 @@ bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats
     // leaves room for the reference mapper's connection points; a frame that outgrows it is tracked on the host path
     int mm = 1;
     for (SDVL *t : trk_) mm = std::max(mm, t->feature_align_.MaxMatches());
+    // (large grids, e.g. 8160 cells at 3840x2160 / 32: the cap stays 4096 rows; a keyframe with more goes to the host path)
     track_cap_ = std::min(4096, 2 * (mm + cells));
     track_cells_ = cells;
     dev_->Check(sdvl_track_create(dev_->ctx(), B, track_cap_, track_cap_, cells, mm, Config::MaxRansacIts(), &track_), "sdvl_track_create");
