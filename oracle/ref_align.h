@@ -237,6 +237,9 @@ struct Matcher {
   OrbDetector detector;
   Params prm;
   Camera cam;
+  // how far the last SearchPoint got (0 rejected before the patch, 1 no corner matched, 2 AlignPatch did not converge, 3 found) and
+  // the index of the corner SearchFeatures chose, -1 if none: instrumentation for the tests, the reference has neither
+  int last_stage = 0, last_best = -1;
 
   Matcher(int size, const Params &p, const Camera &c) : patch_size(size), detector(p.orb_size), prm(p), cam(c) {
     patch.assign(static_cast<size_t>(size) * size, 0);
@@ -258,6 +261,8 @@ struct Matcher {
     int slevel;
     const int level = ref.level;
     Vec2 pxa{0, 0}, pxb{0, 0};
+    last_stage = 0;
+    last_best = -1;
     const SE3 pose = cur->pose * ref.ref_pose.Inverse();
     const SE3 ref_world = ref.ref_pose.Inverse();
     if (fixed) {
@@ -280,6 +285,7 @@ struct Matcher {
     WarpMatrixAffine(Vec2{ref.px, ref.py}, ref.f, 1.0 / idepth, pose, level, &affine);
     slevel = GetSearchLevel(affine);
     CreatePatch(affine, img, Vec2{ref.px, ref.py}, level, slevel);
+    last_stage = 1;
 
     range = prm.search_size;
     for (int i = 1; i <= slevel; i++) range *= 1.2;
@@ -289,12 +295,14 @@ struct Matcher {
     else GetCornersInRangeLine(*cur, pxa, pxb, level, range, &indices);
 
     if (!SearchFeatures(cur, indices, px, ref.desc)) return false;
+    last_stage = 2;
 
     Vec2 px_scaled{px->x / (1 << slevel), px->y / (1 << slevel)};
     if (AlignPatch((*cur->pyr)[slevel], border_patch.data(), patch.data(), &px_scaled)) {
       px->x = px_scaled.x * (1 << slevel);
       px->y = px_scaled.y * (1 << slevel);
       *flevel = slevel;
+      last_stage = 3;
       return true;
     }
     return false;
@@ -358,7 +366,7 @@ struct Matcher {
   bool SearchFeatures(SearchCur *cur, const std::vector<int> &indices, Vec2 *px, const uint8_t *desc) {
     int sumA = 0, sumAA = 0, sumB, sumBB, sumAB;
     Vec2 best_px{0, 0};
-    int threshold, best_score, score;
+    int threshold, best_score, score, best_index = -1;
     if (prm.use_orb) threshold = kMinOrbThreshold;
     else threshold = patch_size * patch_size * kMaxSsdPerPixel;
     best_score = threshold + 1;
@@ -381,10 +389,12 @@ struct Matcher {
       }
       if (score < best_score) {
         best_score = score;
+        best_index = index;
         best_px = Vec2{static_cast<double>(corner.x * (1 << level)), static_cast<double>(corner.y * (1 << level))};
       }
     }
     if (best_score >= threshold) return false;
+    last_best = best_index;
     *px = best_px;
     return true;
   }

@@ -198,6 +198,15 @@ int sdvl_ref_search_point(const uint8_t *ref_img, const uint8_t *cur_img, int w,
                           const double *feat_bearing, int feat_level, const uint8_t *feat_desc, double idepth,
                           double idepth_std, int fixed, int n_corners, const int32_t *corners, double *px_io,
                           int *out_level, uint8_t *out_border_patch, int *out_slevel) {
+  return sdvl_ref_search_point_ex(ref_img, cur_img, w, h, p, cam, ref_pose, cur_pose, feat_px, feat_bearing, feat_level, feat_desc, idepth,
+                                  idepth_std, fixed, n_corners, corners, px_io, out_level, out_border_patch, out_slevel, nullptr, nullptr);
+}
+
+int sdvl_ref_search_point_ex(const uint8_t *ref_img, const uint8_t *cur_img, int w, int h, const sdvl_ref_params *p,
+                             const double *cam, const double *ref_pose, const double *cur_pose, const double *feat_px,
+                             const double *feat_bearing, int feat_level, const uint8_t *feat_desc, double idepth,
+                             double idepth_std, int fixed, int n_corners, const int32_t *corners, double *px_io,
+                             int *out_level, uint8_t *out_border_patch, int *out_slevel, int *out_stage, int *out_best_corner) {
   const Params q = ToParams(p);
   Pyramid pr(ref_img, w, h, w, q.pyramid_levels), pc(cur_img, w, h, w, q.pyramid_levels);
   std::vector<Corner> cs(n_corners);
@@ -224,6 +233,8 @@ int sdvl_ref_search_point(const uint8_t *ref_img, const uint8_t *cur_img, int w,
     m.WarpMatrixAffine(Vec2{ref.px, ref.py}, ref.f, 1.0 / idepth, ToSE3(cur_pose) * ToSE3(ref_pose).Inverse(), feat_level, &A);
     *out_slevel = m.GetSearchLevel(A);
   }
+  if (out_stage) *out_stage = m.last_stage;
+  if (out_best_corner) *out_best_corner = m.last_best;
   return found ? 1 : 0;
 }
 

@@ -59,6 +59,13 @@ int sdvl_ref_search_point(const uint8_t *ref_img, const uint8_t *cur_img, int w,
                           const double *feat_bearing, int feat_level, const uint8_t *feat_desc, double idepth,
                           double idepth_std, int fixed, int n_corners, const int32_t *corners, double *px_io,
                           int *out_level, uint8_t *out_border_patch, int *out_slevel);
+/* the same call, and how far it got: out_stage = 0 rejected before the patch (out_border_patch is not written then), 1 no corner
+ * matched, 2 AlignPatch did not converge, 3 found; out_best_corner = index of the corner SearchFeatures chose, -1 if none */
+int sdvl_ref_search_point_ex(const uint8_t *ref_img, const uint8_t *cur_img, int w, int h, const sdvl_ref_params *p,
+                             const double *cam, const double *ref_pose, const double *cur_pose, const double *feat_px,
+                             const double *feat_bearing, int feat_level, const uint8_t *feat_desc, double idepth,
+                             double idepth_std, int fixed, int n_corners, const int32_t *corners, double *px_io,
+                             int *out_level, uint8_t *out_border_patch, int *out_slevel, int *out_stage, int *out_best_corner);
 /* matcher.cc:359-445 */
 int sdvl_ref_align_patch(const uint8_t *img, int w, int h, int stride, const uint8_t *border_patch,
                          const uint8_t *patch, double *px_io, int max_its);

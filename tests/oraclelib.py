@@ -212,7 +212,12 @@ class Oracle:
         return dict(T=T, n=n, error=err.value, chi2=chi2.value, its=its)
 
     def search_point(self, ref_img, cur_img, cam, ref_pose, cur_pose, feat_px, feat_bearing, feat_level, feat_desc,
-                     idepth, idepth_std, fixed, corners, px0):
+                     idepth, idepth_std, fixed, corners, px0, use_orb=None):
+        """use_orb: None = as self.params says, else this call alone matches with ORB (True) or ZMSSD (False)"""
+        params = self.params
+        if use_orb is not None:
+            params = Params.from_buffer_copy(self.params)
+            params.use_orb = int(use_orb)
         ref_img = np.ascontiguousarray(ref_img, np.uint8); cur_img = np.ascontiguousarray(cur_img, np.uint8)
         h, w = ref_img.shape
         cam = np.ascontiguousarray(cam, np.float64)
@@ -220,12 +225,13 @@ class Oracle:
         feat_px = np.ascontiguousarray(feat_px, np.float64); feat_bearing = np.ascontiguousarray(feat_bearing, np.float64)
         feat_desc = np.ascontiguousarray(feat_desc, np.uint8); corners = np.ascontiguousarray(corners, np.int32)
         px = np.array(px0, np.float64); lvl = C.c_int(-1); border = np.zeros(100, np.uint8); slevel = C.c_int(-1)
-        found = self.lib.sdvl_ref_search_point(
-            ptr(ref_img, u8p), ptr(cur_img, u8p), w, h, C.byref(self.params), ptr(cam, f64p), ptr(ref_pose, f64p),
+        stage = C.c_int(-1); best = C.c_int(-1)
+        found = self.lib.sdvl_ref_search_point_ex(
+            ptr(ref_img, u8p), ptr(cur_img, u8p), w, h, C.byref(params), ptr(cam, f64p), ptr(ref_pose, f64p),
             ptr(cur_pose, f64p), ptr(feat_px, f64p), ptr(feat_bearing, f64p), int(feat_level), ptr(feat_desc, u8p),
             C.c_double(idepth), C.c_double(idepth_std), int(fixed), len(corners), ptr(corners, i32p), ptr(px, f64p),
-            C.byref(lvl), ptr(border, u8p), C.byref(slevel))
-        return dict(found=found, px=px, level=lvl.value, border=border, slevel=slevel.value)
+            C.byref(lvl), ptr(border, u8p), C.byref(slevel), C.byref(stage), C.byref(best))
+        return dict(found=found, px=px, level=lvl.value, border=border, slevel=slevel.value, stage=stage.value, best_corner=best.value)
 
     def align_patch(self, img, border, patch, px0, max_its=10):
         img = np.ascontiguousarray(img, np.uint8); h, w = img.shape
@@ -336,3 +342,130 @@ def quat_rot(q):
 def trajectory_pose(orc, k, xi=XI):
     """T_k = Exp(k * xi) as a world->camera pose (7 doubles)."""
     return orc.se3_exp(np.asarray(xi) * k)
+
+
+def search_request_meta(orc, img_ref, img_cur, T_ref, T_cur, cam4, n_req, seed, fixed, noise=0.0):
+    """SearchPoint requests seeded on the reference frame's corners: points of the plane z = 2 (world = camera 0) searched in the
+    current frame.  Inverse depth on the plane (times 1 + noise N(0,1)), idepth_std 5 % of it for fixed requests and 10 % for
+    epipolar ones, px0 = the projection + N(0, 0.7 px).  -> (list of dict(px, bearing, level, desc, idepth, istd, px0), corners of
+    the current frame)"""
+    rng = np.random.default_rng(seed)
+    cref = orc.detect_pyramid(img_ref)
+    ccur = orc.detect_pyramid(img_cur)
+    pyr_ref = orc.pyramid(img_ref, 5)
+    sel = rng.choice(len(cref), size=min(n_req, len(cref)), replace=False)
+    Tw = orc.se3_inv(T_ref)
+    Rw, tw = quat_to_R(Tw[:4]), Tw[4:]
+    Rc, tc = quat_to_R(T_cur[:4]), T_cur[4:]
+    meta = []
+    for ci in sel:
+        x, y, l = cref[ci]
+        px = np.array([x * (1 << l), y * (1 << l)], np.float64)
+        ray = np.array([(px[0] - cam4[2]) / cam4[0], (px[1] - cam4[3]) / cam4[1], 1.0])
+        bearing = ray / np.linalg.norm(ray)
+        rw = Rw @ bearing
+        s = (2.0 - tw[2]) / rw[2]
+        desc, _ = orc.orb_describe(pyr_ref[l], [[x, y]])
+        idepth = 1.0 / s * (1.0 + noise * rng.normal())
+        istd = 0.05 * idepth if fixed else 0.1 * idepth
+        Pw = Rw @ (bearing * s) + tw
+        pc = Rc @ Pw + tc
+        px0 = np.array([cam4[2] + cam4[0] * pc[0] / pc[2], cam4[3] + cam4[1] * pc[1] / pc[2]]) + rng.normal(size=2) * 0.7
+        meta.append(dict(px=px, bearing=bearing, level=int(l), desc=desc[0], idepth=idepth, istd=istd, px0=px0))
+    return meta, ccur
+
+
+def fill_search_reqs(sdvl, meta, f_ref, f_cur, T_ref, T_cur, fixed):
+    """the SearchReq array of the product for the requests of search_request_meta, between two uploaded frames"""
+    reqs = (sdvl.SearchReq * len(meta))()
+    for r, m in zip(reqs, meta):
+        r.cur, r.ref = f_cur.h.value, f_ref.h.value
+        for k in range(7):
+            r.cur_pose[k], r.ref_pose[k] = T_cur[k], T_ref[k]
+        r.px[0], r.px[1] = m["px"]
+        r.bearing[0], r.bearing[1], r.bearing[2] = m["bearing"]
+        r.idepth, r.idepth_std = m["idepth"], m["istd"]
+        r.px0[0], r.px0[1] = m["px0"]
+        r.level, r.fixed = m["level"], int(fixed)
+        for k in range(32):
+            r.desc[k] = int(m["desc"][k])
+    return reqs
+
+
+# ---- SearchPoint under warps that are far from the identity (tests/test_oracle_warp_independent.py, tests/test_gpu_search_warp.py)
+WARP_CAM = np.array([525.0, 525.0, 319.5, 239.5])
+_D = np.pi / 180.0
+# view -> (twist of the current view in se3_exp's order, the reference view being the identity pose; SearchPoint calls of 120 that
+# the ORACLE finds on its own with ORB matching (fixed, epipolar) and with ZMSSD matching (fixed, epipolar), measured on the CPU)
+WARP_VIEWS = {
+    "roll30": ((0, 0, 0, 0, 0, 30 * _D), (47, 54), (43, 61)),
+    "roll90": ((0, 0, 0, 0, 0, 90 * _D), (28, 40), (29, 40)),                                    # I00 ~ 0
+    "tilt25": ((0.9, 0, -0.2, 0, -25 * _D, 0), (21, 24), (29, 30)),                              # anisotropic, sheared
+    "zoom1.9-roll20": ((0.05, 0, -(2 - 2 / 1.9), 0, 0, 20 * _D), (8, 9), (8, 9)),
+    "zoom0.6": ((0, 0, -(2 - 2 / 0.6), 0, 0, 0), (4, 6), (18, 18)),      # det < 1; no corner's patch leaves the image: warp_border_case
+}
+_warp_views, _warp_cases, _warp_border_cases = {}, {}, {}
+
+
+def warp_view(orc, synth, view):
+    """-> (reference image, current image, reference pose, current pose) of one view, rendered once per session"""
+    if view not in _warp_views:
+        if "ref" not in _warp_views:
+            T_ref = orc.se3_exp(np.zeros(6))
+            _warp_views["ref"] = (synth.render(T_ref, WARP_CAM, 640, 480, texture=0), T_ref)
+        T_cur = orc.se3_exp(np.array(WARP_VIEWS[view][0], np.float64))
+        _warp_views[view] = _warp_views["ref"] + (synth.render(T_cur, WARP_CAM, 640, 480, texture=0), T_cur)
+    img_ref, T_ref, img_cur, T_cur = _warp_views[view]
+    return img_ref, img_cur, T_ref, T_cur
+
+
+def warp_view_case(orc, synth, view, fixed, use_orb=True):
+    """the 120 requests of one view and the oracle's answer to each, computed once per session and shared (read-only)"""
+    key = (view, bool(fixed), bool(use_orb))
+    if key not in _warp_cases:
+        img_ref, img_cur, T_ref, T_cur = warp_view(orc, synth, view)
+        meta, ccur = search_request_meta(orc, img_ref, img_cur, T_ref, T_cur, WARP_CAM, 120, 11, fixed)
+        want = [orc.search_point(img_ref, img_cur, WARP_CAM, T_ref, T_cur, m["px"], m["bearing"], m["level"], m["desc"], m["idepth"],
+                                 m["istd"], fixed, ccur, m["px0"], use_orb=use_orb) for m in meta]
+        listed = WARP_VIEWS[view][1 if use_orb else 2][0 if fixed else 1]
+        _warp_cases[key] = dict(img_ref=img_ref, img_cur=img_cur, T_ref=T_ref, T_cur=T_cur, meta=meta, ccur=ccur, want=want,
+                                found_floor=listed // 2)
+    return _warp_cases[key]
+
+
+def warp_border_case(orc, synth, view):
+    """Requests that are no corners: points 6, 7 and 9 pixels (of their level, 0 to 2) inside each border of the reference image,
+    the nearest the margin test of matcher.cc:83 lets through, on the plane, fixed, px0 = their projection into the current view.
+    Rolled or spread by 1 / 0.6 their sample grids cross the border of the reference image.  No detected corner lies where such a
+    point lands in the current view, so the current frame's corner list is the detected one plus, per request, three corners at
+    and next to its projection on each level the request searches: the search then gets as far as the match and the LK.  The oracle
+    answers with ZMSSD matching, where the patch's own pixels, the zeroed ones included, pick the corner.  Same keys as
+    warp_view_case, shared (read-only)."""
+    if view not in _warp_border_cases:
+        img_ref, img_cur, T_ref, T_cur = warp_view(orc, synth, view)
+        Rc, tc = quat_to_R(T_cur[:4]), T_cur[4:]
+        meta, extra = [], []
+        for level in range(3):
+            rows, cols = 480 >> level, 640 >> level
+            ys, xs = range(20, rows - 20, rows // 5), range(20, cols - 20, cols // 5)
+            spots = [(d, y) for d in (6, 7, 9) for y in ys] + [(cols - 1 - d, y) for d in (6, 7, 9) for y in ys]
+            spots += [(x, d) for d in (6, 7, 9) for x in xs] + [(x, rows - 1 - d) for d in (6, 7, 9) for x in xs]
+            spots += [(6, 6), (cols - 7, 6), (6, rows - 7), (cols - 7, rows - 7)]
+            for x, y in spots:
+                px = np.array([x, y], np.float64) * (1 << level)
+                ray = np.array([(px[0] - WARP_CAM[2]) / WARP_CAM[0], (px[1] - WARP_CAM[3]) / WARP_CAM[1], 1.0])
+                bearing = ray / np.linalg.norm(ray)
+                idepth = bearing[2] / 2.0                         # on the plane z = 2 (the reference pose is the identity)
+                pc = Rc @ (bearing / idepth) + tc
+                px0 = np.array([WARP_CAM[2] + WARP_CAM[0] * pc[0] / pc[2], WARP_CAM[3] + WARP_CAM[1] * pc[1] / pc[2]])
+                meta.append(dict(px=px, bearing=bearing, level=level, desc=np.zeros(32, np.uint8), idepth=idepth, istd=0.05 * idepth, px0=px0))
+                for cl in range(max(0, level - 1), min(2, level + 1) + 1):    # the levels a request of this level searches
+                    for dx, dy in ((0, 0), (2, 0), (-1, 2)):
+                        cx, cy = int(round(px0[0] / (1 << cl))) + dx, int(round(px0[1] / (1 << cl))) + dy
+                        if 8 <= cx < (640 >> cl) - 8 and 8 <= cy < (480 >> cl) - 8:
+                            extra.append((cx, cy, cl))
+        ccur = np.concatenate([orc.detect_pyramid(img_cur), np.array(sorted(set(extra)), np.int32)])
+        want = [orc.search_point(img_ref, img_cur, WARP_CAM, T_ref, T_cur, m["px"], m["bearing"], m["level"], m["desc"], m["idepth"],
+                                 m["istd"], True, ccur, m["px0"], use_orb=False) for m in meta]
+        _warp_border_cases[view] = dict(img_ref=img_ref, img_cur=img_cur, T_ref=T_ref, T_cur=T_cur, meta=meta, ccur=ccur, want=want)
+    return _warp_border_cases[view]

@@ -402,47 +402,13 @@ def test_filter_corners_selection_on_the_device(ctx, sdvl, orc, synth):
 # ------------------------------------------------------------------------------------------------ K7
 def search_requests(sdvl, orc, ctx, img_ref, img_cur, T_ref, T_cur, cam4, n_req, seed, fixed, noise=0.0, describe=True):
     """points seeded on the reference frame's corners (plane z=2 in world = camera 0), searched in the current frame"""
-    h, w = img_ref.shape
-    rng = np.random.default_rng(seed)
-    cref = orc.detect_pyramid(img_ref)
-    ccur = orc.detect_pyramid(img_cur)
-    pyr_ref = orc.pyramid(img_ref, 5)
-    sel = rng.choice(len(cref), size=min(n_req, len(cref)), replace=False)
+    from oraclelib import fill_search_reqs, search_request_meta
+    meta, ccur = search_request_meta(orc, img_ref, img_cur, T_ref, T_cur, cam4, n_req, seed, fixed, noise)
     f_ref, f_cur = ctx.frame(img_ref), ctx.frame(img_cur)
     f_cur.set_corners(ccur)
     if describe:   # otherwise the search computes the descriptors it compares on the spot (matcher.cc:266-269)
         ctx.orb_describe([f_cur], want=False)
-    Tw = orc.se3_inv(T_ref)
-    from oraclelib import quat_to_R
-    Rw, tw = quat_to_R(Tw[:4]), Tw[4:]
-    Rc, tc = quat_to_R(T_cur[:4]), T_cur[4:]
-    reqs = (sdvl.SearchReq * len(sel))()
-    meta = []
-    for i, ci in enumerate(sel):
-        x, y, l = cref[ci]
-        px = np.array([x * (1 << l), y * (1 << l)], np.float64)
-        ray = np.array([(px[0] - cam4[2]) / cam4[0], (px[1] - cam4[3]) / cam4[1], 1.0])
-        bearing = ray / np.linalg.norm(ray)
-        rw = Rw @ bearing
-        s = (2.0 - tw[2]) / rw[2]
-        desc, _ = orc.orb_describe(pyr_ref[l], [[x, y]])
-        idepth = 1.0 / s * (1.0 + noise * rng.normal())
-        istd = 0.05 * idepth if fixed else 0.1 * idepth
-        Pw = Rw @ (bearing * s) + tw
-        pc = Rc @ Pw + tc
-        px0 = np.array([cam4[2] + cam4[0] * pc[0] / pc[2], cam4[3] + cam4[1] * pc[1] / pc[2]]) + rng.normal(size=2) * 0.7
-        r = reqs[i]
-        r.cur, r.ref = f_cur.h.value, f_ref.h.value
-        for k in range(7):
-            r.cur_pose[k], r.ref_pose[k] = T_cur[k], T_ref[k]
-        r.px[0], r.px[1] = px
-        r.bearing[0], r.bearing[1], r.bearing[2] = bearing
-        r.idepth, r.idepth_std = idepth, istd
-        r.px0[0], r.px0[1] = px0
-        r.level, r.fixed = int(l), int(fixed)
-        for k in range(32):
-            r.desc[k] = int(desc[0, k])
-        meta.append(dict(px=px, bearing=bearing, level=int(l), desc=desc[0], idepth=idepth, istd=istd, px0=px0))
+    reqs = fill_search_reqs(sdvl, meta, f_ref, f_cur, T_ref, T_cur, fixed)
     return reqs, meta, ccur, f_ref, f_cur
 
 
