@@ -377,9 +377,10 @@ int sdvl_ref_tracker_handle_frame(void *t, const uint8_t *img, int stride, sdvl_
 // obs[n][6] = {ax, ay, px, py, pz, level}: feature bearing (ax, ay, 1), fixed 3D point, pyramid level.
 // rand_seed / rand_skip position the glibc stream; n_draws returns how many rand() calls the RANSAC loop made.
 // in_idx / out_idx receive the final inlier / outlier lists as indices into obs (reference order).
-int sdvl_ref_pose_from_matches(const sdvl_ref_params *p, int w, int h, const double *cam, int n, const double *obs,
-                               unsigned rand_seed, int rand_skip, double *pose7_io, int *n_draws, int *n_in, int *in_idx,
-                               int *n_out, int *out_idx) {
+// refined (may be null): 1 if an OptimizePose found features to converge on and set the frame's pose (feature_align.cc:222-224).
+int sdvl_ref_pose_from_matches_ex(const sdvl_ref_params *p, int w, int h, const double *cam, int n, const double *obs,
+                                  unsigned rand_seed, int rand_skip, double *pose7_io, int *n_draws, int *n_in, int *in_idx,
+                                  int *n_out, int *out_idx, int *refined) {
   ScenePlane pl;
   Tracker t(ToParams(p), ToCam(cam, w, h), pl, SE3());
   t.rng.Seed(rand_seed);
@@ -407,8 +408,14 @@ int sdvl_ref_pose_from_matches(const sdvl_ref_params *p, int w, int h, const dou
     draws++;
   }
   *n_draws = draws;
+  // ConvergePose fails only on an empty feature list (every feature here has a point), :367-368
+  bool pose_set = !t.inliers.empty();
   t.OptimizePose(frame, &t.inliers, &t.outliers);
-  if (t.RescueOutliers(frame, &t.inliers, &t.outliers)) t.OptimizePose(frame, &t.inliers, &t.outliers);
+  if (t.RescueOutliers(frame, &t.inliers, &t.outliers)) {
+    pose_set = pose_set || !t.inliers.empty();
+    t.OptimizePose(frame, &t.inliers, &t.outliers);
+  }
+  if (refined) *refined = pose_set ? 1 : 0;
   auto index_of = [&](const std::shared_ptr<RFeature> &f) {
     for (int i = 0; i < n; i++) if (found[i] == f) return i;
     return -1;
@@ -419,6 +426,12 @@ int sdvl_ref_pose_from_matches(const sdvl_ref_params *p, int w, int h, const dou
   for (int i = 0; i < *n_out; i++) out_idx[i] = index_of(t.outliers[i]);
   FromSE3(frame->pose, pose7_io);
   return 0;
+}
+int sdvl_ref_pose_from_matches(const sdvl_ref_params *p, int w, int h, const double *cam, int n, const double *obs,
+                               unsigned rand_seed, int rand_skip, double *pose7_io, int *n_draws, int *n_in, int *in_idx,
+                               int *n_out, int *out_idx) {
+  return sdvl_ref_pose_from_matches_ex(p, w, h, cam, n, obs, rand_seed, rand_skip, pose7_io, n_draws, n_in, in_idx, n_out, out_idx,
+                                       nullptr);
 }
 
 // Camera::UndistortImage = cv::undistort (camera.cc:100-105): cam4 = fx fy u0 v0, dist5 = d0..d4 (k1 k2 p1 p2 k3)

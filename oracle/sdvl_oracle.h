@@ -87,6 +87,10 @@ void sdvl_ref_remap_weights(int16_t *out4096);
 int sdvl_ref_pose_from_matches(const sdvl_ref_params *p, int w, int h, const double *cam, int n, const double *obs,
                                unsigned rand_seed, int rand_skip, double *pose7_io, int *n_draws, int *n_in, int *in_idx,
                                int *n_out, int *out_idx);
+/* the same, and refined (may be null) = 1 if an OptimizePose set the frame's pose (feature_align.cc:222-224) */
+int sdvl_ref_pose_from_matches_ex(const sdvl_ref_params *p, int w, int h, const double *cam, int n, const double *obs,
+                                  unsigned rand_seed, int rand_skip, double *pose7_io, int *n_draws, int *n_in, int *in_idx,
+                                  int *n_out, int *out_idx, int *refined);
 
 /* closed-loop tracker: sdvl.cc:55-130 with the plane map stub (oracle/ref_tracker.h) */
 void *sdvl_ref_tracker_create(const sdvl_ref_params *p, int w, int h, const double *cam, const double *plane4,

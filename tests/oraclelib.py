@@ -179,12 +179,12 @@ class Oracle:
         """SelectInliers + OptimizePose on obs[n][6] = ax, ay, px, py, pz, level"""
         cam = np.ascontiguousarray(cam, np.float64); obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 6)
         n = len(obs); pose = np.array(pose, np.float64)
-        nd = C.c_int(); ni = C.c_int(); no = C.c_int()
+        nd = C.c_int(); ni = C.c_int(); no = C.c_int(); rf = C.c_int()
         ii = np.zeros(max(n, 1), np.int32); oi = np.zeros(max(n, 1), np.int32)
-        self.lib.sdvl_ref_pose_from_matches(C.byref(self.params), w, h, ptr(cam, f64p), n, ptr(obs, f64p), C.c_uint(rand_seed),
-                                            int(rand_skip), ptr(pose, f64p), C.byref(nd), C.byref(ni), ptr(ii, i32p),
-                                            C.byref(no), ptr(oi, i32p))
-        return dict(pose=pose, n_draws=nd.value, inliers=ii[:ni.value].copy(), outliers=oi[:no.value].copy())
+        self.lib.sdvl_ref_pose_from_matches_ex(C.byref(self.params), w, h, ptr(cam, f64p), n, ptr(obs, f64p), C.c_uint(rand_seed),
+                                               int(rand_skip), ptr(pose, f64p), C.byref(nd), C.byref(ni), ptr(ii, i32p),
+                                               C.byref(no), ptr(oi, i32p), C.byref(rf))
+        return dict(pose=pose, n_draws=nd.value, inliers=ii[:ni.value].copy(), outliers=oi[:no.value].copy(), refined=rf.value)
 
     def undistort(self, img, cam, dist):
         """Camera::UndistortImage = cv::undistort; cam = fx fy u0 v0, dist = d0..d4"""
@@ -337,6 +337,22 @@ def quat_rot(q):
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
                      [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def make_matches(orc, n, seed, outlier_frac=0.25, noise_px=0.4, fx=525.0):
+    """n matches of a camera that moved by a small twist: obs rows = ax, ay, px, py, pz, level"""
+    rng = np.random.default_rng(seed)
+    true_pose = orc.se3_exp(np.array([0.03, -0.02, 0.01, 0.004, -0.006, 0.003]) * (1 + seed % 3))
+    guess = orc.se3_exp(np.zeros(6))
+    P = np.stack([rng.uniform(-1.2, 1.2, n), rng.uniform(-0.9, 0.9, n), rng.uniform(1.5, 3.0, n)], 1)
+    R = quat_rot(true_pose[:4])
+    pc = P @ R.T + true_pose[4:]
+    a = pc[:, :2] / pc[:, 2:3] + rng.normal(0, noise_px / fx, (n, 2))
+    bad = rng.random(n) < outlier_frac
+    a[bad] += rng.uniform(-40, 40, (int(bad.sum()), 2)) / fx
+    lvl = rng.integers(0, 3, n)
+    obs = np.concatenate([a, P, lvl[:, None].astype(np.float64)], 1)
+    return obs, guess
 
 
 def trajectory_pose(orc, k, xi=XI):

@@ -8,7 +8,7 @@ import importlib
 import numpy as np
 import pytest
 
-from oraclelib import EUROC_CAM, TUM_CAM, trajectory_pose
+from oraclelib import EUROC_CAM, TUM_CAM, make_matches, trajectory_pose
 
 pytestmark = pytest.mark.gpu
 POSE_TOL = 1e-4   # BASELINE.json: "pose and patch-offset deltas within 1e-4"
@@ -862,23 +862,6 @@ def test_empty_batches_and_flat_frames(ctx, sdvl, orc):
 
 
 # ------------------------------------------------------------------------------------------------ K8
-def make_matches(orc, n, seed, outlier_frac=0.25, noise_px=0.4, fx=525.0):
-    """n matches of a camera that moved by a small twist: obs rows = ax, ay, px, py, pz, level"""
-    rng = np.random.default_rng(seed)
-    true_pose = orc.se3_exp(np.array([0.03, -0.02, 0.01, 0.004, -0.006, 0.003]) * (1 + seed % 3))
-    guess = orc.se3_exp(np.zeros(6))
-    P = np.stack([rng.uniform(-1.2, 1.2, n), rng.uniform(-0.9, 0.9, n), rng.uniform(1.5, 3.0, n)], 1)
-    from oraclelib import quat_rot
-    R = quat_rot(true_pose[:4])
-    pc = P @ R.T + true_pose[4:]
-    a = pc[:, :2] / pc[:, 2:3] + rng.normal(0, noise_px / fx, (n, 2))
-    bad = rng.random(n) < outlier_frac
-    a[bad] += rng.uniform(-40, 40, (int(bad.sum()), 2)) / fx
-    lvl = rng.integers(0, 3, n)
-    obs = np.concatenate([a, P, lvl[:, None].astype(np.float64)], 1)
-    return obs, guess
-
-
 @pytest.mark.parametrize("sizes", [(150, 40, 5, 3, 1, 0), (256, 255, 64, 65, 129, 7), (1024, 700, 257)])
 def test_pose_from_matches_equals_oracle(ctx, orc, sizes):
     """RANSAC replay + Tukey Gauss-Newton + rescue on the device: same rand() consumption, same inlier / outlier lists
