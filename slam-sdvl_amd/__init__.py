@@ -380,7 +380,9 @@ class Context:
             out.append(xyl[:k.value].copy())
         return out
 
-    def retain_best(self, packed, n_points, cooperative=False):
+    def retain_best(self, packed, n_points, cooperative=0):
+        """cooperative: 0 = one lane, 2 = the 8-lane group of select_cells, 3 = one wave as in select_pack; 1 (the retired workgroup
+        form) and every other value raise SdvlError"""
         packed = np.ascontiguousarray(packed, np.uint32).copy()
         k = C.c_int()
         self._check(self.lib.sdvl_retain_best(self.h, _ptr(packed, C.POINTER(C.c_uint32)), len(packed), int(n_points), int(cooperative),

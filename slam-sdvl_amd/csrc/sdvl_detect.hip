@@ -10,6 +10,7 @@
 #include <atomic>
 
 #include "sdvl_internal.h"
+#include "sdvl_wave.h"
 
 namespace {
 
@@ -17,12 +18,6 @@ namespace {
 // source tile and the horizontal sums over through LDS behind a wave fence; among the other streams' kernels the 64 x 16 tile
 // of a four-wave workgroup with its three barriers ran 3.5x longer than alone, a wave that never waits for another wave does not).
 constexpr int kPyrTW = 32, kPyrTH = 8;
-
-__device__ __forceinline__ void pyr_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 struct PyrJob {
   const uint8_t *src;
@@ -47,7 +42,7 @@ __global__ __launch_bounds__(kPyrTW * kPyrTH / 4) void pyr_down_kernel(const Pyr
   constexpr int kPyrSWW = kPyrTW / 2 + 2;        // source words of a tile row: bytes [2*tx0 - 4, 2*tx0 + 2*TW + 4)
   constexpr int kPyrPitch = (kPyrSWW + 1) * 4;   // LDS row pitch in bytes (odd number of words: rows start in different banks)
   const auto sync = [] {
-    if (kThreads == 64) pyr_wave_sync();
+    if (kThreads == 64) wave_sync();
     else __syncthreads();
   };
   __shared__ uint32_t s_srcw[kPyrSH * (kPyrSWW + 1)];
@@ -359,12 +354,6 @@ __device__ __forceinline__ int wave_rank4(uint32_t flags, int *wave_total) {
 // is a ballot, and only the tile / score planes of the chosen path are written: 7.5 KB of LDS per cell instead of 13 KB and
 // four wave slots.  A workgroup of four waves spent most of its life waiting — job record, geometry, tile, four barriers —
 // and held four wave slots while it did; one wave per cell holds one, so four times as many cells are in flight per CU.
-__device__ __forceinline__ void fc_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // slot `pos` of a cell's corner list as (uniform base + 32-bit byte offset): one shift, a store with a scalar base
 typedef __attribute__((address_space(1))) uint32_t *FcGlobalWords;
 __device__ __forceinline__ FcGlobalWords fc_slot(FcGlobalWords base, int pos) {
@@ -477,7 +466,7 @@ __global__ __launch_bounds__(64) void fast_cells_wave_kernel(const FastJob *__re
       hw.y = __builtin_amdgcn_perm(0x64646464u, pack, 0x04030402u);
       *reinterpret_cast<uint2 *>(&s_imgh[(row + kPadRows) * kPitchHW + 2 + 2 * (wbase + k)]) = hw;
     }
-    fc_wave_sync();
+    wave_sync();
     const int tw = rw - 6;
     const int npr = tw > 0 ? (tw + 1) >> 1 : 1;
     const _Float16 th = static_cast<_Float16>(t);
@@ -526,7 +515,7 @@ __global__ __launch_bounds__(64) void fast_cells_wave_kernel(const FastJob *__re
           }
         }
       }
-      fc_wave_sync();
+      wave_sync();
 #pragma unroll
       for (int ps = 0; ps < 3; ps++) {
         if (ps < nqpass) {
@@ -583,7 +572,7 @@ __global__ __launch_bounds__(64) void fast_cells_wave_kernel(const FastJob *__re
       s_img[(row + kPadRows) * kPitchW + 1 + wbase + k] = pk[k];
       s_score[(row + 1) * kPitchW + 1 + wbase + k] = 0;
     }
-    fc_wave_sync();
+    wave_sync();
     // ---- phase A: compass pre-test of the lane's 16 pixels (row `row`, columns 16 (lane & 1) ..)
     uint32_t cflags = 0;
     if (row >= 3 && row < rh - 3) {
@@ -619,7 +608,7 @@ __global__ __launch_bounds__(64) void fast_cells_wave_kernel(const FastJob *__re
       for (int k = 0; k < 16; k++)
         if (cflags & (1u << k)) s_list[cpos++] = static_cast<uint16_t>((row << 5) | (wbase * 4 + k));
     }
-    fc_wave_sync();
+    wave_sync();
     // ---- phase C: one candidate per lane and round; the corners are compacted in place at the head of the list (a corner's
     // slot never lies behind the candidate it came from), their scores go to the score plane
     uint8_t *score_bytes = reinterpret_cast<uint8_t *>(s_score);
@@ -639,11 +628,11 @@ __global__ __launch_bounds__(64) void fast_cells_wave_kernel(const FastJob *__re
         }
       }
       const unsigned long long m = __ballot(is);
-      fc_wave_sync();  // every lane has read its candidate
+      wave_sync();  // every lane has read its candidate
       if (is) s_list[ncorner + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0))] = static_cast<uint16_t>(rc);
       ncorner += __popcll(m);
     }
-    fc_wave_sync();
+    wave_sync();
     // ---- 3x3 strict non-max suppression of the corners and ordered output
     for (int j0 = 0; j0 < ncorner; j0 += 64) {
       const int j = j0 + lane;
@@ -702,7 +691,7 @@ __global__ __launch_bounds__(64) void fast_cells_wide_kernel(const FastJob *__re
   for (int z = lane; z < kWideTile * kWideTile / 4; z += 64) s_scorew[z] = 0u;
   if (lane < rw)
     for (int r = 0; r < rh; r++) s_img[r * kWideTile + lane] = img[static_cast<size_t>(r) * W + lane];
-  fc_wave_sync();
+  wave_sync();
   const int x = lane;
   const bool tested_col = x >= 3 && x < rw - 3;
   for (int r = 3; r < rh - 3; r++) {
@@ -712,7 +701,7 @@ __global__ __launch_bounds__(64) void fast_cells_wide_kernel(const FastJob *__re
     const int best = fast_corner_best(p, kWideTile, t);
     if (best > t) s_score[r * kWideTile + x] = static_cast<uint8_t>((best - 1) & 0xFF);
   }
-  fc_wave_sync();
+  wave_sync();
   uint32_t *out = job.cell_kps + static_cast<size_t>(gcell) * kp_cap;
   int base = 0;
   for (int r = 3; r < rh - 3; r++) {
@@ -868,7 +857,8 @@ __device__ __forceinline__ void sel_insertion_sort(uint32_t *v, int first, int l
   }
 }
 
-// std::nth_element(v+first, v+nth, v+last, response-greater)
+// std::nth_element(v+first, v+nth, v+last, response-greater).  The loop is sel_introselect_from's, kept as a copy: the compiler infers
+// that function's argument ranges over ALL its callers, and a call from here changes the code of the selection kernels.
 __device__ __forceinline__ void sel_nth_element(uint32_t *v, int first, int nth, int last) {
   if (first == last || nth == last) return;
   int depth_limit = (31 - __clz(last - first)) * 2;  // std::__lg(n) * 2
@@ -918,8 +908,8 @@ __device__ __forceinline__ int sel_retain_best(uint32_t *v, int len, int n_point
 constexpr int kSelMaxCells = 2048;  // cells of one level in the select_cells form of the default sizes (SDVL_MAX_LEVEL_CELLS beyond)
 constexpr int kSelFts = 4096;       // concatenated selection of one level before the final retainBest (the least spill area per level)
 
-// Round 3: the selection is two launches of NARROW workgroups instead of one 1024-thread workgroup per (frame, level) that held
-// 128 KB of LDS (a whole CU's worth: among the other streams' kernels it waited for a CU to drain, 104 us alone -> 460 us):
+// The selection is two launches of NARROW workgroups.  (Round 3 retired the form before: one 1024-thread workgroup per (frame, level)
+// that held 128 KB of LDS — a whole CU's worth: among the other streams' kernels it waited for a CU to drain, 104 us alone -> 460 us.)
 //   select_cells_kernel  one WAVE per (frame, level, 8 consecutive cells): the level's quota (one number, below), then the cells'
 //                        retainBest by groups of 8 lanes; 11 KB of LDS, no workgroup barrier
 //   select_pack_kernel   one 256-thread workgroup per frame: wave l concatenates level l's surviving lists and runs the level's
@@ -951,78 +941,6 @@ struct SelJob {
   int corner_cap;              // corners the frame's resident list holds
 };
 
-constexpr int kSelThreads = 1024;  // 16 waves: one lane per cell leaves <= ~20 divergent lanes per wave
-constexpr int kSelWaves = kSelThreads / 64;
-constexpr int kSelParMin = 96;     // ranges shorter than this are finished by one lane
-
-// block-wide exclusive prefix sum of one int per thread; returns the exclusive prefix, *total = block sum
-__device__ __forceinline__ int block_exclusive_scan(int v, int *s_wave, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int n = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += n;
-  }
-  __syncthreads();  // s_wave may still be read from a previous call
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kSelWaves; w++) {
-    const int x = s_wave[w];
-    if (w < wave) base += x;
-    tot += x;
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
-// The two-pointer partitions of libstdc++ (__unguarded_partition and the bidirectional __partition) swap the k-th
-// element that stops the left scan with the k-th element that stops the right scan for as long as the former lies left
-// of the latter; no position takes part in two swaps.  So the final arrangement follows from two rank computations:
-//   left-stoppers  L[0] < L[1] < ...  (ascending positions),  right-stoppers  R[0] > R[1] > ...  (descending positions),
-//   K = #{k : L[k] < R[k]},  swap v[L[k]] <-> v[R[k]] for k < K.
-// All threads call this with identical arguments.  is_left / is_right classify a packed keypoint.
-template <typename FL, typename FR>
-__device__ __forceinline__ void block_two_pointer_partition(uint32_t *v, int first, int last, uint16_t *Ls, uint16_t *Rs, int *s_wave, FL is_left, FR is_right,
-                                            int *out_K, int *out_nL, int *out_nR) {
-  const int tid = threadIdx.x;
-  const int n = last - first;
-  const int chunk = (n + kSelThreads - 1) / kSelThreads;
-  const int my0 = min(last, first + tid * chunk), my1 = min(last, my0 + chunk);
-  int cl = 0, cr = 0;
-  for (int i = my0; i < my1; i++) {
-    const uint32_t x = v[i];
-    cl += is_left(x) ? 1 : 0;
-    cr += is_right(x) ? 1 : 0;
-  }
-  int nL = 0, nR = 0;
-  int el = block_exclusive_scan(cl, s_wave, &nL);
-  int er = block_exclusive_scan(cr, s_wave, &nR);
-  for (int i = my0; i < my1; i++) {
-    const uint32_t x = v[i];
-    if (is_left(x)) Ls[el++] = static_cast<uint16_t>(i);
-    if (is_right(x)) Rs[nR - 1 - (er++)] = static_cast<uint16_t>(i);
-  }
-  __syncthreads();
-  const int m = min(nL, nR);
-  int ck = 0;
-  for (int k = tid; k < m; k += kSelThreads) ck += (Ls[k] < Rs[k]) ? 1 : 0;
-  int K = 0;
-  block_exclusive_scan(ck, s_wave, &K);
-  for (int k = tid; k < K; k += kSelThreads) {
-    const int a = Ls[k], b = Rs[k];
-    const uint32_t t = v[a];
-    v[a] = v[b];
-    v[b] = t;
-  }
-  __syncthreads();
-  *out_K = K;
-  *out_nL = nL;
-  *out_nR = nR;
-}
-
 // sequential continuation of __introselect from an intermediate state (one lane)
 __device__ __forceinline__ void sel_introselect_from(uint32_t *v, int first, int nth, int last, int depth_limit) {
   while (last - first > 3) {
@@ -1041,91 +959,10 @@ __device__ __forceinline__ void sel_introselect_from(uint32_t *v, int first, int
   sel_insertion_sort(v, first, last);
 }
 
-// cv::KeyPointsFilter::retainBest(v[0..len), n_points) by the whole workgroup; every thread gets the new length
-__device__ __forceinline__ int block_retain_best(uint32_t *v, int len, int n_points, uint16_t *Ls, uint16_t *Rs, int *s_wave) {
-  if (!(n_points >= 0 && len > n_points)) return len;
-  if (n_points == 0) return 0;
-  const int tid = threadIdx.x;
-  // ---- std::nth_element(v, v + n_points, v + len)
-  {
-    int first = 0, last = len;
-    const int nth = n_points;
-    int depth_limit = (31 - __clz(len)) * 2;
-    while (last - first > 3 && last - first >= kSelParMin && depth_limit > 0) {
-      --depth_limit;
-      if (tid == 0) {
-        const int mid = first + (last - first) / 2;
-        sel_move_median_to_first(v, first, first + 1, mid, last - 1);
-      }
-      __syncthreads();
-      const uint32_t pv = v[first] >> 24;
-      int K, nL, nR;
-      block_two_pointer_partition(
-          v, first + 1, last, Ls, Rs, s_wave, [pv](uint32_t x) { return !((x >> 24) > pv); }, [pv](uint32_t x) { return !(pv > (x >> 24)); }, &K,
-          &nL, &nR);
-      // where the left scan finally stops: the next original left-stopper or the slot the last swap filled from the left
-      int cut = 0x7FFFFFFF;
-      if (K < nL) cut = Ls[K];
-      if (K > 0) cut = min(cut, static_cast<int>(Rs[K - 1]));
-      __syncthreads();  // Ls/Rs are rewritten by the next round
-      if (cut <= nth) first = cut;
-      else last = cut;
-    }
-    if (tid == 0) sel_introselect_from(v, first, nth, last, depth_limit);
-    __syncthreads();
-  }
-  // ---- std::partition(v + n_points, v + len, response >= amb)
-  const uint32_t amb = v[n_points - 1] >> 24;
-  int new_len;
-  if (len - n_points >= kSelParMin) {
-    int K, nL, nR;
-    block_two_pointer_partition(
-        v, n_points, len, Ls, Rs, s_wave, [amb](uint32_t x) { return !((x >> 24) >= amb); }, [amb](uint32_t x) { return (x >> 24) >= amb; }, &K, &nL,
-        &nR);
-    new_len = n_points + nR;  // the elements that satisfy the predicate end up in front
-    __syncthreads();
-  } else {
-    __shared__ int s_len;
-    if (tid == 0) {
-      int first = n_points, last = len;
-      int res = -1;
-      while (res < 0) {
-        while (true) {
-          if (first == last) { res = first; break; }
-          else if ((v[first] >> 24) >= amb) ++first;
-          else break;
-        }
-        if (res >= 0) break;
-        --last;
-        while (true) {
-          if (first == last) { res = first; break; }
-          else if (!((v[last] >> 24) >= amb)) --last;
-          else break;
-        }
-        if (res >= 0) break;
-        kp_swap(v, first, last);
-        ++first;
-      }
-      s_len = res;
-    }
-    __syncthreads();
-    new_len = s_len;
-    __syncthreads();
-  }
-  return new_len;
-}
-
-
-// ---- the same retainBest by a GROUP of G consecutive lanes of one wave (G = 16: four cells per wave; G = 64: one wave for
+// ---- the same retainBest by a GROUP of G consecutive lanes of one wave (G = 8: eight cells per wave; G = 64: one wave for
 // the per-level list).  No s_barrier: the lanes of a wave execute their LDS instructions in order, a fence keeps the
 // compiler from moving them.  Groups of one wave may follow different control flow; inside a group every branch depends
 // on group-uniform values only, so __ballot (active lanes) always carries the whole group.
-__device__ __forceinline__ void sel_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <int G>
 __device__ __forceinline__ unsigned long long group_ballot(bool p, int shift) {
   const unsigned long long b = __ballot(p);
@@ -1136,9 +973,15 @@ __device__ __forceinline__ unsigned long long group_ballot(bool p, int shift) {
 constexpr int kSelGroupMin = 4;  // ranges shorter than this are finished by the group's first lane (>= 4: the median-of-3 positions must differ)
 constexpr int kSelGroup = 8;     // lanes that share a cell's retainBest in select_cells_kernel
 
-// block_two_pointer_partition for a group: left-stoppers ascending in Ls[0..nL), right-stoppers ASCENDING in Rs[0..nR) (the
-// k-th from the right is Rs[nR - 1 - k]); L[k] < R[k] is monotone in k, so K is a count.  Returns K; *cut = where the left
-// scan finally stops (the next original left-stopper or the slot the last swap filled from the left).
+// The two-pointer partitions of libstdc++ (__unguarded_partition and the bidirectional __partition) swap the k-th
+// element that stops the left scan with the k-th element that stops the right scan for as long as the former lies left
+// of the latter; no position takes part in two swaps.  So the final arrangement follows from two rank computations:
+//   left-stoppers  L[0] < L[1] < ...  (ascending positions),  right-stoppers  R[0] > R[1] > ...  (descending positions),
+//   K = #{k : L[k] < R[k]},  swap v[L[k]] <-> v[R[k]] for k < K.
+// All lanes of the group call this with identical arguments.  is_left / is_right classify a packed keypoint.
+// Left-stoppers ascending in Ls[0..nL), right-stoppers ASCENDING in Rs[0..nR) (the k-th from the right is Rs[nR - 1 - k]);
+// L[k] < R[k] is monotone in k, so K is a count.  Returns K; *cut = where the left scan finally stops (the next original
+// left-stopper or the slot the last swap filled from the left).
 template <int G, typename IDX, typename FL, typename FR>
 __device__ __forceinline__ int group_two_pointer_partition(uint32_t *v, int first, int last, IDX *Ls, IDX *Rs, int sub, int shift, FL is_left,
                                                            FR is_right, int *out_nR, int *out_cut) {
@@ -1158,7 +1001,7 @@ __device__ __forceinline__ int group_two_pointer_partition(uint32_t *v, int firs
     nL += __popcll(bl);
     nR += __popcll(br);
   }
-  sel_wave_sync();
+  wave_sync();
   const int m = min(nL, nR);
   int K = 0;
   int a0 = 0, b0 = 0;  // the lane's pair of the first chunk stays in registers for the swap
@@ -1183,7 +1026,7 @@ __device__ __forceinline__ int group_two_pointer_partition(uint32_t *v, int firs
     v[a] = v[b];
     v[b] = t;
   }
-  sel_wave_sync();
+  wave_sync();
   *out_nR = nR;
   *out_cut = cut;
   return K;
@@ -1208,12 +1051,12 @@ __device__ __forceinline__ int group_retain_best(uint32_t *v, int len, int n_poi
       if (kp_gt(va, vb)) pick = kp_gt(vb, vc) ? ib : (kp_gt(va, vc) ? ic : ia);
       else pick = kp_gt(va, vc) ? ia : (kp_gt(vb, vc) ? ic : ib);
       const uint32_t vp = pick == ia ? va : (pick == ib ? vb : vc);
-      sel_wave_sync();  // all lanes have read before the exchange is stored
+      wave_sync();  // all lanes have read before the exchange is stored
       if (sub == 0) {
         v[first] = vp;
         v[pick] = vf;
       }
-      sel_wave_sync();
+      wave_sync();
       const uint32_t pv = vp >> 24;
       int nR, cut;
       group_two_pointer_partition<G, IDX>(
@@ -1223,7 +1066,7 @@ __device__ __forceinline__ int group_retain_best(uint32_t *v, int len, int n_poi
       else last = cut;
     }
     if (sub == 0) sel_introselect_from(v, first, nth, last, depth_limit);
-    sel_wave_sync();
+    wave_sync();
   }
   // ---- std::partition(v + n_points, v + len, response >= amb)
   const uint32_t amb = v[n_points - 1] >> 24;
@@ -1234,17 +1077,6 @@ __device__ __forceinline__ int group_retain_best(uint32_t *v, int len, int n_poi
 }
 
 constexpr int kSelCellsPerWave = 64 / kSelGroup;  // 8 cells per wave
-
-// sum over the 64 lanes (all active), result in every lane: DPP adds inside the 16-lane rows, two row broadcasts, one readlane
-__device__ __forceinline__ int sel_wave_sum(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xe, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xc, false);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return __builtin_amdgcn_readlane(v, 63);
-}
 
 // The quota loop of FastDetector::SelectPixels (fast_detector.cc:108-135) for one level, by one wave.  Every pass hands each cell that
 // still has keypoints left min(left, npercell) more, so after any pass a cell holds min(count, S) with S = the npercell values summed
@@ -1262,8 +1094,8 @@ __device__ __forceinline__ int sel_level_quota(const CNT *cnt, int ncells, int c
       sel += min(n, S);
       left += n > S ? 1 : 0;
     }
-    selected = sel_wave_sum(sel);
-    cells_left = sel_wave_sum(left);
+    selected = wave_sum_i32(sel);
+    cells_left = wave_sum_i32(left);
   }
   return S;
 }
@@ -1300,8 +1132,8 @@ __global__ __launch_bounds__(64) void select_cells_kernel(const SelJob *__restri
     s_cnt[c] = static_cast<CNT>(n);
     zeros += n == 0 ? 1 : 0;
   }
-  const int nempty = sel_wave_sum(zeros) - lv.not_run[l];
-  sel_wave_sync();
+  const int nempty = wave_sum_i32(zeros) - lv.not_run[l];
+  wave_sync();
   const int S = sel_level_quota<CNT>(s_cnt, ncells, ncells - nempty, lv.quota[l], lane);
   // ---- G lanes per cell
   const int g = lane / G, sub = lane % G, shift = lane - sub;
@@ -1314,9 +1146,9 @@ __global__ __launch_bounds__(64) void select_cells_kernel(const SelJob *__restri
     uint32_t *list = job.cell_kps + static_cast<size_t>(cbeg + c) * stride;
     uint32_t *v = s_list[g];
     for (int k = sub; k < cnt; k += G) v[k] = list[k];
-    sel_wave_sync();
+    wave_sync();
     nl = group_retain_best<G, CNT>(v, cnt, nsel, s_glr[g], s_glr[g] + cnt, sub, shift);
-    sel_wave_sync();
+    wave_sync();
     for (int k = sub; k < nl; k += G) list[k] = v[k];
   }
   if (sub == 0) job.cell_newlen[cbeg + c] = nl;
@@ -1371,7 +1203,7 @@ __global__ __launch_bounds__(256) void select_pack_kernel(const SelJob *__restri
           const uint32_t *src = job.cell_kps + static_cast<size_t>(cbeg + c) * lv.kp_stride;
           for (int k = 0; k < len; k++) v[dst++] = src[k];
         }
-        sel_wave_sync();
+        wave_sync();
         n = nfts;
         if (nfts > lv.quota[l]) {
           uint16_t *Ls = reinterpret_cast<uint16_t *>(v + lv.fts_cap[l]);
@@ -1384,13 +1216,13 @@ __global__ __launch_bounds__(256) void select_pack_kernel(const SelJob *__restri
           const uint32_t *src = job.cell_kps + static_cast<size_t>(cbeg + c) * lv.kp_stride;
           for (int k = 0; k < len; k++) v[dst++] = src[k];
         }
-        sel_wave_sync();
+        wave_sync();
         n = nfts;
         if (nfts > lv.quota[l]) {
           uint16_t *Ls = reinterpret_cast<uint16_t *>(v + lv.spill_cap[l]);  // (spill_cap <= 65536: positions fit 16 bits)
           n = group_retain_best<64, uint16_t>(v, nfts, lv.quota[l], Ls, Ls + lv.spill_cap[l], lane, 0);
         }
-        sel_wave_sync();
+        wave_sync();
       }
       if (lane == 0) s_n[l] = fits ? n : (n | 0x40000000);  // bit 30: the list lies in the spill area
     } else if (lane == 0) {
@@ -1485,38 +1317,30 @@ __global__ __launch_bounds__(256) void select_pack_kernel(const SelJob *__restri
   }
 }
 
-// diagnostic: retainBest of one list by one thread (tests the libstdc++ restatement against the host calls)
-__global__ __launch_bounds__(kSelThreads) void retain_best_kernel(uint32_t *v, int len, int n_points, int *out_len, int cooperative) {
+// diagnostic: retainBest of one list by ONE WAVE in the forms the selection kernels use (tests the libstdc++ restatement against the
+// host calls).  (The arguments of the two group_retain_best calls are part of what the compiler knows inside select_cells and
+// select_pack: the lane stays the unsigned threadIdx.x.)
+__global__ __launch_bounds__(64) void retain_best_kernel(uint32_t *v, int len, int n_points, int *out_len, int form) {
   __shared__ uint32_t s_v[kSelFts];
   __shared__ uint16_t s_l[kSelFts], s_r[kSelFts];
-  __shared__ int s_wave[kSelWaves];
-  if (cooperative == 1 && len <= kSelFts) {  // the workgroup-cooperative form
-    for (int i = threadIdx.x; i < len; i += kSelThreads) s_v[i] = v[i];
-    __syncthreads();
-    const int n = block_retain_best(s_v, len, n_points, s_l, s_r, s_wave);
-    __syncthreads();
-    for (int i = threadIdx.x; i < len; i += kSelThreads) v[i] = s_v[i];
-    if (threadIdx.x == 0) *out_len = n;
-  } else if (cooperative == 2 && len <= SDVL_CELL_KP_CAP) {  // the lane-group form used per cell (run by the wave's second group: shifted ballots)
+  if (form == 2 && len <= SDVL_CELL_KP_CAP) {  // the lane-group form used per cell (run by the wave's second group: shifted ballots)
     uint8_t *gl = reinterpret_cast<uint8_t *>(s_l), *gr = reinterpret_cast<uint8_t *>(s_r);
-    for (int i = threadIdx.x; i < len; i += kSelThreads) s_v[i] = v[i];
-    __syncthreads();
+    for (int i = threadIdx.x; i < len; i += 64) s_v[i] = v[i];
+    wave_sync();
     if (threadIdx.x >= kSelGroup && threadIdx.x < 2 * kSelGroup) {
       const int n = group_retain_best<kSelGroup, uint8_t>(s_v, len, n_points, gl, gr, threadIdx.x - kSelGroup, kSelGroup);
       if (threadIdx.x == kSelGroup) *out_len = n;
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < len; i += kSelThreads) v[i] = s_v[i];
-  } else if (cooperative == 3 && len <= kSelFts) {            // the one-wave form used for the per-level list
-    for (int i = threadIdx.x; i < len; i += kSelThreads) s_v[i] = v[i];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      const int n = group_retain_best<64, uint16_t>(s_v, len, n_points, s_l, s_r, threadIdx.x, 0);
-      if (threadIdx.x == 0) *out_len = n;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < len; i += kSelThreads) v[i] = s_v[i];
-  } else if (threadIdx.x == 0) {        // one lane
+    wave_sync();
+    for (int i = threadIdx.x; i < len; i += 64) v[i] = s_v[i];
+  } else if (form == 3 && len <= kSelFts) {    // the one-wave form used for the per-level list
+    for (int i = threadIdx.x; i < len; i += 64) s_v[i] = v[i];
+    wave_sync();
+    const int n = group_retain_best<64, uint16_t>(s_v, len, n_points, s_l, s_r, threadIdx.x, 0);
+    if (threadIdx.x == 0) *out_len = n;
+    wave_sync();
+    for (int i = threadIdx.x; i < len; i += 64) v[i] = s_v[i];
+  } else if (threadIdx.x == 0) {               // one lane
     *out_len = sel_retain_best(v, len, n_points);
   }
 }
@@ -1556,18 +1380,11 @@ int sdvl_pyramid_build(sdvl_ctx *ctx, int n, sdvl_frame *const *frames) {
   return SDVL_OK;
 }
 
-int sdvl_fast_num_cells(int width, int height, const sdvl_detect_params *p, int *cells_per_level, int *total) {
-  if (!p || p->cell_size <= 0 || p->max_fast_levels < 1 || p->max_fast_levels > 4) return SDVL_ERR_INVALID;
-  int w = width, h = height, tot = 0;
-  for (int l = 0; l < p->max_fast_levels; l++) {
-    const int wc = (w + p->cell_size - 1) / p->cell_size, hc = (h + p->cell_size - 1) / p->cell_size;
-    if (cells_per_level) cells_per_level[l] = wc * hc;
-    tot += wc * hc;
-    w /= 2;
-    h /= 2;
-  }
-  if (total) *total = tot;
-  return SDVL_OK;
+int sdvl_cell_kp_cap(int cell_size) {
+  if (cell_size < 8 || cell_size > SDVL_MAX_CELL_SIZE) return 0;
+  if (cell_size <= 32) return SDVL_CELL_KP_CAP;
+  const int half = (cell_size - 6 + 1) / 2;  // tested pixels per row, every second one at most survives the suppression
+  return half * half;
 }
 
 // Detection scratch of one batch slot: the per-cell FAST lists and counts, the lengths after the per-cell retainBest and the spill area
@@ -1599,23 +1416,6 @@ static int detect_scratch(sdvl_ctx *ctx, int n, const DetectSlot &L, uint8_t **b
   return SDVL_OK;
 }
 
-int sdvl_cell_kp_cap(int cell_size) {
-  if (cell_size < 8 || cell_size > SDVL_MAX_CELL_SIZE) return 0;
-  if (cell_size <= 32) return SDVL_CELL_KP_CAP;
-  const int half = (cell_size - 6 + 1) / 2;  // tested pixels per row, every second one at most survives the suppression
-  return half * half;
-}
-
-int64_t sdvl_detect_scratch_bytes(int width, int height, const sdvl_detect_params *p) {
-  int total = 0, per_level[4] = {0, 0, 0, 0};
-  if (sdvl_fast_num_cells(width, height, p, per_level, &total) != SDVL_OK) return -1;
-  const int kp_cap = sdvl_cell_kp_cap(p->cell_size);
-  if (kp_cap == 0) return -1;
-  size_t spill_words = 0;
-  for (int l = 0; l < p->max_fast_levels; l++) spill_words += 2 * static_cast<size_t>(sel_spill_cap(per_level[l]));
-  return static_cast<int64_t>(detect_slot_layout(total, kp_cap, spill_words).bytes);
-}
-
 // the share (of 64) of a cell's probed pixels that must pass the compass test for the cell to take the dense path
 // (SDVL_FAST_DENSE_NUM: 0 = every cell dense, 64 = every cell through the candidate list; A/B and the sweep of profiles/r05)
 static int fast_cells_dense_num() {
@@ -1627,6 +1427,131 @@ static int fast_cells_dense_num() {
     return n < 0 ? 0 : (n > 64 ? 64 : n);
   }();
   return v;
+}
+
+// The detection grid of one frame shape worked out ONCE: what the FAST and selection kernels are told about it, the sizes of their
+// launches and the scratch of a batch slot.  Lives on the caller's stack.
+struct DetectPlan {
+  FastLevels lv;
+  SelLevels sl;
+  int total_cells, kp_cap;
+  int n_slices;     // select_cells: waves per frame
+  int sel_form;     // select_cells: 0 = cells <= 32 px and levels of <= kSelMaxCells cells, 1 = such cells in larger levels, 2 = cells of 33 .. 64 px
+  size_t pack_lds;  // select_pack: dynamic LDS of the levels' lists (the bins' histogram comes on top)
+  DetectSlot slot;
+};
+
+// Arithmetic only, refuses nothing (detect_plan_frames does): lw / lh = the sizes of the p->max_fast_levels (1 .. 4) pyramid levels,
+// p->cell_size > 0; nfeatures = -1: no selection follows, the quotas stay 0.
+static DetectPlan detect_plan(const int *lw, const int *lh, const sdvl_detect_params *p, int nfeatures) {
+  DetectPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  FastLevels &lv = pl.lv;
+  SelLevels &sl = pl.sl;
+  const int cs = p->cell_size, margin = p->margin;
+  lv.n_levels = sl.n_levels = p->max_fast_levels;
+  lv.cell_size = sl.cell_size = cs;
+  lv.margin = sl.margin = margin;
+  lv.threshold = p->fast_threshold < 0 ? 0 : (p->fast_threshold > 255 ? 255 : p->fast_threshold);
+  lv.dense_num = fast_cells_dense_num();
+  pl.kp_cap = sl.kp_stride = sdvl_cell_kp_cap(cs);
+  // level quotas, fast_detector.cc:161-174
+  const double scale = 1.2;
+  double factor = 1.0, val = 0.0;
+  for (int i = 0; i < lv.n_levels; i++) { val += factor; factor /= scale; }
+  int levelfeatures = nfeatures < 0 ? 0 : static_cast<int>(nfeatures / val);
+  int max_cells = 0;
+  for (int l = 0; l < lv.n_levels; l++) {
+    lv.wcells[l] = sl.wcells[l] = (lw[l] + cs - 1) / cs;
+    sl.hcells[l] = (lh[l] + cs - 1) / cs;
+    max_cells = std::max(max_cells, sl.wcells[l] * sl.hcells[l]);
+  }
+  pl.sel_form = cs > kTile ? 2 : (max_cells > kSelMaxCells ? 1 : 0);
+  const int sel_cells_per_wave = pl.sel_form == 2 ? 1 : kSelCellsPerWave;
+  size_t spill_words = 0;
+  for (int l = 0; l < lv.n_levels; l++) {
+    const int ncells = sl.wcells[l] * sl.hcells[l];
+    lv.cell_begin[l] = sl.cell_begin[l] = pl.total_cells;
+    pl.total_cells += ncells;
+    sl.quota[l] = levelfeatures;
+    levelfeatures = static_cast<int>(levelfeatures / scale);
+    // cells whose ROI the margin swallows (cv::FAST is never called on them, fast_detector.cc:84-94): a cell runs when its row of
+    // cells and its column of cells both keep pixels
+    int rows_run = 0, cols_run = 0;
+    for (int ci = 0; ci < sl.hcells[l]; ci++) rows_run += std::min(lh[l] - margin, ci * cs + cs) > std::max(margin, ci * cs) ? 1 : 0;
+    for (int cj = 0; cj < sl.wcells[l]; cj++) cols_run += std::min(lw[l] - margin, cj * cs + cs) > std::max(margin, cj * cs) ? 1 : 0;
+    sl.not_run[l] = ncells - rows_run * cols_run;
+    sl.slice_begin[l] = pl.n_slices;
+    pl.n_slices += (ncells + sel_cells_per_wave - 1) / sel_cells_per_wave;
+    // LDS entries of the level's concatenated list in select_pack: the quota loop selects < quota + cells, ties that the per-cell
+    // retainBest keeps come on top (half as many again; a longer list is worked on in HBM)
+    sl.fts_cap[l] = std::min(kSelFts, ((sl.quota[l] + ncells) * 3 / 2 + 63) / 64 * 64);
+    pl.pack_lds += static_cast<size_t>(sl.fts_cap[l]) * 8;
+    sl.spill_cap[l] = sel_spill_cap(ncells);
+    sl.spill_off[l] = static_cast<int>(spill_words);
+    spill_words += 2 * static_cast<size_t>(sl.spill_cap[l]);
+  }
+  lv.cell_begin[lv.n_levels] = sl.cell_begin[sl.n_levels] = pl.total_cells;
+  sl.slice_begin[sl.n_levels] = pl.n_slices;
+  pl.slot = detect_slot_layout(pl.total_cells, pl.kp_cap, spill_words);
+  return pl;
+}
+
+// the plan of a bare frame size (levels halve as the pyramid's do), for the two size queries: as permissive as they have always been
+static bool detect_plan_size(int width, int height, const sdvl_detect_params *p, DetectPlan *pl) {
+  if (!p || p->cell_size <= 0 || p->max_fast_levels < 1 || p->max_fast_levels > 4) return false;
+  int lw[4], lh[4];
+  for (int l = 0, w = width, h = height; l < p->max_fast_levels; l++, w /= 2, h /= 2) {
+    lw[l] = w;
+    lh[l] = h;
+  }
+  *pl = detect_plan(lw, lh, p, -1);
+  return true;
+}
+
+int sdvl_fast_num_cells(int width, int height, const sdvl_detect_params *p, int *cells_per_level, int *total) {
+  DetectPlan pl;
+  if (!detect_plan_size(width, height, p, &pl)) return SDVL_ERR_INVALID;
+  for (int l = 0; l < pl.lv.n_levels && cells_per_level; l++) cells_per_level[l] = pl.lv.cell_begin[l + 1] - pl.lv.cell_begin[l];
+  if (total) *total = pl.total_cells;
+  return SDVL_OK;
+}
+
+int64_t sdvl_detect_scratch_bytes(int width, int height, const sdvl_detect_params *p) {
+  DetectPlan pl;
+  if (!detect_plan_size(width, height, p, &pl) || pl.kp_cap == 0) return -1;
+  return static_cast<int64_t>(pl.slot.bytes);
+}
+
+// the plan of a batch of frames, with every refusal the detection launches have (n >= 1)
+static int detect_plan_frames(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_detect_params *p, int nfeatures, DetectPlan *pl) {
+  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= SDVL_MAX_CELL_SIZE, "cell_size must be in [8,64]");
+  SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "max_fast_levels must be in [1,4]");
+  SDVL_REQUIRE(ctx, p->margin >= 0, "margin must not be negative");
+  for (int i = 0; i < n; i++)
+    SDVL_REQUIRE(ctx, frames[i] && frames[i]->width == frames[0]->width && frames[i]->height == frames[0]->height &&
+                          frames[i]->v.levels == frames[0]->v.levels,
+                 "frames of one batch must share size and pyramid depth");
+  SDVL_REQUIRE(ctx, p->max_fast_levels <= frames[0]->v.levels, "max_fast_levels exceeds the pyramid depth");
+  *pl = detect_plan(frames[0]->v.lw, frames[0]->v.lh, p, nfeatures);
+  for (int l = 0; l < pl->lv.n_levels; l++)  // (sdvl_keypoint::cell is 16-bit; the count arrays of select_cells)
+    SDVL_REQUIRE(ctx, pl->lv.cell_begin[l + 1] - pl->lv.cell_begin[l] <= SDVL_MAX_LEVEL_CELLS,
+                 "too many cells in one level (8192: at most 3840x2160 at cell 32)");
+  return SDVL_OK;
+}
+
+// frame f's FAST job on the batch slot at `slot`
+static FastJob fast_job(const DetectPlan &pl, const sdvl_frame *f, uint8_t *slot) {
+  FastJob j;
+  memset(&j, 0, sizeof(j));
+  for (int l = 0; l < pl.lv.n_levels; l++) {
+    j.level[l] = f->v.level[l];
+    j.lw[l] = f->v.lw[l];
+    j.lh[l] = f->v.lh[l];
+  }
+  j.cell_kps = reinterpret_cast<uint32_t *>(slot + pl.slot.kps_off);
+  j.cell_counts = reinterpret_cast<int32_t *>(slot + pl.slot.counts_off);
+  return j;
 }
 
 // the per-cell geometry table of fast_cells_kernel for this frame shape and grid, built once and kept in HBM
@@ -1676,75 +1601,46 @@ static int fast_cell_table(sdvl_ctx *ctx, const FastLevels &lv, const sdvl_frame
   return SDVL_OK;
 }
 
+// per-cell FAST of n frames (jobs in device memory): one wave per cell, in the form the cell size asks for
+static int fast_launch(sdvl_ctx *ctx, const DetectPlan &pl, int n, sdvl_frame *const *frames, const FastJob *jobs) {
+  const CellGeo *d_cells = nullptr;
+  const int rc = fast_cell_table(ctx, pl.lv, frames[0], &d_cells);
+  if (rc) return rc;
+  const dim3 grid((pl.total_cells + 31) / 32 * 32, n);
+  if (pl.lv.cell_size <= kTile) SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, grid, dim3(64), jobs, pl.lv, d_cells);
+  else SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wide_kernel, grid, dim3(64), jobs, pl.lv, d_cells, pl.kp_cap);
+  return SDVL_OK;
+}
+
 int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_detect_params *p, int cap,
                     sdvl_keypoint *out_kps, int32_t *out_cell_offsets) {
   if (!ctx || !p || n < 0 || (n > 0 && (!frames || !out_kps || !out_cell_offsets))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= SDVL_MAX_CELL_SIZE, "cell_size must be in [8,64]");
-  SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "max_fast_levels must be in [1,4]");
-  SDVL_REQUIRE(ctx, p->margin >= 0 && cap > 0, "bad margin / capacity");
-  const int kp_cap = sdvl_cell_kp_cap(p->cell_size);
-  const int W = frames[0]->width, H = frames[0]->height;
-  FastLevels lv;
-  memset(&lv, 0, sizeof(lv));
-  lv.n_levels = p->max_fast_levels;
-  lv.cell_size = p->cell_size;
-  lv.margin = p->margin;
-  lv.threshold = p->fast_threshold < 0 ? 0 : (p->fast_threshold > 255 ? 255 : p->fast_threshold);
-  lv.dense_num = fast_cells_dense_num();
-  int total_cells = 0;
-  for (int l = 0; l < lv.n_levels; l++) {
-    SDVL_REQUIRE(ctx, l < frames[0]->v.levels, "max_fast_levels exceeds the pyramid depth");
-    const int w = frames[0]->v.lw[l], h = frames[0]->v.lh[l];
-    lv.cell_begin[l] = total_cells;
-    lv.wcells[l] = (w + p->cell_size - 1) / p->cell_size;
-    const int ncells = lv.wcells[l] * ((h + p->cell_size - 1) / p->cell_size);
-    SDVL_REQUIRE(ctx, ncells <= SDVL_MAX_LEVEL_CELLS, "too many cells in one level (8192: at most 3840x2160 at cell 32)");  // (sdvl_keypoint::cell is 16-bit)
-    total_cells += ncells;
-  }
-  lv.cell_begin[lv.n_levels] = total_cells;
-  for (int i = 0; i < n; i++)
-    SDVL_REQUIRE(ctx, frames[i] && frames[i]->width == W && frames[i]->height == H && frames[i]->v.levels == frames[0]->v.levels,
-                 "frames of one batch must share size and pyramid depth");
-  const DetectSlot slot = detect_slot_layout(total_cells, kp_cap, 2 * kSelFts * static_cast<size_t>(lv.n_levels));  // (no selection here)
+  SDVL_REQUIRE(ctx, cap > 0, "capacity must be positive");
+  DetectPlan pl;
+  int rc = detect_plan_frames(ctx, n, frames, p, -1, &pl);
+  if (rc) return rc;
+  const FastLevels &lv = pl.lv;
+  const int total_cells = pl.total_cells;
   uint8_t *scratch = nullptr;
-  {
-    const int rc_s = detect_scratch(ctx, n, slot, &scratch);
-    if (rc_s) return rc_s;
-  }
+  rc = detect_scratch(ctx, n, pl.slot, &scratch);
+  if (rc) return rc;
   const size_t job_bytes = sizeof(FastJob) * n;
   const size_t offs_bytes = sizeof(int32_t) * static_cast<size_t>(n) * (total_cells + 1);
   const size_t kps_bytes = sizeof(uint32_t) * static_cast<size_t>(n) * cap;
   void *hs = nullptr, *dsx = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, offs_bytes + kps_bytes, false);
+  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, offs_bytes + kps_bytes, false);
   if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, offs_bytes + kps_bytes, true);
   if (!rc) rc = sdvl_stage_alloc(ctx, job_bytes, &hs, &dsx);
   if (rc) return rc;
   FastJob *hj = static_cast<FastJob *>(hs);
-  for (int i = 0; i < n; i++) {
-    memset(&hj[i], 0, sizeof(FastJob));
-    for (int l = 0; l < lv.n_levels; l++) {
-      hj[i].level[l] = frames[i]->v.level[l];
-      hj[i].lw[l] = frames[i]->v.lw[l];
-      hj[i].lh[l] = frames[i]->v.lh[l];
-    }
-    hj[i].cell_kps = reinterpret_cast<uint32_t *>(scratch + slot.bytes * i + slot.kps_off);
-    hj[i].cell_counts = reinterpret_cast<int32_t *>(scratch + slot.bytes * i + slot.counts_off);
-  }
+  for (int i = 0; i < n; i++) hj[i] = fast_job(pl, frames[i], scratch + pl.slot.bytes * i);
   SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hj, job_bytes));
   int32_t *d_offs = static_cast<int32_t *>(ctx->d_out);
   uint32_t *d_kps = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->d_out) + offs_bytes);
-  const CellGeo *d_cells = nullptr;
-  {
-    const int rc_t = fast_cell_table(ctx, lv, frames[0], &d_cells);
-    if (rc_t) return rc_t;
-  }
-  if (lv.cell_size <= kTile)
-    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), static_cast<const FastJob *>(dsx), lv, d_cells);
-  else
-    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wide_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), static_cast<const FastJob *>(dsx), lv, d_cells,
-                kp_cap);
-  SDVL_LAUNCH(ctx, "compact_cells", compact_cells_kernel, dim3(n), dim3(256), static_cast<const FastJob *>(dsx), total_cells, cap, d_kps, d_offs, kp_cap);
+  rc = fast_launch(ctx, pl, n, frames, static_cast<const FastJob *>(dsx));
+  if (rc) return rc;
+  SDVL_LAUNCH(ctx, "compact_cells", compact_cells_kernel, dim3(n), dim3(256), static_cast<const FastJob *>(dsx), total_cells, cap, d_kps, d_offs, pl.kp_cap);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   int32_t *h_offs = static_cast<int32_t *>(ctx->h_out);
   uint32_t *h_kps = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->h_out) + offs_bytes);
@@ -1790,96 +1686,35 @@ int sdvl_fast_cells(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_
 int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const sdvl_detect_params *p, int nfeatures) {
   if (!ctx || !p || n < 0 || (n > 0 && !frames)) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, p->cell_size >= 8 && p->cell_size <= SDVL_MAX_CELL_SIZE, "cell_size must be in [8,64]");
-  SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "max_fast_levels must be in [1,4]");
-  SDVL_REQUIRE(ctx, p->margin >= 0 && nfeatures >= 0, "bad margin / nfeatures");
-  const int kp_cap = sdvl_cell_kp_cap(p->cell_size);
-  const int W = frames[0]->width, H = frames[0]->height;
-  FastLevels lv;
-  SelLevels sl;
-  memset(&lv, 0, sizeof(lv));
-  memset(&sl, 0, sizeof(sl));
-  lv.n_levels = sl.n_levels = p->max_fast_levels;
-  lv.cell_size = sl.cell_size = p->cell_size;
-  lv.margin = sl.margin = p->margin;
-  lv.threshold = p->fast_threshold < 0 ? 0 : (p->fast_threshold > 255 ? 255 : p->fast_threshold);
-  lv.dense_num = fast_cells_dense_num();
-  // level quotas, fast_detector.cc:161-174
-  const double scale = 1.2;
-  double factor = 1.0, val = 0.0;
-  for (int i = 0; i < p->max_fast_levels; i++) { val += factor; factor /= scale; }
-  int levelfeatures = static_cast<int>(nfeatures / val);
-  int total_cells = 0, n_slices = 0;
-  size_t pack_lds = 0, spill_words = 0;
-  sl.kp_stride = kp_cap;
-  // the select_cells form: level 0 is the largest level
-  const int cells0 = ((frames[0]->v.lw[0] + p->cell_size - 1) / p->cell_size) * ((frames[0]->v.lh[0] + p->cell_size - 1) / p->cell_size);
-  SDVL_REQUIRE(ctx, cells0 <= SDVL_MAX_LEVEL_CELLS, "too many cells in one level for the selection kernel (8192: at most 3840x2160 at cell 32)");
-  const int sel_form = p->cell_size > kTile ? 2 : (cells0 > kSelMaxCells ? 1 : 0);
-  const int sel_cells_per_wave = sel_form == 2 ? 1 : kSelCellsPerWave;
-  for (int l = 0; l < lv.n_levels; l++) {
-    SDVL_REQUIRE(ctx, l < frames[0]->v.levels, "max_fast_levels exceeds the pyramid depth");
-    const int w = frames[0]->v.lw[l], h = frames[0]->v.lh[l];
-    lv.cell_begin[l] = sl.cell_begin[l] = total_cells;
-    lv.wcells[l] = sl.wcells[l] = (w + p->cell_size - 1) / p->cell_size;
-    sl.hcells[l] = (h + p->cell_size - 1) / p->cell_size;
-    const int ncells = sl.wcells[l] * sl.hcells[l];
-    total_cells += ncells;
-    sl.quota[l] = levelfeatures;
-    levelfeatures = static_cast<int>(levelfeatures / scale);
-    // cells whose ROI the margin swallows (cv::FAST is never called on them, fast_detector.cc:84-94)
-    int not_run = 0;
-    for (int ci = 0; ci < sl.hcells[l]; ci++)
-      for (int cj = 0; cj < sl.wcells[l]; cj++) {
-        const bool ran = std::min(h - p->margin, ci * p->cell_size + p->cell_size) > std::max(p->margin, ci * p->cell_size) &&
-                         std::min(w - p->margin, cj * p->cell_size + p->cell_size) > std::max(p->margin, cj * p->cell_size);
-        not_run += ran ? 0 : 1;
-      }
-    sl.not_run[l] = not_run;
-    sl.slice_begin[l] = n_slices;
-    n_slices += (ncells + sel_cells_per_wave - 1) / sel_cells_per_wave;
-    // LDS entries of the level's concatenated list in select_pack: the quota loop selects < quota + cells, ties that the per-cell
-    // retainBest keeps come on top (half as many again; a longer list is worked on in HBM)
-    sl.fts_cap[l] = std::min(kSelFts, ((sl.quota[l] + ncells) * 3 / 2 + 63) / 64 * 64);
-    pack_lds += static_cast<size_t>(sl.fts_cap[l]) * 8;
-    sl.spill_cap[l] = sel_spill_cap(ncells);
-    sl.spill_off[l] = static_cast<int>(spill_words);
-    spill_words += 2 * static_cast<size_t>(sl.spill_cap[l]);
-  }
-  lv.cell_begin[lv.n_levels] = sl.cell_begin[sl.n_levels] = total_cells;
-  sl.slice_begin[sl.n_levels] = n_slices;
-  for (int i = 0; i < n; i++)
-    SDVL_REQUIRE(ctx, frames[i] && frames[i]->width == W && frames[i]->height == H && frames[i]->v.levels == frames[0]->v.levels,
-                 "frames of one batch must share size and pyramid depth");
-  const DetectSlot slot = detect_slot_layout(total_cells, kp_cap, spill_words);
+  SDVL_REQUIRE(ctx, nfeatures >= 0, "nfeatures must not be negative");
+  DetectPlan pl;
+  int rc = detect_plan_frames(ctx, n, frames, p, nfeatures, &pl);
+  if (rc) return rc;
+  const SelLevels &sl = pl.sl;
   uint8_t *scratch = nullptr;
-  {
-    const int rc_s = detect_scratch(ctx, n, slot, &scratch);
-    if (rc_s) return rc_s;
-  }
-  pack_lds += (static_cast<size_t>(std::max(1, frames[0]->bin_cells)) * 4 + 15) / 16 * 16;
+  rc = detect_scratch(ctx, n, pl.slot, &scratch);
+  if (rc) return rc;
+  const size_t pack_lds = pl.pack_lds + (static_cast<size_t>(std::max(1, frames[0]->bin_cells)) * 4 + 15) / 16 * 16;
   const size_t fj_bytes = (sizeof(FastJob) * n + 255) / 256 * 256, sj_bytes = sizeof(SelJob) * n;
   void *hst = nullptr, *dst = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_counts, &ctx->d_counts_bytes, sizeof(int32_t) * n, false);
+  rc = sdvl_ensure(ctx, &ctx->d_counts, &ctx->d_counts_bytes, sizeof(int32_t) * n, false);
   if (!rc) rc = sdvl_stage_alloc(ctx, fj_bytes + sj_bytes, &hst, &dst);
   if (rc) return rc;
   ctx->detect_frames.assign(frames, frames + n);
   FastJob *hf = static_cast<FastJob *>(hst);
   SelJob *hs = reinterpret_cast<SelJob *>(static_cast<uint8_t *>(hst) + fj_bytes);
   for (int i = 0; i < n; i++) {
-    memset(&hf[i], 0, sizeof(FastJob));
+    uint8_t *sb = scratch + pl.slot.bytes * i;
+    hf[i] = fast_job(pl, frames[i], sb);
     memset(&hs[i], 0, sizeof(SelJob));
-    for (int l = 0; l < lv.n_levels; l++) {
-      hf[i].level[l] = frames[i]->v.level[l];
-      hf[i].lw[l] = hs[i].lw[l] = frames[i]->v.lw[l];
-      hf[i].lh[l] = hs[i].lh[l] = frames[i]->v.lh[l];
+    for (int l = 0; l < sl.n_levels; l++) {
+      hs[i].lw[l] = frames[i]->v.lw[l];
+      hs[i].lh[l] = frames[i]->v.lh[l];
     }
-    uint8_t *sb = scratch + slot.bytes * i;
-    hf[i].cell_kps = hs[i].cell_kps = reinterpret_cast<uint32_t *>(sb + slot.kps_off);
-    hf[i].cell_counts = reinterpret_cast<int32_t *>(sb + slot.counts_off);
+    hs[i].cell_kps = hf[i].cell_kps;
     hs[i].cell_counts = hf[i].cell_counts;
-    hs[i].cell_newlen = reinterpret_cast<int32_t *>(sb + slot.newlen_off);
-    hs[i].spill = reinterpret_cast<uint32_t *>(sb + slot.spill_off);
+    hs[i].cell_newlen = reinterpret_cast<int32_t *>(sb + pl.slot.newlen_off);
+    hs[i].spill = reinterpret_cast<uint32_t *>(sb + pl.slot.spill_off);
     hs[i].corner_cap = frames[i]->corner_cap;
     hs[i].corner_hdr = frames[i]->v.corner_hdr;
     hs[i].bin_start = frames[i]->bin_start;
@@ -1894,22 +1729,15 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
   SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dst, hst, fj_bytes + sj_bytes));
   const FastJob *df = static_cast<const FastJob *>(dst);
   const SelJob *ds = reinterpret_cast<const SelJob *>(static_cast<uint8_t *>(dst) + fj_bytes);
-  const CellGeo *d_cells = nullptr;
-  {
-    const int rc_t = fast_cell_table(ctx, lv, frames[0], &d_cells);
-    if (rc_t) return rc_t;
-  }
-  const dim3 sel_grid(static_cast<unsigned>((n + 7) / 8 * 8 * n_slices));
-  if (sel_form == 2) {
-    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wide_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), df, lv, d_cells, kp_cap);
+  rc = fast_launch(ctx, pl, n, frames, df);
+  if (rc) return rc;
+  const dim3 sel_grid(static_cast<unsigned>((n + 7) / 8 * 8 * pl.n_slices));
+  if (pl.sel_form == 2)
     SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint16_t, kWideCellCap, SDVL_MAX_LEVEL_CELLS, 64>), sel_grid, dim3(64), ds, sl, n);
-  } else {
-    SDVL_LAUNCH(ctx, "fast_cells", fast_cells_wave_kernel, dim3((total_cells + 31) / 32 * 32, n), dim3(64), df, lv, d_cells);
-    if (sel_form == 0)
-      SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint8_t, SDVL_CELL_KP_CAP, kSelMaxCells, kSelGroup>), sel_grid, dim3(64), ds, sl, n);
-    else
-      SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint8_t, SDVL_CELL_KP_CAP, SDVL_MAX_LEVEL_CELLS, kSelGroup>), sel_grid, dim3(64), ds, sl, n);
-  }
+  else if (pl.sel_form == 0)
+    SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint8_t, SDVL_CELL_KP_CAP, kSelMaxCells, kSelGroup>), sel_grid, dim3(64), ds, sl, n);
+  else
+    SDVL_LAUNCH(ctx, "select_cells", (select_cells_kernel<uint8_t, SDVL_CELL_KP_CAP, SDVL_MAX_LEVEL_CELLS, kSelGroup>), sel_grid, dim3(64), ds, sl, n);
   // the counts follow the kernels to the host without anyone waiting for them (see sdvl_frames_corner_counts): the pack kernel
   // writes them into device memory and, when results go direct, into the pinned host array as well
   const bool direct = sdvl_ensure(ctx, &ctx->h_counts, &ctx->h_counts_bytes, sizeof(int32_t) * n, true) == SDVL_OK;
@@ -2017,6 +1845,8 @@ int sdvl_frames_corner_counts(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, i
 // diagnostic: cv::KeyPointsFilter::retainBest on packed keypoints (score = top byte) by the device restatement
 int sdvl_retain_best(sdvl_ctx *ctx, uint32_t *packed, int len, int n_points, int cooperative, int *out_len) {
   if (!ctx || !packed || !out_len || len < 0 || len > (1 << 20)) return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, cooperative == 0 || cooperative == 2 || cooperative == 3,
+               "retain_best form must be 0 (one lane), 2 (lane group) or 3 (one wave): the workgroup form 1 was retired");
   if (len == 0) { *out_len = 0; return SDVL_OK; }
   const size_t bytes = sizeof(uint32_t) * len + 64;
   int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, bytes, false);
@@ -2025,7 +1855,7 @@ int sdvl_retain_best(sdvl_ctx *ctx, uint32_t *packed, int len, int n_points, int
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
   memcpy(static_cast<uint8_t *>(ctx->h_out) + 64, packed, sizeof(uint32_t) * len);
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_out, ctx->h_out, bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(retain_best_kernel, dim3(1), dim3(kSelThreads), 0, ctx->stream,
+  hipLaunchKernelGGL(retain_best_kernel, dim3(1), dim3(64), 0, ctx->stream,
                      reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->d_out) + 64), len, n_points, static_cast<int *>(ctx->d_out), cooperative);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));

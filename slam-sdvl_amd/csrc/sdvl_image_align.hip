@@ -16,6 +16,7 @@
 #include "sdvl_internal.h"
 #include "sdvl_math.h"
 #include "sdvl_search_types.h"
+#include "sdvl_wave.h"
 
 namespace {
 
@@ -79,12 +80,6 @@ __device__ __forceinline__ double wave_reduce_n(double *v, int lane) {
     }
   }
   return v[0];
-}
-
-__device__ __forceinline__ void ia_wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // bytes [0, 8) of the row that starts at p (any alignment), from aligned dwords; `need` = how many of them the caller uses
@@ -413,7 +408,7 @@ __device__ __forceinline__ void ia_wave_body(const IaIn job, const Feats F, cons
     for (int it = 0; it < prm.max_its; it++) {
       const int b = eval & 1;
       eval++;
-      ia_wave_fence();
+      wave_sync();
       M3 R;
       V3 Tt;
       {
@@ -510,7 +505,7 @@ __device__ __forceinline__ void ia_wave_body(const IaIn job, const Feats F, cons
         if ((lane & 7) == 0) s_red[b][wave][(lane >> 3) & 7] = tot;
         if (lane == 0) s_chg[b][wave] = any_chg ? 1 : 0;
       }
-      if (kWaves > 1) __syncthreads(); else ia_wave_fence();
+      if (kWaves > 1) __syncthreads(); else wave_sync();
       double Jres[6], sum_c2 = 0.0, sum_n = 0.0;
       bool changed = false;
       {
@@ -547,7 +542,7 @@ __device__ __forceinline__ void ia_wave_body(const IaIn job, const Feats F, cons
         const double t8 = wave_reduce_n<8>(h8, lane);
         if ((lane & 3) == 0) s_redH[wave][(lane >> 2) & 15] = t16;
         if ((lane & 7) == 0) s_redH[wave][16 + ((lane >> 3) & 7)] = t8;
-        if (kWaves > 1) __syncthreads(); else ia_wave_fence();
+        if (kWaves > 1) __syncthreads(); else wave_sync();
         double Hm[36];
         {
           int k = 0;
@@ -575,7 +570,7 @@ __device__ __forceinline__ void ia_wave_body(const IaIn job, const Feats F, cons
 #pragma unroll
           for (int q = 0; q < 6; q++) s_tr[wave][q] = tr[q];
         }
-        ia_wave_fence();
+        wave_sync();
       }
       IA_STAMP(4);
       // ---- Optimize body, image_align.cc:93-124 (every lane, uniform values)
@@ -614,7 +609,7 @@ __device__ __forceinline__ void ia_wave_body(const IaIn job, const Feats F, cons
         for (int r = 0; r < 6; r++) mx[r] = -xs[r];
         const Rigid T0 = se3_from7(s_T[wave]);
         const Rigid T1 = se3_mul(T0, ia_se3_exp(mx));
-        ia_wave_fence();  // every lane has read T before lane 0 replaces it
+        wave_sync();  // every lane has read T before lane 0 replaces it
         if (lane == 0) {
           se3_to7(T0, s_Tbk[wave]);
           se3_to7(T1, s_T[wave]);
@@ -636,7 +631,7 @@ __device__ __forceinline__ void ia_wave_body(const IaIn job, const Feats F, cons
       break;
     }
   }
-  ia_wave_fence();
+  wave_sync();
   if (tid == 0) {
     sdvl_align_result r;
 #pragma unroll
@@ -726,7 +721,7 @@ __device__ __forceinline__ void ia_pre_body(const uint8_t *ref_img, int W, int H
   const double t8 = wave_reduce_n<8>(h8, lane);
   if ((lane & 3) == 0) s_redH[wave][(lane >> 2) & 15] = t16;
   if ((lane & 7) == 0) s_redH[wave][16 + ((lane >> 3) & 7)] = t8;
-  if (kPreWaves > 1) __syncthreads(); else ia_wave_fence();
+  if (kPreWaves > 1) __syncthreads(); else wave_sync();
   if (wave == 0) {
     double Hm[36];
     int k = 0;

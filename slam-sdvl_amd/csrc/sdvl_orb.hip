@@ -24,8 +24,6 @@ struct OrbJob {
   int levels;
 };
 
-__device__ __forceinline__ int wave_sum_i32(int v) { return orb_wave_sum_i32(v); }
-
 // Blocks b and b + 8 share an XCD (observed placement, used for speed only): the `chunks` workgroups of frame f all run on XCD f % 8, so
 // the windows of neighbouring corners — a 10x10 or 31x31 window touches 10 / 31 lines of 128 B, and the corners of a cell row share
 // them — come out of ONE L2 instead of being fetched into all eight (round 2: shi_tomasi fetched 53 MB for 5.5 MB of windows).

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sdvl_math.h"
+#include "sdvl_wave.h"
 
 namespace {
 
@@ -51,18 +52,6 @@ constexpr OrbMomentTable make_orb_moment_table() {
   return t;
 }
 __constant__ OrbMomentTable c_orb_moments = make_orb_moment_table();
-
-// sum over the 64 lanes (all active), result in every lane: data-parallel-primitive adds inside the 16-lane rows, two row
-// broadcasts, one readlane — 7 VALU instructions instead of 6 x (ds_bpermute + add) with their address arithmetic
-__device__ __forceinline__ int orb_wave_sum_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xe, false);  // row_shr:4, banks 1-3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xc, false);  // row_shr:8, banks 2-3: lane 15 of a row holds the row's sum
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3: lane 63 holds the total
-  return __builtin_amdgcn_readlane(v, 63);
-}
 
 // cv::fastAtan2 (degrees), OpenCV >= 2.4.9 scalar polynomial
 __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
@@ -113,8 +102,8 @@ __device__ __forceinline__ uint32_t orb_wave_nibble(const uint8_t *level, uint32
       m01 += v * sp;
     }
   }
-  m10 = orb_wave_sum_i32(m10);
-  m01 = orb_wave_sum_i32(m01);
+  m10 = wave_sum_i32(m10);
+  m01 = wave_sum_i32(m01);
   const float angle_deg = fast_atan2_deg(static_cast<float>(m01), static_cast<float>(m10));
   const float factorPI = static_cast<float>(M_PI / 180.f);
   const float angle = static_cast<float>(static_cast<double>(angle_deg) * factorPI);
@@ -182,8 +171,8 @@ __device__ __forceinline__ uint32_t orb_wave_nibble_win(const uint32_t *win, int
       m01 += v * sp;
     }
   }
-  m10 = orb_wave_sum_i32(m10);
-  m01 = orb_wave_sum_i32(m01);
+  m10 = wave_sum_i32(m10);
+  m01 = wave_sum_i32(m01);
   const float angle_deg = fast_atan2_deg(static_cast<float>(m01), static_cast<float>(m10));
   const float factorPI = static_cast<float>(M_PI / 180.f);
   const float angle = static_cast<float>(static_cast<double>(angle_deg) * factorPI);

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "sdvl_math.h"
+#include "sdvl_wave.h"
 
 namespace {
 
@@ -183,12 +184,6 @@ __global__ __launch_bounds__(kHypDraws) void pose_hypotheses_kernel(const PoseJo
   dst.supporters = 0;  // counted by pose_refine (lazy supporters)
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Round 6: ONE WAVE per draw, for the sets whose launches leave the chip empty (a lone camera: sets of <= 4 trackers; configuration C's
 // groups of 16 — 1600 such waves per launch, four groups at a time — lose 10 % on it and keep the lane form).  The lane
 // form above makes a draw a chain of ~27 k dependent vector instructions (five points one after the other, the pivoted LDLT with every
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(64) void pose_hypotheses_wave_kernel(const PoseJobD
         L.errs[lane] = sqrt(ex * ex + ey * ey);
       }
     }
-    wave_lds_sync();
+    wave_sync();
     // GetMedianVector: element floor(n/2) of the sorted order (extra/utils.cc:215-220) — the insertion sort of converge_pose_small
     // with every index a compile-time constant (the moves predicated), uniform across the wave
     double errs[8];
@@ -279,14 +274,14 @@ __global__ __launch_bounds__(64) void pose_hypotheses_wave_kernel(const PoseJobD
       if (i == 5) scale = 0.85 / prm.fx;
       const M3 R = se3_rot(se3);
       if (mine) hyp_terms(o, R, se3.t, scale, L.terms[lane]);
-      wave_lds_sync();
+      wave_sync();
       if (lane < 28) {
         const bool neg = lane >= 21 && lane < 27;  // b accumulates with -= in the reference, and x - t == x + (-t) exactly
         double acc = 0.0;
         for (int q = 0; q < npts; q++) acc += neg ? -L.terms[q][lane] : L.terms[q][lane];
         L.sums[lane] = acc;
       }
-      wave_lds_sync();
+      wave_sync();
       double A[36], b[6], dT[6];
       {
         int t = 0;
@@ -302,7 +297,7 @@ __global__ __launch_bounds__(64) void pose_hypotheses_wave_kernel(const PoseJobD
 #pragma unroll
       for (int r = 0; r < 6; r++) b[r] = L.sums[21 + r];
       const double new_chi2 = L.sums[27];
-      wave_lds_sync();
+      wave_sync();
       ldlt_solve6_reg<true>(A, b, dT);
       if ((i > 0 && new_chi2 > chi2) || dT[0] != dT[0]) {
         se3 = last;
@@ -502,7 +497,7 @@ __device__ bool converge_pose_wave(RefineLds<kRefWaves> &L, const sdvl_pose_obs 
       L.errs[q] = sqrt(ex * ex + ey * ey);
     }
   }
-  wave_lds_sync();
+  wave_sync();
   // median = element floor(n/2) of the sorted order (what nth_element leaves there)
   const double median = n <= 256 ? wave_kth_smallest<4>(L.errs, n, n / 2, lane) : wave_kth_smallest<RefineLds<kRefWaves>::kObs / 64>(L.errs, n, n / 2, lane);
   double scale = kMADNorm * median;
@@ -553,10 +548,10 @@ __device__ bool converge_pose_wave(RefineLds<kRefWaves> &L, const sdvl_pose_obs 
         }
         for (; j < m; j++) acc += L.terms[j][lane];
       }
-      wave_lds_sync();
+      wave_sync();
     }
     if (lane < 28) L.sums[lane] = acc;
-    wave_lds_sync();
+    wave_sync();
     double A[36], b[6], dT[6];
     {
       int t = 0;
@@ -572,7 +567,7 @@ __device__ bool converge_pose_wave(RefineLds<kRefWaves> &L, const sdvl_pose_obs 
 #pragma unroll
     for (int r = 0; r < 6; r++) b[r] = L.sums[21 + r];
     const double new_chi2 = L.sums[27];
-    wave_lds_sync();
+    wave_sync();
     ldlt_solve6_reg<true>(A, b, dT);
     if ((i > 0 && new_chi2 > chi2) || dT[0] != dT[0]) {
       *se3 = last;
@@ -704,10 +699,10 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
   res.n_draws = it;
   // ---- final CheckReprojectionError with the best hypothesis -> inliers / outliers (feature_align.cc:215)
   for (int q = lane; q < size; q += 64) L.tmp[q] = static_cast<uint16_t>(q);
-  wave_lds_sync();
+  wave_sync();
   int n_in = 0, n_out = 0;
   check_list(obs, L.tmp, size, best, prm.inlier_threshold, L.inl, &n_in, L.outl, &n_out, lane);
-  wave_lds_sync();
+  wave_sync();
   // ---- OptimizePose(frame): feature_align.cc:73-82
   Rigid pose = se3_from7(job.pose);
   for (int pass = 0; pass < 2; pass++) {
@@ -717,21 +712,21 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
       pose = se3;
       res.refined = 1;
       for (int q = lane; q < n_in; q += 64) L.tmp[q] = L.inl[q];
-      wave_lds_sync();
+      wave_sync();
       const int n_c = n_in;
       n_in = 0;
       check_list(obs, L.tmp, n_c, pose, prm.inlier_threshold, L.inl, &n_in, L.outl, &n_out, lane);
-      wave_lds_sync();
+      wave_sync();
     }
     if (pass == 1) break;
     // RescueOutliers, :232-243
     const int init_in = n_in;
     for (int q = lane; q < n_out; q += 64) L.tmp[q] = L.outl[q];
-    wave_lds_sync();
+    wave_sync();
     const int n_c = n_out;
     n_out = 0;
     check_list(obs, L.tmp, n_c, pose, 2 * prm.inlier_threshold, L.inl, &n_in, L.outl, &n_out, lane);
-    wave_lds_sync();
+    wave_sync();
     if (!(n_in > init_in)) break;
   }
   se3_to7(pose, res.pose);

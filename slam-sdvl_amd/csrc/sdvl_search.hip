@@ -68,15 +68,6 @@ __device__ __forceinline__ float interpolate8u(const uint8_t *img, int stride, f
   return w00 * g[o] + w01 * g[o + st] + w10 * g[o + 1u] + w11 * g[o + st + 1u];
 }
 
-// LDS hand-off between the lanes of ONE wave: order the compiler's view of memory, no s_barrier needed
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) { return orb_wave_sum_i32(v); }  // DPP row adds + row broadcasts (sdvl_orb_device.h)
-
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {

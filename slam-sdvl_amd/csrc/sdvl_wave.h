@@ -1,0 +1,27 @@
+// sdvl_wave.h — the two wave64 primitives that more than one kernel file uses.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+// LDS hand-off between the lanes of ONE wave: order the compiler's view of memory, no s_barrier needed (the lanes of a wave execute
+// their LDS instructions in order)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// sum over the 64 lanes (all active), result in every lane: data-parallel-primitive adds inside the 16-lane rows, two row
+// broadcasts, one readlane — 7 VALU instructions instead of 6 x (ds_bpermute + add) with their address arithmetic
+__device__ __forceinline__ int wave_sum_i32(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xe, false);  // row_shr:4, banks 1-3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xc, false);  // row_shr:8, banks 2-3: lane 15 of a row holds the row's sum
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3: lane 63 holds the total
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
+}  // namespace

@@ -210,7 +210,7 @@ def test_feed_slots_and_own_images(ctx, sdvl, orc, synth):
     fa.close(); fo.close(); feed.close(); ctx.device_free(slot)
 
 
-def test_device_retain_best_is_libstdcxx_order(ctx, orc):
+def test_device_retain_best_is_libstdcxx_order(ctx, sdvl, orc):
     """the device restatement of nth_element + partition leaves the list exactly as libstdc++ does"""
     rng = np.random.default_rng(42)
     cases = []
@@ -231,11 +231,12 @@ def test_device_retain_best_is_libstdcxx_order(ctx, orc):
     for v, k in cases:
         want = orc.retain_best(v, k)
         assert np.array_equal(ctx.retain_best(v, k), want), (len(v), k, "one lane")
-        assert np.array_equal(ctx.retain_best(v, k, cooperative=True), want), (len(v), k, "workgroup")
-        if len(v) <= 176:     # a cell's list: 16 lanes of a wave (the form select_cells uses per cell)
-            assert np.array_equal(ctx.retain_best(v, k, cooperative=2), want), (len(v), k, "16 lanes")
+        if len(v) <= 176:     # a cell's list: 8 lanes of a wave (the form select_cells uses per cell)
+            assert np.array_equal(ctx.retain_best(v, k, cooperative=2), want), (len(v), k, "8 lanes")
         if len(v) <= 4096:    # a level's list: one wave (the form select_pack uses per level)
             assert np.array_equal(ctx.retain_best(v, k, cooperative=3), want), (len(v), k, "one wave")
+    with pytest.raises(sdvl.SdvlError):   # the workgroup form is retired
+        ctx.retain_best(cases[0][0], 3, cooperative=1)
 
 
 @pytest.mark.parametrize("shape,cam,ks", [((480, 640), TUM_CAM, [0, 3, 11]), ((480, 752), EUROC_CAM, [2])])
