@@ -37,6 +37,7 @@ struct ImageAlign {
   double H[6][6];
   double Jres[6];
   int its_per_level[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int evals = 0;  // calls of ComputeResiduals: instrumentation for the tests, the reference has none
 
   const std::vector<Image> *pyr1 = nullptr, *pyr2 = nullptr;
   const std::vector<AlignFeature> *feats = nullptr;
@@ -98,6 +99,7 @@ struct ImageAlign {
     const int half_patch = psize / 2;
     const int area = psize * psize;
     const Image &last_img = (*pyr2)[level];
+    evals++;
     if (patches) PrecomputePatches(level);
     const int stride = last_img.cols;
     const int border = half_patch + 1;

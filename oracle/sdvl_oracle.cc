@@ -174,6 +174,13 @@ int sdvl_ref_orb_distance(const uint8_t *a, const uint8_t *b) { return OrbDetect
 int sdvl_ref_image_align(const uint8_t *img1, const uint8_t *img2, int w, int h, const sdvl_ref_params *p,
                          const double *cam, int n, const double *px, const double *bearing, const double *depth,
                          const uint8_t *valid, double *T_io, int fast, double *error, double *chi2, int *its) {
+  return sdvl_ref_image_align_ex(img1, img2, w, h, p, cam, n, px, bearing, depth, valid, T_io, fast, error, chi2, its, nullptr, nullptr);
+}
+
+int sdvl_ref_image_align_ex(const uint8_t *img1, const uint8_t *img2, int w, int h, const sdvl_ref_params *p,
+                            const double *cam, int n, const double *px, const double *bearing, const double *depth,
+                            const uint8_t *valid, double *T_io, int fast, double *error, double *chi2, int *its, int *stop,
+                            int *evals) {
   const Params q = ToParams(p);
   Pyramid p1(img1, w, h, w, q.pyramid_levels), p2(img2, w, h, w, q.pyramid_levels);
   std::vector<AlignFeature> feats(n);
@@ -190,6 +197,8 @@ int sdvl_ref_image_align(const uint8_t *img1, const uint8_t *img2, int w, int h,
   if (error) *error = ia.error;
   if (chi2) *chi2 = ia.chi2;
   if (its) for (int i = 0; i < 8; i++) its[i] = ia.its_per_level[i];
+  if (stop) *stop = ia.stop ? 1 : 0;
+  if (evals) *evals = ia.evals;
   return r;
 }
 

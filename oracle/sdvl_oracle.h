@@ -52,6 +52,12 @@ int sdvl_ref_orb_distance(const uint8_t *a, const uint8_t *b);
 int sdvl_ref_image_align(const uint8_t *img1, const uint8_t *img2, int w, int h, const sdvl_ref_params *p,
                          const double *cam, int n, const double *px, const double *bearing, const double *depth,
                          const uint8_t *valid, double *T_io, int fast, double *error, double *chi2, int *its);
+/* the same call, and what it does not return: stop = ImageAlign::stop_ at the end (image_align.cc:99, 105), evals = how often
+ * ComputeResiduals ran */
+int sdvl_ref_image_align_ex(const uint8_t *img1, const uint8_t *img2, int w, int h, const sdvl_ref_params *p,
+                            const double *cam, int n, const double *px, const double *bearing, const double *depth,
+                            const uint8_t *valid, double *T_io, int fast, double *error, double *chi2, int *its, int *stop,
+                            int *evals);
 /* matcher.cc:45-121 on pyramids built from the two level-0 images.  corners = [n][3], descs: lazily computed.
  * px_io: in = search centre for fixed points; out = match.  returns found; out_level */
 int sdvl_ref_search_point(const uint8_t *ref_img, const uint8_t *cur_img, int w, int h, const sdvl_ref_params *p,

@@ -205,11 +205,12 @@ class Oracle:
         cam = np.ascontiguousarray(cam, np.float64); px = np.ascontiguousarray(px, np.float64)
         bearing = np.ascontiguousarray(bearing, np.float64); depth = np.ascontiguousarray(depth, np.float64)
         valid = np.ascontiguousarray(valid, np.uint8); T = np.array(T, np.float64)
-        err = C.c_double(); chi2 = C.c_double(); its = np.zeros(8, np.int32)
-        n = self.lib.sdvl_ref_image_align(ptr(img1, u8p), ptr(img2, u8p), w, h, C.byref(self.params), ptr(cam, f64p),
-                                          len(px), ptr(px, f64p), ptr(bearing, f64p), ptr(depth, f64p), ptr(valid, u8p),
-                                          ptr(T, f64p), int(fast), C.byref(err), C.byref(chi2), ptr(its, i32p))
-        return dict(T=T, n=n, error=err.value, chi2=chi2.value, its=its)
+        err = C.c_double(); chi2 = C.c_double(); its = np.zeros(8, np.int32); stop = C.c_int(); evals = C.c_int()
+        n = self.lib.sdvl_ref_image_align_ex(ptr(img1, u8p), ptr(img2, u8p), w, h, C.byref(self.params), ptr(cam, f64p),
+                                             len(px), ptr(px, f64p), ptr(bearing, f64p), ptr(depth, f64p), ptr(valid, u8p),
+                                             ptr(T, f64p), int(fast), C.byref(err), C.byref(chi2), ptr(its, i32p), C.byref(stop),
+                                             C.byref(evals))
+        return dict(T=T, n=n, error=err.value, chi2=chi2.value, its=its, stop=stop.value, evals=evals.value)
 
     def search_point(self, ref_img, cur_img, cam, ref_pose, cur_pose, feat_px, feat_bearing, feat_level, feat_desc,
                      idepth, idepth_std, fixed, corners, px0, use_orb=None):
