@@ -117,28 +117,29 @@ int run_to_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, in
       staged.push_back(i);
     }
   }
-  const size_t gray_pitch = (static_cast<size_t>(w) * h + 255) / 256 * 256, pitch = (img_bytes + 255) / 256 * 256;
-  const size_t scratch_off = dst ? 0 : gray_pitch * n;
-  if (scratch_off + pitch * staged.size() > 0) {
-    int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, scratch_off + pitch * staged.size(), false);
+  const size_t gray_pitch = sdvl_align256(static_cast<size_t>(w) * h), pitch = sdvl_align256(img_bytes);
+  sdvl_layout wk;  // d_work: the gray images (when the caller gave no destinations) | tight copies of the pageable sources
+  const sdvl_part<uint8_t> wk_gray = wk.take<uint8_t>(dst ? 0 : gray_pitch * n), wk_staged = wk.take<uint8_t>(pitch * staged.size());
+  if (wk.bytes() > 0) {
+    int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, wk.bytes(), false);
     if (rc) return rc;
   }
   if (!dst) {
     scratch_dst->resize(n);
-    for (int i = 0; i < n; i++) (*scratch_dst)[i] = static_cast<uint8_t *>(ctx->d_work) + gray_pitch * i;
+    for (int i = 0; i < n; i++) (*scratch_dst)[i] = wk_gray.in(ctx->d_work) + gray_pitch * i;
     dst = scratch_dst->data();
     dst_stride = w;
   }
   if (!staged.empty()) {  // pageable: a tight copy in the context's scratch first
     for (size_t k = 0; k < staged.size(); k++) {
       const int i = staged[k];
-      uint8_t *d = static_cast<uint8_t *>(ctx->d_work) + scratch_off + pitch * k;
+      uint8_t *d = wk_staged.in(ctx->d_work) + pitch * k;
       SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(d, row_bytes, src[i], src_stride, row_bytes, h, hipMemcpyHostToDevice, ctx->stream));
       srcs[i] = d;
       strides[i] = static_cast<long long>(row_bytes);
     }
   }
-  const size_t jb = (sizeof(GrayJob) * n + 255) / 256 * 256;
+  const size_t jb = sizeof(GrayJob) * n;
   void *hs = nullptr, *dsx = nullptr;
   int rc = sdvl_stage_alloc(ctx, jb, &hs, &dsx);
   if (rc) return rc;

@@ -87,7 +87,7 @@ hipError_t sdvl_pull(sdvl_ctx *ctx, void *dst_host_pinned, const void *src_dev, 
 }
 
 int sdvl_stage_alloc(sdvl_ctx *ctx, size_t bytes, void **h, void **d) {
-  const size_t need = (bytes + 255) / 256 * 256;
+  const size_t need = sdvl_align256(bytes);
   const size_t cap = ctx->h_stage_bytes < ctx->d_stage_bytes ? ctx->h_stage_bytes : ctx->d_stage_bytes;
   if (!ctx->h_stage || !ctx->d_stage || ctx->stage_off + need > cap) {
     SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));  // everything staged so far has been consumed; the ring restarts
@@ -101,6 +101,38 @@ int sdvl_stage_alloc(sdvl_ctx *ctx, size_t bytes, void **h, void **d) {
   *h = static_cast<uint8_t *>(ctx->h_stage) + ctx->stage_off;
   *d = static_cast<uint8_t *>(ctx->d_stage) + ctx->stage_off;
   ctx->stage_off += need;
+  return SDVL_OK;
+}
+
+int sdvl_allow_dynamic_lds(sdvl_ctx *ctx, const void *kernel, size_t bytes, std::atomic<unsigned long long> *devices) {
+  const unsigned long long bit = 1ull << (ctx->device & 63);
+  if (!(devices->load(std::memory_order_acquire) & bit)) {
+    SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
+    SDVL_HIP_CHECK(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+    devices->fetch_or(bit, std::memory_order_release);
+  }
+  return SDVL_OK;
+}
+
+int sdvl_check_search_params(sdvl_ctx *ctx, const sdvl_search_params *p) {
+  SDVL_REQUIRE(ctx, p->patch_size == 8, "only patch_size 8 is supported (one wave64 per 8x8 patch)");
+  SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "bad max_fast_levels");
+  SDVL_REQUIRE(ctx, p->max_align_its >= 0 && p->margin >= 4, "bad max_align_its / margin");
+  return SDVL_OK;
+}
+
+int sdvl_check_pose_params(sdvl_ctx *ctx, const sdvl_pose_params *p, int set_its) {
+  SDVL_REQUIRE(ctx, p->max_ransac_points >= 1 && p->max_ransac_points <= 8, "max_ransac_points must be in [1,8]");
+  if (set_its > 0) SDVL_REQUIRE(ctx, p->max_ransac_its == set_its && p->max_optim_pose_its >= 0, "max_ransac_its differs from the set's");
+  SDVL_REQUIRE(ctx, p->max_ransac_its >= 1 && p->max_ransac_its <= 4096 && p->max_optim_pose_its >= 0, "bad iteration limits");
+  return SDVL_OK;
+}
+
+int sdvl_check_align_params(sdvl_ctx *ctx, const sdvl_align_params *p, int levels) {
+  SDVL_REQUIRE(ctx, p->patch_size == 4, "only align_patch_size 4 is supported");
+  SDVL_REQUIRE(ctx, p->min_level >= 0 && p->max_level >= p->min_level && p->max_level < SDVL_MAX_LEVELS, "bad align levels");
+  SDVL_REQUIRE(ctx, p->max_level < levels, "max_align_level exceeds the pyramid depth");
+  SDVL_REQUIRE(ctx, p->max_its >= 0, "bad max_its");
   return SDVL_OK;
 }
 
@@ -477,9 +509,6 @@ int sdvl_ctx_timing_reset(sdvl_ctx *ctx) {
 
 // ---- frames -------------------------------------------------------------------------------------------------
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-
 namespace {
 // Round 3: a frame holds only what stays useful for as long as the frame lives — a keyframe lives for the rest of the run:
 //   level0 | level1 | ... (u8, 256-B aligned, 64 B slack) | corner header {count,0,0,0} + corners[cap] (x,y,level,pad int32)
@@ -492,30 +521,25 @@ struct FrameLayout {
 };
 
 bool frame_layout(int width, int height, int levels, int corner_cap, FrameLayout *L) {
-  size_t off = 0;
+  sdvl_layout lay;
   int w = width, h = height;
   for (int l = 0; l < levels; l++) {
     if (w < 1 || h < 1) return false;
     L->lw[l] = w;
     L->lh[l] = h;
-    L->level_off[l] = off;
-    off = align_up(off + static_cast<size_t>(w) * h + 64, 256);  // +64: slack so that word loads may overrun a row end
+    L->level_off[l] = lay.take<uint8_t>(static_cast<size_t>(w) * h + 64).off;  // +64: slack so that word loads may overrun a row end
     w /= 2;
     h /= 2;
   }
   L->corner_cap = corner_cap;
-  L->corners_off = off;  // 16-byte header {count,0,0,0} + corner records, written by ONE copy
-  off = align_up(off + sizeof(int32_t) * 4 * (static_cast<size_t>(corner_cap) + 1), 256);
-  L->desc_off = off;
-  off = align_up(off + static_cast<size_t>(32) * corner_cap, 256);
+  L->corners_off = lay.take<int32_t>(4 * (static_cast<size_t>(corner_cap) + 1)).off;  // 16-byte header {count,0,0,0} + corner records, written by ONE copy
+  L->desc_off = lay.take<uint8_t>(static_cast<size_t>(32) * corner_cap).off;
   L->bin_gw = (width + 31) / 32;
   const int cells = L->bin_gw * ((height + 31) / 32);
   L->bin_cells = cells <= 4096 ? cells : 0;  // larger grids (3840x2160: 8160 bins): no bins, the searches scan the list — same results
-  L->bin_start_off = off;
-  off = align_up(off + sizeof(int32_t) * (static_cast<size_t>(L->bin_cells) + 1), 256);
-  L->bin_entries_off = off;
-  off = align_up(off + sizeof(uint2) * static_cast<size_t>(L->bin_cells > 0 ? corner_cap : 0), 256);
-  L->bytes = off;
+  L->bin_start_off = lay.take<int32_t>(static_cast<size_t>(L->bin_cells) + 1).off;
+  L->bin_entries_off = lay.take<uint2>(L->bin_cells > 0 ? corner_cap : 0).off;
+  L->bytes = lay.bytes();
   return true;
 }
 
@@ -909,11 +933,13 @@ int sdvl_frames_own_images(sdvl_ctx *ctx, int n, sdvl_frame *const *frames) {
   }
   if (m == 0) return SDVL_OK;
   void *hs = nullptr, *ds = nullptr;
-  const size_t jb = (sizeof(UploadJob) * static_cast<size_t>(m) + 255) / 256 * 256;
-  const int rc = sdvl_stage_alloc(ctx, jb + sizeof(OwnRec) * static_cast<size_t>(m), &hs, &ds);
+  sdvl_layout st;  // staging: gather jobs | registry records
+  const sdvl_part<UploadJob> jobs = st.take<UploadJob>(m);
+  const sdvl_part<OwnRec> recs = st.take<OwnRec>(m);
+  const int rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
   if (rc) return rc;
-  UploadJob *hj = static_cast<UploadJob *>(hs);
-  OwnRec *hr = reinterpret_cast<OwnRec *>(static_cast<uint8_t *>(hs) + jb);
+  UploadJob *hj = jobs.in(hs);
+  OwnRec *hr = recs.in(hs);
   int k = 0, n_reg = 0;
   for (int i = 0; i < n; i++) {
     sdvl_frame *f = frames[i];
@@ -922,12 +948,12 @@ int sdvl_frames_own_images(sdvl_ctx *ctx, int n, sdvl_frame *const *frames) {
     if (f->home == ctx && f->reg_id >= 0) hr[n_reg++] = OwnRec{f->reg_id, 0, f->own_level0};
     f->v.level[0] = f->own_level0;
   }
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, jb + sizeof(OwnRec) * static_cast<size_t>(m)));
-  SDVL_LAUNCH(ctx, "frames_own", frames_upload_kernel, dim3(kUploadChunks, m), dim3(256), static_cast<const UploadJob *>(ds), frames[0]->width,
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  SDVL_LAUNCH(ctx, "frames_own", frames_upload_kernel, dim3(kUploadChunks, m), dim3(256), jobs.cin(ds), frames[0]->width,
               frames[0]->height, frames[0]->width);
   if (n_reg > 0 && ctx->d_registry)
     hipLaunchKernelGGL(registry_level0_kernel, dim3((n_reg + 63) / 64), dim3(64), 0, ctx->stream,
-                       reinterpret_cast<const OwnRec *>(static_cast<uint8_t *>(ds) + jb), n_reg, static_cast<SearchFramePose *>(ctx->d_registry));
+                       recs.cin(ds), n_reg, static_cast<SearchFramePose *>(ctx->d_registry));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
 }

@@ -1396,13 +1396,12 @@ struct DetectSlot {
 // kp_cap entries per cell list; spill_words for the spill areas of all levels together
 static DetectSlot detect_slot_layout(int total_cells, int kp_cap, size_t spill_words) {
   DetectSlot L;
-  size_t off = 0;
-  const auto take = [&off](size_t bytes) { const size_t at = off; off = (off + bytes + 255) / 256 * 256; return at; };
-  L.counts_off = take(sizeof(int32_t) * (static_cast<size_t>(total_cells) + 1));
-  L.newlen_off = take(sizeof(int32_t) * static_cast<size_t>(total_cells));
-  L.kps_off = take(sizeof(uint32_t) * static_cast<size_t>(kp_cap) * static_cast<size_t>(total_cells));
-  L.spill_off = take(sizeof(uint32_t) * spill_words);
-  L.bytes = off;
+  sdvl_layout lay;
+  L.counts_off = lay.take<int32_t>(static_cast<size_t>(total_cells) + 1).off;
+  L.newlen_off = lay.take<int32_t>(total_cells).off;
+  L.kps_off = lay.take<uint32_t>(static_cast<size_t>(kp_cap) * static_cast<size_t>(total_cells)).off;
+  L.spill_off = lay.take<uint32_t>(spill_words).off;
+  L.bytes = lay.bytes();
   return L;
 }
 
@@ -1695,14 +1694,16 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
   rc = detect_scratch(ctx, n, pl.slot, &scratch);
   if (rc) return rc;
   const size_t pack_lds = pl.pack_lds + (static_cast<size_t>(std::max(1, frames[0]->bin_cells)) * 4 + 15) / 16 * 16;
-  const size_t fj_bytes = (sizeof(FastJob) * n + 255) / 256 * 256, sj_bytes = sizeof(SelJob) * n;
+  sdvl_layout st;  // staging: FAST jobs | selection jobs
+  const sdvl_part<FastJob> st_fast = st.take<FastJob>(n);
+  const sdvl_part<SelJob> st_sel = st.take<SelJob>(n);
   void *hst = nullptr, *dst = nullptr;
   rc = sdvl_ensure(ctx, &ctx->d_counts, &ctx->d_counts_bytes, sizeof(int32_t) * n, false);
-  if (!rc) rc = sdvl_stage_alloc(ctx, fj_bytes + sj_bytes, &hst, &dst);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hst, &dst);
   if (rc) return rc;
   ctx->detect_frames.assign(frames, frames + n);
-  FastJob *hf = static_cast<FastJob *>(hst);
-  SelJob *hs = reinterpret_cast<SelJob *>(static_cast<uint8_t *>(hst) + fj_bytes);
+  FastJob *hf = st_fast.in(hst);
+  SelJob *hs = st_sel.in(hst);
   for (int i = 0; i < n; i++) {
     uint8_t *sb = scratch + pl.slot.bytes * i;
     hf[i] = fast_job(pl, frames[i], sb);
@@ -1726,9 +1727,9 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
     frames[i]->hdr_stale = 0;     // the pack kernel rewrites the header
     frames[i]->desc_valid = 0;
   }
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dst, hst, fj_bytes + sj_bytes));
-  const FastJob *df = static_cast<const FastJob *>(dst);
-  const SelJob *ds = reinterpret_cast<const SelJob *>(static_cast<uint8_t *>(dst) + fj_bytes);
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dst, hst, st.bytes()));
+  const FastJob *df = st_fast.cin(dst);
+  const SelJob *ds = st_sel.cin(dst);
   rc = fast_launch(ctx, pl, n, frames, df);
   if (rc) return rc;
   const dim3 sel_grid(static_cast<unsigned>((n + 7) / 8 * 8 * pl.n_slices));
@@ -1746,21 +1747,12 @@ int sdvl_detect_corners(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const s
     // once per device to the most any configuration can ask for (the CU's 160 KB less the kernel's static LDS), whichever thread
     // gets there first — a per-context "already raised" mark let a second context with a smaller size lower it again
     static std::atomic<unsigned long long> attr_devices{0};
-    const unsigned long long bit = 1ull << (ctx->device & 63);
-    if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-      SDVL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(select_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              static_cast<int>(152u << 10)));
-      attr_devices.fetch_or(bit, std::memory_order_release);
-    }
+    const int rc_a = sdvl_allow_dynamic_lds(ctx, reinterpret_cast<const void *>(select_pack_kernel), 152u << 10, &attr_devices);
+    if (rc_a) return rc_a;
     SDVL_REQUIRE(ctx, pack_lds <= (152u << 10), "selection lists of this configuration do not fit a compute unit's LDS");
-    ctx->pack_lds_limit = pack_lds;
   }
-  {
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    sdvl_timer_events(ctx, "select_pack", &ev_a, &ev_b);
-    hipExtLaunchKernelGGL(select_pack_kernel, dim3(n), dim3(256), static_cast<unsigned>(pack_lds), ctx->stream, ev_a, ev_b, 0, ds, sl,
-                          static_cast<int32_t *>(ctx->d_counts), direct ? static_cast<int32_t *>(ctx->h_counts) : nullptr);
-  }
+  SDVL_LAUNCH_LDS(ctx, "select_pack", select_pack_kernel, dim3(n), dim3(256), static_cast<unsigned>(pack_lds), ds, sl, static_cast<int32_t *>(ctx->d_counts),
+                  direct ? static_cast<int32_t *>(ctx->h_counts) : nullptr);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   ctx->counts_gen = ~0ull;
   if (direct) ctx->counts_gen = ctx->wait_gen;

@@ -667,21 +667,24 @@ struct IaPreOut {
   uint8_t *vis;
   double *fac;
 };
+// the d_work layout of nb = n_jobs * n_lv such blocks of `pitch` feature slots, array by array: byte offsets and the total
+struct IaPre {
+  size_t S, fac, vis, bytes;  // [items: nb * 48 * pitch floats, at 0][S: nb * 3 * pitch doubles][fac: nb * 32 doubles][vis bytes]
+  __host__ __device__ IaPre(size_t nb, int pitch)
+      : S(nb * 48 * pitch * sizeof(float)), fac(S + nb * 3 * pitch * sizeof(double)), vis(fac + nb * 32 * sizeof(double)), bytes(vis + nb * pitch) {}
+};
 __device__ __forceinline__ IaPreOut ia_pre_block(void *base, int n_jobs, int n_lv, int pitch, int job, int li) {
-  // [items: n_jobs * n_lv * 48 * pitch floats][S: n_jobs * n_lv * 3 * pitch doubles][fac: n_jobs * n_lv * 32 doubles][vis bytes]
-  const size_t blk = static_cast<size_t>(job) * n_lv + li, nb = static_cast<size_t>(n_jobs) * n_lv;
+  const IaPre L(static_cast<size_t>(n_jobs) * n_lv, pitch);
+  const size_t blk = static_cast<size_t>(job) * n_lv + li;
   uint8_t *b = static_cast<uint8_t *>(base);
   IaPreOut o;
   o.items = reinterpret_cast<float *>(b) + blk * 48 * pitch;
-  o.S = reinterpret_cast<double *>(b + nb * 48 * pitch * sizeof(float)) + blk * 3 * pitch;
-  o.fac = reinterpret_cast<double *>(b + nb * 48 * pitch * sizeof(float) + nb * 3 * pitch * sizeof(double)) + blk * 32;
-  o.vis = b + nb * 48 * pitch * sizeof(float) + nb * 3 * pitch * sizeof(double) + nb * 32 * sizeof(double) + blk * pitch;
+  o.S = reinterpret_cast<double *>(b + L.S) + blk * 3 * pitch;
+  o.fac = reinterpret_cast<double *>(b + L.fac) + blk * 32;
+  o.vis = b + L.vis + blk * pitch;
   return o;
 }
-inline size_t ia_pre_bytes(int n_jobs, int n_lv, int pitch) {
-  const size_t nb = static_cast<size_t>(n_jobs) * n_lv;
-  return (nb * (48 * pitch * sizeof(float) + 3 * pitch * sizeof(double) + 32 * sizeof(double) + pitch) + 255) / 256 * 256;
-}
+inline size_t ia_pre_bytes(int n_jobs, int n_lv, int pitch) { return sdvl_align256(IaPre(static_cast<size_t>(n_jobs) * n_lv, pitch).bytes); }
 
 template <int kPreWaves, class Feats>
 __device__ __forceinline__ void ia_pre_body(const uint8_t *ref_img, int W, int H, int level, int nf, const Feats F, double fx, int pitch, IaPreOut o) {
@@ -806,24 +809,17 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(1, 
 }
 
 // dynamic LDS of the Gauss-Newton kernels: x[4][max_f] doubles + one flag byte per feature
-size_t ia_wave_lds_bytes(int max_f) { return static_cast<size_t>(max_f) * (4 * sizeof(double) + 1) + 64; }
+constexpr size_t ia_wave_lds_bytes(int max_f) { return static_cast<size_t>(max_f) * (4 * sizeof(double) + 1) + 64; }
+static_assert(ia_wave_lds_bytes(kMaxF) == 67648, "the largest job's, the ceiling asked for below");
 
 }  // namespace
 
-// the four-wave kernels may ask for more dynamic LDS than the default limit: the attribute belongs to the kernel object of ONE
-// device — set once per device, whichever thread gets there first
+// the four-wave kernels may ask for more dynamic LDS than the default limit
 static int ia_allow_dynamic_lds(sdvl_ctx *ctx) {
-  static std::atomic<unsigned long long> attr_devices{0};
-  const unsigned long long bit = 1ull << (ctx->device & 63);
-  if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-    SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
-    SDVL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(image_align_track_wave_pre_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            static_cast<int>(ia_wave_lds_bytes(kMaxF))));
-    SDVL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(image_align_wave_pre_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            static_cast<int>(ia_wave_lds_bytes(kMaxF))));
-    attr_devices.fetch_or(bit, std::memory_order_release);
-  }
-  return SDVL_OK;
+  static std::atomic<unsigned long long> track_devices{0}, record_devices{0};
+  int rc = sdvl_allow_dynamic_lds(ctx, reinterpret_cast<const void *>(image_align_track_wave_pre_kernel<4>), ia_wave_lds_bytes(kMaxF), &track_devices);
+  if (!rc) rc = sdvl_allow_dynamic_lds(ctx, reinterpret_cast<const void *>(image_align_wave_pre_kernel<4>), ia_wave_lds_bytes(kMaxF), &record_devices);
+  return rc;
 }
 
 // Queues the alignment of n_jobs frame pairs (no wait).  The feature records come from the host (`features`, staged and
@@ -834,9 +830,8 @@ static int ia_allow_dynamic_lds(sdvl_ctx *ctx) {
 int sdvl_image_align_enqueue(sdvl_ctx *ctx, int n_jobs, const sdvl_align_job *jobs, int n_features, const sdvl_align_feature *features,
                              const sdvl_align_feature *d_features, const sdvl_camera *cam, const sdvl_align_params *p,
                              sdvl_align_result *d_results) {
-  SDVL_REQUIRE(ctx, p->patch_size == 4, "only align_patch_size 4 is supported");
-  SDVL_REQUIRE(ctx, p->min_level >= 0 && p->max_level >= p->min_level && p->max_level < SDVL_MAX_LEVELS, "bad align levels");
-  SDVL_REQUIRE(ctx, p->max_its >= 0, "bad max_its");
+  int rc = sdvl_check_align_params(ctx, p);
+  if (rc) return rc;
   std::vector<int> order(n_jobs);
   int n_small = 0, max_nf_small = 0, max_nf_big = 0;
   for (int j = 0; j < n_jobs; j++) {
@@ -868,18 +863,18 @@ int sdvl_image_align_enqueue(sdvl_ctx *ctx, int n_jobs, const sdvl_align_job *jo
   const int n_big = n_jobs - n_small;
   const int n_lv = p->max_level - p->min_level + 1;
   const int max_f_small = max_nf_small == 0 ? 64 : (max_nf_small + 63) / 64 * 64;
-  const int max_f_big = (max_nf_big + 255) / 256 * 256;
-  const size_t pre_small_bytes = n_small > 0 ? ia_pre_bytes(n_small, n_lv, max_f_small) : 0;
-  const size_t work = pre_small_bytes + (n_big > 0 ? ia_pre_bytes(n_big, n_lv, max_f_big) : 0);
-  const size_t job_bytes = (sizeof(IaJob) * n_jobs + 255) / 256 * 256;
-  const size_t feat_bytes = d_features ? 0 : sizeof(sdvl_align_feature) * static_cast<size_t>(n_features);
-  const size_t res_bytes = sizeof(sdvl_align_result) * n_jobs;
+  const int max_f_big = (max_nf_big + 64 * 4 - 1) / (64 * 4) * (64 * 4);  // four waves share a job's features
+  sdvl_layout w, st;  // d_work: precomputed blocks of the one-wave jobs | of the four-wave jobs ; staging: jobs | feature records (unless they are resident)
+  const sdvl_part<uint8_t> pre_small = w.take<uint8_t>(n_small > 0 ? IaPre(static_cast<size_t>(n_small) * n_lv, max_f_small).bytes : 0);
+  const sdvl_part<uint8_t> pre_big = w.take<uint8_t>(n_big > 0 ? IaPre(static_cast<size_t>(n_big) * n_lv, max_f_big).bytes : 0);
+  const sdvl_part<IaJob> st_jobs = st.take<IaJob>(n_jobs);
+  const sdvl_part<sdvl_align_feature> st_feats = st.take<sdvl_align_feature>(d_features ? 0 : n_features);
   void *hs = nullptr, *dsx = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, work + 256, false);
-  if (!rc && !d_results) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, res_bytes, true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, job_bytes + feat_bytes, &hs, &dsx);
+  rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, w.bytes() + 256, false);
+  if (!rc && !d_results) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, sizeof(sdvl_align_result) * n_jobs, true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  IaJob *hj = static_cast<IaJob *>(hs);
+  IaJob *hj = st_jobs.in(hs);
   for (int q = 0; q < n_jobs; q++) {
     const sdvl_align_job &a = jobs[order[q]];
     IaJob &d = hj[q];
@@ -895,30 +890,27 @@ int sdvl_image_align_enqueue(sdvl_ctx *ctx, int n_jobs, const sdvl_align_job *jo
     d.out_index = order[q];
     for (int k = 0; k < 7; k++) d.T[k] = a.T[k];
   }
-  if (feat_bytes) memcpy(static_cast<uint8_t *>(hs) + job_bytes, features, feat_bytes);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, job_bytes + feat_bytes));
-  const sdvl_align_feature *feats_dev = d_features ? d_features : reinterpret_cast<const sdvl_align_feature *>(static_cast<uint8_t *>(dsx) + job_bytes);
-  Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
+  if (st_feats.count) memcpy(st_feats.in(hs), features, st_feats.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
+  const IaJob *d_jobs = st_jobs.cin(dsx);
+  const sdvl_align_feature *feats_dev = d_features ? d_features : st_feats.cin(dsx);
+  const Cam c = cam_of(*cam);
   // results straight into the context's pinned host buffer (posted PCIe writes, visible once the kernel has completed) unless the caller keeps them on the device
   sdvl_align_result *dst = d_results ? d_results : static_cast<sdvl_align_result *>(ctx->h_out);
+  void *d_pre_small = pre_small.in(ctx->d_work), *d_pre_big = pre_big.in(ctx->d_work);
   if (n_small > 0) {
-    SDVL_LAUNCH(ctx, "image_align_pre", image_align_pre_kernel, dim3(static_cast<unsigned>(n_small) * n_lv), dim3(256), static_cast<const IaJob *>(dsx), feats_dev,
-                c, *p, n_small, max_f_small, ctx->d_work);
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    sdvl_timer_events(ctx, "image_align", &ev_a, &ev_b);
-    hipExtLaunchKernelGGL((image_align_wave_pre_kernel<1>), dim3(n_small), dim3(64), ia_wave_lds_bytes(max_f_small), ctx->stream, ev_a, ev_b, 0,
-                          static_cast<const IaJob *>(dsx), feats_dev, c, *p, n_small, max_f_small, ctx->d_work, dst);
+    SDVL_LAUNCH(ctx, "image_align_pre", image_align_pre_kernel, dim3(static_cast<unsigned>(n_small) * n_lv), dim3(256), d_jobs, feats_dev, c, *p, n_small,
+                max_f_small, d_pre_small);
+    SDVL_LAUNCH_LDS(ctx, "image_align", (image_align_wave_pre_kernel<1>), dim3(n_small), dim3(64), ia_wave_lds_bytes(max_f_small), d_jobs, feats_dev, c, *p,
+                    n_small, max_f_small, d_pre_small, dst);
   }
   if (n_big > 0) {
     const int rc_a = ia_allow_dynamic_lds(ctx);
     if (rc_a) return rc_a;
-    void *pre_big = static_cast<uint8_t *>(ctx->d_work) + pre_small_bytes;
-    SDVL_LAUNCH(ctx, "image_align_pre", image_align_pre_kernel, dim3(static_cast<unsigned>(n_big) * n_lv), dim3(256), static_cast<const IaJob *>(dsx) + n_small,
-                feats_dev, c, *p, n_big, max_f_big, pre_big);
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    sdvl_timer_events(ctx, "image_align_big", &ev_a, &ev_b);
-    hipExtLaunchKernelGGL((image_align_wave_pre_kernel<4>), dim3(n_big), dim3(256), ia_wave_lds_bytes(max_f_big), ctx->stream, ev_a, ev_b, 0,
-                          static_cast<const IaJob *>(dsx) + n_small, feats_dev, c, *p, n_big, max_f_big, pre_big, dst);
+    SDVL_LAUNCH(ctx, "image_align_pre", image_align_pre_kernel, dim3(static_cast<unsigned>(n_big) * n_lv), dim3(256), d_jobs + n_small, feats_dev, c, *p, n_big,
+                max_f_big, d_pre_big);
+    SDVL_LAUNCH_LDS(ctx, "image_align_big", (image_align_wave_pre_kernel<4>), dim3(n_big), dim3(256), ia_wave_lds_bytes(max_f_big), d_jobs + n_small, feats_dev,
+                    c, *p, n_big, max_f_big, d_pre_big, dst);
   }
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
@@ -929,10 +921,8 @@ int sdvl_image_align_enqueue(sdvl_ctx *ctx, int n_jobs, const sdvl_align_job *jo
 int sdvl_image_align_track_enqueue(sdvl_ctx *ctx, int n_jobs, const TrackJobDev *d_jobs, const TrackPoint *d_points, const TrackFeat *d_feats0,
                                    const TrackFeat *d_feats1, int np, int nfeat_cap, int max_nf, int levels, const sdvl_camera *cam,
                                    const sdvl_align_params *p, sdvl_align_result *d_results, int batch_size) {
-  SDVL_REQUIRE(ctx, p->patch_size == 4, "only align_patch_size 4 is supported");
-  SDVL_REQUIRE(ctx, p->min_level >= 0 && p->max_level >= p->min_level && p->max_level < SDVL_MAX_LEVELS, "bad align levels");
-  SDVL_REQUIRE(ctx, p->max_level < levels, "max_align_level exceeds the pyramid depth");
-  SDVL_REQUIRE(ctx, p->max_its >= 0, "bad max_its");
+  int rc = sdvl_check_align_params(ctx, p, levels);
+  if (rc) return rc;
   if (max_nf > kMaxF) {
     ctx->err = "too many features in one alignment job (SDVL_MAX_ALIGN_FEATURES)";
     return SDVL_ERR_CAPACITY;
@@ -944,13 +934,10 @@ int sdvl_image_align_track_enqueue(sdvl_ctx *ctx, int n_jobs, const TrackJobDev 
   const int kw = (max_nf > kLdsMaxF || batch_size <= 32) ? 4 : 1;
   const int max_f = max_nf <= 0 ? 64 * kw : (max_nf + 64 * kw - 1) / (64 * kw) * (64 * kw);
   const int n_lv = p->max_level - p->min_level + 1;
-  const int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, ia_pre_bytes(n_jobs, n_lv, max_f) + 256, false);
+  rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, ia_pre_bytes(n_jobs, n_lv, max_f) + 256, false);
+  if (!rc) rc = ia_allow_dynamic_lds(ctx);
   if (rc) return rc;
-  {
-    const int rc_a = ia_allow_dynamic_lds(ctx);
-    if (rc_a) return rc_a;
-  }
-  const Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
+  const Cam c = cam_of(*cam);
   // Round 6: beside the one-wave Gauss-Newton form (a farm's launches) the precompute runs ONE wave per (job, level) too, its lanes
   // taking the level's features in rounds of 64: a four-wave workgroup is placed when four slots of one CU are free at the same moment,
   // which among the other streams' one-wave workgroups happens far less often than its share — 2.4 -> 1.3 ms of dispatch time per step
@@ -961,15 +948,14 @@ int sdvl_image_align_track_enqueue(sdvl_ctx *ctx, int n_jobs, const TrackJobDev 
   else
   SDVL_LAUNCH(ctx, "image_align_pre", image_align_track_pre_kernel<4>, dim3(static_cast<unsigned>(n_jobs) * n_lv), dim3(256), d_jobs, d_points, d_feats0, d_feats1,
               np, nfeat_cap, c, *p, n_jobs, max_f, ctx->d_work);
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  sdvl_timer_events(ctx, max_nf > kLdsMaxF ? "image_align_big" : "image_align", &ev_a, &ev_b);
+  const char *name = max_nf > kLdsMaxF ? "image_align_big" : "image_align";
   const size_t lds = ia_wave_lds_bytes(max_f);
   if (kw == 4)
-    hipExtLaunchKernelGGL((image_align_track_wave_pre_kernel<4>), dim3(n_jobs), dim3(256), lds, ctx->stream, ev_a, ev_b, 0, d_jobs, d_points, d_feats0, d_feats1,
-                          np, nfeat_cap, c, *p, n_jobs, max_f, ctx->d_work, d_results);
+    SDVL_LAUNCH_LDS(ctx, name, (image_align_track_wave_pre_kernel<4>), dim3(n_jobs), dim3(256), lds, d_jobs, d_points, d_feats0, d_feats1, np, nfeat_cap, c, *p,
+                    n_jobs, max_f, ctx->d_work, d_results);
   else
-    hipExtLaunchKernelGGL((image_align_track_wave_pre_kernel<1>), dim3(n_jobs), dim3(64), lds, ctx->stream, ev_a, ev_b, 0, d_jobs, d_points, d_feats0, d_feats1,
-                          np, nfeat_cap, c, *p, n_jobs, max_f, ctx->d_work, d_results);
+    SDVL_LAUNCH_LDS(ctx, name, (image_align_track_wave_pre_kernel<1>), dim3(n_jobs), dim3(64), lds, d_jobs, d_points, d_feats0, d_feats1, np, nfeat_cap, c, *p,
+                    n_jobs, max_f, ctx->d_work, d_results);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
 }

@@ -9,10 +9,12 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
 #include "../../include/sdvl_hip.h"
+#include "sdvl_layout.h"
 
 // Device view of one frame: everything a kernel needs, passed by value inside job records.
 struct FrameView {
@@ -89,7 +91,6 @@ struct sdvl_ctx {
   // detection scratch (sdvl_detect.hip): per batch slot the per-cell FAST lists, counts and the selection's intermediate lists;
   // dead once the batch's select_pack kernel has run
   void *d_detect = nullptr; size_t d_detect_bytes = 0;
-  size_t pack_lds_limit = 0;            // dynamic LDS select_pack_kernel has been allowed so far
   int corner_cap = SDVL_MAX_CORNERS;    // capacity of the corner list of frames created from now on
   size_t stage_off = 0;  // bump pointer into h_stage/d_stage; reset by every sdvl_stream_wait
   // A search batch (sdvl_search_begin .. sdvl_search_run) is filled by the caller over time and must survive every wait in
@@ -123,13 +124,18 @@ struct sdvl_ctx {
   int align_pending = 0;
   // sdvl_search_run_chain: the search results have landed at chain_ticket; the pose results follow at the stream's tail
   uint32_t chain_ticket = 0;
-  // sdvl_filter_inputs_begin in flight: its mark and the row geometry _end needs
+  // sdvl_filter_inputs_begin or sdvl_filter_corners_begin in flight (one at a time, filter_pending = its frames): the mark and where
+  // the parts that _end reads lie in h_out.  Inputs: per frame `row_cap` scores and `row_bytes` of packed corners (+ descriptors);
+  // corners: per frame a count and up to `max_out` records
   uint32_t filter_ticket = 0;
-  int filter_pending = 0, filter_ccap = 0, filter_desc = 0;
-  size_t filter_sc_bytes = 0, filter_row = 0;
+  int filter_pending = 0;
+  struct { sdvl_part<double> scores; sdvl_part<uint8_t> rows; size_t row_bytes; int row_cap, with_desc; } filter_inputs = {};
+  struct { sdvl_part<int32_t> counts; sdvl_part<sdvl_filtered_corner> recs; int max_out; } filter_corners = {};
   int chain_pending = 0;             // trackers of the chained batch in flight
-  size_t chain_host_off = 0;         // where its pose results start in h_out
-  int chain_obs_total = 0;
+  struct ChainBack {                 // the pose stage's parts that return to the host: the same three, in this order, in d_out and h_out
+    sdvl_part<sdvl_pose_result> res;
+    sdvl_part<int32_t> n_obs, lists;
+  } chain_back;                      // where they lie in h_out
   // iteration budgets of SelectInliers for every match count 0..nits_max_size (row s at s*(s+1)/2), resident in HBM
   void *d_nits = nullptr;
   std::vector<int32_t> nits_host;
@@ -200,7 +206,7 @@ int sdvl_stage_alloc(sdvl_ctx *ctx, size_t bytes, void **h, void **d);
 // is doing — with a farm's 79 MB image transfers under way every job-record copy (a few KB, in front of every kernel) queued up
 // behind ~1.4 ms of somebody else's images, and the groups' steps ran one after the other (host-fed 115-135 k tracked frames/s with
 // the transfers running, 234 k with the same steps and the transfers skipped).  Sources outside the staging ring fall back to the
-// DMA copy.  SDVL_STAGE_DMA=1: always the DMA copy (A/B).
+// DMA copy.
 hipError_t sdvl_push(sdvl_ctx *ctx, void *dst_dev, const void *src_staged, size_t bytes);
 hipError_t sdvl_pull(sdvl_ctx *ctx, void *dst_host_pinned, const void *src_dev, size_t bytes);
 // wait for everything queued on ctx->stream WITHOUT spinning: a mark (sdvl_mark_record) + sleeping polls (sdvl_mark_wait).
@@ -222,13 +228,23 @@ int sdvl_frame_fix_header(sdvl_ctx *ctx, sdvl_frame *f);
 bool sdvl_timer_events(sdvl_ctx *ctx, const char *name, hipEvent_t *a, hipEvent_t *b);
 // (Small results go from the kernels straight into the context's pinned host buffers: host-coherent memory is mapped into the
 // device's address space; the stores are posted PCIe writes, visible to the host once the kernel has completed, i.e. before the
-// sequence number the stream writes behind it — no device buffer + D2H copy packet.)
+// sequence number the stream writes behind it — no device buffer + D2H copy packet.)  `lds`: bytes of dynamic LDS
 
-#define SDVL_LAUNCH(ctx, name, kernel, grid, block, ...)                                                   \
+#define SDVL_LAUNCH_LDS(ctx, name, kernel, grid, block, lds, ...)                                          \
   do {                                                                                                     \
     hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr;                                                           \
     sdvl_timer_events((ctx), (name), &ev_a_, &ev_b_);                                                      \
-    hipExtLaunchKernelGGL(kernel, grid, block, 0, (ctx)->stream, ev_a_, ev_b_, 0, __VA_ARGS__);            \
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, (ctx)->stream, ev_a_, ev_b_, 0, __VA_ARGS__);          \
   } while (0)
+#define SDVL_LAUNCH(ctx, name, kernel, grid, block, ...) SDVL_LAUNCH_LDS(ctx, name, kernel, grid, block, 0, __VA_ARGS__)
+
+// A kernel that may ask for more dynamic LDS than the default limit: the attribute belongs to the kernel object of ONE device — set
+// once per device, whichever thread gets there first.  `devices`: the caller's record (one per kernel) of the devices that have it.
+int sdvl_allow_dynamic_lds(sdvl_ctx *ctx, const void *kernel, size_t bytes, std::atomic<unsigned long long> *devices);
+// One statement of each parameter record's checks (conditions of a single entry point stay with it).  set_its > 0: the tracker set
+// of the call fixes max_ransac_its (sdvl_track_align); levels: depth of the pyramids, where the caller knows one depth for all jobs
+int sdvl_check_search_params(sdvl_ctx *ctx, const sdvl_search_params *p);
+int sdvl_check_pose_params(sdvl_ctx *ctx, const sdvl_pose_params *p, int set_its = 0);
+int sdvl_check_align_params(sdvl_ctx *ctx, const sdvl_align_params *p, int levels = SDVL_MAX_LEVELS);
 
 #endif  // SDVL_INTERNAL_H_

@@ -543,31 +543,28 @@ int sdvl_filter_inputs_begin(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, in
   }
   // device layout: scores[n][ccap] doubles | n rows of {header + corners[ccap] (+ descriptors[ccap])} gathered from the
   // frames by one kernel, so that everything returns in ONE device-to-host copy
-  const size_t sc_bytes = (sizeof(double) * static_cast<size_t>(n) * ccap + 255) / 256 * 256;
   const size_t row = sizeof(int32_t) * 4 * (static_cast<size_t>(ccap) + 1) + (desc ? static_cast<size_t>(ccap) * 32 : 0);
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, sc_bytes + row * n, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, sc_bytes + row * n, true);
+  sdvl_layout o;  // of d_out and h_out alike
+  auto &fi = ctx->filter_inputs;
+  fi = {o.take<double>(static_cast<size_t>(n) * ccap), o.take<uint8_t>(row * n), row, ccap, desc ? 1 : 0};
+  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
   if (rc) return rc;
   OrbJob *d_jobs = nullptr;
   int max_n = 0;
-  rc = fill_jobs(ctx, n, frames, ccap, nullptr, static_cast<double *>(ctx->d_out), &d_jobs, &max_n);
+  rc = fill_jobs(ctx, n, frames, ccap, nullptr, fi.scores.in(ctx->d_out), &d_jobs, &max_n);
   if (rc) return rc;
   max_n = max_n > ccap ? ccap : max_n;
   if (max_n > 0) SDVL_LAUNCH(ctx, "shi_tomasi", shi_tomasi_kernel, xcd_frame_grid(n, shi_chunks(max_n)), dim3(64), d_jobs, n, shi_chunks(max_n));
   {
     const int units = (ccap + 1) + (desc ? 2 * ccap : 0);  // 16-byte units per row
     SDVL_LAUNCH(ctx, "filter_gather", filter_gather_kernel, dim3((units + 255) / 256, n), dim3(256), static_cast<const OrbJob *>(d_jobs),
-                reinterpret_cast<uint4 *>(static_cast<uint8_t *>(ctx->d_out) + sc_bytes), static_cast<int>(row / 16), ccap, desc ? 1 : 0);
+                reinterpret_cast<uint4 *>(fi.rows.in(ctx->d_out)), static_cast<int>(row / 16), ccap, desc ? 1 : 0);
   }
   SDVL_HIP_CHECK(ctx, hipGetLastError());
-  uint8_t *h = static_cast<uint8_t *>(ctx->h_out);
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(h, ctx->d_out, sc_bytes + row * n, hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, fi.rows.off + fi.rows.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_mark_record(ctx, SDVL_MARK_FILTER, &ctx->filter_ticket));
   ctx->filter_pending = n;
-  ctx->filter_ccap = ccap;
-  ctx->filter_desc = desc ? 1 : 0;
-  ctx->filter_sc_bytes = sc_bytes;
-  ctx->filter_row = row;
   return SDVL_OK;
 }
 
@@ -575,14 +572,13 @@ int sdvl_filter_inputs_end(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, int 
                            int32_t *counts) {
   if (!ctx || n < 0 || (n > 0 && (!frames || !xyl || !scores || !counts)) || cap <= 0) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, ctx->filter_pending == n && (desc != nullptr) == (ctx->filter_desc != 0), "sdvl_filter_inputs_end without a matching sdvl_filter_inputs_begin");
+  SDVL_REQUIRE(ctx, ctx->filter_pending == n && (desc != nullptr) == (ctx->filter_inputs.with_desc != 0), "sdvl_filter_inputs_end without a matching sdvl_filter_inputs_begin");
   ctx->filter_pending = 0;
   SDVL_HIP_CHECK(ctx, sdvl_mark_wait(ctx, SDVL_MARK_FILTER, ctx->filter_ticket));
-  const int ccap = ctx->filter_ccap;
-  const size_t sc_bytes = ctx->filter_sc_bytes, row = ctx->filter_row;
-  const uint8_t *h = static_cast<const uint8_t *>(ctx->h_out);
+  const auto &fi = ctx->filter_inputs;
+  const int ccap = fi.row_cap;
   for (int i = 0; i < n; i++) {
-    const uint8_t *src = h + sc_bytes + row * i;
+    const uint8_t *src = fi.rows.cin(ctx->h_out) + fi.row_bytes * i;
     const int32_t *hdr = reinterpret_cast<const int32_t *>(src);
     int cnt = frames[i]->hdr_stale ? 0 : hdr[0];
     if (cnt > cap) {
@@ -596,7 +592,7 @@ int sdvl_filter_inputs_end(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, int 
       xyl[(static_cast<size_t>(i) * cap + k) * 3 + 1] = hdr[4 * (k + 1) + 1];
       xyl[(static_cast<size_t>(i) * cap + k) * 3 + 2] = hdr[4 * (k + 1) + 2];
     }
-    memcpy(scores + static_cast<size_t>(i) * cap, reinterpret_cast<const double *>(h) + static_cast<size_t>(i) * ccap, sizeof(double) * cnt);
+    memcpy(scores + static_cast<size_t>(i) * cap, fi.scores.cin(ctx->h_out) + static_cast<size_t>(i) * ccap, sizeof(double) * cnt);
     if (desc) memcpy(desc + static_cast<size_t>(i) * cap * 32, src + sizeof(int32_t) * 4 * (static_cast<size_t>(ccap) + 1), static_cast<size_t>(cnt) * 32);
   }
   return SDVL_OK;
@@ -621,58 +617,62 @@ int sdvl_filter_corners_begin(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, c
   }
   const int max_out = n_cells;
   // device: scores[n][ccap] | counts[n] | records[n][max_out] ; host mirror of counts + records
-  const size_t sc_bytes = (sizeof(double) * static_cast<size_t>(n) * ccap + 255) / 256 * 256;
-  const size_t cnt_bytes = (sizeof(int32_t) * n + 255) / 256 * 256, rec_bytes = sizeof(sdvl_filtered_corner) * static_cast<size_t>(n) * max_out;
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, sc_bytes + cnt_bytes + rec_bytes, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, cnt_bytes + rec_bytes, true);
+  sdvl_layout o, ho;
+  const sdvl_part<double> scores = o.take<double>(static_cast<size_t>(n) * ccap);
+  const sdvl_part<int32_t> counts = o.take<int32_t>(n);
+  const sdvl_part<sdvl_filtered_corner> recs = o.take<sdvl_filtered_corner>(static_cast<size_t>(n) * max_out);
+  auto &fc = ctx->filter_corners;
+  fc = {ho.take<int32_t>(n), ho.take<sdvl_filtered_corner>(static_cast<size_t>(n) * max_out), max_out};
+  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, ho.bytes(), true);
   if (rc) return rc;
   OrbJob *d_jobs = nullptr;
   int max_n = 0;
-  rc = fill_jobs(ctx, n, frames, ccap, nullptr, static_cast<double *>(ctx->d_out), &d_jobs, &max_n);
+  rc = fill_jobs(ctx, n, frames, ccap, nullptr, scores.in(ctx->d_out), &d_jobs, &max_n);
   if (rc) return rc;
   max_n = max_n > ccap ? ccap : max_n;
   if (max_n > 0) SDVL_LAUNCH(ctx, "shi_tomasi", shi_tomasi_kernel, xcd_frame_grid(n, shi_chunks(max_n)), dim3(64), d_jobs, n, shi_chunks(max_n));
-  const size_t jb = (sizeof(FilterJob) * n + 255) / 256 * 256, mb = sizeof(uint32_t) * static_cast<size_t>(n) * mask_words;
+  sdvl_layout st;  // staging: jobs | lock masks
+  const sdvl_part<FilterJob> st_jobs = st.take<FilterJob>(n);
+  const sdvl_part<uint32_t> st_locked = st.take<uint32_t>(static_cast<size_t>(n) * mask_words);
   void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, jb + mb, &hs, &dsx);
+  rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  FilterJob *hj = static_cast<FilterJob *>(hs);
-  uint8_t *d8 = static_cast<uint8_t *>(ctx->d_out);
+  FilterJob *hj = st_jobs.in(hs);
   for (int i = 0; i < n; i++) {
     const FrameView &v = frames[i]->v;
     memset(&hj[i], 0, sizeof(FilterJob));
     for (int l = 0; l < v.levels; l++) { hj[i].level[l] = v.level[l]; hj[i].lw[l] = v.lw[l]; hj[i].lh[l] = v.lh[l]; }
     hj[i].corners = v.corners;
     hj[i].n_ptr = v.corner_hdr;
-    hj[i].scores = reinterpret_cast<const double *>(d8) + static_cast<size_t>(i) * ccap;
-    hj[i].locked = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(dsx) + jb) + static_cast<size_t>(i) * mask_words;
-    hj[i].out = reinterpret_cast<sdvl_filtered_corner *>(d8 + sc_bytes + cnt_bytes) + static_cast<size_t>(i) * max_out;
-    hj[i].out_count = reinterpret_cast<int32_t *>(d8 + sc_bytes) + i;
+    hj[i].scores = scores.cin(ctx->d_out) + static_cast<size_t>(i) * ccap;
+    hj[i].locked = st_locked.cin(dsx) + static_cast<size_t>(i) * mask_words;
+    hj[i].out = recs.in(ctx->d_out) + static_cast<size_t>(i) * max_out;
+    hj[i].out_count = counts.in(ctx->d_out) + i;
     hj[i].levels = v.levels;
     hj[i].ccap = ccap;
   }
-  memcpy(static_cast<uint8_t *>(hs) + jb, locked_cells, mb);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, jb + mb));
+  memcpy(st_locked.in(hs), locked_cells, st_locked.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
   if (n_cells <= kBinCellsSmall && ccap <= kBinCornersSmall)
-    SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCellsSmall, kBinCornersSmall>), dim3(n), dim3(256), static_cast<const FilterJob *>(dsx),
+    SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCellsSmall, kBinCornersSmall>), dim3(n), dim3(256), st_jobs.cin(dsx),
                 cell_size, grid_w, n_cells, margin, min_feature_score, max_out);
   else if (n_cells <= kBinCells)
-    SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCells, kFilterMaxCorners>), dim3(n), dim3(256), static_cast<const FilterJob *>(dsx),
+    SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCells, kFilterMaxCorners>), dim3(n), dim3(256), st_jobs.cin(dsx),
                 cell_size, grid_w, n_cells, margin, min_feature_score, max_out);
   else if (n_cells <= 4096)
-    SDVL_LAUNCH(ctx, "filter_select", filter_select_kernel, dim3(n), dim3(256), static_cast<const FilterJob *>(dsx), cell_size, grid_w, n_cells, margin,
+    SDVL_LAUNCH(ctx, "filter_select", filter_select_kernel, dim3(n), dim3(256), st_jobs.cin(dsx), cell_size, grid_w, n_cells, margin,
                 min_feature_score, max_out);
   else
     SDVL_LAUNCH(ctx, "filter_select", (filter_select_binned_kernel<kBinCellsLarge, kFilterMaxCorners, kBinSlotsLarge>), dim3(n), dim3(256),
-                static_cast<const FilterJob *>(dsx), cell_size, grid_w, n_cells, margin, min_feature_score, max_out);
-  SDVL_LAUNCH(ctx, "filter_describe", filter_describe_kernel, xcd_frame_grid(n, std::min(max_out, 512)), dim3(64), static_cast<const FilterJob *>(dsx),
+                st_jobs.cin(dsx), cell_size, grid_w, n_cells, margin, min_feature_score, max_out);
+  SDVL_LAUNCH(ctx, "filter_describe", filter_describe_kernel, xcd_frame_grid(n, std::min(max_out, 512)), dim3(64), st_jobs.cin(dsx),
               max_out, n, std::min(max_out, 512));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, sdvl_pull(ctx, ctx->h_out, d8 + sc_bytes, cnt_bytes + rec_bytes));
+  // counts | records: the tail of the device layout is the whole of the host's, part for part the same sizes: one pull
+  SDVL_HIP_CHECK(ctx, sdvl_pull(ctx, fc.counts.in(ctx->h_out), counts.in(ctx->d_out), fc.recs.off + fc.recs.bytes()));
   SDVL_HIP_CHECK(ctx, sdvl_mark_record(ctx, SDVL_MARK_FILTER, &ctx->filter_ticket));
   ctx->filter_pending = n;
-  ctx->filter_ccap = max_out;
-  ctx->filter_sc_bytes = cnt_bytes;
   return SDVL_OK;
 }
 
@@ -682,10 +682,10 @@ int sdvl_filter_corners_end(sdvl_ctx *ctx, int n, int cap, int32_t *counts, sdvl
   SDVL_REQUIRE(ctx, ctx->filter_pending == n, "sdvl_filter_corners_end without a matching sdvl_filter_corners_begin");
   ctx->filter_pending = 0;
   SDVL_HIP_CHECK(ctx, sdvl_mark_wait(ctx, SDVL_MARK_FILTER, ctx->filter_ticket));
-  const int max_out = ctx->filter_ccap;
-  const uint8_t *h = static_cast<const uint8_t *>(ctx->h_out);
-  const int32_t *hc = reinterpret_cast<const int32_t *>(h);
-  const sdvl_filtered_corner *hr = reinterpret_cast<const sdvl_filtered_corner *>(h + ctx->filter_sc_bytes);
+  const auto &fc = ctx->filter_corners;
+  const int max_out = fc.max_out;
+  const int32_t *hc = fc.counts.cin(ctx->h_out);
+  const sdvl_filtered_corner *hr = fc.recs.cin(ctx->h_out);
   for (int i = 0; i < n; i++) {
     if (hc[i] > max_out || hc[i] > cap) {
       ctx->err = "more filtered corners than the output holds";
@@ -735,34 +735,35 @@ int sdvl_orb_describe_points(sdvl_ctx *ctx, const sdvl_frame *f, int n, const in
     const int x = xyl[3 * i], y = xyl[3 * i + 1], l = xyl[3 * i + 2];
     SDVL_REQUIRE(ctx, l >= 0 && l < f->v.levels && x >= 0 && y >= 0 && x < f->v.lw[l] && y < f->v.lh[l], "point outside its pyramid level");
   }
-  // device scratch: d_stage = corners[n][4] | OrbJob ; d_out = desc[n][32] | angle[n]
-  const size_t c_bytes = sizeof(int32_t) * 4 * n, d_bytes = 32 * static_cast<size_t>(n), a_bytes = sizeof(float) * n;
-  const size_t job_off = (c_bytes + 255) / 256 * 256;
-  const size_t a_off = (d_bytes + 255) / 256 * 256;
+  sdvl_layout st, o;  // staging: corners[n][4] | OrbJob ; d_out and h_out: desc[n][32] | angle[n]
+  const sdvl_part<int32_t> st_corners = st.take<int32_t>(4 * static_cast<size_t>(n));
+  const sdvl_part<OrbJob> st_job = st.take<OrbJob>(1);
+  const sdvl_part<uint8_t> o_desc = o.take<uint8_t>(32 * static_cast<size_t>(n));
+  const sdvl_part<float> o_angle = o.take<float>(n);
   void *hs = nullptr, *dsx = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, a_off + a_bytes, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, a_off + a_bytes, true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, job_off + sizeof(OrbJob), &hs, &dsx);
+  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  int32_t *hc = static_cast<int32_t *>(hs);
+  int32_t *hc = st_corners.in(hs);
   for (int i = 0; i < n; i++) { hc[4 * i] = xyl[3 * i]; hc[4 * i + 1] = xyl[3 * i + 1]; hc[4 * i + 2] = xyl[3 * i + 2]; hc[4 * i + 3] = 0; }
-  OrbJob *hj = reinterpret_cast<OrbJob *>(static_cast<uint8_t *>(hs) + job_off);
+  OrbJob *hj = st_job.in(hs);
   memset(hj, 0, sizeof(OrbJob));
   for (int l = 0; l < f->v.levels; l++) { hj->level[l] = f->v.level[l]; hj->lw[l] = f->v.lw[l]; hj->lh[l] = f->v.lh[l]; }
-  hj->corners = static_cast<int32_t *>(dsx);
-  hj->desc = static_cast<uint8_t *>(ctx->d_out);
+  hj->corners = st_corners.in(dsx);
+  hj->desc = o_desc.in(ctx->d_out);
   hj->out = nullptr;
-  hj->out_angle = reinterpret_cast<float *>(static_cast<uint8_t *>(ctx->d_out) + a_off);
+  hj->out_angle = o_angle.in(ctx->d_out);
   hj->n_ptr = nullptr;
   hj->n = n;
   hj->levels = f->v.levels;
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, job_off + sizeof(OrbJob)));
-  SDVL_LAUNCH(ctx, "orb_describe", orb_describe_kernel, xcd_frame_grid(1, n), dim3(64), reinterpret_cast<const OrbJob *>(static_cast<uint8_t *>(dsx) + job_off), 1, n);
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
+  SDVL_LAUNCH(ctx, "orb_describe", orb_describe_kernel, xcd_frame_grid(1, n), dim3(64), st_job.cin(dsx), 1, n);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, a_off + a_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out_desc, ctx->h_out, d_bytes);
-  if (out_angle_deg) memcpy(out_angle_deg, static_cast<uint8_t *>(ctx->h_out) + a_off, a_bytes);
+  memcpy(out_desc, o_desc.in(ctx->h_out), o_desc.bytes());
+  if (out_angle_deg) memcpy(out_angle_deg, o_angle.in(ctx->h_out), o_angle.bytes());
   return SDVL_OK;
 }
 
@@ -775,28 +776,29 @@ int sdvl_hamming_argmin(sdvl_ctx *ctx, int n, const uint8_t *queries, const int3
   const int total = cand_offsets[n];
   SDVL_REQUIRE(ctx, total == 0 || cand_desc, "candidate descriptors missing");
   SDVL_REQUIRE(ctx, threshold >= 0 && threshold <= 256, "threshold outside [0, 256]");
-  // staged: queries[n][32] | offsets[n+1] | cands[total][32] | HammingJob ; d_out = best[n][2]
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t q_bytes = 32 * static_cast<size_t>(n), o_off = up(q_bytes), c_off = o_off + up(sizeof(int32_t) * (n + 1)),
-               j_off = c_off + up(32 * static_cast<size_t>(total)), r_bytes = sizeof(int32_t) * 2 * n;
+  sdvl_layout st;  // staging: queries[n][32] | offsets[n+1] | cands[total][32] | HammingJob ; d_out = best[n][2]
+  const sdvl_part<uint8_t> st_queries = st.take<uint8_t>(32 * static_cast<size_t>(n));
+  const sdvl_part<int32_t> st_offsets = st.take<int32_t>(static_cast<size_t>(n) + 1);
+  const sdvl_part<uint8_t> st_cands = st.take<uint8_t>(32 * static_cast<size_t>(total));
+  const sdvl_part<HammingJob> st_job = st.take<HammingJob>(1);
+  const size_t r_bytes = sizeof(int32_t) * 2 * n;
   void *hs = nullptr, *dsx = nullptr;
   int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, r_bytes, false);
   if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, r_bytes, true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, j_off + sizeof(HammingJob), &hs, &dsx);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  uint8_t *h = static_cast<uint8_t *>(hs), *d = static_cast<uint8_t *>(dsx);
-  memcpy(h, queries, q_bytes);
-  memcpy(h + o_off, cand_offsets, sizeof(int32_t) * (n + 1));
-  if (total) memcpy(h + c_off, cand_desc, 32 * static_cast<size_t>(total));
-  HammingJob *hj = reinterpret_cast<HammingJob *>(h + j_off);
-  hj->queries = d;
-  hj->offsets = reinterpret_cast<const int32_t *>(d + o_off);
-  hj->cands = d + c_off;
+  memcpy(st_queries.in(hs), queries, st_queries.bytes());
+  memcpy(st_offsets.in(hs), cand_offsets, st_offsets.bytes());
+  if (total) memcpy(st_cands.in(hs), cand_desc, st_cands.bytes());
+  HammingJob *hj = st_job.in(hs);
+  hj->queries = st_queries.in(dsx);
+  hj->offsets = st_offsets.in(dsx);
+  hj->cands = st_cands.in(dsx);
   hj->best = static_cast<int32_t *>(ctx->d_out);
   hj->n = n;
   hj->threshold = threshold;
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, j_off + sizeof(HammingJob)));
-  SDVL_LAUNCH(ctx, "hamming_argmin", hamming_argmin_kernel, dim3(n), dim3(64), reinterpret_cast<const HammingJob *>(d + j_off));
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
+  SDVL_LAUNCH(ctx, "hamming_argmin", hamming_argmin_kernel, dim3(n), dim3(64), st_job.cin(dsx));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, r_bytes, hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));

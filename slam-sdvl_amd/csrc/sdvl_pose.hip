@@ -151,6 +151,8 @@ __device__ bool converge_pose_small(const sdvl_pose_obs *obs, const int *idx, in
 // waves are few and narrow: 64-thread workgroups).  It converges the first kHypDraws draws; pose_refine converges the rest on demand
 // and counts every draw's supporters as its replay of the RANSAC loop reaches the draw.
 constexpr int kHypDraws = 64;     // draws of one workgroup = lanes of its wave
+// dynamic LDS of pose_hypotheses_kernel: s_hyp_cache[max_ransac_points][6][kHypDraws] doubles, <= 24 KB (max_ransac_points <= 8)
+size_t hyp_cache_bytes(int max_ransac_points) { return static_cast<size_t>(max_ransac_points) * 6 * kHypDraws * sizeof(double); }
 
 __global__ __launch_bounds__(kHypDraws) void pose_hypotheses_kernel(const PoseJobDev *__restrict__ jobs, const sdvl_pose_obs *__restrict__ obs_all,
                                                                     const int32_t *__restrict__ rand_idx, sdvl_pose_params prm,
@@ -172,7 +174,7 @@ __global__ __launch_bounds__(kHypDraws) void pose_hypotheses_kernel(const PoseJo
     int sel[8];
     for (int i = 0; i < npoints; i++) sel[i] = (index + i) % size;
     Rigid se3;
-    extern __shared__ double s_hyp_cache[];  // [max_ransac_points][6][64]
+    extern __shared__ double s_hyp_cache[];  // hyp_cache_bytes()
     if (converge_pose_small<true>(obs, sel, npoints, se3_from7(job.pose), prm.fx, prm.max_optim_pose_its, &se3, s_hyp_cache, threadIdx.x)) {
       r.ok = 1;
       se3_to7(se3, r.se3);
@@ -761,13 +763,8 @@ int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseJobDev *d_jobs
                 static_cast<HypResult *>(d_hyp));
   } else {
     hyp_ready = std::min(p->max_ransac_its, kHypDraws);  // the first wave of draws; the rest on demand (pose_refine)
-    {
-      hipEvent_t ev_a = nullptr, ev_b = nullptr;
-      sdvl_timer_events(ctx, "pose_hypotheses", &ev_a, &ev_b);
-      const size_t cache_bytes = static_cast<size_t>(p->max_ransac_points) * 6 * 64 * sizeof(double);  // <= 24.5 KB (max_ransac_points <= 8)
-      hipExtLaunchKernelGGL(pose_hypotheses_kernel, dim3((hyp_ready + kHypDraws - 1) / kHypDraws, n_jobs), dim3(kHypDraws), cache_bytes, ctx->stream, ev_a, ev_b,
-                            0, d_jobs, d_obs, d_rand, *p, static_cast<HypResult *>(d_hyp));
-    }
+    SDVL_LAUNCH_LDS(ctx, "pose_hypotheses", pose_hypotheses_kernel, dim3((hyp_ready + kHypDraws - 1) / kHypDraws, n_jobs), dim3(kHypDraws),
+                    hyp_cache_bytes(p->max_ransac_points), d_jobs, d_obs, d_rand, *p, static_cast<HypResult *>(d_hyp));
     // the supporters: counted by pose_refine as its replay of the RANSAC loop reaches a draw
   }
   const int lazy = !wave_form ? 1 : 0;
@@ -789,8 +786,8 @@ extern "C" int sdvl_pose_from_matches(sdvl_ctx *ctx, int n_jobs, const sdvl_pose
                                       sdvl_pose_result *results, int32_t *out_lists) {
   if (!ctx || !p || n_jobs < 0 || (n_jobs > 0 && (!jobs || !results)) || n_obs < 0 || (n_obs > 0 && (!obs || !out_lists))) return SDVL_ERR_INVALID;
   if (n_jobs == 0) return SDVL_OK;
-  SDVL_REQUIRE(ctx, p->max_ransac_points >= 1 && p->max_ransac_points <= 8, "max_ransac_points must be in [1,8]");
-  SDVL_REQUIRE(ctx, p->max_ransac_its >= 1 && p->max_ransac_its <= 4096 && p->max_optim_pose_its >= 0, "bad iteration limits");
+  int rc = sdvl_check_pose_params(ctx, p);
+  if (rc) return rc;
   SDVL_REQUIRE(ctx, rand_idx && nits_table, "rand / nits tables missing");
   for (int j = 0; j < n_jobs; j++) {
     const sdvl_pose_job &a = jobs[j];
@@ -805,18 +802,19 @@ extern "C" int sdvl_pose_from_matches(sdvl_ctx *ctx, int n_jobs, const sdvl_pose
     for (int h = 0; h < p->max_ransac_its && size > 0; h++)
       SDVL_REQUIRE(ctx, rand_idx[a.rand_begin + h] >= 0 && rand_idx[a.rand_begin + h] < size, "rand index outside the match list");
   }
-  const size_t jb = (sizeof(PoseJobDev) * n_jobs + 255) / 256 * 256, ob = (sizeof(sdvl_pose_obs) * static_cast<size_t>(n_obs) + 255) / 256 * 256;
-  const size_t rb = (sizeof(int32_t) * static_cast<size_t>(n_rand) + 255) / 256 * 256, nb = (sizeof(int32_t) * static_cast<size_t>(n_nits) + 255) / 256 * 256;
-  const size_t hyp_bytes = sizeof(HypResult) * static_cast<size_t>(n_jobs) * p->max_ransac_its;
-  const size_t res_bytes = (sizeof(sdvl_pose_result) * n_jobs + 255) / 256 * 256, list_bytes = sizeof(int32_t) * static_cast<size_t>(n_obs);
+  sdvl_layout st, o;  // staging: jobs | observations | rand indices | budgets ; d_out and h_out: results | lists ; d_work: the hypotheses alone
+  const sdvl_part<PoseJobDev> st_jobs = st.take<PoseJobDev>(n_jobs);
+  const sdvl_part<sdvl_pose_obs> st_obs = st.take<sdvl_pose_obs>(n_obs);
+  const sdvl_part<int32_t> st_rand = st.take<int32_t>(n_rand), st_nits = st.take<int32_t>(n_nits);
+  const sdvl_part<sdvl_pose_result> o_res = o.take<sdvl_pose_result>(n_jobs);
+  const sdvl_part<int32_t> o_lists = o.take<int32_t>(n_obs);
   void *hs = nullptr, *dsx = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, hyp_bytes + 256, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, res_bytes + list_bytes, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, res_bytes + list_bytes, true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, jb + ob + rb + nb, &hs, &dsx);
+  rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, sizeof(HypResult) * static_cast<size_t>(n_jobs) * p->max_ransac_its, false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  uint8_t *h8 = static_cast<uint8_t *>(hs), *d8 = static_cast<uint8_t *>(dsx);
-  PoseJobDev *hj = reinterpret_cast<PoseJobDev *>(h8);
+  PoseJobDev *hj = st_jobs.in(hs);
   for (int j = 0; j < n_jobs; j++) {
     hj[j].obs_begin = jobs[j].obs_begin;
     hj[j].n_obs = jobs[j].obs_end - jobs[j].obs_begin;
@@ -825,25 +823,20 @@ extern "C" int sdvl_pose_from_matches(sdvl_ctx *ctx, int n_jobs, const sdvl_pose
     memcpy(hj[j].pose, jobs[j].pose, sizeof(double) * 7);
     hj[j].pad_ = 0.0;
   }
-  if (n_obs) memcpy(h8 + jb, obs, sizeof(sdvl_pose_obs) * static_cast<size_t>(n_obs));
-  memcpy(h8 + jb + ob, rand_idx, sizeof(int32_t) * static_cast<size_t>(n_rand));
-  memcpy(h8 + jb + ob + rb, nits_table, sizeof(int32_t) * static_cast<size_t>(n_nits));
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, jb + ob + rb + nb));
-  const PoseJobDev *dj = reinterpret_cast<const PoseJobDev *>(d8);
-  const sdvl_pose_obs *dobs = reinterpret_cast<const sdvl_pose_obs *>(d8 + jb);
-  const int32_t *drand = reinterpret_cast<const int32_t *>(d8 + jb + ob), *dnits = reinterpret_cast<const int32_t *>(d8 + jb + ob + rb);
-  HypResult *dhyp = static_cast<HypResult *>(ctx->d_work);
-  sdvl_pose_result *dres = static_cast<sdvl_pose_result *>(ctx->d_out);
-  int32_t *dlists = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(ctx->d_out) + res_bytes);
+  if (n_obs) memcpy(st_obs.in(hs), obs, st_obs.bytes());
+  memcpy(st_rand.in(hs), rand_idx, st_rand.bytes());
+  memcpy(st_nits.in(hs), nits_table, st_nits.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
   sdvl_pose_params prm = *p;
   prm.pad_ = 0;  // rand_idx holds indices already reduced modulo the match count
   int max_obs = 0;
   for (int j = 0; j < n_jobs; j++) max_obs = std::max(max_obs, jobs[j].obs_end - jobs[j].obs_begin);
-  rc = sdvl_pose_enqueue_device(ctx, n_jobs, dj, dobs, drand, dnits, &prm, dhyp, dres, dlists, max_obs, n_jobs);
+  rc = sdvl_pose_enqueue_device(ctx, n_jobs, st_jobs.cin(dsx), st_obs.cin(dsx), st_rand.cin(dsx), st_nits.cin(dsx), &prm, static_cast<HypResult *>(ctx->d_work),
+                                o_res.in(ctx->d_out), o_lists.in(ctx->d_out), max_obs, n_jobs);
   if (rc) return rc;
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, res_bytes + list_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(results, ctx->h_out, sizeof(sdvl_pose_result) * n_jobs);
-  if (n_obs) memcpy(out_lists, static_cast<uint8_t *>(ctx->h_out) + res_bytes, list_bytes);
+  memcpy(results, o_res.in(ctx->h_out), o_res.bytes());
+  if (n_obs) memcpy(out_lists, o_lists.in(ctx->h_out), o_lists.bytes());
   return SDVL_OK;
 }

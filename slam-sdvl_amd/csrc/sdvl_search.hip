@@ -778,25 +778,6 @@ __global__ __launch_bounds__(256) void select_matches_kernel(const ChainFrameDev
   }
 }
 
-void fill_frame(SearchFrame *d, const sdvl_frame *f) {
-  memset(d, 0, sizeof(SearchFrame));
-  for (int l = 0; l < f->v.levels; l++) {
-    d->level[l] = f->v.level[l];
-    d->lw[l] = f->v.lw[l];
-    d->lh[l] = f->v.lh[l];
-  }
-  d->corners = f->v.corners;
-  d->desc = f->desc_valid ? f->v.desc : nullptr;  // null: the search computes what it compares (search_points_kernel)
-  d->n_ptr = f->v.corner_hdr;
-  d->levels = f->v.levels;
-  if (f->bins_valid) {
-    d->bin_start = f->bin_start;
-    d->bin_entries = f->bin_entries;
-    d->bin_gw = f->bin_gw;
-    d->bin_cells = f->bin_cells;
-  }
-}
-
 
 // ---------------------------------------------------------------------------------------------- the mapper's depth filter
 // extra/utils.cc:193-205: A = [R v_ref | v_cur], depth2 = -(A^T A)^-1 A^T t, |depth2[0]|
@@ -963,18 +944,21 @@ __global__ __launch_bounds__(128) void depth_filter_kernel(const SearchReqDev *_
 
 int sdvl_search_launch_device(sdvl_ctx *ctx, int n_slots, const SearchReqDev *d_reqs, const SearchFramePose *d_table,
                               const SearchBlock *d_blocks, int n_blocks, const sdvl_camera *cam, const sdvl_search_params *p,
-                              SearchPrep *d_prep, sdvl_search_res *d_res, sdvl_search_res *h_res, bool prepared) {
-  SDVL_REQUIRE(ctx, p->patch_size == 8, "only patch_size 8 is supported (one wave64 per 8x8 patch)");
-  SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "bad max_fast_levels");
-  SDVL_REQUIRE(ctx, p->max_align_its >= 0 && p->margin >= 4, "bad max_align_its / margin");
+                              SearchPrep *d_prep, sdvl_search_res *d_res, sdvl_search_res *h_res, bool prepared, bool binned) {
+  const int rc = sdvl_check_search_params(ctx, p);
+  if (rc) return rc;
   if (n_slots <= 0 || n_blocks <= 0) return SDVL_OK;
-  Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
+  const Cam c = cam_of(*cam);
   // `prepared`: the kernel that wrote the requests has written their prepare records too (track_project_kernel)
   if (!prepared) SDVL_LAUNCH(ctx, "search_prepare", search_prepare_kernel, dim3((n_slots + 63) / 64), dim3(64), d_reqs, d_table, n_slots, c, *p, d_prep);
-  // device-built batches search frames that came out of sdvl_detect_corners: binned (a frame without bins would still be
-  // searched correctly, its corner list read from HBM)
-  SDVL_LAUNCH(ctx, "search_points", (search_points_kernel<false, 1>), dim3(static_cast<unsigned>((n_blocks + 7) / 8 * 8 * kWavesPerBlock)), dim3(64), d_reqs,
-              d_table, d_blocks, static_cast<const SearchPrep *>(d_prep), c, *p, n_blocks, d_res, h_res);
+  // the one launch of search_points_kernel.  binned: one wave per workgroup, the corners come through the frames' bins (a frame without
+  // bins would still be searched correctly, its corner list read from HBM); otherwise kWavesPerBlock waves per workgroup scan the list
+  if (binned)
+    SDVL_LAUNCH(ctx, "search_points", (search_points_kernel<false, 1>), dim3(static_cast<unsigned>((n_blocks + 7) / 8 * 8 * kWavesPerBlock)), dim3(64), d_reqs,
+                d_table, d_blocks, static_cast<const SearchPrep *>(d_prep), c, *p, n_blocks, d_res, h_res);
+  else
+    SDVL_LAUNCH(ctx, "search_points", (search_points_kernel<true, kWavesPerBlock>), dim3(static_cast<unsigned>((n_blocks + 7) / 8 * 8)), dim3(64 * kWavesPerBlock),
+                d_reqs, d_table, d_blocks, static_cast<const SearchPrep *>(d_prep), c, *p, n_blocks, d_res, h_res);
 #ifdef SDVL_SEARCH_STATS
   {
     static int launches = 0;
@@ -994,9 +978,8 @@ int sdvl_select_matches_launch(sdvl_ctx *ctx, int n_frames, const ChainFrameDev 
                                const int32_t *d_cand_first, const sdvl_search_res *d_res, const double *d_req_point,
                                const sdvl_camera *cam, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs, int32_t *d_nobs, int32_t *d_match_cand) {
   if (n_frames <= 0) return SDVL_OK;
-  Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
-  SDVL_LAUNCH(ctx, "select_matches", select_matches_kernel, dim3(n_frames), dim3(256), d_frames, d_cand_req, d_cand_first, d_res, d_req_point, c,
-              d_jobs, d_obs, d_nobs, d_match_cand);
+  SDVL_LAUNCH(ctx, "select_matches", select_matches_kernel, dim3(n_frames), dim3(256), d_frames, d_cand_req, d_cand_first, d_res, d_req_point,
+              cam_of(*cam), d_jobs, d_obs, d_nobs, d_match_cand);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
 }
@@ -1012,7 +995,9 @@ static_assert(sizeof(sdvl_search_req_packed) == sizeof(SearchReqDev), "public an
 struct SearchBatch {
   void *hs = nullptr, *dsx = nullptr;
   int cap = 0;
-  size_t in_bytes = 0, blk_cap_bytes = 0;
+  sdvl_part<SearchReqDev> reqs;  // both buffers: requests | workgroup table | frame table (up to kSearchTabCap entries)
+  sdvl_part<SearchBlock> blocks;
+  sdvl_part<SearchFramePose> tab;
   std::vector<SearchFramePose> table;
   std::vector<const sdvl_frame *> frames;  // parallel to `table`
   std::unordered_map<const sdvl_frame *, int> where;
@@ -1034,18 +1019,19 @@ int sdvl_search_begin(sdvl_ctx *ctx, int max_requests, sdvl_search_req_packed **
   B.where.clear();
   B.last = -1;
   B.last2 = -1;
-  B.in_bytes = (sizeof(SearchReqDev) * static_cast<size_t>(max_requests) + 255) / 256 * 256;
-  B.blk_cap_bytes = (sizeof(SearchBlock) * static_cast<size_t>(max_requests) + 255) / 256 * 256;
+  sdvl_layout lay;
+  B.reqs = lay.take<SearchReqDev>(max_requests);
+  B.blocks = lay.take<SearchBlock>(max_requests);
+  B.tab = lay.take<SearchFramePose>(kSearchTabCap);
   // the batch's own pinned + device buffers, not the staging ring: the caller fills the records over time and every
   // sdvl_stream_wait in between (buffer growth inside sdvl_search_run, a staging request that wraps) restarts the ring
   if (ctx->search_busy_gen == ctx->wait_gen) SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));  // the previous batch may still be read
-  const size_t need = B.in_bytes + B.blk_cap_bytes + sizeof(SearchFramePose) * kSearchTabCap;
-  int rc = sdvl_ensure(ctx, &ctx->h_search, &ctx->h_search_bytes, need, true);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->d_search, &ctx->d_search_bytes, need, false);
+  int rc = sdvl_ensure(ctx, &ctx->h_search, &ctx->h_search_bytes, lay.bytes(), true);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->d_search, &ctx->d_search_bytes, lay.bytes(), false);
   if (rc) return rc;
   B.hs = ctx->h_search;
   B.dsx = ctx->d_search;
-  *reqs = static_cast<sdvl_search_req_packed *>(B.hs);
+  *reqs = reinterpret_cast<sdvl_search_req_packed *>(B.reqs.in(B.hs));
   return SDVL_OK;
 }
 
@@ -1062,7 +1048,7 @@ int sdvl_search_slot(sdvl_ctx *ctx, const sdvl_frame *f, const double *pose) {
   auto it = B.where.find(f);
   if (it != B.where.end() && memcmp(table[it->second].pose, pose, sizeof(double) * 7) == 0) { B.last = it->second; return B.last; }
   SearchFramePose e;
-  fill_frame(&e.f, f);
+  fill_view(&e.f, f);
   memcpy(e.pose, pose, sizeof(double) * 7);
   e.pad_ = 0.0;
   table.push_back(e);
@@ -1072,38 +1058,38 @@ int sdvl_search_slot(sdvl_ctx *ctx, const sdvl_frame *f, const double *pose) {
   return B.last;
 }
 
-// everything of sdvl_search_run up to and including the queued copy of the results into h_out[0 .. n records); the caller
-// waits.  extra_d / extra_h: room the caller wants behind the search's own use of d_out / h_out (offsets returned).
-static int search_enqueue(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, size_t extra_d, size_t extra_h,
-                          size_t *extra_d_off, size_t *extra_h_off, const SearchReqDev **d_reqs_out = nullptr,
-                          const SearchFramePose **d_table_out = nullptr) {
+// What a search of n requests keeps in the context's result buffers — d_out: results | per-request records of the scalar phase;
+// h_out: results — each at the head, so a caller takes the parts it wants behind them from `d` / `h` before search_enqueue.
+struct SearchOut {
+  sdvl_layout d, h;
+  sdvl_part<sdvl_search_res> res, h_res;
+  sdvl_part<SearchPrep> prep;
+  explicit SearchOut(int n) : res(d.take<sdvl_search_res>(n)), h_res(h.take<sdvl_search_res>(n)), prep(d.take<SearchPrep>(n)) {}
+};
+
+// everything of sdvl_search_run up to and including the queued copy of the results into h_out (so.h_res); the caller waits.
+static int search_enqueue(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const SearchOut &so,
+                          const SearchReqDev **d_reqs_out = nullptr, const SearchFramePose **d_table_out = nullptr) {
   SearchBatch &B = batch_of(ctx);
   SDVL_REQUIRE(ctx, B.hs && n <= B.cap, "sdvl_search_run without a matching sdvl_search_begin");
-  SDVL_REQUIRE(ctx, p->patch_size == 8, "only patch_size 8 is supported (one wave64 per 8x8 patch)");
-  SDVL_REQUIRE(ctx, p->max_fast_levels >= 1 && p->max_fast_levels <= 4, "bad max_fast_levels");
-  SDVL_REQUIRE(ctx, p->max_align_its >= 0 && p->margin >= 4, "bad max_align_its / margin");
+  int rc = sdvl_check_search_params(ctx, p);
+  if (rc) return rc;
   const int n_slots = static_cast<int>(B.table.size());
   for (const SearchFramePose &e : B.table) SDVL_REQUIRE(ctx, p->max_fast_levels <= e.f.levels, "max_fast_levels exceeds the pyramid depth");
-  SearchReqDev *hreq = static_cast<SearchReqDev *>(B.hs);
+  void *hs = B.hs, *dsx = B.dsx;
+  SearchReqDev *hreq = B.reqs.in(hs);
   for (int i = 0; i < n; i++) {
     const SearchReqDev &d = hreq[i];
     SDVL_REQUIRE(ctx, d.cur >= 0 && d.cur < n_slots && d.ref >= 0 && d.ref < n_slots, "request names a frame slot outside the batch");
     SDVL_REQUIRE(ctx, d.level >= 0 && d.level < B.table[d.ref].f.levels, "feature level outside the reference pyramid");
     SDVL_REQUIRE(ctx, d.idepth == d.idepth && d.idepth != 0.0, "inverse depth must be finite and non-zero");
   }
-  const size_t in_bytes = B.in_bytes, blk_cap_bytes = B.blk_cap_bytes;
-  const size_t out_bytes = sizeof(sdvl_search_res) * static_cast<size_t>(n);
-  const size_t out_dev_bytes = (out_bytes + 255) / 256 * 256;
-  const size_t prep_bytes = (sizeof(SearchPrep) * static_cast<size_t>(n) + 255) / 256 * 256;
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, out_dev_bytes + prep_bytes + extra_d, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, out_dev_bytes + extra_h, true);
+  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, so.d.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, so.h.bytes(), true);
   if (rc) return rc;
-  if (extra_d_off) *extra_d_off = out_dev_bytes + prep_bytes;
-  if (extra_h_off) *extra_h_off = out_dev_bytes;
-  void *hs = B.hs, *dsx = B.dsx;
   ctx->search_busy_gen = ctx->wait_gen;  // from here on the batch buffers are read by queued copies and kernels
   // workgroups: runs of up to kWavesPerBlock consecutive requests that search the same current frame
-  SearchBlock *hblk = reinterpret_cast<SearchBlock *>(static_cast<uint8_t *>(hs) + in_bytes);
+  SearchBlock *hblk = B.blocks.in(hs);
   int n_blocks = 0;
   for (int i = 0; i < n;) {
     int cnt = 1;
@@ -1116,48 +1102,34 @@ static int search_enqueue(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
   const std::vector<SearchFramePose> &table = B.table;
   const SearchFramePose *d_table = nullptr;
   if (table.size() <= kSearchTabCap) {
-    memcpy(static_cast<uint8_t *>(hs) + in_bytes + blk_cap_bytes, table.data(), sizeof(SearchFramePose) * table.size());
-    SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, in_bytes + blk_cap_bytes + sizeof(SearchFramePose) * table.size()));
-    d_table = reinterpret_cast<const SearchFramePose *>(static_cast<uint8_t *>(dsx) + in_bytes + blk_cap_bytes);
+    memcpy(B.tab.in(hs), table.data(), sizeof(SearchFramePose) * table.size());
+    SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, B.tab.off + sizeof(SearchFramePose) * table.size()));
+    d_table = B.tab.cin(dsx);
   } else {  // more distinct (frame, pose) pairs than the staging reserve: the table travels through the work buffer
-    SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, in_bytes + blk_cap_bytes));
+    SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, B.tab.off));
     rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, sizeof(SearchFramePose) * table.size(), false);
     if (rc) return rc;
     SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_work, table.data(), sizeof(SearchFramePose) * table.size(), hipMemcpyHostToDevice, ctx->stream));
     SDVL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // `table` is pageable and reused by the next batch
     d_table = static_cast<const SearchFramePose *>(ctx->d_work);
   }
-  if (d_reqs_out) *d_reqs_out = static_cast<const SearchReqDev *>(dsx);
+  const SearchReqDev *d_reqs = B.reqs.cin(dsx);
+  if (d_reqs_out) *d_reqs_out = d_reqs;
   if (d_table_out) *d_table_out = d_table;
-  Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
-  // d_out: results | per-request records of the scalar phase
-  SearchPrep *d_prep = reinterpret_cast<SearchPrep *>(static_cast<uint8_t *>(ctx->d_out) + out_dev_bytes);
-  SDVL_LAUNCH(ctx, "search_prepare", search_prepare_kernel, dim3((n + 63) / 64), dim3(64), static_cast<const SearchReqDev *>(dsx), d_table, n, c,
-              *p, d_prep);
   bool all_binned = true;
   for (const sdvl_frame *f : B.frames) all_binned = all_binned && f->bins_valid;
-  if (all_binned) {
-    SDVL_LAUNCH(ctx, "search_points", (search_points_kernel<false, 1>), dim3(static_cast<unsigned>((n_blocks + 7) / 8 * 8 * kWavesPerBlock)), dim3(64),
-                static_cast<const SearchReqDev *>(dsx), d_table, reinterpret_cast<const SearchBlock *>(static_cast<uint8_t *>(dsx) + in_bytes),
-                static_cast<const SearchPrep *>(d_prep), c, *p, n_blocks, static_cast<sdvl_search_res *>(ctx->d_out),
-                static_cast<sdvl_search_res *>(ctx->h_out));
-  } else {
-    SDVL_LAUNCH(ctx, "search_points", (search_points_kernel<true, kWavesPerBlock>), dim3(static_cast<unsigned>((n_blocks + 7) / 8 * 8)), dim3(64 * kWavesPerBlock),
-                static_cast<const SearchReqDev *>(dsx), d_table, reinterpret_cast<const SearchBlock *>(static_cast<uint8_t *>(dsx) + in_bytes),
-                static_cast<const SearchPrep *>(d_prep), c, *p, n_blocks, static_cast<sdvl_search_res *>(ctx->d_out),
-                static_cast<sdvl_search_res *>(ctx->h_out));
-  }
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  return SDVL_OK;
+  return sdvl_search_launch_device(ctx, n, d_reqs, d_table, B.blocks.cin(dsx), n_blocks, cam, p, so.prep.in(ctx->d_out), so.res.in(ctx->d_out),
+                                   so.h_res.in(ctx->h_out), /*prepared*/ false, all_binned);
 }
 
 int sdvl_search_run(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, sdvl_search_res *out) {
   if (!ctx || !cam || !p || n < 0 || (n > 0 && !out)) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  const int rc = search_enqueue(ctx, n, cam, p, 0, 0, nullptr, nullptr);
+  const SearchOut so(n);
+  const int rc = search_enqueue(ctx, n, cam, p, so);
   if (rc) return rc;
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out, ctx->h_out, sizeof(sdvl_search_res) * static_cast<size_t>(n));
+  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
   return SDVL_OK;
 }
 
@@ -1192,8 +1164,7 @@ int sdvl_ensure_nits_table(sdvl_ctx *ctx, int npoints_cfg, int max_its, int max_
   ctx->d_nits = nullptr;
   SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
   SDVL_HIP_CHECK(ctx, hipMalloc(&ctx->d_nits, entries * sizeof(int32_t)));
-  // on the context's own stream, not the legacy stream (whose implicit synchronisation collides with a capture under way on another
-  // thread of the farm: SDVL_STEP_GRAPH=1)
+  // on the context's own stream, not the legacy stream (whose implicit synchronisation would reach the other threads of a farm)
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_nits, t.data(), entries * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   SDVL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->nits_points = npoints_cfg;
@@ -1208,8 +1179,8 @@ int sdvl_search_run_chain(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
   if (!ctx || !cam || !p || !pp || n <= 0 || !out || n_frames <= 0 || !frames || n_cand < 0 || (n_cand > 0 && (!cand_req || !cand_first)) ||
       !req_point || n_rand < 0 || !rand_raw)
     return SDVL_ERR_INVALID;
-  SDVL_REQUIRE(ctx, pp->max_ransac_points >= 1 && pp->max_ransac_points <= 8, "max_ransac_points must be in [1,8]");
-  SDVL_REQUIRE(ctx, pp->max_ransac_its >= 1 && pp->max_ransac_its <= 4096 && pp->max_optim_pose_its >= 0, "bad iteration limits");
+  int rc = sdvl_check_pose_params(ctx, pp);
+  if (rc) return rc;
   ctx->chain_pending = 0;
   int obs_total = 0, max_size = 0;
   for (int f = 0; f < n_frames; f++) {
@@ -1226,25 +1197,28 @@ int sdvl_search_run_chain(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
     SDVL_REQUIRE(ctx, cand_first[k] >= 0 && cand_first[k] <= k, "cand_first must point at or before the candidate");
   }
   for (int k = 0; k < n_rand; k++) SDVL_REQUIRE(ctx, rand_raw[k] >= 0, "rand() values are non-negative");
-  int rc = sdvl_ensure_nits_table(ctx, pp->max_ransac_points, pp->max_ransac_its, max_size);
+  rc = sdvl_ensure_nits_table(ctx, pp->max_ransac_points, pp->max_ransac_its, max_size);
   if (rc) return rc;
-  // behind the search's buffers — device: jobs | obs | hypotheses | results | n_obs | lists ; host: results | n_obs | lists
-  const size_t jb = (sizeof(PoseJobDev) * n_frames + 255) / 256 * 256, ob = (sizeof(sdvl_pose_obs) * static_cast<size_t>(obs_total) + 255) / 256 * 256;
-  const size_t hb = (sdvl_pose_hyp_bytes() * static_cast<size_t>(n_frames) * pp->max_ransac_its + 255) / 256 * 256;
-  const size_t rb = (sizeof(sdvl_pose_result) * n_frames + 255) / 256 * 256, nb = (sizeof(int32_t) * n_frames + 255) / 256 * 256;
-  const size_t lb = (sizeof(int32_t) * static_cast<size_t>(obs_total) + 255) / 256 * 256;
-  size_t d_off = 0, h_off = 0;
-  rc = search_enqueue(ctx, n, cam, p, jb + ob + hb + rb + nb + lb, rb + nb + lb, &d_off, &h_off);
+  // behind the search's parts — device: jobs | obs | hypotheses | results | n_obs | lists ; host: results | n_obs | lists
+  SearchOut so(n);
+  const sdvl_part<PoseJobDev> jobs = so.d.take<PoseJobDev>(n_frames);
+  const sdvl_part<sdvl_pose_obs> obs = so.d.take<sdvl_pose_obs>(obs_total);
+  const sdvl_part<uint8_t> hyp = so.d.take<uint8_t>(sdvl_pose_hyp_bytes() * static_cast<size_t>(n_frames) * pp->max_ransac_its);
+  const auto take_back = [&](sdvl_layout &L) { return sdvl_ctx::ChainBack{L.take<sdvl_pose_result>(n_frames), L.take<int32_t>(n_frames), L.take<int32_t>(obs_total)}; };
+  const sdvl_ctx::ChainBack back = take_back(so.d), h_back = take_back(so.h);
+  rc = search_enqueue(ctx, n, cam, p, so);
   if (rc) return rc;
   SDVL_HIP_CHECK(ctx, sdvl_mark_record(ctx, SDVL_MARK_CHAIN, &ctx->chain_ticket));  // the search results are on the host from here on
   // inputs of the selection + pose stage: one staged copy
-  const size_t fb = (sizeof(ChainFrameDev) * n_frames + 255) / 256 * 256, cb = (sizeof(int32_t) * static_cast<size_t>(n_cand) + 255) / 256 * 256;
-  const size_t pb = (sizeof(double) * 3 * static_cast<size_t>(n) + 255) / 256 * 256, rndb = (sizeof(int32_t) * static_cast<size_t>(n_rand) + 255) / 256 * 256;
+  sdvl_layout st;
+  const sdvl_part<ChainFrameDev> st_frames = st.take<ChainFrameDev>(n_frames);
+  const sdvl_part<int32_t> st_cand_req = st.take<int32_t>(n_cand), st_cand_first = st.take<int32_t>(n_cand);
+  const sdvl_part<double> st_req_point = st.take<double>(3 * static_cast<size_t>(n));
+  const sdvl_part<int32_t> st_rand = st.take<int32_t>(n_rand);
   void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, fb + 2 * cb + pb + rndb, &hs, &dsx);
+  rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  uint8_t *h8 = static_cast<uint8_t *>(hs), *d8 = static_cast<uint8_t *>(dsx);
-  ChainFrameDev *hf = reinterpret_cast<ChainFrameDev *>(h8);
+  ChainFrameDev *hf = st_frames.in(hs);
   int ob_run = 0;
   for (int f = 0; f < n_frames; f++) {
     hf[f].cand_begin = frames[f].cand_begin;
@@ -1258,35 +1232,27 @@ int sdvl_search_run_chain(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
     ob_run += frames[f].max_matches;
   }
   if (n_cand) {
-    memcpy(h8 + fb, cand_req, sizeof(int32_t) * static_cast<size_t>(n_cand));
-    memcpy(h8 + fb + cb, cand_first, sizeof(int32_t) * static_cast<size_t>(n_cand));
+    memcpy(st_cand_req.in(hs), cand_req, st_cand_req.bytes());
+    memcpy(st_cand_first.in(hs), cand_first, st_cand_first.bytes());
   }
-  memcpy(h8 + fb + 2 * cb, req_point, sizeof(double) * 3 * static_cast<size_t>(n));
-  if (n_rand) memcpy(h8 + fb + 2 * cb + pb, rand_raw, sizeof(int32_t) * static_cast<size_t>(n_rand));
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, fb + 2 * cb + pb + rndb));
-  uint8_t *dx = static_cast<uint8_t *>(ctx->d_out) + d_off;
-  PoseJobDev *d_jobs = reinterpret_cast<PoseJobDev *>(dx);
-  sdvl_pose_obs *d_obs = reinterpret_cast<sdvl_pose_obs *>(dx + jb);
-  void *d_hyp = dx + jb + ob;
-  sdvl_pose_result *d_res = reinterpret_cast<sdvl_pose_result *>(dx + jb + ob + hb);
-  int32_t *d_nobs = reinterpret_cast<int32_t *>(dx + jb + ob + hb + rb);
-  int32_t *d_lists = reinterpret_cast<int32_t *>(dx + jb + ob + hb + rb + nb);
-  Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
-  SDVL_LAUNCH(ctx, "select_matches", select_matches_kernel, dim3(n_frames), dim3(256), reinterpret_cast<const ChainFrameDev *>(d8),
-              reinterpret_cast<const int32_t *>(d8 + fb), reinterpret_cast<const int32_t *>(d8 + fb + cb),
-              static_cast<const sdvl_search_res *>(ctx->d_out), reinterpret_cast<const double *>(d8 + fb + 2 * cb), c, d_jobs, d_obs, d_nobs,
-              static_cast<int32_t *>(nullptr));
+  memcpy(st_req_point.in(hs), req_point, st_req_point.bytes());
+  if (n_rand) memcpy(st_rand.in(hs), rand_raw, st_rand.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
+  void *const dx = ctx->d_out;
+  rc = sdvl_select_matches_launch(ctx, n_frames, st_frames.cin(dsx), st_cand_req.cin(dsx), st_cand_first.cin(dsx), so.res.cin(dx), st_req_point.cin(dsx),
+                                  cam, jobs.in(dx), obs.in(dx), back.n_obs.in(dx), nullptr);
+  if (rc) return rc;
   sdvl_pose_params prm = *pp;
   prm.pad_ = 1;  // raw rand() values: the kernel reduces them modulo the match count it finds in the job
-  rc = sdvl_pose_enqueue_device(ctx, n_frames, d_jobs, d_obs, reinterpret_cast<const int32_t *>(d8 + fb + 2 * cb + pb),
-                                static_cast<const int32_t *>(ctx->d_nits), &prm, d_hyp, d_res, d_lists, max_size, n_frames);
+  rc = sdvl_pose_enqueue_device(ctx, n_frames, jobs.in(dx), obs.in(dx), st_rand.cin(dsx), static_cast<const int32_t *>(ctx->d_nits), &prm, hyp.in(dx),
+                                back.res.in(dx), back.lists.in(dx), max_size, n_frames);
   if (rc) return rc;
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(static_cast<uint8_t *>(ctx->h_out) + h_off, dx + jb + ob + hb, rb + nb + lb, hipMemcpyDeviceToHost, ctx->stream));
+  // results | n_obs | lists are the tail of both layouts, part for part the same sizes: one copy
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(h_back.res.in(ctx->h_out), back.res.in(dx), so.h.bytes() - h_back.res.off, hipMemcpyDeviceToHost, ctx->stream));
   ctx->chain_pending = n_frames;
-  ctx->chain_host_off = h_off;
-  ctx->chain_obs_total = obs_total;
+  ctx->chain_back = h_back;
   SDVL_HIP_CHECK(ctx, sdvl_mark_wait(ctx, SDVL_MARK_CHAIN, ctx->chain_ticket));
-  memcpy(out, ctx->h_out, sizeof(sdvl_search_res) * static_cast<size_t>(n));
+  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
   return SDVL_OK;
 }
 
@@ -1295,11 +1261,10 @@ int sdvl_search_chain_end(sdvl_ctx *ctx, int n_frames, sdvl_pose_result *results
   SDVL_REQUIRE(ctx, ctx->chain_pending == n_frames, "sdvl_search_chain_end without a matching sdvl_search_run_chain");
   ctx->chain_pending = 0;
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  const size_t rb = (sizeof(sdvl_pose_result) * n_frames + 255) / 256 * 256, nb = (sizeof(int32_t) * n_frames + 255) / 256 * 256;
-  const uint8_t *h = static_cast<const uint8_t *>(ctx->h_out) + ctx->chain_host_off;
-  memcpy(results, h, sizeof(sdvl_pose_result) * n_frames);
-  memcpy(n_obs, h + rb, sizeof(int32_t) * n_frames);
-  memcpy(lists, h + rb + nb, sizeof(int32_t) * static_cast<size_t>(ctx->chain_obs_total));
+  const sdvl_ctx::ChainBack &back = ctx->chain_back;
+  memcpy(results, back.res.in(ctx->h_out), back.res.bytes());
+  memcpy(n_obs, back.n_obs.in(ctx->h_out), back.n_obs.bytes());
+  memcpy(lists, back.lists.in(ctx->h_out), back.lists.bytes());
   return SDVL_OK;
 }
 
@@ -1350,28 +1315,24 @@ int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const s
     SDVL_REQUIRE(ctx, state[i].track_row >= -1 && (state[i].track_row < n_rows || !set), "depth filter: track_row outside the tables");
     SDVL_REQUIRE(ctx, state[i].sigma2 > 0.0 && state[i].z_range > 0.0, "depth filter: sigma2 and z_range must be positive");
   }
-  const size_t sb = (sizeof(sdvl_depth_state) * static_cast<size_t>(n) + 255) / 256 * 256;
-  const size_t ob = (sizeof(sdvl_depth_out) * static_cast<size_t>(n) + 255) / 256 * 256;
-  size_t d_off = 0, h_off = 0;
+  SearchOut so(n);
+  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
   const SearchReqDev *d_reqs = nullptr;
   const SearchFramePose *d_table = nullptr;
-  int rc = search_enqueue(ctx, n, cam, p, ob, ob, &d_off, &h_off, &d_reqs, &d_table);
+  int rc = search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
   if (rc) return rc;
+  const size_t state_bytes = sizeof(sdvl_depth_state) * static_cast<size_t>(n);  // staged: the states alone
   void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, sb, &hs, &dsx);
+  rc = sdvl_stage_alloc(ctx, state_bytes, &hs, &dsx);
   if (rc) return rc;
-  memcpy(hs, state, sizeof(sdvl_depth_state) * static_cast<size_t>(n));
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, sb));
-  Cam c{cam->width, cam->height, cam->fx, cam->fy, cam->u0, cam->v0};
-  sdvl_depth_out *d_fout = reinterpret_cast<sdvl_depth_out *>(static_cast<uint8_t *>(ctx->d_out) + d_off);
-  sdvl_depth_out *h_fout = reinterpret_cast<sdvl_depth_out *>(static_cast<uint8_t *>(ctx->h_out) + h_off);
-  SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table,
-              static_cast<const sdvl_search_res *>(ctx->d_out), static_cast<const sdvl_depth_state *>(dsx), n, c, *fp, rows, n_rows, d_fout,
-              h_fout);
+  memcpy(hs, state, state_bytes);
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, state_bytes));
+  SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table, so.res.cin(ctx->d_out),
+              static_cast<const sdvl_depth_state *>(dsx), n, cam_of(*cam), *fp, rows, n_rows, d_fout.in(ctx->d_out), h_fout.in(ctx->h_out));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out, ctx->h_out, sizeof(sdvl_search_res) * static_cast<size_t>(n));
-  memcpy(fout, h_fout, sizeof(sdvl_depth_out) * static_cast<size_t>(n));
+  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
+  memcpy(fout, h_fout.in(ctx->h_out), h_fout.bytes());
   return SDVL_OK;
 }
 
@@ -1390,16 +1351,18 @@ int sdvl_align_patches(sdvl_ctx *ctx, int n, const sdvl_frame *const *frames, co
   if (!ctx || n < 0 || (n > 0 && (!frames || !levels || !border || !patch || !uv_io || !converged))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
   SDVL_REQUIRE(ctx, max_its >= 0, "bad max_its");
-  const size_t jb = (sizeof(PatchJob) * n + 255) / 256 * 256, bb = (static_cast<size_t>(n) * 100 + 255) / 256 * 256;
-  const size_t pb = static_cast<size_t>(n) * 64;
-  const size_t ob_uv = (sizeof(double) * 2 * n + 255) / 256 * 256, ob_its = (sizeof(int32_t) * n + 255) / 256 * 256;
-  const size_t ob = ob_uv + ob_its + n;
-  void *hsv = nullptr, *dsv = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, ob, false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, ob, true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, jb + bb + pb, &hsv, &dsv);
+  sdvl_layout st, o;  // staging: jobs | borders (100 bytes each) | patches (64 bytes each); d_out and h_out: uv | iterations | converged
+  const sdvl_part<PatchJob> st_jobs = st.take<PatchJob>(n);
+  const sdvl_part<uint8_t> st_border = st.take<uint8_t>(static_cast<size_t>(n) * 100), st_patch = st.take<uint8_t>(static_cast<size_t>(n) * 64);
+  const sdvl_part<double> o_uv = o.take<double>(2 * static_cast<size_t>(n));
+  const sdvl_part<int32_t> o_its = o.take<int32_t>(n);
+  const sdvl_part<uint8_t> o_conv = o.take<uint8_t>(n);
+  void *hs = nullptr, *ds = nullptr;
+  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
   if (rc) return rc;
-  PatchJob *hj = static_cast<PatchJob *>(hsv);
+  PatchJob *hj = st_jobs.in(hs);
   for (int i = 0; i < n; i++) {
     SDVL_REQUIRE(ctx, frames[i] && levels[i] >= 0 && levels[i] < frames[i]->v.levels, "bad frame / level");
     hj[i].img = frames[i]->v.level[levels[i]];
@@ -1408,19 +1371,17 @@ int sdvl_align_patches(sdvl_ctx *ctx, int n, const sdvl_frame *const *frames, co
     hj[i].u = uv_io[2 * i];
     hj[i].v = uv_io[2 * i + 1];
   }
-  uint8_t *hs = static_cast<uint8_t *>(hsv), *ds = static_cast<uint8_t *>(dsv);
-  memcpy(hs + jb, border, static_cast<size_t>(n) * 100);
-  memcpy(hs + jb + bb, patch, pb);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, jb + bb + pb));
-  uint8_t *dout = static_cast<uint8_t *>(ctx->d_out);
-  SDVL_LAUNCH(ctx, "align_patches", align_patches_kernel, dim3((n + kWavesPerBlock - 1) / kWavesPerBlock), dim3(64 * kWavesPerBlock), reinterpret_cast<const PatchJob *>(ds), ds + jb, ds + jb + bb, n, max_its, reinterpret_cast<double *>(dout), dout + ob_uv + ob_its, reinterpret_cast<int32_t *>(dout + ob_uv));
+  memcpy(st_border.in(hs), border, st_border.bytes());
+  memcpy(st_patch.in(hs), patch, st_patch.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  SDVL_LAUNCH(ctx, "align_patches", align_patches_kernel, dim3((n + kWavesPerBlock - 1) / kWavesPerBlock), dim3(64 * kWavesPerBlock), st_jobs.cin(ds),
+              st_border.cin(ds), st_patch.cin(ds), n, max_its, o_uv.in(ctx->d_out), o_conv.in(ctx->d_out), o_its.in(ctx->d_out));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  const uint8_t *ho = static_cast<const uint8_t *>(ctx->h_out);
-  memcpy(uv_io, ho, sizeof(double) * 2 * n);
-  if (its) memcpy(its, ho + ob_uv, sizeof(int32_t) * n);
-  memcpy(converged, ho + ob_uv + ob_its, n);
+  memcpy(uv_io, o_uv.in(ctx->h_out), o_uv.bytes());
+  if (its) memcpy(its, o_its.in(ctx->h_out), o_its.bytes());
+  memcpy(converged, o_conv.in(ctx->h_out), o_conv.bytes());
   return SDVL_OK;
 }
 

@@ -28,6 +28,31 @@ struct SearchFrame {
   int pad2_[2];
 };
 
+// bins_pending: the frame's corners (and their bins) are produced by a detection that is queued BEHIND this call and ahead of the
+// kernels that will read the view (sdvl_track_align -> sdvl_detect_corners -> sdvl_track_search): the view names the frame's bin
+// arrays although the host does not call them valid yet.  sdvl_track_search checks that the detection did come (track_clear_bins).
+inline void fill_view(SearchFrame *d, const sdvl_frame *f, bool bins_pending = false) {
+  memset(d, 0, sizeof(SearchFrame));
+  for (int l = 0; l < f->v.levels; l++) {
+    d->level[l] = f->v.level[l];
+    d->lw[l] = f->v.lw[l];
+    d->lh[l] = f->v.lh[l];
+  }
+  d->corners = f->v.corners;
+  d->desc = f->desc_valid ? f->v.desc : nullptr;  // null: a search computes the descriptors it compares (search_points_kernel)
+  d->n_ptr = f->v.corner_hdr;
+  d->levels = f->v.levels;
+  if (f->bins_valid || (bins_pending && f->bin_cells > 0)) {
+    d->bin_start = f->bin_start;
+    d->bin_entries = f->bin_entries;
+    d->bin_gw = f->bin_gw;
+    d->bin_cells = f->bin_cells;
+  }
+}
+
+// the kernels' camera record (sdvl_math.h) from the public one
+inline sdvl::Cam cam_of(const sdvl_camera &c) { return sdvl::Cam{c.width, c.height, c.fx, c.fy, c.u0, c.v0}; }
+
 // (frame, pose) pairs are shared by many requests of a launch: they go into a table, requests carry two indices
 struct SearchFramePose {
   SearchFrame f;
@@ -122,10 +147,10 @@ extern "C" TrackPoint *sdvl_track_points_device(sdvl_track_set *set, int *max_po
 // ---- launch helpers of sdvl_search.hip for callers whose records already live in HBM (no copies, no wait) --------------
 // search_prepare + search_points over n_slots request records (a record with level < 0 is a dead slot) dealt to workgroups
 // by the n_blocks entries of d_blocks (a block with count 0 is skipped); d_res receives one result per slot, h_res (may
-// be null) the same records in pinned host memory
+// be null) the same records in pinned host memory.  binned: every frame searched came out of sdvl_detect_corners
 int sdvl_search_launch_device(sdvl_ctx *ctx, int n_slots, const SearchReqDev *d_reqs, const SearchFramePose *d_table,
                               const SearchBlock *d_blocks, int n_blocks, const sdvl_camera *cam, const sdvl_search_params *p,
-                              SearchPrep *d_prep, sdvl_search_res *d_res, sdvl_search_res *h_res, bool prepared = false);
+                              SearchPrep *d_prep, sdvl_search_res *d_res, sdvl_search_res *h_res, bool prepared = false, bool binned = true);
 // second half of SelectPoints for n_frames trackers (feature_align.cc:105-149): d_cand_req may be null (candidate k of a
 // tracker = request cand_begin + k); d_match_cand (may be null) receives, per selected match, its candidate index
 // relative to cand_begin, at obs_begin + rank

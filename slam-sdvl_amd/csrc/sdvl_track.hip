@@ -41,28 +41,6 @@ struct RegisterRec {  // sdvl_frame_register
   int id, pad_;
 };
 
-// bins_pending: the frame's corners (and their bins) are produced by a detection that is queued BEHIND this call and ahead of the
-// kernels that will read the view (sdvl_track_align -> sdvl_detect_corners -> sdvl_track_search): the view names the frame's bin
-// arrays although the host does not call them valid yet.  sdvl_track_search checks that the detection did come (track_clear_bins).
-void fill_view(SearchFrame *d, const sdvl_frame *f, bool bins_pending = false) {
-  memset(d, 0, sizeof(SearchFrame));
-  for (int l = 0; l < f->v.levels; l++) {
-    d->level[l] = f->v.level[l];
-    d->lw[l] = f->v.lw[l];
-    d->lh[l] = f->v.lh[l];
-  }
-  d->corners = f->v.corners;
-  d->desc = f->desc_valid ? f->v.desc : nullptr;  // null: a search computes the descriptors it compares (search_points_kernel)
-  d->n_ptr = f->v.corner_hdr;
-  d->levels = f->v.levels;
-  if (f->bins_valid || (bins_pending && f->bin_cells > 0)) {
-    d->bin_start = f->bin_start;
-    d->bin_entries = f->bin_entries;
-    d->bin_gw = f->bin_gw;
-    d->bin_cells = f->bin_cells;
-  }
-}
-
 // the rare case behind fill_view's bins_pending: current frames whose corners did not come out of sdvl_detect_corners (set by hand)
 // have no bins: their views go back to "scan the whole corner list"
 __global__ __launch_bounds__(64) void track_clear_bins_kernel(TrackJobDev *__restrict__ jobs, const uint8_t *__restrict__ no_bins, int n) {
@@ -97,6 +75,15 @@ __global__ __launch_bounds__(256) void track_upload_kernel(const UploadRec *__re
 
 constexpr int kProjThreads = 512;
 
+// dynamic LDS of track_project_kernel for `stride` feature slots — s_key [stride] 64-bit at 0 | s_px [stride][2] doubles | s_cell
+// [stride] 16-bit | 64 spare: byte offsets of the parts and the total
+struct ProjLds {
+  size_t px, cell, bytes;
+  __host__ __device__ constexpr explicit ProjLds(size_t stride) : px(8 * stride), cell(px + 16 * stride), bytes(cell + 2 * stride + 64) {}
+};
+constexpr size_t kProjLdsDefault = 60 * 1024, kProjLdsMax = ProjLds(4096).bytes;  // beyond the first the limit is raised, to the largest set's (<= 4096 features)
+static_assert(kProjLdsMax == 106560, "track_project at stride 4096");
+
 // ProjectPoints + the first half of SelectPoints (feature_align.cc:88-118,285-339)
 __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const TrackJobDev *__restrict__ jobs, TrackPoint *__restrict__ points,
                                                                      const TrackFeat *__restrict__ feats0, const TrackFeat *__restrict__ feats1,
@@ -109,9 +96,10 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
                                                                      SearchBlock *__restrict__ blocks, ChainFrameDev *__restrict__ chain,
                                                                      sdvl_search_params sprm, SearchPrep *__restrict__ prep) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+  const ProjLds lds(stride);
   unsigned long long *s_key = reinterpret_cast<unsigned long long *>(s_dyn);  // [stride] sort key of feature i, ~0 = not a candidate
-  double *s_px = reinterpret_cast<double *>(s_key + stride);                   // [stride][2] its projection
-  uint16_t *s_cell = reinterpret_cast<uint16_t *>(s_px + 2 * static_cast<size_t>(stride));  // [stride] cell of the candidate at sorted position k
+  double *s_px = reinterpret_cast<double *>(s_dyn + lds.px);                   // [stride][2] its projection
+  uint16_t *s_cell = reinterpret_cast<uint16_t *>(s_dyn + lds.cell);           // [stride] cell of the candidate at sorted position k
   __shared__ double s_pose[7];
   __shared__ int s_ncand;
   const int j = blockIdx.x, tid = threadIdx.x;
@@ -234,6 +222,13 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
   }
 }
 
+// dynamic LDS of track_commit_kernel for `stride` candidate slots and at most `mm` matches — s_before [stride + 1] 16-bit at 0 |
+// s_found [stride] bytes | 64 spare | (8-byte aligned) s_depth [mm] doubles: byte offsets of the parts and the total
+struct CommitLds {
+  size_t found, depth, bytes;
+  __host__ __device__ CommitLds(size_t stride, size_t mm) : found(2 * (stride + 1)), depth((found + stride + 64 + 7) / 8 * 8), bytes(depth + 8 * mm) {}
+};
+
 // second half of SelectPoints as bookkeeping (feature_align.cc:105-149), RemoveOutliers (:245-256), the new feature list
 __global__ __launch_bounds__(256) void track_commit_kernel(const TrackJobDev *__restrict__ jobs, TrackPoint *__restrict__ points,
                                                            const TrackFeat *__restrict__ feats0_c, const TrackFeat *__restrict__ feats1_c,
@@ -245,9 +240,10 @@ __global__ __launch_bounds__(256) void track_commit_kernel(const TrackJobDev *__
                                                            SearchFramePose *__restrict__ registry, sdvl_track_result *__restrict__ h_results,
                                                            sdvl_track_feature_out *__restrict__ h_feats, sdvl_track_point_stat *__restrict__ h_stats) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+  const CommitLds lds(stride, mm);
   uint16_t *s_before = reinterpret_cast<uint16_t *>(s_dyn);  // [stride + 1] matches selected among the candidates before k
-  uint8_t *s_found = reinterpret_cast<uint8_t *>(s_before + stride + 1);  // [stride]
-  double *s_depth = reinterpret_cast<double *>(s_dyn + (static_cast<size_t>(stride + 1) * 2 + stride + 64 + 7) / 8 * 8);  // [mm]
+  uint8_t *s_found = s_dyn + lds.found;                      // [stride]
+  double *s_depth = reinterpret_cast<double *>(s_dyn + lds.depth);  // [mm] depths of the new frame's points
   __shared__ int s_wave[4];
   __shared__ int s_attempts, s_deleted, s_lk, s_npoints;
   __shared__ double s_median;
@@ -416,25 +412,22 @@ struct sdvl_track_set {
   // tables
   TrackPoint *d_points = nullptr;
   TrackFeat *d_feats[2] = {nullptr, nullptr};
-  // per-step scratch, all sized for n jobs
+  // per-step scratch, all sized for n jobs: parts of one allocation (cut up in sdvl_track_create)
   uint8_t *d_scratch = nullptr;
-  size_t scratch_bytes = 0;
-  TrackJobDev *d_jobs;
-  uint16_t *d_cell_rank;
-  int32_t *d_rand;
-  sdvl_align_result *d_ares;
-  SearchReqDev *d_reqs;
-  SearchPrep *d_prep;
-  sdvl_search_res *d_res;
-  double *d_reqpt;
-  int32_t *d_cfirst, *d_cfeat;
-  SearchBlock *d_blocks;
-  ChainFrameDev *d_chain;
-  PoseJobDev *d_pjobs;
-  sdvl_pose_obs *d_obs;
-  void *d_hyp;
-  sdvl_pose_result *d_pres;
-  int32_t *d_lists, *d_nobs;
+  sdvl_part<TrackJobDev> djobs;
+  sdvl_part<uint16_t> cell_rank;
+  sdvl_part<sdvl_align_result> ares;
+  sdvl_part<SearchReqDev> reqs;
+  sdvl_part<SearchPrep> prep;
+  sdvl_part<sdvl_search_res> res;
+  sdvl_part<double> reqpt;
+  sdvl_part<int32_t> rand, cfirst, cfeat, lists, nobs;
+  sdvl_part<SearchBlock> blocks;
+  sdvl_part<ChainFrameDev> chain;
+  sdvl_part<PoseJobDev> pjobs;
+  sdvl_part<sdvl_pose_obs> obs;
+  sdvl_part<uint8_t> hyp;
+  sdvl_part<sdvl_pose_result> pres;
   // pinned host mirrors, written by track_commit
   uint8_t *h_pinned = nullptr;
   sdvl_track_result *h_results;
@@ -448,21 +441,9 @@ struct sdvl_track_set {
   int stride = 0;
   int phase = 0;  // 0 idle, 1 aligned, 2 searched
   uint32_t ticket = 0;
-  // SDVL_STEP_GRAPH=1 (A/B): the search -> pose -> commit chain of a step as a HIP graph.  The chain is captured
-  // every step (its scalars and launch geometry follow the step's feature counts), the instantiated graph is UPDATED in place with
-  // the new capture (same topology) and launched as one submission.
   sdvl_camera cam;
   sdvl_track_params prm;
 };
-
-namespace {
-template <typename T>
-T *carve(uint8_t *&p, size_t count) {
-  T *r = reinterpret_cast<T *>(p);
-  p += (sizeof(T) * count + 255) / 256 * 256;
-  return r;
-}
-}  // namespace
 
 extern "C" {
 
@@ -488,41 +469,37 @@ int sdvl_track_create(sdvl_ctx *ctx, int n, int max_points, int max_features, in
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->d_points), sizeof(TrackPoint) * N * s->np);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_feats[0]), sizeof(TrackFeat) * NF);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_feats[1]), sizeof(TrackFeat) * NF);
-  // scratch: computed by carving a null base first
-  for (int pass = 0; pass < 2 && e == hipSuccess; pass++) {
-    uint8_t *p = pass ? s->d_scratch : nullptr;
-    s->d_jobs = carve<TrackJobDev>(p, N);
-    s->d_cell_rank = carve<uint16_t>(p, N * s->cells);
-    s->d_rand = carve<int32_t>(p, N * s->max_its);
-    s->d_ares = carve<sdvl_align_result>(p, N);
-    s->d_reqs = carve<SearchReqDev>(p, NF);
-    s->d_prep = carve<SearchPrep>(p, NF);
-    s->d_res = carve<sdvl_search_res>(p, NF);
-    s->d_reqpt = carve<double>(p, NF * 3);
-    s->d_cfirst = carve<int32_t>(p, NF);
-    s->d_cfeat = carve<int32_t>(p, NF);
-    s->d_blocks = carve<SearchBlock>(p, NF / kWavesPerBlock);
-    s->d_chain = carve<ChainFrameDev>(p, N);
-    s->d_pjobs = carve<PoseJobDev>(p, N);
-    s->d_obs = carve<sdvl_pose_obs>(p, N * s->mm);
-    s->d_hyp = carve<uint8_t>(p, sdvl_pose_hyp_bytes() * N * s->max_its);
-    s->d_pres = carve<sdvl_pose_result>(p, N);
-    s->d_lists = carve<int32_t>(p, N * s->mm);
-    s->d_nobs = carve<int32_t>(p, N);
-    if (!pass) {
-      s->scratch_bytes = reinterpret_cast<size_t>(p);
-      e = hipMalloc(reinterpret_cast<void **>(&s->d_scratch), s->scratch_bytes);
-    }
-  }
+  sdvl_layout L;
+  s->djobs = L.take<TrackJobDev>(N);  // jobs | cell ranks | rand values lead: sdvl_track_align pushes them as one block
+  s->cell_rank = L.take<uint16_t>(N * s->cells);
+  s->rand = L.take<int32_t>(N * s->max_its);
+  s->ares = L.take<sdvl_align_result>(N);
+  s->reqs = L.take<SearchReqDev>(NF);
+  s->prep = L.take<SearchPrep>(NF);
+  s->res = L.take<sdvl_search_res>(NF);
+  s->reqpt = L.take<double>(NF * 3);
+  s->cfirst = L.take<int32_t>(NF);
+  s->cfeat = L.take<int32_t>(NF);
+  s->blocks = L.take<SearchBlock>(NF / kWavesPerBlock);
+  s->chain = L.take<ChainFrameDev>(N);
+  s->pjobs = L.take<PoseJobDev>(N);
+  s->obs = L.take<sdvl_pose_obs>(N * s->mm);
+  s->hyp = L.take<uint8_t>(sdvl_pose_hyp_bytes() * N * s->max_its);
+  s->pres = L.take<sdvl_pose_result>(N);
+  s->lists = L.take<int32_t>(N * s->mm);
+  s->nobs = L.take<int32_t>(N);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_scratch), L.bytes());
   if (e == hipSuccess) {
-    const size_t hb = (sizeof(sdvl_track_result) * N + 255) / 256 * 256, fb = (sizeof(sdvl_track_feature_out) * NF + 255) / 256 * 256;
-    const size_t sb = sizeof(sdvl_track_point_stat) * N * s->np;
-    e = hipHostMalloc(reinterpret_cast<void **>(&s->h_pinned), hb + fb + sb, hipHostMallocDefault);
+    sdvl_layout H;  // pinned mirrors
+    const sdvl_part<sdvl_track_result> results = H.take<sdvl_track_result>(N);
+    const sdvl_part<sdvl_track_feature_out> feats = H.take<sdvl_track_feature_out>(NF);
+    const sdvl_part<sdvl_track_point_stat> stats = H.take<sdvl_track_point_stat>(N * s->np);
+    e = hipHostMalloc(reinterpret_cast<void **>(&s->h_pinned), H.bytes(), hipHostMallocDefault);
     if (e == hipSuccess) {
-      memset(s->h_pinned, 0, hb + fb + sb);
-      s->h_results = reinterpret_cast<sdvl_track_result *>(s->h_pinned);
-      s->h_feats = reinterpret_cast<sdvl_track_feature_out *>(s->h_pinned + hb);
-      s->h_stats = reinterpret_cast<sdvl_track_point_stat *>(s->h_pinned + hb + fb);
+      memset(s->h_pinned, 0, H.bytes());
+      s->h_results = results.in(s->h_pinned);
+      s->h_feats = feats.in(s->h_pinned);
+      s->h_stats = stats.in(s->h_pinned);
     }
   }
   if (e != hipSuccess) {
@@ -605,13 +582,15 @@ static int track_upload_rows(sdvl_ctx *ctx, sdvl_track_set *s, int n, const int3
     tf += n_features[i];
   }
   SDVL_REQUIRE(ctx, (tp == 0 || points) && (tf == 0 || features), "null rows");
-  const size_t rb = (sizeof(UploadRec) * n + 255) / 256 * 256, pb = (sizeof(TrackPoint) * tp + 255) / 256 * 256, fb = sizeof(TrackFeat) * tf;
+  sdvl_layout st;  // staging: records | point rows | feature rows
+  const sdvl_part<UploadRec> st_recs = st.take<UploadRec>(n);
+  const sdvl_part<TrackPoint> st_points = st.take<TrackPoint>(tp);
+  const sdvl_part<TrackFeat> st_feats = st.take<TrackFeat>(tf);
   void *hs = nullptr, *dsx = nullptr;
-  int rc = sdvl_stage_alloc(ctx, rb + pb + fb, &hs, &dsx);
+  int rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  uint8_t *h8 = static_cast<uint8_t *>(hs), *d8 = static_cast<uint8_t *>(dsx);
-  UploadRec *recs = reinterpret_cast<UploadRec *>(h8);
-  TrackPoint *hp = reinterpret_cast<TrackPoint *>(h8 + rb);
+  UploadRec *recs = st_recs.in(hs);
+  TrackPoint *hp = st_points.in(hs);
   size_t po = 0, fo = 0;
   for (int i = 0; i < n; i++) {
     const int p0 = append ? s->n_points[trackers[i]] : 0, f0 = append ? s->n_feat[feat_buf[i]][trackers[i]] : 0;
@@ -633,11 +612,10 @@ static int track_upload_rows(sdvl_ctx *ctx, sdvl_track_set *s, int n, const int3
     po += n_points[i];
     fo += n_features[i];
   }
-  if (fb) memcpy(h8 + rb + pb, features, fb);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, rb + pb + fb));
-  SDVL_LAUNCH(ctx, "track_upload", track_upload_kernel, dim3(n), dim3(256), reinterpret_cast<const UploadRec *>(d8),
-              reinterpret_cast<const TrackPoint *>(d8 + rb), reinterpret_cast<const TrackFeat *>(d8 + rb + pb), s->d_points, s->d_feats[0],
-              s->d_feats[1], s->np, s->nf);
+  if (tf) memcpy(st_feats.in(hs), features, st_feats.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
+  SDVL_LAUNCH(ctx, "track_upload", track_upload_kernel, dim3(n), dim3(256), st_recs.cin(dsx), st_points.cin(dsx), st_feats.cin(dsx), s->d_points,
+              s->d_feats[0], s->d_feats[1], s->np, s->nf);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   // every record was valid and the rows are on their way: only now do the host-side counts follow (a failed call leaves them untouched)
   for (int i = 0; i < n; i++) {
@@ -662,8 +640,8 @@ int sdvl_track_align(sdvl_ctx *ctx, sdvl_track_set *s, int n_jobs, const sdvl_tr
   if (!ctx || !s || s->ctx != ctx || n_jobs <= 0 || !jobs || !cell_rank || !rand_raw || !cam || !p) return SDVL_ERR_INVALID;
   SDVL_REQUIRE(ctx, s->phase == 0, "sdvl_track_align while a step is in flight");
   SDVL_REQUIRE(ctx, n_jobs <= s->n, "more jobs than trackers");
-  SDVL_REQUIRE(ctx, p->pose.max_ransac_points >= 1 && p->pose.max_ransac_points <= 8, "max_ransac_points must be in [1,8]");
-  SDVL_REQUIRE(ctx, p->pose.max_ransac_its == s->max_its && p->pose.max_optim_pose_its >= 0, "max_ransac_its differs from the set's");
+  int rc = sdvl_check_pose_params(ctx, &p->pose, s->max_its);
+  if (rc) return rc;
   SDVL_REQUIRE(ctx, p->cell_size >= 1 && p->patch_size >= 0 && p->max_failed >= 0, "bad track parameters");
   {
     const int gw = static_cast<int>(ceil(cam->width / p->cell_size)), gh = static_cast<int>(ceil(cam->height / p->cell_size));
@@ -681,23 +659,21 @@ int sdvl_track_align(sdvl_ctx *ctx, sdvl_track_set *s, int n_jobs, const sdvl_tr
   }
   for (int k = 0; k < n_jobs * s->cells; k++) SDVL_REQUIRE(ctx, cell_rank[k] < s->cells, "cell rank out of range");
   for (int k = 0; k < n_jobs * s->max_its; k++) SDVL_REQUIRE(ctx, rand_raw[k] >= 0, "rand() values are non-negative");
-  int rc = sdvl_ensure_nits_table(ctx, p->pose.max_ransac_points, p->pose.max_ransac_its, s->mm);
+  rc = sdvl_ensure_nits_table(ctx, p->pose.max_ransac_points, p->pose.max_ransac_its, s->mm);
   if (rc) return rc;
   s->stride = (max_nf + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock;
   if (s->stride < kWavesPerBlock) s->stride = kWavesPerBlock;
   s->cam = *cam;
   s->prm = *p;
   s->jobs.assign(jobs, jobs + n_jobs);
-  // jobs | cell ranks | rand values: staged at the offsets the three arrays have in the set's scratch (they were carved one behind
-  // the other), so ONE push lands all of them — every push is a launch on the step's critical path
-  const size_t jb = static_cast<size_t>(reinterpret_cast<uint8_t *>(s->d_cell_rank) - reinterpret_cast<uint8_t *>(s->d_jobs));
-  const size_t cb = static_cast<size_t>(reinterpret_cast<uint8_t *>(s->d_rand) - reinterpret_cast<uint8_t *>(s->d_cell_rank));
-  const size_t rb = sizeof(int32_t) * static_cast<size_t>(n_jobs) * s->max_its;
+  // jobs | cell ranks | rand values: the staged block mirrors the head of the set's scratch (the three parts lead it), part for part
+  // at the scratch's own offsets, so ONE push lands all of them — every push is a launch on the step's critical path
+  const size_t rand_bytes = sizeof(int32_t) * static_cast<size_t>(n_jobs) * s->max_its;
+  const size_t head_bytes = s->rand.off + rand_bytes;
   void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, jb + cb + rb, &hs, &dsx);
+  rc = sdvl_stage_alloc(ctx, head_bytes, &hs, &dsx);
   if (rc) return rc;
-  uint8_t *h8 = static_cast<uint8_t *>(hs), *d8 = static_cast<uint8_t *>(dsx);
-  TrackJobDev *hj = reinterpret_cast<TrackJobDev *>(h8);
+  TrackJobDev *hj = s->djobs.in(hs);
   for (int j = 0; j < n_jobs; j++) {
     const sdvl_track_job &a = jobs[j];
     TrackJobDev &d = hj[j];
@@ -718,14 +694,13 @@ int sdvl_track_align(sdvl_ctx *ctx, sdvl_track_set *s, int n_jobs, const sdvl_tr
     memcpy(d.T0, a.T, sizeof(double) * 7);
     d.pad2_ = 0.0;
   }
-  memcpy(h8 + jb, cell_rank, sizeof(uint16_t) * static_cast<size_t>(n_jobs) * s->cells);
-  memcpy(h8 + jb + cb, rand_raw, rb);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, s->d_jobs, h8, jb + cb + rb));
-  (void)d8;
+  memcpy(s->cell_rank.in(hs), cell_rank, sizeof(uint16_t) * static_cast<size_t>(n_jobs) * s->cells);
+  memcpy(s->rand.in(hs), rand_raw, rand_bytes);
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, s->d_scratch, hs, head_bytes));
   // the alignment reads the tables itself (image_align_track_*): no feature records, no launch in between
-  rc = sdvl_image_align_track_enqueue(ctx, n_jobs, static_cast<const TrackJobDev *>(s->d_jobs), static_cast<const TrackPoint *>(s->d_points),
+  rc = sdvl_image_align_track_enqueue(ctx, n_jobs, s->djobs.cin(s->d_scratch), static_cast<const TrackPoint *>(s->d_points),
                                       static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->np, s->nf, max_nf,
-                                      jobs[0].cur->v.levels, cam, &p->align, s->d_ares, s->n);
+                                      jobs[0].cur->v.levels, cam, &p->align, s->ares.in(s->d_scratch), s->n);
   if (rc) return rc;
   s->phase = 1;
   return SDVL_OK;
@@ -739,8 +714,9 @@ int sdvl_track_search(sdvl_ctx *ctx, sdvl_track_set *s) {
     SDVL_REQUIRE(ctx, !a.cur->hdr_stale, "current frame has a new image but no corners (detect or set corners first)");
     SDVL_REQUIRE(ctx, s->prm.search.max_fast_levels <= a.cur->v.levels, "max_fast_levels exceeds the pyramid depth");
   }
-  const Cam c{s->cam.width, s->cam.height, s->cam.fx, s->cam.fy, s->cam.u0, s->cam.v0};
+  const Cam c = cam_of(s->cam);
   const int stride = s->stride;
+  uint8_t *const D = s->d_scratch;
   SearchFramePose *registry = static_cast<SearchFramePose *>(ctx->d_registry);
   {
     // sdvl_track_align named the current frames' corner bins before the detection that fills them was queued (fill_view): frames
@@ -756,7 +732,7 @@ int sdvl_track_search(sdvl_ctx *ctx, sdvl_track_set *s) {
       uint8_t *hm = static_cast<uint8_t *>(hs);
       for (int j = 0; j < n_jobs; j++) hm[j] = (s->jobs[j].cur->bin_cells > 0 && (never || !s->jobs[j].cur->bins_valid)) ? 1 : 0;
       SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, static_cast<size_t>(n_jobs)));
-      hipLaunchKernelGGL(track_clear_bins_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, ctx->stream, s->d_jobs, static_cast<const uint8_t *>(dsx), n_jobs);
+      hipLaunchKernelGGL(track_clear_bins_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, ctx->stream, s->djobs.in(D), static_cast<const uint8_t *>(dsx), n_jobs);
       SDVL_HIP_CHECK(ctx, hipGetLastError());
     }
   }
@@ -764,60 +740,42 @@ int sdvl_track_search(sdvl_ctx *ctx, sdvl_track_set *s) {
   // (The chain as a HIP graph was measured in rounds 4 and 5 — 2.69 k against 2.96 k frames/s for a lone camera, nothing for a farm:
   //  launches are not the cost — and removed in round 6.)
   // (one-time set-up calls stay outside a capture)
-  if (static_cast<size_t>(stride) * (8 + 16 + 2) + 64 > 60 * 1024) {  // track_project beyond the default dynamic LDS limit: raise it once per device
+  const size_t proj_lds = ProjLds(stride).bytes;
+  if (proj_lds > kProjLdsDefault) {  // track_project beyond the default dynamic LDS limit: raise it once per device
     static std::atomic<unsigned long long> attr_devices{0};
-    const unsigned long long bit = 1ull << (ctx->device & 63);
-    if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-      SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
-      SDVL_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(track_project_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              4096 * (8 + 16 + 2) + 64));
-      attr_devices.fetch_or(bit, std::memory_order_release);
-    }
+    const int rc_a = sdvl_allow_dynamic_lds(ctx, reinterpret_cast<const void *>(track_project_kernel), kProjLdsMax, &attr_devices);
+    if (rc_a) return rc_a;
   }
   {
-    const size_t lds = static_cast<size_t>(stride) * (8 + 16 + 2) + 64;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    sdvl_timer_events(ctx, "track_project", &ev_a, &ev_b);
     // a lane per feature of last_frame: 256 lanes cover the ~190 features of the metric configuration, configuration C's ~850 take 512.
     // Round 6: a farm's launches (sets of more than 32 trackers) take 128 — among the other streams' one-wave workgroups a workgroup
     // is placed when ALL its waves find a slot on one CU at the same moment, and four are found far less often than two: the kernel's
     // dispatch time in company is how long its workgroups wait to be placed (2.0 -> 1.5 ms per step of 16 groups, +3 % tracked frames/s;
     // 64 threads: +1 % — the rank loop gets longer)
     const int proj_threads = stride <= 256 ? (s->n > 32 ? 128 : 256) : kProjThreads;
-    hipExtLaunchKernelGGL(track_project_kernel, dim3(n_jobs), dim3(proj_threads), lds, ctx->stream, ev_a, ev_b, 0,
-                          static_cast<const TrackJobDev *>(s->d_jobs), s->d_points, static_cast<const TrackFeat *>(s->d_feats[0]),
-                          static_cast<const TrackFeat *>(s->d_feats[1]), s->np, s->nf, stride, s->mm, s->max_its,
-                          static_cast<const sdvl_align_result *>(s->d_ares), static_cast<const uint16_t *>(s->d_cell_rank), s->cells, c,
-                          s->prm.cell_size, s->prm.patch_size, registry, s->d_reqs, s->d_reqpt, s->d_cfirst, s->d_cfeat, s->d_blocks, s->d_chain,
-                          s->prm.search, s->d_prep);
+    SDVL_LAUNCH_LDS(ctx, "track_project", track_project_kernel, dim3(n_jobs), dim3(proj_threads), proj_lds, s->djobs.cin(D), s->d_points,
+                    static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->np, s->nf, stride, s->mm,
+                    s->max_its, s->ares.cin(D), s->cell_rank.cin(D), s->cells, c, s->prm.cell_size, s->prm.patch_size, registry, s->reqs.in(D),
+                    s->reqpt.in(D), s->cfirst.in(D), s->cfeat.in(D), s->blocks.in(D), s->chain.in(D), s->prm.search, s->prep.in(D));
     SDVL_HIP_CHECK(ctx, hipGetLastError());
   }
-  int rc = sdvl_search_launch_device(ctx, n_jobs * stride, s->d_reqs, registry, s->d_blocks, n_jobs * (stride / kWavesPerBlock), &s->cam,
-                                     &s->prm.search, s->d_prep, s->d_res, nullptr, /*prepared*/ true);
+  int rc = sdvl_search_launch_device(ctx, n_jobs * stride, s->reqs.in(D), registry, s->blocks.in(D), n_jobs * (stride / kWavesPerBlock), &s->cam,
+                                     &s->prm.search, s->prep.in(D), s->res.in(D), nullptr, /*prepared*/ true);
   if (rc) return rc;
   // match ranks are not needed separately: track_commit derives them again from the same flags
-  rc = sdvl_select_matches_launch(ctx, n_jobs, s->d_chain, nullptr, s->d_cfirst, s->d_res, s->d_reqpt, &s->cam, s->d_pjobs, s->d_obs, s->d_nobs,
-                                  nullptr);
+  rc = sdvl_select_matches_launch(ctx, n_jobs, s->chain.in(D), nullptr, s->cfirst.in(D), s->res.in(D), s->reqpt.in(D), &s->cam, s->pjobs.in(D),
+                                  s->obs.in(D), s->nobs.in(D), nullptr);
   if (rc) return rc;
   sdvl_pose_params pp = s->prm.pose;
   pp.pad_ = 1;  // raw rand() values: the kernel reduces them modulo the match count it finds in the job
-  rc = sdvl_pose_enqueue_device(ctx, n_jobs, s->d_pjobs, s->d_obs, s->d_rand, static_cast<const int32_t *>(ctx->d_nits), &pp, s->d_hyp, s->d_pres,
-                                s->d_lists, s->mm, s->n);
+  rc = sdvl_pose_enqueue_device(ctx, n_jobs, s->pjobs.in(D), s->obs.in(D), s->rand.in(D), static_cast<const int32_t *>(ctx->d_nits), &pp, s->hyp.in(D),
+                                s->pres.in(D), s->lists.in(D), s->mm, s->n);
   if (rc) return rc;
-  {
-    // s_before | s_found | (8-byte aligned) depths of the new frame's points, at most mm of them
-    const size_t lds = (static_cast<size_t>(stride + 1) * 2 + stride + 64 + 7) / 8 * 8 + static_cast<size_t>(s->mm) * 8;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    sdvl_timer_events(ctx, "track_commit", &ev_a, &ev_b);
-    hipExtLaunchKernelGGL(track_commit_kernel, dim3(n_jobs), dim3(256), lds, ctx->stream, ev_a, ev_b, 0, static_cast<const TrackJobDev *>(s->d_jobs),
-                          s->d_points, static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->d_feats[0],
-                          s->d_feats[1], s->np, s->nf, stride, s->mm, static_cast<const ChainFrameDev *>(s->d_chain),
-                          static_cast<const int32_t *>(s->d_cfirst), static_cast<const int32_t *>(s->d_cfeat),
-                          static_cast<const sdvl_search_res *>(s->d_res), static_cast<const sdvl_pose_result *>(s->d_pres),
-                          static_cast<const int32_t *>(s->d_lists), static_cast<const sdvl_align_result *>(s->d_ares), c, s->prm.max_failed, registry,
-                          s->h_results, s->h_feats, s->h_stats);
-    SDVL_HIP_CHECK(ctx, hipGetLastError());
-  }
+  SDVL_LAUNCH_LDS(ctx, "track_commit", track_commit_kernel, dim3(n_jobs), dim3(256), CommitLds(stride, s->mm).bytes, s->djobs.cin(D), s->d_points,
+                  static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->d_feats[0], s->d_feats[1], s->np,
+                  s->nf, stride, s->mm, s->chain.cin(D), s->cfirst.cin(D), s->cfeat.cin(D), s->res.cin(D), s->pres.cin(D), s->lists.cin(D),
+                  s->ares.cin(D), c, s->prm.max_failed, registry, s->h_results, s->h_feats, s->h_stats);
+  SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, sdvl_mark_record(ctx, SDVL_MARK_CHAIN, &s->ticket));
   s->phase = 2;
   return SDVL_OK;

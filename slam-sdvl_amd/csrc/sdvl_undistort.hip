@@ -386,8 +386,10 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
   double key[12] = {cam->fx, cam->fy, cam->u0, cam->v0, dist->d[0], dist->d[1], dist->d[2], dist->d[3], dist->d[4], static_cast<double>(w), static_cast<double>(h),
                     static_cast<double>(src_stride)};  // (the quad records hold source offsets)
   if (!ctx->d_undist_map || memcmp(key, ctx->undist_key, sizeof(key)) != 0) {
-    const size_t px_bytes = (sizeof(uint32_t) * (wide_map ? 2 : 1) * static_cast<size_t>(pitch) * h + 255) / 256 * 256;
-    const size_t map_bytes = px_bytes + sizeof(QuadRec) * static_cast<size_t>(pitch / 4) * h;
+    sdvl_layout m;  // the map's allocation: per-pixel words | per-quad records
+    const sdvl_part<uint32_t> px = m.take<uint32_t>((wide_map ? 2 : 1) * static_cast<size_t>(pitch) * h);
+    const sdvl_part<QuadRec> quads = m.take<QuadRec>(static_cast<size_t>(pitch / 4) * h);
+    const size_t map_bytes = m.bytes();
     if (ctx->undist_map_bytes < map_bytes) {
       if (ctx->d_undist_map) {
         SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));  // remaps that read the old map may still be queued
@@ -399,19 +401,19 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
       SDVL_HIP_CHECK(ctx, hipMalloc(&ctx->d_undist_map, map_bytes));
       ctx->undist_map_bytes = map_bytes;
     }
-    const size_t xb = (sizeof(double) * w + 255) / 256 * 256, yb = sizeof(double) * h;
+    sdvl_layout st;  // staging: the column table | the row table
+    const sdvl_part<double> st_xw = st.take<double>(w), st_yw = st.take<double>(h);
     void *hs = nullptr, *dsx = nullptr;
-    int rc = sdvl_stage_alloc(ctx, xb + yb, &hs, &dsx);
+    int rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
     if (rc) return rc;
-    uint8_t *h8 = static_cast<uint8_t *>(hs), *d8 = static_cast<uint8_t *>(dsx);
-    if (!build_tables(w, h, cam, reinterpret_cast<double *>(h8), reinterpret_cast<double *>(h8 + xb))) {
+    if (!build_tables(w, h, cam, st_xw.in(hs), st_yw.in(hs))) {
       ctx->err = "camera matrix is singular";
       return SDVL_ERR_INVALID;
     }
-    SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, xb + yb));
-    const double *d_xw = reinterpret_cast<const double *>(d8), *d_yw = reinterpret_cast<const double *>(d8 + xb);
-    uint32_t *d_map = static_cast<uint32_t *>(ctx->d_undist_map);
-    QuadRec *d_quads = reinterpret_cast<QuadRec *>(static_cast<uint8_t *>(ctx->d_undist_map) + px_bytes);
+    SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
+    const double *d_xw = st_xw.cin(dsx), *d_yw = st_yw.cin(dsx);
+    uint32_t *d_map = px.in(ctx->d_undist_map);
+    QuadRec *d_quads = quads.in(ctx->d_undist_map);
     if (wide_map) {
       SDVL_LAUNCH(ctx, "undistort_map", undistort_map_kernel<true>, dim3((pitch + 255) / 256, h), dim3(256), d_xw, d_yw, P, pitch, d_map);
       SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<true>, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(d_map), pitch, P, d_quads);
@@ -420,12 +422,12 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
       SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<false>, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(d_map), pitch, P, d_quads);
     }
     SDVL_HIP_CHECK(ctx, hipGetLastError());
-    ctx->undist_quads = static_cast<uint8_t *>(ctx->d_undist_map) + px_bytes;
+    ctx->undist_quads = d_quads;
     memcpy(ctx->undist_key, key, sizeof(key));
     ctx->undist_maps_built++;
   }
   // ---- the remap
-  const size_t jb = (sizeof(UndistJob) * n + 255) / 256 * 256;
+  const size_t jb = sizeof(UndistJob) * n;
   void *hs = nullptr, *dsx = nullptr;
   int rc = sdvl_stage_alloc(ctx, jb, &hs, &dsx);
   if (rc) return rc;

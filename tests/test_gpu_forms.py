@@ -19,12 +19,12 @@ from test_gpu_parity import POSE_TOL, align_inputs, frames_of, search_requests
 pytestmark = pytest.mark.gpu
 
 T_ID = np.array([1, 0, 0, 0, 0, 0, 0], np.float64)
-K_LDS_MAX_F = 384          # csrc/sdvl_image_align.hip:25 (one wave per job up to this many features)
+K_LDS_MAX_F = 384          # csrc/sdvl_image_align.hip:26 (one wave per job up to this many features)
 MAX_ALIGN_FEATURES = 2048  # SDVL_MAX_ALIGN_FEATURES, include/sdvl_hip.h:37
-SEARCH_TAB_CAP = 2048      # kSearchTabCap, csrc/sdvl_search.hip:1030
+SEARCH_TAB_CAP = 2048      # kSearchTabCap, csrc/sdvl_search.hip:1014
 WAVES_PER_BLOCK = 4        # kWavesPerBlock: requests per search workgroup, patch jobs per align-patches workgroup
 BIN_CELLS_SMALL, BIN_CORNERS_SMALL, BIN_CELLS = 512, 2048, 2048   # csrc/sdvl_orb.hip:234-235
-REMAP_FRAMES = 4           # kRemapFrames, csrc/sdvl_undistort.hip:157
+REMAP_FRAMES = 4           # kRemapFrames, csrc/sdvl_undistort.hip:194
 
 ALIGN_COUNTS = [1, 63, 64, 65, 128, 129, 383, 384, 385, 767, 768, 769, 2048]
 
@@ -94,7 +94,7 @@ def assert_align_matches(r, want):
 @pytest.mark.parametrize("n_feat", ALIGN_COUNTS)
 def test_image_align_feature_counts(ctx, sdvl, orc, ia, n_feat):
     """one job at every count on both sides of a wave (64), of two rounds, of kLdsMaxF (one wave per job up to 384, four waves
-    beyond: csrc/sdvl_image_align.hip:863) and at the SDVL_MAX_ALIGN_FEATURES cap"""
+    beyond: csrc/sdvl_image_align.hip:859) and at the SDVL_MAX_ALIGN_FEATURES cap"""
     res, forms = align_timed(ctx, [(ia["frames"][0], ia["frames"][2], 0, n_feat, T_ID)], ia["feats"], ia["cam"], sdvl.default_align_params())
     assert forms == {"image_align" if n_feat <= K_LDS_MAX_F else "image_align_big"}
     want = oracle_align(orc, ia, 2, 0, n_feat)
@@ -150,7 +150,7 @@ def mixed_jobs(ia):
 
 def test_image_align_mixed_batch_equals_each_job_alone(ctx, sdvl, ia):
     """small and big jobs in one call: small-first reorder, results scattered back through IaJob::out_index, the big jobs'
-    precompute behind the small jobs' (csrc/sdvl_image_align.hip:860-925).  max_f only sets the LDS / precompute pitch, the
+    precompute behind the small jobs' (csrc/sdvl_image_align.hip:855-921).  max_f only sets the LDS / precompute pitch, the
     sums run in the same order: every result is bit-identical to the job run alone"""
     jobs = mixed_jobs(ia)
     ap = sdvl.default_align_params()
@@ -296,8 +296,8 @@ def test_align_store_equals_image_align(ctx, sdvl, ia):
 
 # ------------------------------------------------------------------------------------------------ search
 def search_table_size(reqs):
-    """entries of the batch's frame table: sdvl_search_slot (csrc/sdvl_search.hip:1060-1083) for the current then the reference
-    (frame, pose) of every request, in request order (pack_requests, :1318-1319)"""
+    """entries of the batch's frame table: sdvl_search_slot (csrc/sdvl_search.hip:1046-1067) for the current then the reference
+    (frame, pose) of every request, in request order (pack_requests, :1292-1293)"""
     table, where, last, last2 = [], {}, -1, -1
     for r in reqs:
         for f, pose in ((r.cur, tuple(r.cur_pose)), (r.ref, tuple(r.ref_pose))):
@@ -351,16 +351,27 @@ def sub_requests(sdvl, reqs, idx):
     return out
 
 
-@pytest.mark.parametrize("n_req", [SEARCH_TAB_CAP - 1, SEARCH_TAB_CAP, 2100])
+def raw_bytes(arr):
+    return C.string_at(C.addressof(arr), C.sizeof(arr))
+
+
+SEARCH_FIRST_RUN = {}   # n_req -> the result bytes of the module's first run at that size
+
+
+@pytest.mark.parametrize("n_req", [SEARCH_TAB_CAP - 1, SEARCH_TAB_CAP, 2100, 1, 32, 33, 64, 65, pytest.param(32, id="32-again")])
 def test_search_points_frame_table_over_the_staging_cap(ctx, sdvl, many, n_req):
     """a frame table of 2048, 2049 and 2101 (frame, pose) entries: up to kSearchTabCap it rides in the staging copy, beyond it goes
-    through the work buffer with a copy of its own (csrc/sdvl_search.hip:1127-1138).  Found, level and offsets bit-equal to the
-    oracle; the chosen corner equals that of the same requests run in batches whose tables stay under the cap"""
+    through the work buffer with a copy of its own (csrc/sdvl_search.hip:1112-1123).  Found, level and offsets bit-equal to the
+    oracle; the chosen corner equals that of the same requests run in batches whose tables stay under the cap.
+    Behind the large batches, in buffers that have grown: 1 request, and 32 / 33 and 64 / 65, where the packed requests (120 B:
+    32 are 15 x 256) and the results (40 B: 32 are 5 x 256) fill their part of a buffer to the last byte and run one record over;
+    32 a second time answers bit for bit as the first"""
     reqs = sub_requests(sdvl, many["reqs"], range(n_req))
     n_tab = search_table_size(reqs)
     assert n_tab == n_req + 1                                   # the current frame once, every reference pose its own entry
     sp = sdvl.default_search_params()
     res = ctx.search_points(reqs, many["cam"], sp)
+    assert raw_bytes(res) == SEARCH_FIRST_RUN.setdefault(n_req, raw_bytes(res))
     chunks = [ctx.search_points(sub_requests(sdvl, reqs, range(b, min(b + 1000, n_req))), many["cam"], sp) for b in range(0, n_req, 1000)]
     n_found = 0
     for i in range(n_req):
@@ -373,14 +384,10 @@ def test_search_points_frame_table_over_the_staging_cap(ctx, sdvl, many, n_req):
     assert n_found >= n_req // 4
 
 
-def test_search_points_filter_frame_table_over_the_staging_cap(ctx, sdvl, orc, many):
-    """sdvl_search_points_filter with 2101 table entries: depth_filter_kernel reads the frame table where the search left it, in
-    the work buffer.  Outcomes and counters exact, filter state within 1e-11 relative, as test_depth_filter_behind_the_search"""
-    reqs, meta, n = many["reqs"], many["meta"], len(many["reqs"])
-    assert search_table_size(reqs) > SEARCH_TAB_CAP
+def depth_states(sdvl, meta, max_failed):
+    """a depth-filter state per request: the seed's depth, random counters, every 7th far away, every 11th fixed"""
     rng = np.random.default_rng(8)
-    max_failed = 15
-    states = (sdvl.DepthState * n)()
+    states = (sdvl.DepthState * len(meta))()
     for i, m in enumerate(meta):
         s = states[i]
         s.rho, s.sigma2 = m["idepth"], m["istd"] ** 2
@@ -393,6 +400,15 @@ def test_search_points_filter_frame_table_over_the_staging_cap(ctx, sdvl, orc, m
             s.position[k] = [0.1 * (i % 5), -0.05 * (i % 3), 2.0][k]
         s.n_failed = int(rng.integers(0, max_failed + 1))
         s.track_row = -1
+    return states
+
+
+def check_search_points_filter(ctx, sdvl, orc, many, n):
+    """the first n requests of `many` through sdvl_search_points_filter: outcomes and counters exact, filter state within 1e-11
+    relative, as test_depth_filter_behind_the_search -> the outcomes seen"""
+    reqs, meta = sub_requests(sdvl, many["reqs"], range(n)), many["meta"][:n]
+    max_failed = 15
+    states = depth_states(sdvl, meta, max_failed)
     fp = sdvl.DepthParams()
     fp.px_error_angle = math.atan(1.0 / (2.0 * TUM_CAM[0])) * 2.0
     fp.min_depth, fp.scale_min_dist, fp.max_failed = 0.25, 0.25, max_failed
@@ -416,11 +432,26 @@ def test_search_points_filter_frame_table_over_the_staging_cap(ctx, sdvl, orc, m
             outcomes.add(want & 0xFF)
     finally:
         ref.close()
+    return outcomes
+
+
+def test_search_points_filter_frame_table_over_the_staging_cap(ctx, sdvl, orc, many):
+    """sdvl_search_points_filter with 2101 table entries: depth_filter_kernel reads the frame table where the search left it, in
+    the work buffer.  Outcomes and counters exact, filter state within 1e-11 relative, as test_depth_filter_behind_the_search"""
+    assert search_table_size(many["reqs"]) > SEARCH_TAB_CAP
+    outcomes = check_search_points_filter(ctx, sdvl, orc, many, len(many["reqs"]))
     assert len(outcomes) >= 3, outcomes
 
 
+@pytest.mark.parametrize("n", [32, 33])
+def test_search_points_filter_states_that_fill_their_part(ctx, sdvl, orc, many, n):
+    """32 depth-filter states (104 B each) are 13 x 256 bytes: their part of the staged block has no padding behind it; 33 run one
+    record over.  The outcome records (80 B) follow the search's own parts in the result buffers.  Same acceptance as above"""
+    check_search_points_filter(ctx, sdvl, orc, many, n)
+
+
 def search_blocks(cur_of_request):
-    """the search's workgroups: runs of up to kWavesPerBlock consecutive requests of one current frame (csrc/sdvl_search.hip:1117-1123)"""
+    """the search's workgroups: runs of up to kWavesPerBlock consecutive requests of one current frame (csrc/sdvl_search.hip:1102-1109)"""
     blocks, i, n = [], 0, len(cur_of_request)
     while i < n:
         cnt = 1
@@ -435,7 +466,7 @@ def search_blocks(cur_of_request):
 def test_search_points_workgroups_of_every_run_length(ctx, sdvl, orc, synth, binned):
     """requests in runs of 1..9 of one current frame, alternating between two current frames: workgroups of 1..4 requests, runs
     split across workgroups.  Every frame from sdvl_detect_corners (binned): search_points_kernel<false, 1>; frames with
-    set_corners: <true, kWavesPerBlock> (csrc/sdvl_search.hip:1145-1157).  Results equal the oracle's and those of the same
+    set_corners: <true, kWavesPerBlock> (csrc/sdvl_search.hip:947-956).  Results equal the oracle's and those of the same
     requests in sorted order"""
     imgs = frames_of(synth, orc, TUM_CAM, 640, 480, [0, 4, 7])
     T = [trajectory_pose(orc, k) for k in (0, 4, 7)]
@@ -495,7 +526,7 @@ def test_search_points_workgroups_of_every_run_length(ctx, sdvl, orc, synth, bin
     (1024, 1024, 16, None, "unbinned"),  # 4096 cells, the grid's limit
 ])
 def test_filter_corners_forms(ctx, sdvl, orc, synth, w, h, cell, n_corners, form):
-    """the three forms of filter_select (csrc/sdvl_orb.hip:655-663): binned with 512 cells and 2048 corners at most, binned with
+    """the three forms of filter_select (csrc/sdvl_orb.hip:663-674): binned with 512 cells and 2048 corners at most, binned with
     2048 cells at most, unbinned beyond.  Kept indices, their truncated scores and ORB descriptors as the oracle's (the checks of
     test_filter_corners_selection_on_the_device), with a few cells locked"""
     gw, gh = (w + cell - 1) // cell, (h + cell - 1) // cell
@@ -541,7 +572,7 @@ def test_filter_corners_forms(ctx, sdvl, orc, synth, w, h, cell, n_corners, form
 @pytest.mark.parametrize("h,w", [(61, 128), (70, 129), (131, 255), (483, 752)])
 def test_undistort_batches_fill_and_miss_frame_groups(ctx, sdvl, orc, h, w):
     """batches of 1, 3, 4, 5, 8 and 9 distinct images: frame groups of kRemapFrames (4) that are complete (the kFull branch) and
-    a last group of 1..3 (csrc/sdvl_undistort.hip:234-244); widths of one tile, one pixel over, not a multiple of four, and the
+    a last group of 1..3 (csrc/sdvl_undistort.hip:272-282); widths of one tile, one pixel over, not a multiple of four, and the
     EuRoC width; heights that leave a partial tile row.  Plain form and fused upload, every frame byte for byte as the oracle's"""
     cam4 = np.array([0.8 * w, 0.82 * w, w / 2.0 - 0.4, h / 2.0 + 0.3])
     dist = TUM_DIST if w >= 640 else np.array([-0.45, 0.3, 0.01, -0.008, 0.05])
@@ -551,7 +582,7 @@ def test_undistort_batches_fill_and_miss_frame_groups(ctx, sdvl, orc, h, w):
     assert all((wnt != im).mean() > 0.3 for wnt, im in zip(want, imgs))
     c = sdvl.Camera(w, h, *cam4)
     batches = (1, 3, 4, 5, 8, 9)
-    # frames of each workgroup's group: nf = min(n - f0, kRemapFrames) (csrc/sdvl_undistort.hip:234); kFull where nf == 4
+    # frames of each workgroup's group: nf = min(n - f0, kRemapFrames) (csrc/sdvl_undistort.hip:272); kFull where nf == 4
     assert {min(n - f0, REMAP_FRAMES) for n in batches for f0 in range(0, n, REMAP_FRAMES)} == {1, 3, 4}
     for n in batches:
         got = ctx.undistort(imgs[:n], c, dist)
@@ -568,14 +599,20 @@ def test_undistort_batches_fill_and_miss_frame_groups(ctx, sdvl, orc, h, w):
 
 
 # ------------------------------------------------------------------------------------------------ align patches
-@pytest.mark.parametrize("n", [1, 3, 4, 5, 9])
-def test_align_patches_workgroup_tails(ctx, orc, synth, n):
-    """kWavesPerBlock patch jobs per workgroup (csrc/sdvl_search.hip:1425): a lone job, a partial, a full, one over and two full
-    workgroups plus one; each job on its own frame and pyramid level, bit-exact against the oracle"""
-    ks = [0, 3, 6]
-    imgs = frames_of(synth, orc, TUM_CAM, 640, 480, ks)
-    pyrs = [orc.pyramid(im, 5) for im in imgs]
-    corners = [orc.detect_pyramid(im) for im in imgs]
+@pytest.fixture(scope="module")
+def patch_scene(orc, synth):
+    """three frames of the trajectory, their pyramids and corners"""
+    imgs = frames_of(synth, orc, TUM_CAM, 640, 480, [0, 3, 6])
+    return imgs, [orc.pyramid(im, 5) for im in imgs], [orc.detect_pyramid(im) for im in imgs]
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 9, 8, 16, 17, 64, 65])
+def test_align_patches_workgroup_tails(ctx, orc, patch_scene, n):
+    """kWavesPerBlock patch jobs per workgroup (csrc/sdvl_search.hip:1389): a lone job, a partial, a full, one over and two full
+    workgroups plus one; each job on its own frame and pyramid level, bit-exact against the oracle.  Then the counts at which a part
+    of the staged block or of the results is a whole number of 256-byte units, and one job more: 8 job records (32 B), 16 start
+    points (16 B), 64 borders (100 B: 25 x 256)"""
+    imgs, pyrs, corners = patch_scene
     fr = [ctx.frame(im) for im in imgs]
     rng = np.random.default_rng(300 + n)
     frames, levels, border, patch, uv0, meta = [], [], [], [], [], []
@@ -590,7 +627,7 @@ def test_align_patches_workgroup_tails(ctx, orc, synth, n):
         uv0.append(np.array([x, y], np.float64) + rng.uniform(-1.5, 1.5, 2))
         meta.append(fi)
     assert len(set(zip(meta, levels))) == min(n, 9)
-    assert (n + WAVES_PER_BLOCK - 1) // WAVES_PER_BLOCK == [1, 1, 1, 2, 3][[1, 3, 4, 5, 9].index(n)]
+    assert (n + WAVES_PER_BLOCK - 1) // WAVES_PER_BLOCK == {1: 1, 3: 1, 4: 1, 5: 2, 9: 3, 8: 2, 16: 4, 17: 5, 64: 16, 65: 17}[n]
     uv, conv, its = ctx.align_patches(frames, levels, np.stack(border), np.stack(patch), np.stack(uv0))
     n_conv = 0
     for i in range(n):

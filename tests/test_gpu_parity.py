@@ -271,6 +271,12 @@ def test_shi_tomasi_and_orb_bit_exact(ctx, sdvl, orc, synth):
         assert np.array_equal(desc[m], wd), "ORB bits level %d" % l
         gd, ga = ctx.orb_describe_points(f, corners[m])
         assert np.array_equal(gd, wd) and np.array_equal(ga, wa)
+    # 16 corner records (16 B) and 8 descriptors (32 B) are 256 bytes: the staged corners and the returned descriptors with no
+    # padding behind them, and one corner more
+    assert len(corners) > 17
+    for k in (8, 16, 17):
+        gd, _ = ctx.orb_describe_points(f, corners[:k])
+        assert np.array_equal(gd, desc[:k]), k
     f.close()
 
 
@@ -296,6 +302,7 @@ def test_hamming_argmin_matches_search_features_rule(ctx, orc):
         lists.append(c)
     for thr in (100, 0, 256, 37):
         gi, gd = ctx.hamming_argmin(queries, lists, thr)
+        want = []
         for i in range(n):
             best, bi = thr + 1, -1
             for j, c in enumerate(lists[i]):
@@ -305,7 +312,13 @@ def test_hamming_argmin_matches_search_features_rule(ctx, orc):
                     best, bi = d, j
             if best >= thr:
                 bi = -1
+            want.append((bi, best))
             assert (gi[i], gd[i]) == (bi, best), (thr, i)
+        if thr == 100:
+            # 8 queries (32 B) are 256 bytes, 63 queries have 64 offsets (256 bytes): the staged parts with no padding behind them
+            for m in (8, 9, 63, 64):
+                gi, gd = ctx.hamming_argmin(queries[:m], lists[:m], thr)
+                assert list(zip(gi.tolist(), gd.tolist())) == want[:m], m
     gi, gd = ctx.hamming_argmin(np.zeros((0, 32), np.uint8), [], 100)
     assert len(gi) == 0
 
@@ -863,10 +876,13 @@ def test_empty_batches_and_flat_frames(ctx, sdvl, orc):
 
 
 # ------------------------------------------------------------------------------------------------ K8
-@pytest.mark.parametrize("sizes", [(150, 40, 5, 3, 1, 0), (256, 255, 64, 65, 129, 7), (1024, 700, 257)])
+@pytest.mark.parametrize("sizes", [(150, 40, 5, 3, 1, 0), (256, 255, 64, 65, 129, 7), (1024, 700, 257),
+                                   (16,) * 16, (16,) * 17, (8,) * 32, (8,) * 33], ids=lambda s: "%dx%d" % (len(s), s[0]) if len(s) > 6 else None)
 def test_pose_from_matches_equals_oracle(ctx, orc, sizes):
     """RANSAC replay + Tukey Gauss-Newton + rescue on the device: same rand() consumption, same inlier / outlier lists
-    in the same order; pose within 1e-9 (device sin/cos inside SE3::Exp differ from libm by an ulp)"""
+    in the same order; pose within 1e-9 (device sin/cos inside SE3::Exp differ from libm by an ulp).
+    16 jobs of 16 matches: the job records (80 B), the 256 observations (48 B) and the 16 x 100 draws (4 B) each fill their part of
+    the staged block to the last byte; 32 jobs: so do the results (72 B); 17 and 33 run one record over"""
     cam = TUM_CAM
     jobs, wants = [], []
     for j, n in enumerate(sizes):
@@ -882,7 +898,8 @@ def test_pose_from_matches_equals_oracle(ctx, orc, sizes):
         assert np.array_equal(g["outliers"], w["outliers"]), j
         assert np.abs(g["pose"] - w["pose"]).max() <= 1e-9, (j, g["pose"], w["pose"])
     # the big jobs really exercise RANSAC: outliers were rejected and the true motion recovered
-    assert len(got[0]["outliers"]) >= 10 and len(got[0]["inliers"]) >= 90
+    if sizes[0] >= 150:
+        assert len(got[0]["outliers"]) >= 10 and len(got[0]["inliers"]) >= 90
 
 
 def test_pose_from_matches_many_draws(ctx, orc):

@@ -7,9 +7,9 @@ Acceptance is that of the four pose tests of tests/test_gpu_parity.py: n_draws, 
 the pose is within 1e-9 (the device's sin and cos inside SE3::Exp differ from libm's by an ulp).
 
 The dispatch (sdvl_pose_enqueue_device) picks the form from the number of jobs and the largest job of a call:
-  csrc/sdvl_pose.hip:762  wave_form = batch_size <= 4          one wave per draw, else one lane per draw with only the first 64
+  csrc/sdvl_pose.hip:759  wave_form = batch_size <= 4          one wave per draw, else one lane per draw with only the first 64
                                                                 draws converged ahead and the rest on demand in pose_refine
-  csrc/sdvl_pose.hip:782  max_obs > 256 || batch_size <= 32     pose_refine_kernel<3> (helper waves), else pose_refine_kernel<1>
+  csrc/sdvl_pose.hip:774  max_obs > 256 || batch_size <= 32     pose_refine_kernel<3> (helper waves), else pose_refine_kernel<1>
                                                                 with its 256-entry LDS lists
 Both forms of a pair carry the same kernel timer name, so each test restates the condition it aims at and asserts it on its batch.
 
@@ -57,7 +57,7 @@ def wanted(orc, name):
 
 
 def forms_of(names):
-    """(wave_form, three_wave_refine) of a call with these jobs, as csrc/sdvl_pose.hip:762 and :782 compute them"""
+    """(wave_form, three_wave_refine) of a call with these jobs, as csrc/sdvl_pose.hip:759 and :774 compute them"""
     batch_size, max_obs = len(names), max(len(case(n)["obs"]) for n in names)
     return batch_size <= 4, (max_obs > 256 or batch_size <= 32)
 
@@ -123,7 +123,7 @@ def check_batches(ctx, orc, names, size, fillers, want_forms, must_hold=()):
 
 # ------------------------------------------------------------------------------------------------ every case in every form
 def test_every_case_alone(ctx, orc):
-    """batch_size 1 <= 4: pose_hypotheses_wave_kernel (sdvl_pose.hip:762); batch_size <= 32: pose_refine_kernel<3> (:782), also for
+    """batch_size 1 <= 4: pose_hypotheses_wave_kernel (sdvl_pose.hip:759); batch_size <= 32: pose_refine_kernel<3> (:774), also for
     the jobs of 1 to 9 matches that leave the helper waves nothing to do"""
     for name in CASES:
         assert forms_of([name]) == (True, True)
@@ -134,19 +134,19 @@ def test_every_case_alone(ctx, orc):
 
 
 def test_every_case_in_a_batch_of_4(ctx, orc):
-    """batch_size 4 <= 4: still the wave form (:762), four jobs of different sizes behind one grid; pose_refine_kernel<3> (:782)"""
+    """batch_size 4 <= 4: still the wave form (:759), four jobs of different sizes behind one grid; pose_refine_kernel<3> (:774)"""
     assert check_batches(ctx, orc, list(CASES), 4, FILLERS, (True, True)) >= len(CASES)
 
 
 @pytest.mark.parametrize("size", [5, 32])
 def test_every_case_in_the_lane_form_with_helper_waves(ctx, orc, size):
-    """batch_size 5 > 4: pose_hypotheses_kernel, one lane per draw (:762-775); 5 and 32 <= 32: pose_refine_kernel<3> (:782), counting
+    """batch_size 5 > 4: pose_hypotheses_kernel, one lane per draw (:759-769); 5 and 32 <= 32: pose_refine_kernel<3> (:774), counting
     the supporters as its replay reaches a draw and converging draws past 64 on demand"""
     assert check_batches(ctx, orc, list(CASES), size, FILLERS, (False, True)) >= len(CASES)
 
 
 def test_every_case_up_to_256_matches_in_the_one_wave_refine(ctx, orc):
-    """batch_size 33 > 32 and max_obs == 256 exactly, not above: pose_refine_kernel<1> with its 256-entry LDS lists (:782-787).
+    """batch_size 33 > 32 and max_obs == 256 exactly, not above: pose_refine_kernel<1> with its 256-entry LDS lists (:774-779).
     The four cases above 256 matches cannot reach this form; the 256-match case is in every batch."""
     names = [n for n in CASES if len(case(n)["obs"]) <= 256]
     assert len(names) == len(CASES) - 4
@@ -154,7 +154,7 @@ def test_every_case_up_to_256_matches_in_the_one_wave_refine(ctx, orc):
 
 
 def test_every_case_in_a_batch_of_33_with_one_job_of_257(ctx, orc):
-    """batch_size 33 > 32 but one job of 257 matches: max_obs > 256 sends the WHOLE batch to pose_refine_kernel<3> (:782)"""
+    """batch_size 33 > 32 but one job of 257 matches: max_obs > 256 sends the WHOLE batch to pose_refine_kernel<3> (:774)"""
     fillers = FILLERS + ["roll30-257"]
     names = [n for n in CASES if n != "roll30-257"]
     assert check_batches(ctx, orc, names, 33, fillers, (False, True), must_hold=["roll30-257"]) >= len(names)
@@ -218,7 +218,7 @@ def test_rank_deficient_hypotheses(ctx, orc, size):
                          ids=["wave-form", "lane-form"])
 def test_a_batch_equals_each_job_alone(ctx, orc, names):
     """a job's answer does not depend on its neighbours, nor on the form its hypotheses were made in: n_draws, lists, refined and the
-    bits of the pose of a job in a mixed batch (the wave form for 4 jobs, the lane form for 8: :762) equal those of the job in a call
+    bits of the pose of a job in a mixed batch (the wave form for 4 jobs, the lane form for 8: :759) equal those of the job in a call
     of its own.  (The final pose is pose_refine_kernel<3>'s in all these calls and depends on the hypotheses only through the lists.)"""
     assert forms_of(names) == (len(names) <= 4, True)
     together = run(ctx, orc, names, DEFAULTS)
