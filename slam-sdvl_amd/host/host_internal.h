@@ -1,7 +1,8 @@
 // host_internal.h — what the two translation units of the host layer share besides sdvl_host.h (not installed):
 //   frontend.cc    Device, Frame, Feature, FastDetector, ORBDetector, ImageAlign, Matcher, FeatureAlign — the hot path's classes
-//   standalone.cc  Camera, Point, Map / PlaneMap, SDVL, SDVLBatch — what the reference's own sdvl.cc / map.cc / point.cc /
-//                  camera.cc provide in its tree (INTEGRATION.md route A)
+//   standalone.cc  Camera, Point, Map / PlaneMap, SDVL — what the reference's own camera.cc / point.cc / map.cc / sdvl.cc provide in
+//                  its tree (INTEGRATION.md route A) — and SDVLBatch: tables, shared pieces of a step, relocalisation, the tabled step,
+//                  the host-driven step, epilogue and mappers
 #ifndef SDVL_HOST_INTERNAL_H_
 #define SDVL_HOST_INTERNAL_H_
 

@@ -185,13 +185,13 @@ class SDVL {
   Map *map_;
   ORBDetector orb_detector_;
   RandStream rng_;
-  State state_;
+  State state_ = STATE_FIRST_FRAME;
   std::shared_ptr<Frame> current_frame_, last_frame_, last_kf_, pending_kf_;
-  TrackingQuality tracking_quality_;
+  TrackingQuality tracking_quality_ = TRACKING_GOOD;
   Vector6d vel_;
   FeatureAlign feature_align_;
-  int lost_frames_, matches_, attempts_;
-  int frame_counter_;
+  int lost_frames_ = 0, matches_ = 0, attempts_ = 0;
+  int frame_counter_ = 0;
   SE3 first_pose_;
   FrameStats stats_;
   bool relocalize_pending_ = false;
@@ -261,42 +261,79 @@ class SDVLBatch {
  public:
   StageTimes stage_times;
  private:
+  friend class SDVL;
   Device *dev_;
   std::vector<SDVL *> trk_;
   int threads_;
+  // ParallelFor as Frame's batched calls take it (CreateBatch hands the body over by value, FilterCornersEnd by reference)
+  std::function<void(int, std::function<void(int)>)> pfor_;
+  std::function<void(int, const std::function<void(int)> &)> pfor_ref_;
   std::vector<sdvl_search_req> scratch_reqs_;  // per-step request / pose batches, reused so that they never reallocate
   FeatureAlign::PoseBatch scratch_pose_;
   std::vector<double> scratch_points_;  // sdvl_search_run_chain inputs, same idea
   std::vector<int32_t> chain_cand_req_, chain_cand_first_, chain_rand_;
-  // ---- device-resident tables
+  // ---- what every form of a step shares
+  struct Step;      // what the stages of one step hand to each other (defined in standalone.cc)
+  struct HostStep;  // Step + the requests and pose jobs of the host-driven form
+  enum FrameStart { kFirstFrame, kLost, kRunning };
+  FrameStart BeginFrame(int i, const std::shared_ptr<Frame> &frame, FrameStats &st);
+  void DetectOnSideStream(const std::vector<std::shared_ptr<Frame>> &frames, bool fork);
+  void FetchCornerCounts(const std::vector<std::shared_ptr<Frame>> &frames, FrameStats *stats);
+  void CollectKeyframes(Step &s, bool fetch_counts);
+  void GatherRows(const std::vector<int> &up, bool own_buf);
+  void SyncStats(SDVL &t);
+  void EpilogueAndMapper(Step &s);
+  void FinishKeyframes(Step &s);
+  void RunMappers();
+  // ---- the step on the device-resident tables
   bool HandleFramesTracked(const std::vector<Image> &imgs, FrameStats *stats);  // false: not applicable this step
+  bool TrackedStepApplies();
+  bool EnsureTrackSet();
+  void TakeLookAhead(Step &s);
+  void QueueLookAhead(const Step &s);
+  void RelocalizeIntoStep(Step &s);
+  sdvl_track_params AssembleTrackJobs(const Step &s);
+  void SubmitTracked(Step &s);
+  void ReplayTracked(Step &s);
+  void SaveTrackedFrames(Step &s);
+  void InvalidateStaleTables();
+  int TrackOnHost(SDVL &t, FrameStats *st);
+  bool BuildTable(SDVL &t);
+  bool UploadTables(const std::vector<int> &need, std::vector<char> *built);
+  bool AppendSeeds(SDVL &t, const std::shared_ptr<Frame> &kf);  // rows of the points seeded on kf -> track_.up_points / up_feats
   std::vector<Image> next_imgs_;                        // SetNextImages: what the next step will be given
   std::vector<std::shared_ptr<Frame>> ahead_frames_;    // their frames, pyramids and detection queued
   std::vector<const void *> ahead_src_;                 // the images they were made from
-  void HandleFramesGeneric(const std::vector<Image> &imgs, FrameStats *stats);
-  bool BuildTable(SDVL &t);
-  bool UploadTables(const std::vector<int> &need, std::vector<char> *built);
-  void RelocalizeLost(const std::vector<int> &lost, FrameStats *stats, std::vector<char> *found);
-  int TrackOnHost(SDVL &t, FrameStats *st);
-  bool AppendSeeds(SDVL &t, const std::shared_ptr<Frame> &kf);  // rows of the points seeded on kf -> track_.up_points / up_feats
-  void SyncStats(SDVL &t);
-  void FetchCornerCounts(const std::vector<std::shared_ptr<Frame>> &frames, FrameStats *stats);
-  void EpilogueAndMapper(const std::vector<std::shared_ptr<Frame>> &frames, FrameStats *stats, std::vector<std::shared_ptr<Frame>> *kfs,
-                         std::vector<int> *kf_owner, bool filter_begun);
   sdvl_track_set *track_ = nullptr;
-  // keyframe feature records of the trackers that are relocalising (SDVL::RelocCache): one bump-allocated store per batch
-  sdvl_align_store *reloc_store_ = nullptr;
-  int reloc_cap_ = 0, reloc_used_ = 0;
-  unsigned long long reloc_epoch_ = 0;  // 0: no store yet
-  void RelocAlign(const std::vector<sdvl_align_job> &jobs, const sdvl_align_params &ap, std::vector<sdvl_align_result> *res);
   int track_cells_ = 0, track_cap_ = 0;
-  friend class SDVL;
   std::vector<sdvl_track_job> tr_jobs_;
   std::vector<uint16_t> tr_rank_;
   std::vector<int32_t> tr_rand_;
   std::vector<sdvl_track_result> tr_res_;
   std::vector<sdvl_track_point> tr_up_points_;
   std::vector<sdvl_track_feature> tr_up_feats_;
+  std::vector<int32_t> tr_up_trk_, tr_up_buf_, tr_up_np_, tr_up_nf_;  // whose rows those are, for which buffer, how many
+  // ---- relocalisation inside the tabled step
+  void RelocalizeLost(const std::vector<int> &lost, FrameStats *stats, std::vector<char> *found);
+  void PackRelocCache(SDVL &t, std::vector<sdvl_align_feature> *packed);
+  void RefreshRelocStore(const std::vector<int> &lost);
+  void RelocAlignKeyframes(const std::vector<int> &lost, std::vector<int> *first, std::vector<sdvl_align_result> *res);
+  void RelocAlign(const std::vector<sdvl_align_job> &jobs, const sdvl_align_params &ap, std::vector<sdvl_align_result> *res);
+  // keyframe feature records of the trackers that are relocalising (SDVL::RelocCache): one bump-allocated store per batch
+  sdvl_align_store *reloc_store_ = nullptr;
+  int reloc_cap_ = 0, reloc_used_ = 0;
+  unsigned long long reloc_epoch_ = 0;  // 0: no store yet
+  // ---- the host-driven step
+  void HandleFramesGeneric(const std::vector<Image> &imgs, FrameStats *stats);
+  bool RelocalizeOnHost(SDVL &t, FrameStats &st);
+  void AlignImages(HostStep &s);
+  void PackRequests(HostStep &s);
+  void PackChain(HostStep &s);
+  void CollectRequests(HostStep &s);
+  void LaunchSearch(HostStep &s);
+  void ReplaySelect(HostStep &s);
+  void LaunchPose(HostStep &s);
+  void CommitAndSave(HostStep &s);
 };
 
 }  // namespace sdvl
