@@ -655,6 +655,55 @@ int sdvl_track_collect(sdvl_ctx *ctx, sdvl_track_set *set, int n_jobs, sdvl_trac
 const sdvl_track_feature_out *sdvl_track_features(const sdvl_track_set *set, int job);
 const sdvl_track_point_stat *sdvl_track_stats(const sdvl_track_set *set, int job);
 
+/* ---- two-frame initialisation: the two OpenCV calls of HomographyInit (homography_init.cc:185-282) ----------------------
+ * cv::calcOpticalFlowPyrLK as TrackSecondFrame calls it (:195-198).  A job is a pair of frames of one size with their pyramids
+ * built (the levels are the frames' own, sdvl_pyramid_build) and a range of points; all jobs of a call run in one launch, one wave
+ * per point.  prev_xy[n_pts][2] are level-0 pixels of `prev`; next_xy[n_pts][2] carries the initial flow on entry
+ * (OPTFLOW_USE_INITIAL_FLOW) and the result on exit; status[n_pts] = 1 tracked, 0 lost; err[n_pts] (may be NULL) = mean absolute
+ * difference of the window at the result.  Float32 arithmetic, reads outside a level clamp to its edge, a result outside the image
+ * is lost: tests/klt_restatement.py is the specification.  Points outside every job's range come back lost. */
+typedef struct sdvl_klt_job {
+  const sdvl_frame *prev, *next;
+  int32_t pt_begin, pt_end;
+} sdvl_klt_job;
+
+typedef struct sdvl_klt_params {
+  int32_t win_size;  /* 30 (only 30 is supported: a lane owns 15 of the 900 window pixels) */
+  int32_t max_level; /* pyramid levels - 1 = 4; below the frames' level count */
+  int32_t max_its;   /* 30 */
+  int32_t pad_;
+  double eps;               /* 0.001: stop at |delta| <= eps */
+  double min_eig_threshold; /* 1e-4 */
+} sdvl_klt_params;
+
+int sdvl_klt_track(sdvl_ctx *ctx, int n_jobs, const sdvl_klt_job *jobs, int n_pts, const float *prev_xy, float *next_xy, uint8_t *status,
+                   float *err, const sdvl_klt_params *params);
+
+/* The RANSAC of cv::findHomography(src, dst, CV_RANSAC, threshold) (:253) in FP64, one job per tracker.  src_xy / dst_xy[n_m][2] are
+ * the matches of all jobs; draws4[n_draws][4] the 4-index subsets (relative to the job's m_begin) the caller WOULD draw, a copy of
+ * its random stream as rand_idx is for sdvl_pose_from_matches: the device never draws.  The sequential loop is replayed exactly:
+ * draws in order, at most min(max_its, draws of the job); a draw with a repeated index or three collinear points is an iteration
+ * without a model; a strictly larger support (> 3) becomes the best and shrinks the budget to log(1 - confidence) / log(1 - w^4)
+ * (the budget table is built inside, with libm).  result.n_its draws are to be committed on the real stream;
+ * inlier_lists[m_begin ..) receives n_inliers ascending indices relative to m_begin.  tests/homography_restatement.py is the
+ * specification.  At most SDVL_MAX_LEVEL_CELLS matches per job (SDVL_ERR_CAPACITY beyond). */
+typedef struct sdvl_homography_job {
+  int32_t m_begin, m_end;       /* range in src_xy / dst_xy */
+  int32_t draw_begin, draw_end; /* range in draws4 (subsets, not indices) */
+} sdvl_homography_job;
+
+typedef struct sdvl_homography_result {
+  double H[9];        /* of the best draw's four points, row-major, H[8] = 1; zeros without a model */
+  int32_t best_draw;  /* relative to draw_begin, -1: no draw had more than 3 supporters */
+  int32_t n_its;
+  int32_t n_inliers;
+  int32_t pad_;
+} sdvl_homography_result;
+
+int sdvl_homography_ransac(sdvl_ctx *ctx, int n_jobs, const sdvl_homography_job *jobs, int n_m, const double *src_xy, const double *dst_xy,
+                           int n_draws, const int32_t *draws4, double threshold, int max_its, double confidence,
+                           sdvl_homography_result *results, int32_t *inlier_lists);
+
 /* ---- synthetic sequence generator (no dataset ships with the repo) ------------------------------- */
 struct sdvl_synth_view;
 /* renders n views of the textured plane straight into HBM: dev_out + i*frame_bytes, row stride = width */

@@ -134,6 +134,7 @@ ABI_SYMBOLS = [
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
     "sdvl_frames_own_images", "sdvl_feed_create", "sdvl_feed_destroy", "sdvl_feed_last_error", "sdvl_feed_slot_arrived", "sdvl_feed_images", "sdvl_ctx_feed_acquire", "sdvl_ctx_feed_release", "sdvl_frame_footprint_cap", "sdvl_ctx_set_corner_capacity", "sdvl_frame_corner_capacity", "sdvl_detect_scratch_bytes",
+    "sdvl_klt_track", "sdvl_homography_ransac",
     "sdvl_ctx_set_wait_spin", "sdvl_ctx_fork_mark", "sdvl_ctx_fork_begin", "sdvl_ctx_fork_end", "sdvl_host_alloc_pinned", "sdvl_host_free_pinned", "sdvl_host_register", "sdvl_host_unregister",
 ]
 
@@ -256,6 +257,24 @@ class PoseParams(C.Structure):
 
 class PoseResult(C.Structure):
     _fields_ = [("pose", C.c_double * 7), ("n_draws", C.c_int32), ("n_inliers", C.c_int32), ("n_outliers", C.c_int32), ("refined", C.c_int32)]
+
+
+class KltJob(C.Structure):
+    """sdvl_klt_job: a pair of frames (same size, pyramids built) and a range of the call's points"""
+    _fields_ = [("prev", C.c_void_p), ("next", C.c_void_p), ("pt_begin", C.c_int32), ("pt_end", C.c_int32)]
+
+
+class KltParams(C.Structure):
+    _fields_ = [("win_size", C.c_int32), ("max_level", C.c_int32), ("max_its", C.c_int32), ("pad_", C.c_int32),
+                ("eps", C.c_double), ("min_eig_threshold", C.c_double)]
+
+
+class HomographyJob(C.Structure):
+    _fields_ = [("m_begin", C.c_int32), ("m_end", C.c_int32), ("draw_begin", C.c_int32), ("draw_end", C.c_int32)]
+
+
+class HomographyResult(C.Structure):
+    _fields_ = [("H", C.c_double * 9), ("best_draw", C.c_int32), ("n_its", C.c_int32), ("n_inliers", C.c_int32), ("pad_", C.c_int32)]
 
 
 def ransac_budget_table(size, max_points, max_its):
@@ -613,6 +632,63 @@ class Context:
                             inliers=lists[b:b + res[k].n_inliers].copy(),
                             outliers=lists[b + res[k].n_inliers:b + res[k].n_inliers + res[k].n_outliers].copy()))
         return out
+
+    def klt_track(self, jobs, win_size=30, max_level=4, max_its=30, eps=0.001, min_eig_threshold=1e-4):
+        """cv::calcOpticalFlowPyrLK as HomographyInit::TrackSecondFrame calls it (homography_init.cc:195-198), all jobs in one launch.
+        jobs: list of (prev Frame, next Frame, prev_xy [n][2], initial next_xy [n][2]).
+        Returns per job dict(xy float32 [n][2], status bool [n], err float32 [n])."""
+        kj = (KltJob * max(len(jobs), 1))()
+        prev_all, next_all = [], []
+        at = 0
+        for k, (fp, fn, pxy, nxy) in enumerate(jobs):
+            pxy = np.asarray(pxy, np.float32).reshape(-1, 2)
+            nxy = np.asarray(nxy, np.float32).reshape(-1, 2)
+            assert len(pxy) == len(nxy)
+            kj[k].prev, kj[k].next = fp.h.value, fn.h.value
+            kj[k].pt_begin, kj[k].pt_end = at, at + len(pxy)
+            at += len(pxy)
+            prev_all.append(pxy)
+            next_all.append(nxy)
+        prev = np.ascontiguousarray(np.concatenate(prev_all) if jobs else np.zeros((0, 2)), np.float32)
+        nxt = np.ascontiguousarray(np.concatenate(next_all) if jobs else np.zeros((0, 2)), np.float32).copy()
+        status = np.zeros(max(at, 1), np.uint8)
+        err = np.zeros(max(at, 1), np.float32)
+        prm = KltParams(win_size, max_level, max_its, 0, eps, min_eig_threshold)
+        self.lib.sdvl_klt_track.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_klt_track(self.h, len(jobs), kj, at, prev.ctypes.data, nxt.ctypes.data, status.ctypes.data, err.ctypes.data,
+                                            C.byref(prm)))
+        return [dict(xy=nxt[kj[k].pt_begin:kj[k].pt_end].copy(), status=status[kj[k].pt_begin:kj[k].pt_end].astype(bool),
+                     err=err[kj[k].pt_begin:kj[k].pt_end].copy()) for k in range(len(jobs))]
+
+    def homography_ransac(self, jobs, threshold, max_its=2000, confidence=0.995):
+        """The RANSAC of cv::findHomography(src, dst, CV_RANSAC, threshold) (homography_init.cc:253), all jobs in one call.
+        jobs: list of (src [n][2], dst [n][2], draws4 [k][4]: the 4-subsets the caller's random stream would draw, indices into the
+        job's matches).  Returns per job dict(H [3][3], best_draw, n_its, inliers)."""
+        n = len(jobs)
+        hj = (HomographyJob * max(n, 1))()
+        src_all, dst_all, draw_all = [np.zeros((0, 2))], [np.zeros((0, 2))], [np.zeros((0, 4), np.int32)]
+        m_at = d_at = 0
+        for k, (src, dst, draws) in enumerate(jobs):
+            src = np.asarray(src, np.float64).reshape(-1, 2)
+            dst = np.asarray(dst, np.float64).reshape(-1, 2)
+            draws = np.asarray(draws, np.int32).reshape(-1, 4)
+            assert len(src) == len(dst)
+            hj[k].m_begin, hj[k].m_end = m_at, m_at + len(src)
+            hj[k].draw_begin, hj[k].draw_end = d_at, d_at + len(draws)
+            m_at += len(src)
+            d_at += len(draws)
+            src_all.append(src); dst_all.append(dst); draw_all.append(draws)
+        src = np.ascontiguousarray(np.concatenate(src_all), np.float64)
+        dst = np.ascontiguousarray(np.concatenate(dst_all), np.float64)
+        draws = np.ascontiguousarray(np.concatenate(draw_all), np.int32)
+        res = (HomographyResult * max(n, 1))()
+        lists = np.zeros(max(m_at, 1), np.int32)
+        self.lib.sdvl_homography_ransac.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_homography_ransac(self.h, n, hj, m_at, src.ctypes.data, dst.ctypes.data, d_at, draws.ctypes.data,
+                                                    float(threshold), int(max_its), float(confidence), res, lists.ctypes.data))
+        return [dict(H=np.array(list(res[k].H)).reshape(3, 3), best_draw=res[k].best_draw, n_its=res[k].n_its,
+                     inliers=lists[hj[k].m_begin:hj[k].m_begin + res[k].n_inliers].copy()) for k in range(n)]
 
     def undistort(self, imgs, cam, dist, frames=None):
         """Camera::UndistortImage for a batch of host images (numpy u8 [h, w]).  With `frames` the result becomes their

@@ -24,4 +24,18 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
   return __builtin_amdgcn_readlane(v, 63);
 }
 
+// the same for floats: lanes without a source add 0.0f, every lane gets the same bits
+#define SDVL_DPP_F32(x, ctrl, rows, banks) \
+  __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rows, banks, false))
+__device__ __forceinline__ float wave_sum_dpp_f32(float x) {
+  x += SDVL_DPP_F32(x, 0x111, 0xf, 0xf);
+  x += SDVL_DPP_F32(x, 0x112, 0xf, 0xf);
+  x += SDVL_DPP_F32(x, 0x114, 0xf, 0xe);
+  x += SDVL_DPP_F32(x, 0x118, 0xf, 0xc);
+  x += SDVL_DPP_F32(x, 0x142, 0xa, 0xf);
+  x += SDVL_DPP_F32(x, 0x143, 0xc, 0xf);
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+}
+#undef SDVL_DPP_F32
+
 }  // namespace

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "sdvl_host.h"
+#include "homography_init.h"
 
 using namespace sdvl;
 
@@ -132,6 +133,20 @@ int sdvlh_batch_set_color(void *bp, int format) {
     return -1;
   }
   b->format = format;
+  return 0;
+}
+
+// the trackers of the batch take the reference's two-frame initialisation (SDVL::SetTwoFrameInit) instead of the plane bootstrap; needs
+// the reference's mapper (sdvlh_set_mapper(1) before the batch was created)
+int sdvlh_batch_set_two_frame_init(void *bp, int on) {
+  Batch *b = static_cast<Batch *>(bp);
+  if (!b) return -1;
+  try {
+    for (auto &t : b->trackers) t->SetTwoFrameInit(on != 0);
+  } catch (const std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
   return 0;
 }
 
@@ -976,5 +991,41 @@ int sdvlh_farm_run(void *fp, int n_steps, const void *const *dev_frames, int str
   if (f->failed) { g_err = f->err; return -1; }
   return 0;
 }
+
+// ---- two-frame initialisation, the host arithmetic behind the device stages (homography_init.h)
+// src / dst [n][2] of HomographyInit::ComputeHomography (homography_init.cc:243-250) for tracked pixels: the input of sdvl_homography_ransac
+int sdvlh_homography_matches(int n, const float *pixels1, const float *pixels2, const double *cam4, double *src, double *dst) {
+  if (n < 0 || !cam4 || (n > 0 && (!pixels1 || !pixels2 || !src || !dst))) return -1;
+  HomographyMath h(cam4, 0.0, 1.0);
+  h.SetTracks(n, pixels1, pixels2);
+  std::memcpy(src, h.Src().data(), sizeof(double) * 2 * n);
+  std::memcpy(dst, h.Dst().data(), sizeof(double) * 2 * n);
+  return 0;
+}
+// ComputeHomography from the RANSAC's inliers on, and the scaling of InitSecondFrame.  out_R9 / out_t3: frame 1 -> frame 2, scaled;
+// out_counts4 = {inliers of CheckInliers, inliers of CheckDecompositionInliers, visibility score 0, visibility score 1};
+// out_inliers [n] and out_tri [n][3] may be null.  1 = initialised, 0 = refused (homography_init.cc:99-103), -1 = bad argument
+int sdvlh_homography_from_inliers(int n, const float *pixels1, const float *pixels2, const double *cam4, double inlier_error_threshold,
+                                  double map_scale, int min_init_corners, int n_ransac_inliers, const int32_t *ransac_inliers, double *out_H9,
+                                  double *out_R9, double *out_t3, int32_t *out_counts4, double *out_depth, int32_t *out_inliers, double *out_tri) {
+  if (n <= 0 || !pixels1 || !pixels2 || !cam4 || !ransac_inliers || !out_H9 || !out_R9 || !out_t3 || !out_counts4 || !out_depth) return -1;
+  HomographyMath h(cam4, inlier_error_threshold, map_scale);
+  h.SetTracks(n, pixels1, pixels2);
+  const bool ok = h.ComputeHomography(n_ransac_inliers, ransac_inliers, min_init_corners);
+  std::memcpy(out_H9, h.BestH(), sizeof(double) * 9);
+  std::memcpy(out_R9, h.Rotation(), sizeof(double) * 9);
+  std::memcpy(out_t3, h.Translation(), sizeof(double) * 3);
+  out_counts4[0] = h.NumHomographyInliers();
+  out_counts4[1] = static_cast<int32_t>(h.Inliers().size());
+  out_counts4[2] = h.VisibilityScore(0);
+  out_counts4[3] = h.VisibilityScore(1);
+  *out_depth = h.MedianDepth();
+  if (out_inliers) std::copy(h.Inliers().begin(), h.Inliers().end(), out_inliers);
+  if (out_tri && !h.Triangulations().empty()) std::memcpy(out_tri, h.Triangulations().data(), sizeof(double) * 3 * n);
+  return ok ? 1 : 0;
+}
+// test hooks: the two Jacobi routines
+void sdvlh_jacobi_eigen_sym(int n, double *A, double *V, double *eig) { JacobiEigenSym(n, A, V, eig); }
+void sdvlh_jacobi_svd3(const double *A, double *U, double *s, double *V) { JacobiSvd3(A, U, s, V); }
 
 }  // extern "C"

@@ -23,7 +23,7 @@
 namespace sdvl {
 
 // Map stand-in for synthetic scenes: seeds one FIXED point per FilterCorners() corner of a keyframe, depth from a
-// known scene plane n.X = d (replaces homography_init + depth filter, both out of scope).
+// known scene plane n.X = d (stands in for homography_init + depth filter).
 class PlaneMap : public Map {
  public:
   PlaneMap(const Vector3d &n, double d) : n_(n), d_(d) {}
@@ -45,7 +45,8 @@ class PlaneMap : public Map {
 };
 
 // map.h:44-139 — the reference's mapper in SEQUENTIAL mode (main.cc:148-149: SDVL::Mapping() = Map::UpdateMap() after every
-// frame).  The first keyframe is still bootstrapped from the scene plane (homography_init is out of scope); every later
+// frame).  The first keyframe is bootstrapped from the scene plane unless the tracker takes the two-frame initialisation
+// (SDVL::SetTwoFrameInit, homography_init.cc); every later
 // keyframe goes through UpdateCandidates / CheckConnections / AddConnectionsPoints / InitCandidates, ordinary frames
 // through UpdateCandidates / CheckRedundantKeyframes.  Bundle adjustment is out of scope and not run.
 // Every SearchPoint the mapper would issue one at a time is emitted as a request instead (Emit*), evaluated for MANY
@@ -91,6 +92,9 @@ class MapperMap : public PlaneMap {
   long Updates() const { return updates_; }  // UpdateMap calls that found a frame to work on
   bool IsThreaded() const { return running_; }
 
+  // map.h: Map::AddCandidate — a point of the two-frame initialisation enters the depth filter's list (homography_init.cc:171)
+  void AddCandidate(const std::shared_ptr<Point> &p) { candidates_.push_back(p); version_++; }
+
   struct Stats { int candidates = 0, converged = 0, initialized = 0, linked = 0, connected = 0, keyframes = 0; };
   Stats GetStats() const;
 
@@ -128,15 +132,16 @@ typedef std::pair<std::shared_ptr<Point>, Vector2d> PointInfo;
 typedef std::list<PointInfo> GridCell;
 
 class SDVLBatch;
+class HomographyInit;
 
-// sdvl.h:36-108.  The two-frame homography bootstrap is out of scope: the first frame becomes a keyframe at
-// `first_pose` and the Map seeds its points (PlaneMap for synthetic scenes).
+// sdvl.h:36-108.  By default the first frame becomes a keyframe at `first_pose` and the Map seeds its points from a scene plane
+// (PlaneMap for synthetic scenes); SetTwoFrameInit(true) takes the reference's two-frame homography bootstrap instead.
 class SDVL {
  public:
   enum State { STATE_FIRST_FRAME, STATE_SECOND_FRAME, STATE_RUNNING };
   enum TrackingQuality { TRACKING_GOOD, TRACKING_INSUFFICIENT, TRACKING_BAD };
-  // sdvl.h:49: the tracker owns its map (the reference's mapper, MapperMap).  The two-frame homography bootstrap is out of
-  // scope, so the first keyframe's points come from a scene plane: z = Config::MapScale() in the first camera's frame (the
+  // sdvl.h:49: the tracker owns its map (the reference's mapper, MapperMap).  Unless SetTwoFrameInit(true) is called,
+  // the first keyframe's points come from a scene plane: z = Config::MapScale() in the first camera's frame (the
   // depth the reference's initialisation normalises the map to) unless SetBootstrapPlane says otherwise.  A Device for the
   // calling thread is created if none is bound yet (GPU 0, or SDVL_GPU).
   explicit SDVL(Camera *camera);
@@ -144,6 +149,14 @@ class SDVL {
   SDVL(Camera *camera, Map *map, const SE3 &first_pose = SE3());
   ~SDVL();
   void SetBootstrapPlane(const Vector3d &n, double d);
+  // The reference's first-frame / second-frame states (sdvl.cc:132-177, HomographyInit) instead of the plane bootstrap: the first
+  // frame's filtered corners are tracked (device KLT) until their median shift reaches SDVL.min_avg_shift, then a homography is
+  // fitted (device RANSAC), decomposed and triangulated, and the points enter the map as depth-filter candidates.  Needs the
+  // reference's mapper (MapperMap): throws std::runtime_error with any other map.  Not built: Map::TransformInitialMap (the world
+  // frame stays the first camera's) and BundleAdjustment.  Deviation: an initialisation that fails with empty lists (sdvl.cc:66-69,
+  // where the reference stays stuck) makes HandleFrame return false and starts over with the next frame as first frame.
+  void SetTwoFrameInit(bool on);
+  bool TwoFrameInit() const { return two_frame_init_; }
   // sdvl.h:52-54 (the UI's queries)
   void GetCameraTrail(std::vector<std::pair<SE3, bool>> *positions);
   void GetPoints(std::vector<Vector3d> *positions);
@@ -174,6 +187,10 @@ class SDVL {
   void GetMotionModel();
   void ResetMotionModel();
   void SaveFirstFrame(FrameStats &st);
+  bool InitFirstFrame(FrameStats &st);                       // sdvl.cc:132-148 (two-frame initialisation)
+  void SecondFrameDone(bool initialised, FrameStats &st);    // sdvl.cc:154-176 behind HomographyInit::InitSecondFrame
+  bool two_frame_init_ = false, init_failed_ = false;
+  std::unique_ptr<HomographyInit> h_init_;
   int TrackingDecision();
   void StartRelocalizing();
   void Relocalized(const std::shared_ptr<Frame> &kf, FrameStats &st);
@@ -277,6 +294,9 @@ class SDVLBatch {
   struct HostStep;  // Step + the requests and pose jobs of the host-driven form
   enum FrameStart { kFirstFrame, kLost, kRunning };
   FrameStart BeginFrame(int i, const std::shared_ptr<Frame> &frame, FrameStats &st);
+  // the two-frame initialisation of every tracker of the step that is in its first-frame or second-frame state: ONE sdvl_klt_track
+  // call and ONE sdvl_homography_ransac call for all of them
+  void InitializeTrackers(Step &s);
   void DetectOnSideStream(const std::vector<std::shared_ptr<Frame>> &frames, bool fork);
   void FetchCornerCounts(const std::vector<std::shared_ptr<Frame>> &frames, FrameStats *stats);
   void CollectKeyframes(Step &s, bool fetch_counts);

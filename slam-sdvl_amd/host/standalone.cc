@@ -6,6 +6,7 @@
 // HandleFrames; the host-driven step (HandleFramesGeneric); what follows the decisions (EpilogueAndMapper, FinishKeyframes, RunMappers).
 // Reference line numbers are cited at each function; device work goes through the C-ABI (include/sdvl_hip.h) only.
 #include "sdvl_host.h"
+#include "homography_init.h"
 #include "host_internal.h"
 
 #include <algorithm>
@@ -433,6 +434,56 @@ void SDVL::SaveFirstFrame(FrameStats &st) {
   st.keyframe = 1;
 }
 
+void SDVL::SetTwoFrameInit(bool on) {
+  if (on && !dynamic_cast<MapperMap *>(map_)) throw std::runtime_error("SDVL::SetTwoFrameInit needs the reference's mapper (MapperMap)");
+  two_frame_init_ = on;
+  if (on && !h_init_) h_init_.reset(new HomographyInit(map_, Config::MinAvgShift()));
+}
+
+// sdvl.cc:132-148
+bool SDVL::InitFirstFrame(FrameStats &st) {
+  st.state = 0;
+  current_frame_->CreateCorners(Config::MaxFastLevels(), 2 * Config::NumFeatures());
+  current_frame_->SetPose(SE3());
+  last_frame_ = current_frame_;  // sdvl.cc:63-64
+  last_kf_ = current_frame_;
+  track_.valid = false;
+  if (!h_init_->InitFirstFrame(current_frame_)) return false;
+  current_frame_->SetKeyframe();
+  map_->AddKeyframe(current_frame_, false);
+  state_ = STATE_SECOND_FRAME;
+  st.keyframe = 1;
+  return true;
+}
+
+// sdvl.cc:154-176 behind HomographyInit::InitSecondFrame, and :66-71
+void SDVL::SecondFrameDone(bool initialised, FrameStats &st) {
+  st.state = 1;
+  track_.valid = false;
+  if (!initialised) {
+    if (h_init_->HasError()) {  // :155-158, :66-69: the reference is lost for good here; this tracker starts over (stated deviation)
+      std::cerr << "[ERROR] Homography couldn't be performed" << std::endl;
+      h_init_->Reset();
+      state_ = STATE_FIRST_FRAME;
+      init_failed_ = true;
+      st.state = 0;
+      return;
+    }
+    last_frame_ = current_frame_;  // :160 returns true: :70-71 run
+    last_kf_ = current_frame_;
+    return;
+  }
+  current_frame_->SetKeyframe();  // :164-165
+  map_->AddKeyframe(current_frame_, false);
+  // (Map::TransformInitialMap and BundleAdjustment, :168-172, are not built: the world frame stays the first camera's)
+  h_init_->Reset();
+  state_ = STATE_RUNNING;
+  last_frame_ = current_frame_;
+  last_kf_ = current_frame_;
+  st.state = 2;
+  st.keyframe = 1;
+}
+
 // sdvl.cc:97-100: CalcTrackingQuality, then NeedKeyframe.  0 = tracking lost, 1 = ordinary frame, 2 = new keyframe
 int SDVL::TrackingDecision() {
   CalcTrackingQuality(matches_, attempts_);
@@ -498,7 +549,7 @@ bool SDVL::HandleFrame(const Image &img) {
     track_.valid = false;
     throw;
   }
-  return true;
+  return !init_failed_;  // sdvl.cc:66-69
 }
 
 void SDVL::Mapping() {
@@ -876,6 +927,7 @@ struct SDVLBatch::Step {
   vector<shared_ptr<Frame>> frames;  // this step's frame of every tracker
   // trackers that execute ProcessFrame this step / that relocalise first / that relocalised onto a keyframe no table can express
   vector<int> run, lost, host_run;
+  vector<int> init;                  // trackers in the first-frame / second-frame state of the two-frame initialisation
   vector<char> decision;             // per tracker: 0 = tracking lost / not tracked, 1 = ordinary frame, 2 = new keyframe
   vector<shared_ptr<Frame>> kfs;     // the keyframes the mapping stage seeds, and whose they are
   vector<int> kf_owner;
@@ -909,11 +961,83 @@ SDVLBatch::FrameStart SDVLBatch::BeginFrame(int i, const shared_ptr<Frame> &fram
   t.current_frame_ = frame;
   t.current_frame_->SetID(t.frame_counter_++);
   if (t.state_ != SDVL::STATE_RUNNING) {
-    t.SaveFirstFrame(st);
+    if (!t.two_frame_init_) t.SaveFirstFrame(st);  // otherwise InitializeTrackers, once every tracker's frame is known
     return kFirstFrame;
   }
   st.state = 2;
   return t.lost_frames_ >= 3 ? kLost : kRunning;  // relocalize = lost_frames_ >= 3, sdvl.cc:73
+}
+
+// sdvl.cc:61-71,132-177 for the trackers of the step that take the two-frame initialisation.  First-frame trackers: CreateCorners for
+// 2 x NumFeatures (:135), InitFirstFrame, keyframe.  Second-frame trackers: the KLT of all of them in ONE call, then — for those whose
+// shift and count pass (:234) — the RANSACs in ONE call, and per tracker the rest of ComputeHomography and InitSecondFrame.
+void SDVLBatch::InitializeTrackers(Step &s) {
+  vector<int> second;
+  for (int i : s.init) {
+    SDVL &t = *trk_[i];
+    t.init_failed_ = false;
+    if (t.state_ == SDVL::STATE_FIRST_FRAME) {
+      if (!t.InitFirstFrame(s.stats[i])) std::cerr << "[ERROR] First frame couldn't be initialized" << std::endl;  // :138-139: stays in the state
+    } else {
+      second.push_back(i);
+    }
+  }
+  if (second.empty()) return;
+  // ---- TrackSecondFrame of every tracker: one sdvl_klt_track call
+  vector<sdvl_klt_job> jobs(second.size());
+  vector<float> prev, next;
+  int at = 0;
+  for (size_t k = 0; k < second.size(); k++) {
+    SDVL &t = *trk_[second[k]];
+    s.stats[second[k]].state = 1;
+    t.h_init_->BeginSecondFrame(t.current_frame_, at, &jobs[k]);
+    const int n = t.h_init_->NumPixels();
+    prev.insert(prev.end(), t.h_init_->Pixels1(), t.h_init_->Pixels1() + 2 * n);
+    next.insert(next.end(), t.h_init_->Pixels2(), t.h_init_->Pixels2() + 2 * n);
+    at += n;
+  }
+  vector<uint8_t> status(std::max(at, 1));
+  const sdvl_klt_params kp = {30, Config::PyramidLevels() - 1, 30, 0, 0.001, 1e-4};  // homography_init.cc:195-198
+  dev_->Check(sdvl_klt_track(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), at, prev.data(), next.data(), status.data(), nullptr, &kp),
+              "sdvl_klt_track");
+  vector<int> fit;  // trackers whose shift and count pass
+  vector<char> done(second.size(), 0);
+  for (size_t k = 0; k < second.size(); k++) {
+    SDVL &t = *trk_[second[k]];
+    const int n = t.h_init_->NumPixels();
+    std::copy(next.begin() + 2 * jobs[k].pt_begin, next.begin() + 2 * (jobs[k].pt_begin + n), t.h_init_->Pixels2());
+    if (t.h_init_->FinishTrack(status.data() + jobs[k].pt_begin)) fit.push_back(static_cast<int>(k));
+  }
+  // ---- cv::findHomography's RANSAC of every tracker that goes on: one sdvl_homography_ransac call
+  const int max_its = 2000;
+  vector<sdvl_homography_job> hjobs(fit.size());
+  vector<double> src, dst;
+  vector<int32_t> draws;
+  int m_at = 0;
+  for (size_t f = 0; f < fit.size(); f++) {
+    SDVL &t = *trk_[second[fit[f]]];
+    vector<double> a, b;
+    vector<int32_t> d;
+    t.h_init_->HomographyInput(t.rng_, max_its, &a, &b, &d);
+    hjobs[f] = sdvl_homography_job{m_at, m_at + t.h_init_->NumPixels(), static_cast<int32_t>(f) * max_its, static_cast<int32_t>(f + 1) * max_its};
+    src.insert(src.end(), a.begin(), a.end());
+    dst.insert(dst.end(), b.begin(), b.end());
+    draws.insert(draws.end(), d.begin(), d.end());
+    m_at += t.h_init_->NumPixels();
+  }
+  if (!fit.empty()) {
+    vector<sdvl_homography_result> res(fit.size());
+    vector<int32_t> inl(std::max(m_at, 1));
+    dev_->Check(sdvl_homography_ransac(dev_->ctx(), static_cast<int>(fit.size()), hjobs.data(), m_at, src.data(), dst.data(),
+                                       static_cast<int>(fit.size()) * max_its, draws.data(), 2. / trk_[0]->camera_->GetFx(), max_its, 0.995,
+                                       res.data(), inl.data()),
+                "sdvl_homography_ransac");
+    for (size_t f = 0; f < fit.size(); f++) {
+      SDVL &t = *trk_[second[fit[f]]];
+      done[fit[f]] = t.h_init_->FinishSecondFrame(res[f], inl.data() + hjobs[f].m_begin, &t.rng_) ? 1 : 0;
+    }
+  }
+  for (size_t k = 0; k < second.size(); k++) trk_[second[k]]->SecondFrameDone(done[k] != 0, s.stats[second[k]]);
 }
 
 // Corner detection of `frames`; fork: on the context's side stream, from the caller's sdvl_ctx_fork_mark on (see SubmitTracked).
@@ -1452,10 +1576,12 @@ bool SDVLBatch::HandleFramesTracked(const vector<Image> &imgs, FrameStats *stats
   for (int i = 0; i < B; i++) {
     const FrameStart start = BeginFrame(i, s.frames[i], stats[i]);
     if (start == kLost) s.lost.push_back(i);
+    if (start == kFirstFrame && trk_[i]->two_frame_init_) s.init.push_back(i);
     if (start != kRunning) continue;
     trk_[i]->SetMotionModel();
     s.run.push_back(i);
   }
+  if (!s.init.empty()) InitializeTrackers(s);
   if (!s.lost.empty()) RelocalizeIntoStep(s);
   if (!s.run.empty()) {
     SubmitTracked(s);
@@ -1801,10 +1927,12 @@ void SDVLBatch::HandleFramesGeneric(const vector<Image> &imgs, FrameStats *stats
   for (int i = 0; i < B; i++) {
     const FrameStart start = BeginFrame(i, s.frames[i], stats[i]);
     stats[i].host_path = 1;
+    if (start == kFirstFrame && trk_[i]->two_frame_init_) s.init.push_back(i);
     if (start == kFirstFrame || (start == kLost && !RelocalizeOnHost(*trk_[i], stats[i]))) continue;
     trk_[i]->SetMotionModel();
     s.run.push_back(i);
   }
+  if (!s.init.empty()) InitializeTrackers(s);
   AlignImages(s);
   // ---- stage 2: the search requests, in one of three forms
   s.Stage(ST_PREPARE);

@@ -96,7 +96,8 @@ def bind_to_gpu_numa_node(gpu=0):
 
 def set_mapper(on):
     """map mode of the batches / farms created afterwards: the reference's mapper in sequential mode (map.cc) instead of
-    the plane map stub; the first keyframe is bootstrapped from the scene plane in both modes"""
+    the plane map stub; the first keyframe is bootstrapped from the scene plane in both modes unless the batch is told
+    TrackerBatch.set_two_frame_init(True)"""
     load_host_library().sdvlh_set_mapper(int(bool(on)))
 
 
@@ -187,6 +188,16 @@ class TrackerBatch:
         if self.lib.sdvlh_batch_set_color(self.h, code) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         self.channels = PIXEL_CHANNELS[code]
+
+    def set_two_frame_init(self, on=True):
+        """the trackers start from the camera alone: the reference's two-frame initialisation (first frame's corners tracked by device
+        KLT until the median shift reaches SDVL.min_avg_shift, homography by device RANSAC, decomposition, triangulation, points as
+        depth-filter candidates) instead of the plane bootstrap.  FrameStats.state is 0 on the first frame, 1 while the second frame is
+        awaited, 2 from the frame that initialises.  Requires the reference's mapper: call set_mapper(True) BEFORE creating the batch,
+        otherwise this raises"""
+        self.lib.sdvlh_batch_set_two_frame_init.argtypes = [C.c_void_p, C.c_int]
+        if self.lib.sdvlh_batch_set_two_frame_init(self.h, int(bool(on))) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
 
     def step_device_transient(self, dev_ptrs):
         """frames in HBM that stay valid for THIS step only (a slot of an input ring): aliased while tracked, frames that become
