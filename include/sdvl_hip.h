@@ -704,6 +704,56 @@ int sdvl_homography_ransac(sdvl_ctx *ctx, int n_jobs, const sdvl_homography_job 
                            int n_draws, const int32_t *draws4, double threshold, int max_its, double confidence,
                            sdvl_homography_result *results, int32_t *inlier_lists);
 
+/* ---- local bundle adjustment: Bundle::Local (extra/bundle.cc:26-224) as g2o runs it, J independent problems in one launch ----------
+ * One problem = the window Map::BundleAdjustment (map.cc:844-869) hands to Bundle::Local: poses[kf_begin .. kf_end) with the free ones
+ * first (fixed[k] != 0: the fixed keyframes of bundle.cc:129-139 and a local keyframe with id 0, :123), points[pt_begin .. pt_end)
+ * and edges[edge_begin .. edge_end), each naming a point and a pose by their index INSIDE the problem (at most one edge per pair).
+ * Ranges of different problems do not overlap and ascend.  Poses are 7 doubles as everywhere; the camera is shared (bundle.cc:180-183).
+ * The device runs both stages (optimize(5) with Huber, the outlier test, optimize(10) on the level-0 edges, :192-209) with the
+ * Levenberg-Marquardt loop, the Schur complement and a dense Cholesky inside one kernel, in FP64 and without floating-point atomics:
+ * the same problem gives the same bits wherever it stands in a call.  tests/bundle_restatement.py is the specification.
+ * On return poses and points hold the estimates (:211-223), edge_levels[n_e] the level every edge ended on (:203), pose_stages[n_kf] /
+ * point_stages[n_pt] bit s = the vertex had an active edge in stage s (a vertex without one is not optimised).  A problem whose
+ * status is not SDVL_BUNDLE_OK leaves its poses and points as given.  More than SDVL_BUNDLE_MAX_FREE free poses in any problem:
+ * SDVL_ERR_CAPACITY, nothing is written.  Fixed poses, points and edges are limited by memory only. */
+#define SDVL_BUNDLE_MAX_FREE 16      /* 2 x SDVL.max_search_keyframes + the new keyframe = 11 at the reference's default */
+#define SDVL_BUNDLE_OK 0
+#define SDVL_BUNDLE_EMPTY 1          /* no pose or no point */
+#define SDVL_BUNDLE_NO_EDGES 2       /* no edge reaches a free pose: nothing to solve */
+#define SDVL_BUNDLE_NONFINITE 3      /* chi2 of the given estimates is not finite (NaN / infinite input, a point on a camera plane) */
+
+typedef struct sdvl_bundle_problem {
+  int32_t kf_begin, kf_end;     /* kfs then fixed_kfs, bundle.cc:118-139 */
+  int32_t pt_begin, pt_end;     /* lpoints, :151-158 */
+  int32_t edge_begin, edge_end; /* projections, :161-189 */
+} sdvl_bundle_problem;
+
+typedef struct sdvl_bundle_edge { /* EdgeSE3ProjectXYZ, bundle.cc:170-185 */
+  int32_t point, keyframe;  /* setVertex(0, ...), setVertex(1, ...) */
+  double u, v;              /* setMeasurement((*it_fts)->GetPosition()) */
+} sdvl_bundle_edge;
+
+typedef struct sdvl_bundle_stage { /* one optimize() call, optimization_algorithm_levenberg.cpp:61-164 */
+  double lambda;                /* _currentLambda at the end */
+  double chi2_before, chi2_after; /* activeRobustChi2 at iteration 0 and of the last accepted estimates */
+  int32_t iterations, trials;   /* solve() calls; _levenbergIterations summed */
+  int32_t accepted_mask;        /* bit i: iteration i ended on an accepted trial */
+  int32_t pad_;
+  int32_t trials_per_it[10];    /* qmax of every iteration */
+} sdvl_bundle_stage;
+
+typedef struct sdvl_bundle_result {
+  sdvl_bundle_stage stage[2];
+  int32_t status;               /* SDVL_BUNDLE_* */
+  int32_t n_level1;             /* edges the outlier test moved to level 1, bundle.cc:202-203 */
+  int32_t n_free;               /* free poses of the problem */
+  int32_t pad_;
+} sdvl_bundle_result;
+
+int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed,
+                       int n_pt, double *points, int n_e, const sdvl_bundle_edge *edges, const sdvl_camera *cam, int32_t *edge_levels,
+                       int32_t *pose_stages, int32_t *point_stages, sdvl_bundle_result *results);
+
 /* ---- synthetic sequence generator (no dataset ships with the repo) ------------------------------- */
 struct sdvl_synth_view;
 /* renders n views of the textured plane straight into HBM: dev_out + i*frame_bytes, row stride = width */

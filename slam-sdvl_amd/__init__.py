@@ -134,7 +134,7 @@ ABI_SYMBOLS = [
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
     "sdvl_frames_own_images", "sdvl_feed_create", "sdvl_feed_destroy", "sdvl_feed_last_error", "sdvl_feed_slot_arrived", "sdvl_feed_images", "sdvl_ctx_feed_acquire", "sdvl_ctx_feed_release", "sdvl_frame_footprint_cap", "sdvl_ctx_set_corner_capacity", "sdvl_frame_corner_capacity", "sdvl_detect_scratch_bytes",
-    "sdvl_klt_track", "sdvl_homography_ransac",
+    "sdvl_klt_track", "sdvl_homography_ransac", "sdvl_bundle_adjust",
     "sdvl_ctx_set_wait_spin", "sdvl_ctx_fork_mark", "sdvl_ctx_fork_begin", "sdvl_ctx_fork_end", "sdvl_host_alloc_pinned", "sdvl_host_free_pinned", "sdvl_host_register", "sdvl_host_unregister",
 ]
 
@@ -153,6 +153,8 @@ def load_library():
         lib.sdvl_last_error.argtypes = [C.c_void_p]
         lib.sdvl_ctx_stream.restype = C.c_void_p
         lib.sdvl_ctx_stream.argtypes = [C.c_void_p]
+        lib.sdvl_bundle_adjust.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -275,6 +277,29 @@ class HomographyJob(C.Structure):
 
 class HomographyResult(C.Structure):
     _fields_ = [("H", C.c_double * 9), ("best_draw", C.c_int32), ("n_its", C.c_int32), ("n_inliers", C.c_int32), ("pad_", C.c_int32)]
+
+
+class BundleProblem(C.Structure):
+    """sdvl_bundle_problem: ranges of one local window in the call's poses (free ones first), points and edges"""
+    _fields_ = [("kf_begin", C.c_int32), ("kf_end", C.c_int32), ("pt_begin", C.c_int32), ("pt_end", C.c_int32),
+                ("edge_begin", C.c_int32), ("edge_end", C.c_int32)]
+
+
+class BundleEdge(C.Structure):
+    _fields_ = [("point", C.c_int32), ("keyframe", C.c_int32), ("u", C.c_double), ("v", C.c_double)]
+
+
+class BundleStage(C.Structure):
+    _fields_ = [("lam", C.c_double), ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("iterations", C.c_int32),
+                ("trials", C.c_int32), ("accepted_mask", C.c_int32), ("pad_", C.c_int32), ("trials_per_it", C.c_int32 * 10)]
+
+
+class BundleResult(C.Structure):
+    _fields_ = [("stage", BundleStage * 2), ("status", C.c_int32), ("n_level1", C.c_int32), ("n_free", C.c_int32), ("pad_", C.c_int32)]
+
+
+BUNDLE_MAX_FREE = 16
+BUNDLE_OK, BUNDLE_EMPTY, BUNDLE_NO_EDGES, BUNDLE_NONFINITE = 0, 1, 2, 3
 
 
 def ransac_budget_table(size, max_points, max_its):
@@ -689,6 +714,49 @@ class Context:
                                                     float(threshold), int(max_its), float(confidence), res, lists.ctypes.data))
         return [dict(H=np.array(list(res[k].H)).reshape(3, 3), best_draw=res[k].best_draw, n_its=res[k].n_its,
                      inliers=lists[hj[k].m_begin:hj[k].m_begin + res[k].n_inliers].copy()) for k in range(n)]
+
+    def bundle_adjust(self, problems, cam):
+        """Bundle::Local (extra/bundle.cc:110-223) for every problem of the list in one launch.
+        problems: dicts with poses [n_kf][7] (free ones first), fixed [n_kf], points [n_pt][3], edge_pt [n_e], edge_kf [n_e] (indices
+        inside the problem), edge_uv [n_e][2]; cam = (fx, fy, cx, cy).  The inputs are not modified.
+        Returns per problem dict(status, poses, points, levels [n_e], pose_stages [n_kf], point_stages [n_pt], n_level1,
+        stages: two dicts(iterations, trials, lam, chi2_before, chi2_after, trials_per_it, accepted_its))."""
+        n = len(problems)
+        bp = (BundleProblem * max(n, 1))()
+        poses_all, fixed_all, pts_all = [np.zeros((0, 7))], [np.zeros(0, np.int32)], [np.zeros((0, 3))]
+        edge_n = sum(len(p["edge_pt"]) for p in problems)
+        be = np.zeros(max(edge_n, 1), np.dtype([("point", np.int32), ("keyframe", np.int32), ("u", np.float64), ("v", np.float64)]))
+        assert be.dtype.itemsize == C.sizeof(BundleEdge)
+        k_at = p_at = e_at = 0
+        for j, p in enumerate(problems):
+            poses = np.asarray(p["poses"], np.float64).reshape(-1, 7)
+            pts = np.asarray(p["points"], np.float64).reshape(-1, 3)
+            uv = np.asarray(p["edge_uv"], np.float64).reshape(-1, 2)
+            assert len(p["fixed"]) == len(poses) and len(p["edge_pt"]) == len(p["edge_kf"]) == len(uv)
+            bp[j] = BundleProblem(k_at, k_at + len(poses), p_at, p_at + len(pts), e_at, e_at + len(uv))
+            sl = be[e_at:e_at + len(uv)]
+            sl["point"], sl["keyframe"], sl["u"], sl["v"] = p["edge_pt"], p["edge_kf"], uv[:, 0], uv[:, 1]
+            k_at += len(poses); p_at += len(pts); e_at += len(uv)
+            poses_all.append(poses); fixed_all.append(np.asarray(p["fixed"], np.int32)); pts_all.append(pts)
+        poses = np.ascontiguousarray(np.concatenate(poses_all), np.float64).copy()
+        fixed = np.ascontiguousarray(np.concatenate(fixed_all), np.int32)
+        pts = np.ascontiguousarray(np.concatenate(pts_all), np.float64).copy()
+        levels = np.zeros(max(e_at, 1), np.int32)
+        kstage, pstage = np.zeros(max(k_at, 1), np.int32), np.zeros(max(p_at, 1), np.int32)
+        res = (BundleResult * max(n, 1))()
+        c = Camera(0.0, 0.0, float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]))
+        self._check(self.lib.sdvl_bundle_adjust(self.h, n, bp, k_at, poses.ctypes.data, fixed.ctypes.data, p_at, pts.ctypes.data, e_at, be.ctypes.data,
+                                                C.byref(c), levels.ctypes.data, kstage.ctypes.data, pstage.ctypes.data, res))
+        out = []
+        for j in range(n):
+            b, r = bp[j], res[j]
+            stages = [dict(iterations=s.iterations, trials=s.trials, lam=s.lam, chi2_before=s.chi2_before, chi2_after=s.chi2_after,
+                           trials_per_it=list(s.trials_per_it)[:s.iterations],
+                           accepted_its=[bool(s.accepted_mask >> i & 1) for i in range(s.iterations)]) for s in r.stage]
+            out.append(dict(status=r.status, n_level1=r.n_level1, n_free=r.n_free, stages=stages, poses=poses[b.kf_begin:b.kf_end].copy(),
+                            points=pts[b.pt_begin:b.pt_end].copy(), levels=levels[b.edge_begin:b.edge_end].copy(),
+                            pose_stages=kstage[b.kf_begin:b.kf_end].copy(), point_stages=pstage[b.pt_begin:b.pt_end].copy()))
+        return out
 
     def undistort(self, imgs, cam, dist, frames=None):
         """Camera::UndistortImage for a batch of host images (numpy u8 [h, w]).  With `frames` the result becomes their

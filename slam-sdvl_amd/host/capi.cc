@@ -150,6 +150,45 @@ int sdvlh_batch_set_two_frame_init(void *bp, int on) {
   return 0;
 }
 
+// the mappers of the batch bundle-adjust every new keyframe (SDVL::SetBundleAdjustment, map.cc:130-137); needs the reference's mapper
+// (sdvlh_set_mapper(1) before the batch was created)
+int sdvlh_batch_set_bundle_adjustment(void *bp, int on) {
+  Batch *b = static_cast<Batch *>(bp);
+  if (!b) return -1;
+  try {
+    for (auto &t : b->trackers) t->SetBundleAdjustment(on != 0);
+  } catch (const std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+  return 0;
+}
+
+// tracker i's adjustments so far: counts6 = runs, skipped (windows over SDVL_BUNDLE_MAX_FREE free poses), and the last window's free
+// poses, fixed poses, points and edges; *last = its sdvl_bundle_result (zeros before the first run)
+int sdvlh_batch_bundle_stats(void *bp, int i, long long *counts6, sdvl_bundle_result *last) {
+  Batch *b = static_cast<Batch *>(bp);
+  if (!b || i < 0 || i >= static_cast<int>(b->maps.size()) || !counts6 || !last) return -1;
+  MapperMap *m = dynamic_cast<MapperMap *>(b->maps[i].get());
+  if (!m) return -1;
+  const BundleStats &s = m->GetBundleStats();
+  counts6[0] = s.runs; counts6[1] = s.skipped; counts6[2] = s.n_free; counts6[3] = s.n_fixed; counts6[4] = s.n_points; counts6[5] = s.n_edges;
+  *last = s.last;
+  return 0;
+}
+
+// the poses (7 doubles each, oldest first) of tracker i's keyframes and their frame ids; returns how many there are (at most cap are written)
+int sdvlh_batch_keyframe_poses(void *bp, int i, int cap, double *poses7, int *ids) {
+  Batch *b = static_cast<Batch *>(bp);
+  if (!b || i < 0 || i >= static_cast<int>(b->maps.size())) return -1;
+  const std::vector<std::shared_ptr<Frame>> &kfs = b->maps[i]->GetKeyframes();
+  for (int k = 0; k < static_cast<int>(kfs.size()) && k < cap; k++) {
+    kfs[k]->GetPose().ToArray(poses7 + 7 * k);
+    ids[k] = kfs[k]->GetID();
+  }
+  return static_cast<int>(kfs.size());
+}
+
 // map mode of the batches created AFTER the call: 0 = plane map stub (every keyframe seeded from the scene plane),
 // 1 = the reference's mapper in sequential mode (map.cc; the first keyframe is still bootstrapped from the plane)
 void sdvlh_set_mapper(int on) { g_use_mapper = on != 0; }

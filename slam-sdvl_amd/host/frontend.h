@@ -268,6 +268,10 @@ class Frame : public std::enable_shared_from_this<Frame> {
   bool HasFlatFeatures() const { return flat_ != nullptr; }
   bool IsRegistered() const { return registered_; }
   void SetRegistered() { registered_ = true; }
+  void ClearRegistered() { registered_ = false; }  // the pose changed behind the registry (bundle adjustment): registered again on next use
+  // frame.h:77-78: the last bundle adjustment that used the frame
+  int GetLastBA() const { return last_ba_; }
+  void SetLastBA(int id) { last_ba_ = id; }
   std::vector<Vector3i> &GetCorners();  // host mirror of the HBM corner list, filled on first call
   int GetNumCorners();                  // corner count without mirroring the list
   std::vector<int> &GetFilteredCorners() { return filtered_corners_; }
@@ -398,6 +402,7 @@ class Frame : public std::enable_shared_from_this<Frame> {
   void MaterializeFeatures();
   void DropFlat();
   bool registered_ = false;  // the context's (frame, pose) registry holds this frame with its current pose
+  int last_ba_ = -1;
   bool features_removed_ = false;
   double scene_depth_hint_ = 0.0;
   bool scene_depth_hint_valid_ = false;
@@ -550,7 +555,7 @@ class FeatureAlign {
 
 // wall-clock per stage of SDVLBatch::HandleFrames, accumulated (seconds); index = StageId
 enum StageId { ST_UPLOAD_PYR = 0, ST_FAST, ST_SELECT, ST_CORNERS_ORB, ST_PRELUDE, ST_IMAGE_ALIGN, ST_PREPARE, ST_SEARCH, ST_FINISH, ST_POSE, ST_MAPPING,
-               ST_EPILOGUE, ST_MAPPER, ST_TOTAL, ST_MAP_CANDIDATES, ST_MAP_CONNECTIONS, ST_MAP_INIT, ST_MAP_FINISH, ST_MAP_BEGIN, ST_MAP_EMIT, ST_MAP_SEARCH, ST_MAP_APPLY, ST_RELOCALIZE, ST_COUNT };
+               ST_EPILOGUE, ST_MAPPER, ST_TOTAL, ST_MAP_CANDIDATES, ST_MAP_CONNECTIONS, ST_MAP_INIT, ST_MAP_FINISH, ST_MAP_BEGIN, ST_MAP_EMIT, ST_MAP_SEARCH, ST_MAP_APPLY, ST_RELOCALIZE, ST_MAP_BUNDLE, ST_COUNT };
 struct StageTimes {
   double t[ST_COUNT] = {0};
   long steps = 0;

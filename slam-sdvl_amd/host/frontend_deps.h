@@ -122,6 +122,9 @@ class Point {
   // points once instead (a feature of the keyframe is in its point's list and vice versa)
   int SeenStamp() const { return seen_stamp_; }
   void SetSeenStamp(int frame_id) { seen_stamp_ = frame_id; }
+  // point.h:73-74: the last bundle adjustment that used the point
+  int GetLastBA() const { return last_ba_; }
+  void SetLastBA(int id) { last_ba_ = id; }
   static void ConsumeId();  // what constructing and discarding a Point does to the id counter
   static double ComputeTau(const SE3 &pose, const Vector3d &v, double depth, double px_error_angle);
   static double PDFNormal(double mean, double sd, double x);
@@ -140,6 +143,7 @@ class Point {
   double cos_alpha_ = 1.0, last_distance_ = 1.0;
   int track_row_ = -1;
   int seen_stamp_ = -1;
+  int last_ba_ = -1;
   bool dev_trashed_ = false;
   std::list<std::shared_ptr<Feature>> features_;
 };

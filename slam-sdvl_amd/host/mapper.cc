@@ -222,6 +222,58 @@ void MapperMap::AddKeyframe(const shared_ptr<Frame> &frame, bool search) {
   keyframes_.push_back(frame);
   retired_.push_back(frame);
   last_kf_ = frame;
+  if (bundle_on_) ba_kf_ = frame;  // :157
+}
+
+// ---- Map::BundleAdjustment, map.cc:844-869, and its call at the end of Map::UpdateMap, :130-137
+void MapperMap::SetBundleAdjustment(bool on) {
+  if (on && running_) throw std::runtime_error("MapperMap::SetBundleAdjustment: bundle adjustment runs in sequential mode only, the mapper thread is started");
+  bundle_on_ = on;
+  if (!on) ba_kf_.reset();
+}
+
+bool MapperMap::PrepareBundle(BundleProblem *out, int min_keyframes) {
+  if (!bundle_on_ || !ba_kf_ || static_cast<int>(keyframes_.size()) <= min_keyframes) return false;  // :131-132
+  vector<shared_ptr<Frame>> fov_kfs;
+  ba_kf_->GetBestConnections(&fov_kfs, 2 * Config::MaxSearchKeyframes());  // :850-851
+  fov_kfs.push_back(ba_kf_);
+  if (fov_kfs.size() <= 1) return false;  // :860-861, the keyframe keeps waiting
+  // Bundle::Local finds the fixed keyframes through Point::GetFeatures(): a keyframe whose tracked features are still flat records
+  // (Frame::LinkPointsOnMaterialize) has not told its points yet
+  for (const shared_ptr<Frame> &kf : keyframes_)
+    if (kf->HasFlatFeatures()) kf->GetFeatures();
+  ba_kf_.reset();  // :868
+  if (!Bundle::Collect(fov_kfs, out)) return false;
+  if (out->n_free > SDVL_BUNDLE_MAX_FREE) {  // more than the device solver takes (SDVL.max_search_keyframes above 7): this adjustment is left out
+    bundle_stats_.skipped++;
+    return false;
+  }
+  return true;
+}
+
+void MapperMap::FinishBundle(const BundleProblem &problem, const sdvl_bundle_result &result, const vector<Frame *> &moved) {
+  bundle_stats_.runs++;
+  bundle_stats_.n_free = problem.n_free;
+  bundle_stats_.n_fixed = static_cast<int>(problem.kfs.size()) - problem.n_free;
+  bundle_stats_.n_points = static_cast<int>(problem.points.size());
+  bundle_stats_.n_edges = static_cast<int>(problem.edges.size());
+  bundle_stats_.last = result;
+  if (result.status != SDVL_BUNDLE_OK) return;  // nothing was written
+  // what the device holds of the old estimates: the (frame, pose) registry entries of the keyframes that moved (registered again by the
+  // next table that names them), the tracker's table rows (inverse depths and bearings of the points, rebuilt before the next step) and
+  // the relocalisation store's keyframe records (checked against Version())
+  for (Frame *f : moved) f->ClearRegistered();
+  tables_dirty_ = true;
+  Touch();
+}
+
+void MapperMap::BundleAdjustment(int min_keyframes) {
+  BundleProblem problem;
+  if (!PrepareBundle(&problem, min_keyframes)) return;
+  vector<sdvl_bundle_result> results;
+  vector<vector<Frame *>> moved;
+  Bundle::Solve(Device::Current(), *camera_, {&problem}, &results, &moved);
+  FinishBundle(problem, results[0], moved[0]);
 }
 
 // map.cc:190-205,692-706
@@ -763,6 +815,7 @@ MapperMap::~MapperMap() { Stop(); }
 
 void MapperMap::Start() {
   if (running_) return;
+  if (bundle_on_) throw std::runtime_error("MapperMap::Start: bundle adjustment is on and runs in sequential mode only");
   tracker_device_ = Device::CurrentOrNull();
   running_ = true;
   thread_ = std::thread(&MapperMap::Run, this);
@@ -835,6 +888,7 @@ void MapperMap::UpdateMap() {
     }
   }
   FinishUpdate();
+  BundleAdjustment();  // :130-137
 }
 
 }  // namespace sdvl

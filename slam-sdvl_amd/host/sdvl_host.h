@@ -19,6 +19,7 @@
 #define SDVL_HOST_H_
 
 #include "frontend.h"
+#include "bundle.h"
 
 namespace sdvl {
 
@@ -48,7 +49,7 @@ class PlaneMap : public Map {
 // frame).  The first keyframe is bootstrapped from the scene plane unless the tracker takes the two-frame initialisation
 // (SDVL::SetTwoFrameInit, homography_init.cc); every later
 // keyframe goes through UpdateCandidates / CheckConnections / AddConnectionsPoints / InitCandidates, ordinary frames
-// through UpdateCandidates / CheckRedundantKeyframes.  Bundle adjustment is out of scope and not run.
+// through UpdateCandidates / CheckRedundantKeyframes.  Local bundle adjustment (map.cc:130-137) runs behind them when SetBundleAdjustment(true).
 // Every SearchPoint the mapper would issue one at a time is emitted as a request instead (Emit*), evaluated for MANY
 // trackers in one K7 launch, and the reference's sequential logic is replayed over the results (Apply*) — the same
 // speculate-then-replay scheme FeatureAlign uses (SearchPoint is a pure function of its arguments).
@@ -81,6 +82,19 @@ class MapperMap : public PlaneMap {
   void EmitInitCandidates(std::vector<sdvl_search_req> *reqs);   // after Frame::FilterCorners of CurrentFrame()
   void ApplyInitCandidates(const sdvl_search_res *res);
   void FinishUpdate();                                           // CheckRedundantKeyframes + trash for ordinary frames
+  // ---- local bundle adjustment, the end of Map::UpdateMap (map.cc:130-137) and Map::BundleAdjustment (map.cc:844-869); off by default.
+  // Sequential mode only: throws while the mapper thread runs, and Start() throws while it is on.
+  void SetBundleAdjustment(bool on);
+  bool BundleAdjustmentOn() const { return bundle_on_; }
+  // the window of ba_kf_, if the map has more than `min_keyframes` keyframes and a keyframe is waiting (:131-132; SaveSecondFrame asks
+  // without the size test, sdvl.cc:172).  false: nothing to solve — no waiting keyframe, a keyframe without connections (:860-861), no
+  // points (bundle.cc:91-92), or more free poses than SDVL_BUNDLE_MAX_FREE (skipped and counted)
+  bool PrepareBundle(BundleProblem *out, int min_keyframes = 2);
+  // behind Bundle::Solve: books the result; the keyframes that moved leave the device's pose registry, the tracking tables and the
+  // relocalisation store are told that they are stale
+  void FinishBundle(const BundleProblem &problem, const sdvl_bundle_result &result, const std::vector<Frame *> &moved);
+  void BundleAdjustment(int min_keyframes = 2);  // the three for this map alone: one sdvl_bundle_adjust call
+  const BundleStats &GetBundleStats() const { return bundle_stats_; }
   // the whole of it for one tracker (one launch per phase)
   void UpdateMap() override;
   // map.cc:49-71: the mapper thread of threaded mode.  It works on a Device of its own (one sdvl_ctx = one HIP stream per
@@ -107,6 +121,9 @@ class MapperMap : public PlaneMap {
   int num_kfs_ = 0, initial_kf_id_ = 0, last_kf_checked_ = -1;
   bool relocalizing_ = false;
   Stats stats_;
+  bool bundle_on_ = false;
+  std::shared_ptr<Frame> ba_kf_;  // map.h:125: the keyframe waiting for its bundle adjustment (set in AddKeyframe)
+  BundleStats bundle_stats_;
   // state of the update in flight
   std::shared_ptr<Frame> cur_;
   double depth_mean_ = 0.0;
@@ -153,10 +170,14 @@ class SDVL {
   // frame's filtered corners are tracked (device KLT) until their median shift reaches SDVL.min_avg_shift, then a homography is
   // fitted (device RANSAC), decomposed and triangulated, and the points enter the map as depth-filter candidates.  Needs the
   // reference's mapper (MapperMap): throws std::runtime_error with any other map.  Not built: Map::TransformInitialMap (the world
-  // frame stays the first camera's) and BundleAdjustment.  Deviation: an initialisation that fails with empty lists (sdvl.cc:66-69,
+  // frame stays the first camera's).  Deviation: an initialisation that fails with empty lists (sdvl.cc:66-69,
   // where the reference stays stuck) makes HandleFrame return false and starts over with the next frame as first frame.
   void SetTwoFrameInit(bool on);
   bool TwoFrameInit() const { return two_frame_init_; }
+  // Map::BundleAdjustment after every keyframe update of a map with more than two keyframes (map.cc:130-137), on the device
+  // (sdvl_bundle_adjust).  Off by default.  Needs the reference's mapper in sequential mode: throws std::runtime_error with any other map
+  // and while the mapper thread runs.
+  void SetBundleAdjustment(bool on);
   // sdvl.h:52-54 (the UI's queries)
   void GetCameraTrail(std::vector<std::pair<SE3, bool>> *positions);
   void GetPoints(std::vector<Vector3d> *positions);

@@ -434,6 +434,12 @@ void SDVL::SaveFirstFrame(FrameStats &st) {
   st.keyframe = 1;
 }
 
+void SDVL::SetBundleAdjustment(bool on) {
+  MapperMap *m = dynamic_cast<MapperMap *>(map_);
+  if (!m) throw std::runtime_error("SDVL::SetBundleAdjustment needs the reference's mapper (MapperMap)");
+  m->SetBundleAdjustment(on);
+}
+
 void SDVL::SetTwoFrameInit(bool on) {
   if (on && !dynamic_cast<MapperMap *>(map_)) throw std::runtime_error("SDVL::SetTwoFrameInit needs the reference's mapper (MapperMap)");
   two_frame_init_ = on;
@@ -475,7 +481,10 @@ void SDVL::SecondFrameDone(bool initialised, FrameStats &st) {
   }
   current_frame_->SetKeyframe();  // :164-165
   map_->AddKeyframe(current_frame_, false);
-  // (Map::TransformInitialMap and BundleAdjustment, :168-172, are not built: the world frame stays the first camera's)
+  // (Map::TransformInitialMap, :168-170, is not built: the world frame stays the first camera's)
+  // :172, map_.BundleAdjustment() without UpdateMap's size test: the second keyframe has no connections yet (CheckConnections runs in its
+  // mapper update), so the window is that keyframe alone and Map::BundleAdjustment returns at map.cc:860 with the keyframe still waiting
+  if (MapperMap *m = dynamic_cast<MapperMap *>(map_)) m->BundleAdjustment(0);
   h_init_->Reset();
   state_ = STATE_RUNNING;
   last_frame_ = current_frame_;
@@ -2115,6 +2124,26 @@ void SDVLBatch::RunMappers() {
   }
   sub.reset(new StageClock(ST_MAP_FINISH));
   ParallelFor(M, [&](int k) { mm[k]->FinishUpdate(); });
+  // local bundle adjustment (map.cc:130-137): the windows of all the step's mappers in ONE sdvl_bundle_adjust call
+  bool any_bundle = false;
+  for (int k = 0; k < M; k++) any_bundle = any_bundle || mm[k]->BundleAdjustmentOn();
+  if (!any_bundle) return;
+  sub.reset(new StageClock(ST_MAP_BUNDLE));
+  vector<BundleProblem> windows(M);
+  vector<char> has(M, 0);
+  ParallelFor(M, [&](int k) { has[k] = mm[k]->PrepareBundle(&windows[k]) ? 1 : 0; });
+  vector<BundleProblem *> problems;
+  vector<int> whose;
+  for (int k = 0; k < M; k++)
+    if (has[k]) {
+      problems.push_back(&windows[k]);
+      whose.push_back(k);
+    }
+  if (problems.empty()) return;
+  vector<sdvl_bundle_result> results;
+  vector<vector<Frame *>> moved;
+  Bundle::Solve(dev_, *trk_[0]->camera_, problems, &results, &moved);
+  for (size_t j = 0; j < problems.size(); j++) mm[whose[j]]->FinishBundle(windows[whose[j]], results[j], moved[j]);
 }
 
 }  // namespace sdvl

@@ -5,7 +5,7 @@
 //   track_sequence --synthetic N [--seed S]                      N frames of the S-A scene, rendered on the host
 //   track_sequence --list frames.txt                             one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB: converted to gray on the
 //                                                                device, SDVL_RGB8) path per line, e.g. a TUM / EuRoC list
-//   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--init plane|two-frame]
+//   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
 //   round 5 (bench.py's latency legs):  [--texture plane|camera]  [--trackers N]  N cameras = N host threads, each with its own Device
 //            (= HIP stream), Camera, Map and SDVL, all fed the same frames;  [--batch]  with --trackers N: the N cameras step together through
 //            ONE sdvl::SDVLBatch::HandleFrames call per frame on one thread and one stream (the batched form of the same call);  [--prerender]  the synthetic frames are rendered on the GPU
@@ -73,7 +73,7 @@ int main(int argc, char **argv) {
   unsigned seed = 20260001;
   double cam4[4] = {517.3, 516.5, 318.6, 255.3}, dist[5] = {0, 0, 0, 0, 0}, plane[4] = {0, 0, 1, 2.0};
   std::string list, cfg;
-  bool mapper = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
+  bool mapper = false, bundle = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
   bool prerender = false, pageable = false, quiet = false, json = false, profile = false, batch = false, lookahead = false;
   int n_trackers = 1;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
@@ -90,6 +90,7 @@ int main(int argc, char **argv) {
     else if (a == "--dist") { need(5); for (int k = 0; k < 5; k++) dist[k] = std::atof(argv[++i]); dist_given = true; }
     else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) plane[k] = std::atof(argv[++i]); }
     else if (a == "--mapper") mapper = true;
+    else if (a == "--bundle") { bundle = true; mapper = true; }  // local bundle adjustment of every new keyframe (SDVL::SetBundleAdjustment; implies --mapper)
     else if (a == "--init") { need(1); const std::string t = argv[++i]; if (t == "two-frame") { two_frame = true; mapper = true; } else if (t != "plane") { std::cerr << "unknown --init " << t << std::endl; return 2; } }
     else if (a == "--texture") { need(1); const std::string t = argv[++i]; if (t == "camera") texture = SDVL_TEXTURE_CAMERA; else if (t != "plane") { std::cerr << "unknown texture " << t << std::endl; return 2; } }
     else if (a == "--trackers") { need(1); n_trackers = std::max(1, std::atoi(argv[++i])); }
@@ -199,6 +200,7 @@ int main(int argc, char **argv) {
         else map.reset(new PlaneMap(Vector3d(plane[0], plane[1], plane[2]), plane[3]));
         SDVL sdvl(&camera, map.get());
         if (two_frame) sdvl.SetTwoFrameInit(true);
+        if (bundle) sdvl.SetBundleAdjustment(true);
         std::vector<uint8_t> px(pool ? 0 : frame_bytes);
         me.ms.reserve(n_frames);
         Image ahead;
@@ -290,6 +292,7 @@ int main(int argc, char **argv) {
           else maps.emplace_back(new PlaneMap(Vector3d(plane[0], plane[1], plane[2]), plane[3]));
           trackers.emplace_back(new SDVL(&camera, maps.back().get()));
           if (two_frame) trackers.back()->SetTwoFrameInit(true);
+          if (bundle) trackers.back()->SetBundleAdjustment(true);
           raw.push_back(trackers.back().get());
         }
         {

@@ -199,6 +199,36 @@ class TrackerBatch:
         if self.lib.sdvlh_batch_set_two_frame_init(self.h, int(bool(on))) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
 
+    def set_bundle_adjustment(self, on=True):
+        """the trackers' mappers run the reference's local bundle adjustment (Map::BundleAdjustment, map.cc:130-137,844-869) after every
+        keyframe update of a map with more than two keyframes: the windows of all trackers of a step are solved in one sdvl_bundle_adjust
+        call.  Off by default.  Requires the reference's mapper: call set_mapper(True) BEFORE creating the batch, otherwise this raises"""
+        self.lib.sdvlh_batch_set_bundle_adjustment.argtypes = [C.c_void_p, C.c_int]
+        if self.lib.sdvlh_batch_set_bundle_adjustment(self.h, int(bool(on))) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+
+    def bundle_stats(self, i):
+        """mapper mode only: dict(runs, skipped, n_free, n_fixed, n_points, n_edges, last) of tracker i; `last` is the BundleResult
+        (sdvl_bundle_result) of its last window, zeros before the first run"""
+        from . import BundleResult
+        counts = (C.c_longlong * 6)()
+        last = BundleResult()
+        self.lib.sdvlh_batch_bundle_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if self.lib.sdvlh_batch_bundle_stats(self.h, int(i), counts, C.byref(last)) != 0:
+            raise RuntimeError("tracker %d has no mapper" % i)
+        out = dict(zip(("runs", "skipped", "n_free", "n_fixed", "n_points", "n_edges"), [int(c) for c in counts]))
+        out["last"] = last
+        return out
+
+    def keyframe_poses(self, i):
+        """(frame ids, poses[n][7]) of tracker i's keyframes, oldest first"""
+        self.lib.sdvlh_batch_keyframe_poses.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        n = self.lib.sdvlh_batch_keyframe_poses(self.h, int(i), 0, None, None)
+        poses = np.zeros((max(n, 1), 7), np.float64)
+        ids = np.zeros(max(n, 1), np.int32)
+        n = self.lib.sdvlh_batch_keyframe_poses(self.h, int(i), n, poses.ctypes.data, ids.ctypes.data)
+        return ids[:n].copy(), poses[:n].copy()
+
     def step_device_transient(self, dev_ptrs):
         """frames in HBM that stay valid for THIS step only (a slot of an input ring): aliased while tracked, frames that become
         keyframes take a copy at the end of the step"""
@@ -209,7 +239,7 @@ class TrackerBatch:
 
     STAGES = ["upload_pyr", "fast", "select", "corners_orb", "prelude", "image_align", "prepare", "search", "finish", "pose", "mapping",
               "epilogue", "mapper", "total", "map_candidates", "map_connections", "map_init", "map_finish",
-              "map_begin", "map_emit", "map_search", "map_apply", "relocalize"]
+              "map_begin", "map_emit", "map_search", "map_apply", "relocalize", "map_bundle"]
 
     def map_stats(self, i):
         """mapper mode only: candidates, converged, initialized, linked, connected, keyframes of tracker i"""
