@@ -257,7 +257,8 @@ def test_closed_loop_with_reference_mapper_batched(trk, orc, synth):
 
 def test_farm_fibers_give_identical_results(trk, orc, synth):
     """TrackerFarm with cooperative group-steps (a worker thread interleaves two groups, switching at GPU waits) must
-    produce exactly the per-frame results of the plain one-step-at-a-time farm"""
+    produce exactly the per-frame results of the plain one-step-at-a-time farm, and so must both forms when there are fewer threads or
+    fibers than groups and group-steps are handed out dynamically"""
     import importlib
     sdvl = importlib.import_module("slam-sdvl_amd")
     import bench as B
@@ -283,6 +284,9 @@ def test_farm_fibers_give_identical_results(trk, orc, synth):
     plain = run(1, 4)
     coop = run(2, 2)
     assert plain == coop
+    # fewer threads / fibers than groups: group-steps are handed out dynamically, the group furthest behind first
+    assert plain == run(1, 3)
+    assert plain == run(2, 1)
     assert all(r[1] == 0 and r[4] >= 100 for r in plain[n:])      # tracking, not idling
 
 
