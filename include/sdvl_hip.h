@@ -759,6 +759,36 @@ struct sdvl_synth_view;
 /* renders n views of the textured plane straight into HBM: dev_out + i*frame_bytes, row stride = width */
 int sdvl_synth_render(sdvl_ctx *ctx, int n, const struct sdvl_synth_view *views, int width, int height,
                       void *dev_out, int64_t frame_bytes);
+/* A scene with depth (csrc/sdvl_synth_scene.h): up to SDVL_SYNTH_MAX_SURFACES textured planar surfaces, each unbounded or a rectangle,
+ * seen by the camera of sdvl_synth_view; every pixel shows the nearest surface its ray hits.  The layout is stated here, once. */
+#define SDVL_SYNTH_MAX_SURFACES 8
+#define SDVL_SYNTH_NO_SURFACE 255     /* surface id of a pixel whose ray hits nothing (its depth is 0) */
+#define SDVL_SYNTH_SCENE_MAX_VIEWS 4096 /* scenes per sdvl_synth_render_scene call: 4096 records of 1208 bytes = 4.7 MB of staging */
+typedef struct sdvl_synth_surface {
+  double plane[4];          /* n.X = d (world) */
+  double origin[3];         /* the point of the surface its texture coordinates (0, 0) belong to */
+  double e1[3], e2[3];      /* orthonormal in-plane axes, the caller's: not checked */
+  double half_u, half_v;    /* half extents along e1 / e2; <= 0: unbounded along that axis */
+  uint32_t seed_add;        /* the surface's texture seed is scene.seed + seed_add */
+  uint32_t pad_;
+} sdvl_synth_surface;
+typedef struct sdvl_synth_scene {
+  double fx, fy, u0, v0;
+  double R[9];              /* rotation of T_cw (world -> camera), row-major */
+  double t[3];              /* translation of T_cw */
+  uint32_t seed, frame_id, texture; /* as in sdvl_synth_view */
+  uint32_t n_surfaces;      /* 0 .. SDVL_SYNTH_MAX_SURFACES */
+  double dist[5];           /* the lens, as in sdvl_synth_view */
+  sdvl_synth_surface surfaces[SDVL_SYNTH_MAX_SURFACES];
+} sdvl_synth_scene;
+/* renders n scenes into HBM: image dev_out + i*frame_bytes (row stride = width) and, where the pointer is not null, the ground truth of
+ * every pixel, frame after frame without padding: dev_depth (float, the camera-frame z of the hit, 0 where nothing is hit) and
+ * dev_surface (uint8, the index of the surface hit, SDVL_SYNTH_NO_SURFACE where nothing is).  n <= SDVL_SYNTH_SCENE_MAX_VIEWS */
+int sdvl_synth_render_scene(sdvl_ctx *ctx, int n, const sdvl_synth_scene *scenes, int width, int height, void *dev_out, int64_t frame_bytes,
+                            float *dev_depth, uint8_t *dev_surface);
+int sdvl_synth_scene_size(void);                                           /* sizeof(sdvl_synth_scene), for binding checks */
+int sdvl_synth_scene_preset(const char *name, sdvl_synth_scene *out);      /* fills n_surfaces and surfaces; -1: no such preset */
+const char *sdvl_synth_scene_preset_names(void);                          /* the preset names, separated by blanks */
 int sdvl_device_malloc(sdvl_ctx *ctx, int64_t bytes, void **out);
 int sdvl_device_free(sdvl_ctx *ctx, void *p);
 int sdvl_device_download(sdvl_ctx *ctx, const void *dev, int64_t bytes, void *host);

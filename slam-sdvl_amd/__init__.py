@@ -120,6 +120,25 @@ class SynthView(C.Structure):
                 ("dist", C.c_double * 5)]
 
 
+SYNTH_MAX_SURFACES = 8
+SYNTH_NO_SURFACE = 255
+SYNTH_SCENE_MAX_VIEWS = 4096
+
+
+class SynthSurface(C.Structure):
+    """sdvl_synth_surface: a textured plane n.X = d, unbounded or a rectangle of half extents (half_u, half_v) along (e1, e2) about origin"""
+    _fields_ = [("plane", C.c_double * 4), ("origin", C.c_double * 3), ("e1", C.c_double * 3), ("e2", C.c_double * 3),
+                ("half_u", C.c_double), ("half_v", C.c_double), ("seed_add", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class SynthScene(C.Structure):
+    """sdvl_synth_scene: the camera, pose, seeds and lens of SynthView and up to SYNTH_MAX_SURFACES surfaces"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("u0", C.c_double), ("v0", C.c_double),
+                ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("seed", C.c_uint32), ("frame_id", C.c_uint32), ("texture", C.c_uint32), ("n_surfaces", C.c_uint32),
+                ("dist", C.c_double * 5), ("surfaces", SynthSurface * SYNTH_MAX_SURFACES)]
+
+
 # every symbol include/sdvl_hip.h declares
 ABI_SYMBOLS = [
     "sdvl_ctx_create", "sdvl_ctx_destroy", "sdvl_last_error", "sdvl_ctx_synchronize", "sdvl_ctx_stream",
@@ -132,7 +151,8 @@ ABI_SYMBOLS = [
     "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
-    "sdvl_synth_render", "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
+    "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
+    "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
     "sdvl_frames_own_images", "sdvl_feed_create", "sdvl_feed_destroy", "sdvl_feed_last_error", "sdvl_feed_slot_arrived", "sdvl_feed_images", "sdvl_ctx_feed_acquire", "sdvl_ctx_feed_release", "sdvl_frame_footprint_cap", "sdvl_ctx_set_corner_capacity", "sdvl_frame_corner_capacity", "sdvl_detect_scratch_bytes",
     "sdvl_klt_track", "sdvl_homography_ransac", "sdvl_bundle_adjust",
     "sdvl_ctx_set_wait_spin", "sdvl_ctx_fork_mark", "sdvl_ctx_fork_begin", "sdvl_ctx_fork_end", "sdvl_host_alloc_pinned", "sdvl_host_free_pinned", "sdvl_host_register", "sdvl_host_unregister",
@@ -155,8 +175,38 @@ def load_library():
         lib.sdvl_ctx_stream.argtypes = [C.c_void_p]
         lib.sdvl_bundle_adjust.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sdvl_synth_scene_preset.argtypes = [C.c_char_p, C.c_void_p]
+        lib.sdvl_synth_scene_preset_names.restype = C.c_char_p
+        lib.sdvl_synth_render_scene.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
+
+
+def synth_scene_presets():
+    """the names sdvl_synth_scene_preset knows"""
+    return load_library().sdvl_synth_scene_preset_names().decode().split()
+
+
+def synth_scene(T_cw, cam, preset=None, seed=20260001, frame_id=0, texture=0, dist=None):
+    """a SynthScene seen from the world -> camera pose T_cw (qw, qx, qy, qz, tx, ty, tz) by the camera cam = (fx, fy, u0, v0), through the
+    lens dist = (k1, k2, p1, p2, k3) if given; its surfaces are those of the named preset (sdvl_synth_scene_preset), none without a name"""
+    s = SynthScene()
+    s.fx, s.fy, s.u0, s.v0 = [float(c) for c in cam]
+    w, x, y, z = [float(q) for q in T_cw[:4]]
+    R = [1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]
+    for i in range(9):
+        s.R[i] = R[i]
+    for i in range(3):
+        s.t[i] = float(T_cw[4 + i])
+    for i in range(5):
+        s.dist[i] = float(dist[i]) if dist is not None else 0.0
+    s.seed, s.frame_id, s.texture = int(seed), int(frame_id), int(texture)
+    if preset is not None:
+        if load_library().sdvl_synth_scene_preset(preset.encode(), C.byref(s)) != 0:
+            raise ValueError("unknown scene preset %r (one of %s)" % (preset, ", ".join(synth_scene_presets())))
+    return s
 
 
 def _ptr(a, t):
@@ -829,6 +879,13 @@ class Context:
         n = len(views)
         arr = (SynthView * n)(*views)
         self._check(self.lib.sdvl_synth_render(self.h, n, arr, width, height, C.c_void_p(dev_out), C.c_int64(frame_bytes or width * height)))
+
+    def synth_render_scene(self, scenes, width, height, dev_out, frame_bytes=None, dev_depth=None, dev_surface=None):
+        """renders the SynthScenes into HBM: image i at dev_out + i * frame_bytes; dev_depth (float32) and dev_surface (uint8), where
+        given, get the ground truth of every pixel, width * height entries per scene"""
+        n = len(scenes)
+        arr = (SynthScene * n)(*scenes)
+        self._check(self.lib.sdvl_synth_render_scene(self.h, n, arr, width, height, dev_out, frame_bytes or width * height, dev_depth, dev_surface))
 
 
 def default_detect_params(use_orb=True, orb_size=31, patch_size=8):

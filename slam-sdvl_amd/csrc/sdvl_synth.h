@@ -119,22 +119,55 @@ SDVL_HD inline double sdvl_camera_texture(double X, double Y, double pix, uint32
   return g;
 }
 
-SDVL_HD inline uint8_t sdvl_synth_pixel(const sdvl_synth_view *s, int u, int v) {
-  // ray in camera coords, rotate to world: R^T * r ; camera centre C = -R^T t
-  double rx = (u - s->u0) / s->fx, ry = (v - s->v0) / s->fy;
-  const double rz = 1.0;
-  if (s->dist[0] != 0.0) {
+// The ray of pixel (u, v) in camera coordinates, z = 1: (*rx, *ry).  cam = fx, fy, u0, v0.
+SDVL_HD inline __attribute__((always_inline)) void sdvl_synth_pixel_ray(double fx, double fy, double u0, double v0, const double *dist, int u, int v, double *rx_out, double *ry_out) {
+  double rx = (u - u0) / fx, ry = (v - v0) / fy;
+  if (dist[0] != 0.0) {
     // (rx, ry) is where the LENS put the ray: invert x_d = x kr + 2 p1 x y + p2 (r2 + 2 x2), y_d = y kr + p1 (r2 + 2 y2) + 2 p2 x y by the
     // usual fixed-point iteration (eight rounds; + - * / only)
     const double xd = rx, yd = ry;
     for (int it = 0; it < 8; it++) {
       const double x2 = rx * rx, y2 = ry * ry, r2 = x2 + y2, xy2 = 2.0 * rx * ry;
-      const double kr = 1.0 + ((s->dist[4] * r2 + s->dist[1]) * r2 + s->dist[0]) * r2;
-      const double dx = s->dist[2] * xy2 + s->dist[3] * (r2 + 2.0 * x2), dy = s->dist[2] * (r2 + 2.0 * y2) + s->dist[3] * xy2;
+      const double kr = 1.0 + ((dist[4] * r2 + dist[1]) * r2 + dist[0]) * r2;
+      const double dx = dist[2] * xy2 + dist[3] * (r2 + 2.0 * x2), dy = dist[2] * (r2 + 2.0 * y2) + dist[3] * xy2;
       rx = (xd - dx) / kr;
       ry = (yd - dy) / kr;
     }
   }
+  *rx_out = rx;
+  *ry_out = ry;
+}
+
+// Grey level of pixel (u, v) whose ray met a textured surface at texture coordinates (X, Y), `pix` = world size of a pixel there, or
+// met nothing (hit == 0: the background, val = 0); sensor noise of frame `frame_id` added, clamped and rounded.
+// (always inlined: one body per renderer, as when the shading stood inside sdvl_synth_pixel)
+SDVL_HD inline __attribute__((always_inline)) uint8_t sdvl_synth_shade(uint32_t texture, uint32_t seed, uint32_t frame_id, int hit, double X, double Y, double pix, int u, int v) {
+  double g;
+  if (hit && texture == SDVL_TEXTURE_CAMERA) {
+    g = sdvl_camera_texture(X, Y, pix, seed);
+  } else {
+    double val = 0.0;
+    if (hit) {
+      const double base = 0.0116;  // ~3 px at z = 2 m, fx ~ 517
+      val = 0.30 * sdvl_value_noise(X, Y, base, seed, 0) + 0.26 * sdvl_value_noise(X, Y, base * 2.0, seed, 1) +
+            0.20 * sdvl_value_noise(X, Y, base * 4.0, seed, 2) + 0.14 * sdvl_value_noise(X, Y, base * 8.0, seed, 3) +
+            0.10 * sdvl_value_noise(X, Y, base * 16.0, seed, 4);
+    }
+    // contrast stretch around the mean (sum of 5 uniform-ish terms concentrates near 0.5)
+    g = 128.0 + (val - 0.5) * 560.0;
+  }
+  const uint32_t nz = sdvl_hash3((uint32_t)u, (uint32_t)v, frame_id * 0x632BE5ABu + 0x1234567u) & 7u;  // 0..7
+  g += ((double)nz - 3.5) * 0.6;
+  if (g < 0.0) g = 0.0;
+  if (g > 255.0) g = 255.0;
+  return (uint8_t)(g + 0.5);
+}
+
+SDVL_HD inline uint8_t sdvl_synth_pixel(const sdvl_synth_view *s, int u, int v) {
+  // ray in camera coords, rotate to world: R^T * r ; camera centre C = -R^T t
+  double rx, ry;
+  sdvl_synth_pixel_ray(s->fx, s->fy, s->u0, s->v0, s->dist, u, v, &rx, &ry);
+  const double rz = 1.0;
   const double wx = s->R[0] * rx + s->R[3] * ry + s->R[6] * rz;
   const double wy = s->R[1] * rx + s->R[4] * ry + s->R[7] * rz;
   const double wz = s->R[2] * rx + s->R[5] * ry + s->R[8] * rz;
@@ -143,32 +176,16 @@ SDVL_HD inline uint8_t sdvl_synth_pixel(const sdvl_synth_view *s, int u, int v) 
   const double cz = -(s->R[2] * s->t[0] + s->R[5] * s->t[1] + s->R[8] * s->t[2]);
   const double denom = s->plane[0] * wx + s->plane[1] * wy + s->plane[2] * wz;
   const double num = s->plane[3] - (s->plane[0] * cx + s->plane[1] * cy + s->plane[2] * cz);
-  double val = 0.0;
+  int hit = 0;
+  double X = 0.0, Y = 0.0, pix = 0.0;
   if (denom > 1e-9 || denom < -1e-9) {
     const double k = num / denom;
     if (k > 0.0) {
-      const double X = cx + k * wx, Y = cy + k * wy;
-      if (s->texture == SDVL_TEXTURE_CAMERA) {
-        double g = sdvl_camera_texture(X, Y, k / s->fx, s->seed);
-        const uint32_t nz = sdvl_hash3((uint32_t)u, (uint32_t)v, s->frame_id * 0x632BE5ABu + 0x1234567u) & 7u;
-        g += ((double)nz - 3.5) * 0.6;
-        if (g < 0.0) g = 0.0;
-        if (g > 255.0) g = 255.0;
-        return (uint8_t)(g + 0.5);
-      }
-      const double base = 0.0116;  // ~3 px at z = 2 m, fx ~ 517
-      val = 0.30 * sdvl_value_noise(X, Y, base, s->seed, 0) + 0.26 * sdvl_value_noise(X, Y, base * 2.0, s->seed, 1) +
-            0.20 * sdvl_value_noise(X, Y, base * 4.0, s->seed, 2) + 0.14 * sdvl_value_noise(X, Y, base * 8.0, s->seed, 3) +
-            0.10 * sdvl_value_noise(X, Y, base * 16.0, s->seed, 4);
+      hit = 1;
+      X = cx + k * wx; Y = cy + k * wy; pix = k / s->fx;
     }
   }
-  // contrast stretch around the mean (sum of 5 uniform-ish terms concentrates near 0.5)
-  double g = 128.0 + (val - 0.5) * 560.0;
-  const uint32_t nz = sdvl_hash3((uint32_t)u, (uint32_t)v, s->frame_id * 0x632BE5ABu + 0x1234567u) & 7u;  // 0..7
-  g += ((double)nz - 3.5) * 0.6;
-  if (g < 0.0) g = 0.0;
-  if (g > 255.0) g = 255.0;
-  return (uint8_t)(g + 0.5);
+  return sdvl_synth_shade(s->texture, s->seed, s->frame_id, hit, X, Y, pix, u, v);
 }
 
 #endif  // SDVL_SYNTH_H_

@@ -193,6 +193,27 @@ int sdvlh_batch_point_digest(void *bp, int i, double *out6) {
   return 0;
 }
 
+// the live points tracker i's mapper created (MapperMap::GetMapPoints, after SyncHostState): out4 = x y z fixed per point, the rows
+// and the order of the oracle's sdvl_ref_tracker_mapper_points.  Returns how many there are (at most cap rows are written; out4 may be
+// null with cap 0), or -1 for a tracker on the plane map stub
+int sdvlh_batch_map_points(void *bp, int i, int cap, double *out4) {
+  TrackerGroup *b = AsGroup(bp);
+  if (!b || i < 0 || i >= b->size()) return -1;
+  MapperMap *m = dynamic_cast<MapperMap *>(&b->map(i));
+  if (!m) return -1;
+  int n = -1;
+  const int rc = Guarded([&] {
+    Device::SetCurrent(b->device());
+    b->batch().SyncHostState();
+    const std::vector<MapperMap::MapPoint> pts = m->GetMapPoints();
+    n = static_cast<int>(pts.size());
+    for (int k = 0; k < n && k < cap && out4; k++) {
+      out4[4 * k] = pts[k].x; out4[4 * k + 1] = pts[k].y; out4[4 * k + 2] = pts[k].z; out4[4 * k + 3] = pts[k].fixed ? 1.0 : 0.0;
+    }
+  });
+  return rc ? -2 : n;
+}
+
 // pose stage on the device (default) or with the host implementation; process-wide
 void sdvlh_set_device_pose(int on) { SDVLBatch::SetDevicePose(on != 0); }
 int sdvlh_device_pose() { return SDVLBatch::DevicePose() ? 1 : 0; }

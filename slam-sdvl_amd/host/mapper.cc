@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <set>
 
 #include "config.h"
 #include "sdvl_host.h"
@@ -317,6 +318,23 @@ MapperMap::Stats MapperMap::GetStats() const {
   s.candidates = static_cast<int>(candidates_.size());
   s.keyframes = static_cast<int>(keyframes_.size());
   return s;
+}
+
+std::vector<MapperMap::MapPoint> MapperMap::GetMapPoints() const {
+  std::vector<MapPoint> out;
+  std::set<const Point *> seen;
+  for (const std::shared_ptr<Frame> &kf : keyframes_)
+    for (const std::shared_ptr<Feature> &ft : kf->GetFeatures()) {
+      Point *p = ft ? ft->GetPointRaw() : nullptr;
+      if (!p || p->ToDelete()) continue;
+      Feature *first = p->GetInitFeatureRaw();
+      const std::shared_ptr<Frame> origin = first ? first->GetFrame() : nullptr;
+      if (!origin || origin->GetID() <= initial_kf_id_) continue;
+      if (!seen.insert(p).second) continue;
+      const Vector3d pos = p->GetPosition();
+      out.push_back(MapPoint{pos(0), pos(1), pos(2), p->IsFixed()});
+    }
+  return out;
 }
 
 // head of Map::UpdateMap, map.cc:75-108

@@ -111,6 +111,11 @@ class MapperMap : public PlaneMap {
 
   struct Stats { int candidates = 0, converged = 0, initialized = 0, linked = 0, connected = 0, keyframes = 0; };
   Stats GetStats() const;
+  // The live points the mapper created, x y z fixed each: keyframes oldest first, each keyframe's features in order, each point once;
+  // deleted points and points first seen on the bootstrap keyframe (they come from the plane itself) are left out.  Host state: a
+  // batch's caller runs SDVLBatch::SyncHostState first.
+  struct MapPoint { double x, y, z; bool fixed; };
+  std::vector<MapPoint> GetMapPoints() const;
 
  private:
   void CheckRedundantKeyframes();  // map.cc:619-690

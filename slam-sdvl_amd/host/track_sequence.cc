@@ -5,6 +5,8 @@
 //   track_sequence --synthetic N [--seed S]                      N frames of the S-A scene, rendered on the host
 //   track_sequence --list frames.txt                             one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB: converted to gray on the
 //                                                                device, SDVL_RGB8) path per line, e.g. a TUM / EuRoC list
+//   track_sequence --synthetic N --scene shelf                   N frames of a scene with depth (csrc/sdvl_synth_scene.h: several surfaces, nearest hit) instead of
+//                                                                the one plane; the map still bootstraps from --plane (the default is the scene's wall)
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
 //   round 5 (bench.py's latency legs):  [--texture plane|camera]  [--trackers N]  N cameras = N host threads, each with its own Device
 //            (= HIP stream), Camera, Map and SDVL, all fed the same frames;  [--batch]  with --trackers N: the N cameras step together through
@@ -35,9 +37,10 @@
 
 #include "sdvl_host.h"
 #undef SDVL_HD  // sdvl_math.h and sdvl_synth.h each define their own host/device qualifier macro
-#include "../csrc/sdvl_synth.h"
+#include "../csrc/sdvl_synth_scene.h"
 
 extern "C" int sdvl_synth_render_host(const sdvl_synth_view *view, int width, int height, uint8_t *out, int stride);
+extern "C" int sdvl_synth_render_scene_host(const sdvl_synth_scene *scene, int width, int height, uint8_t *out, int stride, float *depth, uint8_t *surface);
 
 using namespace sdvl;
 
@@ -72,7 +75,7 @@ int main(int argc, char **argv) {
   int W = 640, H = 480, n_synth = 0;
   unsigned seed = 20260001;
   double cam4[4] = {517.3, 516.5, 318.6, 255.3}, dist[5] = {0, 0, 0, 0, 0}, plane[4] = {0, 0, 1, 2.0};
-  std::string list, cfg;
+  std::string list, cfg, scene_name;
   bool mapper = false, bundle = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
   bool prerender = false, pageable = false, quiet = false, json = false, profile = false, batch = false, lookahead = false;
   int n_trackers = 1;
@@ -93,6 +96,7 @@ int main(int argc, char **argv) {
     else if (a == "--bundle") { bundle = true; mapper = true; }  // local bundle adjustment of every new keyframe (SDVL::SetBundleAdjustment; implies --mapper)
     else if (a == "--init") { need(1); const std::string t = argv[++i]; if (t == "two-frame") { two_frame = true; mapper = true; } else if (t != "plane") { std::cerr << "unknown --init " << t << std::endl; return 2; } }
     else if (a == "--texture") { need(1); const std::string t = argv[++i]; if (t == "camera") texture = SDVL_TEXTURE_CAMERA; else if (t != "plane") { std::cerr << "unknown texture " << t << std::endl; return 2; } }
+    else if (a == "--scene") { need(1); scene_name = argv[++i]; }
     else if (a == "--trackers") { need(1); n_trackers = std::max(1, std::atoi(argv[++i])); }
     else if (a == "--batch") batch = true;
     else if (a == "--lookahead") lookahead = true;
@@ -105,6 +109,15 @@ int main(int argc, char **argv) {
     else { std::cerr << "unknown argument " << a << std::endl; return 2; }
   }
   if ((n_synth > 0) == !list.empty()) { std::cerr << "give either --synthetic N or --list file" << std::endl; return 2; }
+  sdvl_synth_scene scene_surfaces = {};  // --scene: n_surfaces and surfaces of the preset
+  if (!scene_name.empty()) {
+    if (n_synth <= 0) { std::cerr << "--scene renders the synthetic sequence: give --synthetic N" << std::endl; return 2; }
+    if (sdvl_synth_scene_preset(scene_name.c_str(), &scene_surfaces) != 0) {
+      std::cerr << "unknown --scene " << scene_name << " (one of: " << sdvl_synth_scene_preset_names() << ")" << std::endl;
+      return 2;
+    }
+  }
+  const bool use_scene = !scene_name.empty();
 
   // main.cc:60-75: configuration file, then the TUM overrides the reference's config_tum_f1.cfg carries
   Config &c = Config::GetInstance();
@@ -150,6 +163,20 @@ int main(int argc, char **argv) {
     for (int q = 0; q < 5; q++) v.dist[q] = dist[q];  // --dist: the frames are what a camera with that lens records (camera.UndistortImage undoes it)
     return v;
   };
+  auto scene_of = [&](int k) {  // the same camera, pose, seeds and lens in front of the preset's surfaces
+    const sdvl_synth_view v = view_of(k);
+    sdvl_synth_scene sc = scene_surfaces;
+    sc.fx = v.fx; sc.fy = v.fy; sc.u0 = v.u0; sc.v0 = v.v0;
+    for (int q = 0; q < 9; q++) sc.R[q] = v.R[q];
+    for (int q = 0; q < 3; q++) sc.t[q] = v.t[q];
+    sc.seed = v.seed; sc.frame_id = v.frame_id; sc.texture = v.texture;
+    for (int q = 0; q < 5; q++) sc.dist[q] = v.dist[q];
+    return sc;
+  };
+  auto render_host = [&](int k, uint8_t *out) {
+    if (use_scene) { const sdvl_synth_scene sc = scene_of(k); sdvl_synth_render_scene_host(&sc, W, H, out, W, nullptr, nullptr); }
+    else { const sdvl_synth_view v = view_of(k); sdvl_synth_render_host(&v, W, H, out, W); }
+  };
 
   try {
     const size_t frame_bytes = static_cast<size_t>(W) * H;
@@ -175,9 +202,15 @@ int main(int argc, char **argv) {
       render_dev->Check(sdvl_device_malloc(rc, static_cast<int64_t>(frame_bytes * chunk), &dbuf), "sdvl_device_malloc");
       for (int k0 = 0; k0 < n_frames; k0 += chunk) {
         const int n = std::min(chunk, n_frames - k0);
-        std::vector<sdvl_synth_view> views;
-        for (int k = k0; k < k0 + n; k++) views.push_back(view_of(k));
-        render_dev->Check(sdvl_synth_render(rc, n, views.data(), W, H, dbuf, static_cast<int64_t>(frame_bytes)), "sdvl_synth_render");
+        if (use_scene) {
+          std::vector<sdvl_synth_scene> scenes;
+          for (int k = k0; k < k0 + n; k++) scenes.push_back(scene_of(k));
+          render_dev->Check(sdvl_synth_render_scene(rc, n, scenes.data(), W, H, dbuf, static_cast<int64_t>(frame_bytes), nullptr, nullptr), "sdvl_synth_render_scene");
+        } else {
+          std::vector<sdvl_synth_view> views;
+          for (int k = k0; k < k0 + n; k++) views.push_back(view_of(k));
+          render_dev->Check(sdvl_synth_render(rc, n, views.data(), W, H, dbuf, static_cast<int64_t>(frame_bytes)), "sdvl_synth_render");
+        }
         render_dev->Check(sdvl_device_download(rc, dbuf, static_cast<int64_t>(frame_bytes * n), pool + frame_bytes * k0), "sdvl_device_download");
       }
       render_dev->Check(sdvl_device_free(rc, dbuf), "sdvl_device_free");
@@ -215,8 +248,7 @@ int main(int argc, char **argv) {
           if (pool) {
             data = pool + frame_bytes * k;
           } else if (n_synth > 0) {
-            const sdvl_synth_view v = view_of(k);
-            sdvl_synth_render_host(&v, W, H, px.data(), W);
+            render_host(k, px.data());
           } else {
             int w = 0, h = 0;
             if (!ReadPNM(files[k], &w, &h, &px, &format) || w != W || h != H) {
@@ -302,7 +334,7 @@ int main(int argc, char **argv) {
           for (int k = 0; k < n_frames; k++) {
             uint8_t *data = px.data();
             if (pool) data = pool + frame_bytes * k;
-            else if (n_synth > 0) { const sdvl_synth_view v = view_of(k); sdvl_synth_render_host(&v, W, H, px.data(), W); }
+            else if (n_synth > 0) render_host(k, px.data());
             int format = PIX_GRAY8;
             if (!pool && n_synth == 0) { int w = 0, h = 0; if (!ReadPNM(files[k], &w, &h, &px, &format) || w != W || h != H) { me.err = "cannot read " + files[k]; return; } data = px.data(); }
             Image img = Image::Wrap(data, W, H, format == PIX_RGB8 ? 3 * W : W, format);

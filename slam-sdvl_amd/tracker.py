@@ -249,6 +249,19 @@ class TrackerBatch:
             raise RuntimeError("tracker %d has no mapper" % i)
         return dict(zip(("candidates", "converged", "initialized", "linked", "connected", "keyframes"), list(out)))
 
+    def map_points(self, i):
+        """mapper mode only: the live points tracker i's mapper created, rows of x y z fixed (float64) — keyframes oldest first, each
+        keyframe's features in order, each point once; deleted points and the bootstrap keyframe's own points are left out"""
+        self.lib.sdvlh_batch_map_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        n = self.lib.sdvlh_batch_map_points(self.h, int(i), 0, None)
+        if n == -1:
+            raise RuntimeError("tracker %d has no mapper" % i)
+        if n < 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        out = np.zeros((max(n, 1), 4), np.float64)
+        n = self.lib.sdvlh_batch_map_points(self.h, int(i), n, out.ctypes.data)
+        return out[:n].copy()
+
     def stage_times(self, reset=False):
         """accumulated wall seconds per host stage of SDVLBatch::HandleFrames -> (dict, steps)"""
         out = (C.c_double * len(self.STAGES))()
