@@ -161,11 +161,16 @@ struct PoseJobDev {
   double pose[7];
   double pad_;
 };
-// queues pose_hypotheses + pose_refine for n_jobs device-resident jobs (no copies, no wait); d_hyp = n_jobs * max_ransac_its
-// records of sdvl_pose_hyp_bytes() each
+// queues the pose stage for n_jobs device-resident jobs (no copies, no wait).  `chain` (sdvl_search_types.h; null: d_jobs and d_obs
+// come ready-made) names the candidates and search results the matches are selected from first.  Sets of more than 4 trackers take one
+// launch, pose_refine (selection, RANSAC draws, replay, refinement), and need neither d_jobs (when `chain` is given) nor d_hyp; sets of
+// <= 4 take select_matches + pose_hypotheses (a wave per draw) + pose_refine and need both: sdvl_pose_separate_launches(batch_size).
+// d_hyp = n_jobs * max_ransac_its records of sdvl_pose_hyp_bytes() each
 size_t sdvl_pose_hyp_bytes();
-// max_obs: the most observations any of the jobs can hold (the device knows the actual counts; the supporter kernel's grid covers this many)
-int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseJobDev *d_jobs, const sdvl_pose_obs *d_obs, const int32_t *d_rand,
+bool sdvl_pose_separate_launches(int batch_size);
+struct PoseChainIn;
+// max_obs: the most observations any of the jobs can hold (the device knows the actual counts)
+int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseChainIn *chain, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs, const int32_t *d_rand,
                              const int32_t *d_nits, const sdvl_pose_params *p, void *d_hyp, sdvl_pose_result *d_res, int32_t *d_lists, int max_obs,
                              int batch_size);  // batch_size: see sdvl_image_align_track_enqueue
 

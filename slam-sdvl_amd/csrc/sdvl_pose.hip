@@ -2,12 +2,13 @@
 // FeatureAlign::OptimizePose / RescueOutliers (feature_align.cc:73-82,218-243) around ConvergePose (:341-421) and
 // CheckReprojectionError (:258-283), for a batch of frames.  SURVEY §8(f) "next" row 1.
 //
-//   pose_hypotheses_kernel : one workgroup per (frame, 128 RANSAC draws).  The reference evaluates draws one after the other
-//       and adapts the iteration budget as it goes; a draw's result does not depend on earlier draws, so all
-//       max_ransac_its draws are evaluated at once and the sequential bookkeeping is replayed afterwards.  Phase 1: one LANE
-//       per draw converges the 5-point pose in registers; phase 2: the (draw, match) pairs of the supporter counts are
-//       dealt to all 512 lanes (integer sums: order-free).
-//   pose_refine_kernel     : one WAVE per frame.  Replays the RANSAC loop over the draw results (iteration budget from a
+//   the draws : the reference evaluates draws one after the other and adapts the iteration budget as it goes; a draw's result does
+//       not depend on earlier draws, so draws are converged side by side and the sequential bookkeeping is replayed over them.
+//       Sets of more than 4 trackers: one LANE per draw converges the 5-point pose in registers, inside pose_refine_kernel, a batch of
+//       draws when the replay needs one; sets of <= 4: pose_hypotheses_wave_kernel, one WAVE per draw, ahead of pose_refine_kernel.
+//   pose_refine_kernel     : one workgroup per frame, the whole stage in wave 0 (sets of more than 4 trackers: ONE launch).  Selects
+//       the matches among the search's candidates (second half of SelectPoints) when the caller is a chain, makes the draws and
+//       replays the RANSAC loop over the draw results (iteration budget from a
 //       host-computed table, so no device log()), then inliers / Tukey-weighted Gauss-Newton / rescue / second pass.
 //       Per-observation work (projection, Jacobian, weight, 28 normal-equation terms) is lane-parallel; lanes 0..27 each
 //       add one term IN OBSERVATION ORDER — the sums carry the rounding of the reference's sequential loop; inlier and
@@ -18,6 +19,7 @@
 #include <algorithm>
 
 #include "sdvl_math.h"
+#include "sdvl_search_types.h"
 #include "sdvl_wave.h"
 
 namespace {
@@ -147,44 +149,17 @@ __device__ bool converge_pose_small(const sdvl_pose_obs *obs, const int *idx, in
   return true;
 }
 
-// pose_hypotheses_kernel converges the draws, one LANE per draw (a dependent FP64 chain of ~105 us; at ~180 VGPRs per lane its
-// waves are few and narrow: 64-thread workgroups).  It converges the first kHypDraws draws; pose_refine converges the rest on demand
-// and counts every draw's supporters as its replay of the RANSAC loop reaches the draw.
-constexpr int kHypDraws = 64;     // draws of one workgroup = lanes of its wave
-// dynamic LDS of pose_hypotheses_kernel: s_hyp_cache[max_ransac_points][6][kHypDraws] doubles, <= 24 KB (max_ransac_points <= 8)
-size_t hyp_cache_bytes(int max_ransac_points) { return static_cast<size_t>(max_ransac_points) * 6 * kHypDraws * sizeof(double); }
-
-__global__ __launch_bounds__(kHypDraws) void pose_hypotheses_kernel(const PoseJobDev *__restrict__ jobs, const sdvl_pose_obs *__restrict__ obs_all,
-                                                                    const int32_t *__restrict__ rand_idx, sdvl_pose_params prm,
-                                                                    HypResult *__restrict__ hyp) {
-  const PoseJobDev &job = jobs[blockIdx.y];
-  const int h = blockIdx.x * kHypDraws + threadIdx.x;
-  if (h >= prm.max_ransac_its) return;
-  const int size = job.n_obs;
-  const sdvl_pose_obs *obs = obs_all + job.obs_begin;
-  // ConvergePose of this draw (feature_align.cc:176-197)
-  HypResult r;
-  r.ok = 0;
-  r.supporters = 0;
-  for (int k = 0; k < 7; k++) r.se3[k] = job.pose[k];
-  if (size > 0) {
-    const int npoints = min(prm.max_ransac_points, size);
-    int index = rand_idx[job.rand_begin + h];  // rand() % size, drawn on the host (feature_align.cc:180) ...
-    if (prm.pad_ & 1) index %= size;           // ... or the raw rand() value when the host could not know `size` yet
-    int sel[8];
-    for (int i = 0; i < npoints; i++) sel[i] = (index + i) % size;
-    Rigid se3;
-    extern __shared__ double s_hyp_cache[];  // hyp_cache_bytes()
-    if (converge_pose_small<true>(obs, sel, npoints, se3_from7(job.pose), prm.fx, prm.max_optim_pose_its, &se3, s_hyp_cache, threadIdx.x)) {
-      r.ok = 1;
-      se3_to7(se3, r.se3);
-    }
-  }
-  HypResult &dst = hyp[static_cast<size_t>(blockIdx.y) * prm.max_ransac_its + h];
-  for (int k = 0; k < 7; k++) dst.se3[k] = r.se3[k];
-  dst.ok = r.ok;
-  dst.supporters = 0;  // counted by pose_refine (lazy supporters)
-}
+// The lane form of the draws (sets of more than 4 trackers) runs inside pose_refine_kernel: a draw is a dependent FP64 chain of
+// ~105 us on one LANE, draws are converged kFirstDraws at a time (lanes beyond idle), a batch when the replay of the RANSAC loop first
+// needs one of its draws.  A draw's result depends on its index alone, so the width changes no result — only how long the wave waits
+// for the slowest draw of a batch, against how many batches a budget that is not met early takes.
+#ifndef SDVL_POSE_FIRST_DRAWS
+#define SDVL_POSE_FIRST_DRAWS 64
+#endif
+constexpr int kFirstDraws = SDVL_POSE_FIRST_DRAWS;
+static_assert(kFirstDraws == 16 || kFirstDraws == 32 || kFirstDraws == 64, "a batch of draws is a part of one wave");
+// the draws' observation cache: [max_ransac_points <= 8][6][64 lanes] doubles of LDS, laid over RefineLds (see pose_refine_kernel)
+constexpr size_t kDrawCacheBytes = 8 * 6 * 64 * sizeof(double);
 
 // Round 6: ONE WAVE per draw, for the sets whose launches leave the chip empty (a lone camera: sets of <= 4 trackers; configuration C's
 // groups of 16 — 1600 such waves per launch, four groups at a time — lose 10 % on it and keep the lane form).  The lane
@@ -584,69 +559,114 @@ __device__ bool converge_pose_wave(RefineLds<kRefWaves> &L, const sdvl_pose_obs 
   return true;
 }
 
+// the match selection of one tracker by ONE wave (statements: sdvl_search_types.h): candidates in rounds of 64, a match's rank = the
+// matches of the rounds before + those of the lanes below (ballot); the found flags of all rounds as 64-bit words in LDS.  Returns the
+// number of matches kept; their observations are in obs_all behind a workgroup-scope fence.
+__device__ int select_matches_wave(const PoseChainIn &in, const ChainFrameDev &fr, sdvl_pose_obs *obs_all, unsigned long long *found_words, int lane) {
+  const int n = fr.cand_end - fr.cand_begin;
+  const int32_t *cfirst = in.cand_first + fr.cand_begin;
+  for (int c0 = 0; c0 < n; c0 += 64) {
+    const int k = c0 + lane;
+    const unsigned long long m = __ballot(k < n && select_found(in, fr, k));
+    if (lane == 0) found_words[c0 >> 6] = m;
+  }
+  wave_sync();
+  int running = 0;
+  for (int c0 = 0; c0 < n && running < fr.max_matches; c0 += 64) {  // (matches beyond max_matches are not kept: no need to rank them)
+    const int k = c0 + lane;
+    const bool sel = k < n && ((found_words[k >> 6] >> (k & 63)) & 1) && select_first_of_cell(found_words, cfirst[k] - fr.cand_begin, k);
+    const unsigned long long m = __ballot(sel);
+    const int rank = running + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0));
+    if (sel && rank < fr.max_matches) select_emit(in, fr, k, rank, obs_all);
+    running += __popcll(m);
+  }
+  // the observations were written by other lanes (and are read by the helper waves behind their barrier): stores complete, compiler told
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  return min(running, fr.max_matches);
+}
+
+// The pose stage of one tracker.  Wave 0, in order: (1) when `chain` names candidates, selects the matches (select_matches_wave); the job
+// — where its observations, rand values and budgets lie, the start pose — stays in registers; (2) converges the RANSAC draws, lane h =
+// draw h of a batch, and replays the RANSAC loop over them; (3) inliers / refinement / rescue.  The helper waves wait at the workgroup
+// barrier for wave 0's first command meanwhile.  hyp != nullptr (sets of <= 4 trackers): the draws were converged and their supporters
+// counted by pose_hypotheses_wave_kernel; the replay reads them.
+// LDS: the found-flag words of (1) and the observation cache of (2) are dead before (3) first writes RefineLds — they lie over it.
 template <int kRefWaves>
-__global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJobDev *__restrict__ jobs, const sdvl_pose_obs *__restrict__ obs_all,
+__global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJobDev *__restrict__ jobs, PoseChainIn chain, sdvl_pose_obs *obs_all,
                                                          const int32_t *__restrict__ nits_table, const HypResult *__restrict__ hyp,
                                                          sdvl_pose_params prm, sdvl_pose_result *__restrict__ results,
-                                                         int32_t *__restrict__ out_lists, int lazy_supporters, const int32_t *__restrict__ rand_idx,
-                                                         int hyp_ready) {
+                                                         int32_t *__restrict__ out_lists, const int32_t *__restrict__ rand_idx) {
   __shared__ RefineLds<kRefWaves> L;
-  const PoseJobDev &job = jobs[blockIdx.x];
+  static_assert(kDrawCacheBytes <= sizeof(RefineLds<kRefWaves>) && kChainMaxCand / 8 <= sizeof(RefineLds<kRefWaves>), "overlays fit");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int size = job.n_obs;
-  const sdvl_pose_obs *obs = obs_all + job.obs_begin;
-  if (wave > 0) {  // helper waves: ConvergePose's terms only (size == 0: wave 0 returns without a command)
-    if (size > 0) refine_helper_loop(L, obs, wave, lane);
+  const int obs_begin = chain.frames ? chain.frames[blockIdx.x].obs_begin : jobs[blockIdx.x].obs_begin;
+  const sdvl_pose_obs *obs = obs_all + obs_begin;
+  if (wave > 0) {  // helper waves: ConvergePose's terms only
+    refine_helper_loop(L, obs, wave, lane);
     return;
   }
+  int size, rand_begin, nits_begin;
+  double pose0[7];
+  if (chain.frames) {
+    const ChainFrameDev &fr = chain.frames[blockIdx.x];
+    size = select_matches_wave(chain, fr, obs_all, reinterpret_cast<unsigned long long *>(&L), lane);
+    rand_begin = fr.rand_begin;
+    nits_begin = size * (size + 1) / 2;  // row `size` of the all-sizes budget table
+    for (int k = 0; k < 7; k++) pose0[k] = fr.pose[k];
+    if (lane == 0) chain.n_obs[blockIdx.x] = size;
+  } else {
+    const PoseJobDev &job = jobs[blockIdx.x];
+    size = job.n_obs;
+    rand_begin = job.rand_begin;
+    nits_begin = job.nits_begin;
+    for (int k = 0; k < 7; k++) pose0[k] = job.pose[k];
+  }
   sdvl_pose_result res;
-  for (int k = 0; k < 7; k++) res.pose[k] = job.pose[k];
+  for (int k = 0; k < 7; k++) res.pose[k] = pose0[k];
   res.n_draws = 0;
   res.n_inliers = 0;
   res.n_outliers = 0;
   res.refined = 0;
   if (size == 0) {  // SelectInliers returns at once; OptimizePose finds no features (feature_align.cc:165-166,220-221)
-    if (lane == 0) results[blockIdx.x] = res;
+    if (lane == 0) {
+      results[blockIdx.x] = res;
+      L.ctl.cmd = 0;  // the helpers leave
+    }
+    __syncthreads();  // A
     return;
   }
   // ---- RANSAC bookkeeping replayed over the draw results (feature_align.cc:172-212).  The loop is inherently serial
-  // (the budget shrinks as supporters improve), so it must not touch memory: lane h holds the supporter count of draws h
-  // and h + 64 (-1 = ConvergePose failed), the loop reads them with readlane; uniform across the lanes.
-  const HypResult *hy = hyp + static_cast<size_t>(blockIdx.x) * prm.max_ransac_its;
-  const int32_t *nits_of = nits_table + job.nits_begin;  // iteration budget after an improvement to s supporters
+  // (the budget shrinks as supporters improve), so it must not touch memory: lane h holds the result of draw base + h (hyp: the supporter
+  // count, -1 = ConvergePose failed), the loop reads them with readlane; uniform across the lanes.
+  const int32_t *nits_of = nits_table + nits_begin;  // iteration budget after an improvement to s supporters
   int best_it = -1;
   int nits = prm.max_ransac_its, best_sup = 0, it = 0;
   double best7[7] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (lazy_supporters) {
+  if (!hyp) {
     // Round 6: the supporters of a draw are counted HERE, when the replay reaches the draw — the reference stops drawing once the budget is
-    // met (typically after 5-10 of the 100 draws when nine matches in ten are inliers), and so does this loop: rounds 3-5 tested every
-    // draw against every match in a launch of its own (24 k of a tracked frame's 694 k instructions) for counts nobody read.  Lane h holds draw
-    // base + h; the loop takes a draw's pose out of it with readlane and counts over the matches in rounds of 64 (an integer sum).
-    for (int base = 0; base < prm.max_ransac_its && it < nits; base += 64) {
+    // met (typically after 5-10 of the 100 draws when nine matches in ten are inliers), and so does this loop.  Lane h converges draw
+    // base + h, exactly as the reference's ConvergePose of that draw (feature_align.cc:176-197); the loop takes a draw's pose out of its
+    // lane with readlane and counts over the matches in rounds of 64 (an integer sum).
+    double *const cache = reinterpret_cast<double *>(&L);
+    for (int base = 0; base < prm.max_ransac_its && it < nits; base += kFirstDraws) {
       const int h = base + lane;
       int ok_h = 0;
       double p7[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      if (h < prm.max_ransac_its) {
-        if (h < hyp_ready) {
-          ok_h = hy[h].ok;
-#pragma unroll
-          for (int k = 0; k < 7; k++) p7[k] = hy[h].se3[k];
-        } else {
-          // a draw beyond those pose_hypotheses_kernel converged (it is launched for the first 64 only: a budget that 64 draws do not
-          // meet is the exception — fewer than ~6 matches in 10 are inliers): its lane converges it here, exactly as that kernel would
-          const int npoints = min(prm.max_ransac_points, size);
-          int index = rand_idx[job.rand_begin + h];
-          if (prm.pad_ & 1) index %= size;
-          int sel[8];
-          for (int i = 0; i < npoints; i++) sel[i] = (index + i) % size;
-          Rigid se3;
-          if (converge_pose_small<false>(obs, sel, npoints, se3_from7(job.pose), prm.fx, prm.max_optim_pose_its, &se3)) {
-            ok_h = 1;
-            se3_to7(se3, p7);
-          }
+      if (lane < kFirstDraws && h < prm.max_ransac_its) {
+        const int npoints = min(prm.max_ransac_points, size);
+        int index = rand_idx[rand_begin + h];  // rand() % size, drawn on the host (feature_align.cc:180) ...
+        if (prm.pad_ & 1) index %= size;       // ... or the raw rand() value when the host could not know `size` yet
+        int sel[8];
+        for (int i = 0; i < npoints; i++) sel[i] = (index + i) % size;
+        Rigid se3;
+        if (converge_pose_small<true>(obs, sel, npoints, se3_from7(pose0), prm.fx, prm.max_optim_pose_its, &se3, cache, lane)) {
+          ok_h = 1;
+          se3_to7(se3, p7);
         }
       }
-      const int end = min(base + 64, prm.max_ransac_its);
+      const int end = min(base + kFirstDraws, prm.max_ransac_its);
       while (it < nits && it < end) {
         const int src = it - base;
         int s_it = -1;
@@ -675,29 +695,34 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
           best_it = it;
           nits = nits_of[best_sup];
 #pragma unroll
-          for (int k = 0; k < 7; k++) best7[k] = u7[k];  // (a draw converged on demand exists in registers only)
+          for (int k = 0; k < 7; k++) best7[k] = u7[k];  // (a draw converged here exists in registers only)
         }
         it++;
       }
     }
-  } else
-  for (int base = 0; base < prm.max_ransac_its && it < nits; base += 64) {
-    const int h = base + lane;
-    int sup = -1;
-    if (h < prm.max_ransac_its && hy[h].ok) sup = hy[h].supporters;
-    const int end = min(base + 64, prm.max_ransac_its);
-    while (it < nits && it < end) {
-      const int s_it = __builtin_amdgcn_readlane(sup, it - base);
-      if (s_it > best_sup) {
-        best_sup = s_it;
-        best_it = it;
-        nits = nits_of[best_sup];
+    wave_sync();  // the cache is dead: RefineLds is written from here on
+  } else {
+    const HypResult *hy = hyp + static_cast<size_t>(blockIdx.x) * prm.max_ransac_its;
+    for (int base = 0; base < prm.max_ransac_its && it < nits; base += 64) {
+      const int h = base + lane;
+      int sup = -1;
+      if (h < prm.max_ransac_its && hy[h].ok) sup = hy[h].supporters;
+      const int end = min(base + 64, prm.max_ransac_its);
+      while (it < nits && it < end) {
+        const int s_it = __builtin_amdgcn_readlane(sup, it - base);
+        if (s_it > best_sup) {
+          best_sup = s_it;
+          best_it = it;
+          nits = nits_of[best_sup];
+        }
+        it++;
       }
-      it++;
     }
+    if (best_it >= 0)
+      for (int k = 0; k < 7; k++) best7[k] = hy[best_it].se3[k];
   }
   Rigid best = se3_identity();  // SE3 best_se3 default-constructed
-  if (best_it >= 0) best = lazy_supporters ? se3_from7(best7) : se3_from7(hy[best_it].se3);
+  if (best_it >= 0) best = se3_from7(best7);
   res.n_draws = it;
   // ---- final CheckReprojectionError with the best hypothesis -> inliers / outliers (feature_align.cc:215)
   for (int q = lane; q < size; q += 64) L.tmp[q] = static_cast<uint16_t>(q);
@@ -706,7 +731,7 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
   check_list(obs, L.tmp, size, best, prm.inlier_threshold, L.inl, &n_in, L.outl, &n_out, lane);
   wave_sync();
   // ---- OptimizePose(frame): feature_align.cc:73-82
-  Rigid pose = se3_from7(job.pose);
+  Rigid pose = se3_from7(pose0);
   for (int pass = 0; pass < 2; pass++) {
     // OptimizePose(frame, &inliers, &outliers), :218-230
     Rigid se3;
@@ -734,7 +759,7 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
   se3_to7(pose, res.pose);
   res.n_inliers = n_in;
   res.n_outliers = n_out;
-  int32_t *lists = out_lists + job.obs_begin;
+  int32_t *lists = out_lists + obs_begin;
   for (int q = lane; q < n_in; q += 64) lists[q] = L.inl[q];
   for (int q = lane; q < n_out; q += 64) lists[n_in + q] = L.outl[q];
   if (lane == 0) {
@@ -748,35 +773,39 @@ __global__ __launch_bounds__(64 * kRefWaves) void pose_refine_kernel(const PoseJ
 
 size_t sdvl_pose_hyp_bytes() { return sizeof(HypResult); }
 
-int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseJobDev *d_jobs, const sdvl_pose_obs *d_obs, const int32_t *d_rand,
+bool sdvl_pose_separate_launches(int batch_size) { return batch_size <= 4; }
+
+int sdvl_pose_enqueue_device(sdvl_ctx *ctx, int n_jobs, const PoseChainIn *chain, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs, const int32_t *d_rand,
                              const int32_t *d_nits, const sdvl_pose_params *p, void *d_hyp, sdvl_pose_result *d_res, int32_t *d_lists, int max_obs,
                              int batch_size) {
   if (max_obs < 1) max_obs = 1;
   if (max_obs > kMaxObs) max_obs = kMaxObs;
-  int hyp_ready = p->max_ransac_its;
+  PoseChainIn in = {};
+  if (chain) in = *chain;
+  const HypResult *hyp = nullptr;
   // one wave per draw pays while every wave finds a SIMD of its own: a lone camera (100 waves), not configuration C's groups of 16
   // (1600 waves per launch, four groups at a time: 46.3 k tracked frames/s with the lane form against 41.3 k, two alternating pairs)
-  const bool wave_form = batch_size <= 4;
-  if (wave_form) {
-    // a small set: one wave per draw, the supporters counted by the same wave (see pose_hypotheses_wave_kernel)
+  if (sdvl_pose_separate_launches(batch_size)) {
+    // a small set: the matches selected by a launch of their own, one wave per draw, the supporters counted by the same wave (see
+    // pose_hypotheses_wave_kernel); pose_refine replays over the records
+    SDVL_REQUIRE(ctx, d_jobs && d_hyp, "the separate launches of the pose stage need job and hypothesis records");
+    if (chain) {
+      const int rc = sdvl_select_matches_launch(ctx, n_jobs, in, d_jobs, d_obs);
+      if (rc) return rc;
+      in = PoseChainIn{};
+    }
     SDVL_LAUNCH(ctx, "pose_hypotheses", pose_hypotheses_wave_kernel, dim3(p->max_ransac_its, n_jobs), dim3(64), d_jobs, d_obs, d_rand, *p,
                 static_cast<HypResult *>(d_hyp));
-  } else {
-    hyp_ready = std::min(p->max_ransac_its, kHypDraws);  // the first wave of draws; the rest on demand (pose_refine)
-    SDVL_LAUNCH_LDS(ctx, "pose_hypotheses", pose_hypotheses_kernel, dim3((hyp_ready + kHypDraws - 1) / kHypDraws, n_jobs), dim3(kHypDraws),
-                    hyp_cache_bytes(p->max_ransac_points), d_jobs, d_obs, d_rand, *p, static_cast<HypResult *>(d_hyp));
-    // the supporters: counted by pose_refine as its replay of the RANSAC loop reaches a draw
+    hyp = static_cast<const HypResult *>(d_hyp);
   }
-  const int lazy = !wave_form ? 1 : 0;
-  // a frame of the metric configuration has <= 200 observations: one wave (three waves with 59 KB of LDS wait longer for a CU among the
+  // otherwise ONE launch: wave 0 of pose_refine selects the matches, converges the draws it needs and replays the RANSAC loop over them.
+  // A frame of the metric configuration has <= 200 observations: one wave (three waves with 59 KB of LDS wait longer for a CU among the
   // other streams' kernels than they save: 2.4 -> 3.9 ms of dispatch time per step); configuration C's ~850: wave 0 + two helpers
   // Round 5: a small batch (a lone camera) takes the helper waves too — nobody else wants the CU
   if (max_obs > 256 || batch_size <= 32)
-    SDVL_LAUNCH(ctx, "pose_refine", pose_refine_kernel<3>, dim3(n_jobs), dim3(192), d_jobs, d_obs, d_nits, static_cast<const HypResult *>(d_hyp), *p, d_res,
-                d_lists, lazy, d_rand, hyp_ready);
+    SDVL_LAUNCH(ctx, "pose_refine", pose_refine_kernel<3>, dim3(n_jobs), dim3(192), d_jobs, in, d_obs, d_nits, hyp, *p, d_res, d_lists, d_rand);
   else
-  SDVL_LAUNCH(ctx, "pose_refine", pose_refine_kernel<1>, dim3(n_jobs), dim3(64), d_jobs, d_obs, d_nits, static_cast<const HypResult *>(d_hyp), *p, d_res,
-              d_lists, lazy, d_rand, hyp_ready);
+    SDVL_LAUNCH(ctx, "pose_refine", pose_refine_kernel<1>, dim3(n_jobs), dim3(64), d_jobs, in, d_obs, d_nits, hyp, *p, d_res, d_lists, d_rand);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
 }
@@ -809,7 +838,8 @@ extern "C" int sdvl_pose_from_matches(sdvl_ctx *ctx, int n_jobs, const sdvl_pose
   const sdvl_part<sdvl_pose_result> o_res = o.take<sdvl_pose_result>(n_jobs);
   const sdvl_part<int32_t> o_lists = o.take<int32_t>(n_obs);
   void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, sizeof(HypResult) * static_cast<size_t>(n_jobs) * p->max_ransac_its, false);
+  const bool separate = sdvl_pose_separate_launches(n_jobs);  // only then are hypothesis records written
+  rc = separate ? sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, sizeof(HypResult) * static_cast<size_t>(n_jobs) * p->max_ransac_its, false) : SDVL_OK;
   if (!rc) rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
   if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
   if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
@@ -831,7 +861,7 @@ extern "C" int sdvl_pose_from_matches(sdvl_ctx *ctx, int n_jobs, const sdvl_pose
   prm.pad_ = 0;  // rand_idx holds indices already reduced modulo the match count
   int max_obs = 0;
   for (int j = 0; j < n_jobs; j++) max_obs = std::max(max_obs, jobs[j].obs_end - jobs[j].obs_begin);
-  rc = sdvl_pose_enqueue_device(ctx, n_jobs, st_jobs.cin(dsx), st_obs.cin(dsx), st_rand.cin(dsx), st_nits.cin(dsx), &prm, static_cast<HypResult *>(ctx->d_work),
+  rc = sdvl_pose_enqueue_device(ctx, n_jobs, nullptr, st_jobs.in(dsx), st_obs.in(dsx), st_rand.cin(dsx), st_nits.cin(dsx), &prm, separate ? ctx->d_work : nullptr,
                                 o_res.in(ctx->d_out), o_lists.in(ctx->d_out), max_obs, n_jobs);
   if (rc) return rc;
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));

@@ -707,39 +707,26 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void align_patches_kernel(cons
   }
 }
 
-// ---- second half of FeatureAlign::SelectPoints (feature_align.cc:105-149) on the device, for sdvl_search_run_chain:
-// candidates come cell by cell in the reference's order; a cell's first found candidate is a match; the first
-// max_matches matches are kept.  One workgroup per tracker; the matches leave as pose observations (feature_align.cc:132
-// creates the Feature — bearing = Camera::Unproject(px) — SelectInliers reads bearing/z, the point and 1/2^level).
-constexpr int kChainMaxCand = 16384;  // candidates of one tracker the kernel can flag in LDS
-
-__global__ __launch_bounds__(256) void select_matches_kernel(const ChainFrameDev *__restrict__ frames, const int32_t *__restrict__ cand_req,
-                                                             const int32_t *__restrict__ cand_first, const sdvl_search_res *__restrict__ res,
-                                                             const double *__restrict__ req_point, Cam cam, PoseJobDev *__restrict__ jobs,
-                                                             sdvl_pose_obs *__restrict__ obs, int32_t *__restrict__ n_obs_out,
-                                                             int32_t *__restrict__ match_cand) {
-  __shared__ uint8_t s_found[kChainMaxCand];
+// ---- second half of FeatureAlign::SelectPoints on the device (statements: sdvl_search_types.h) as a launch of its own, for the sets
+// of <= 4 trackers, whose pose stage stays on separate launches (sdvl_pose_enqueue_device).  One workgroup per tracker; the matches
+// leave as pose observations and a PoseJobDev.
+__global__ __launch_bounds__(256) void select_matches_kernel(PoseChainIn in, PoseJobDev *__restrict__ jobs, sdvl_pose_obs *__restrict__ obs) {
+  __shared__ unsigned long long s_found[kChainMaxCand / 64];
   __shared__ int s_wave[4];
-  const ChainFrameDev &fr = frames[blockIdx.x];
+  const ChainFrameDev &fr = in.frames[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = fr.cand_end - fr.cand_begin;
-  const int32_t *cfirst = cand_first + fr.cand_begin;
-  // cand_req == nullptr: candidate k was searched with request cand_begin + k (batches built on the device)
-  const auto req_of = [&](int k) { return cand_req ? cand_req[fr.cand_begin + k] : fr.cand_begin + k; };
-  for (int k = tid; k < n; k += 256) {
-    const int r = req_of(k);
-    s_found[k] = (r >= 0 && res[r].found != 0) ? 1 : 0;
+  const int32_t *cfirst = in.cand_first + fr.cand_begin;
+  for (int c0 = 0; c0 < n; c0 += 256) {
+    const int k = c0 + tid;
+    const unsigned long long m = __ballot(k < n && select_found(in, fr, k));
+    if (lane == 0 && c0 + 64 * wave < n) s_found[(c0 >> 6) + wave] = m;
   }
   __syncthreads();
   int running = 0;
   for (int c0 = 0; c0 < n; c0 += 256) {
     const int k = c0 + tid;
-    bool sel = false;
-    if (k < n && s_found[k]) {
-      sel = true;
-      for (int j = cfirst[k] - fr.cand_begin; j < k; j++)
-        if (s_found[j]) { sel = false; break; }
-    }
+    const bool sel = k < n && ((s_found[k >> 6] >> (k & 63)) & 1) && select_first_of_cell(s_found, cfirst[k] - fr.cand_begin, k);
     const unsigned long long m = __ballot(sel);
     const int below = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0));
     __syncthreads();  // s_wave of the previous round has been read
@@ -748,20 +735,7 @@ __global__ __launch_bounds__(256) void select_matches_kernel(const ChainFrameDev
     int base = running;
     for (int w = 0; w < wave; w++) base += s_wave[w];
     const int rank = base + below;
-    if (sel && rank < fr.max_matches) {
-      const sdvl_search_res &r = res[req_of(k)];
-      if (match_cand) match_cand[fr.obs_begin + rank] = k;
-      const V3 v = cam_unproject(cam, {r.px[0], r.px[1]});
-      sdvl_pose_obs o;
-      o.ax = v.x / v.z;
-      o.ay = v.y / v.z;
-      const double *P = req_point + 3 * static_cast<size_t>(req_of(k));
-      o.px = P[0];
-      o.py = P[1];
-      o.pz = P[2];
-      o.inv_cov = 1.0 / (1 << r.level);
-      obs[fr.obs_begin + rank] = o;
-    }
+    if (sel && rank < fr.max_matches) select_emit(in, fr, k, rank, obs);
     running += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
   }
   if (tid == 0) {
@@ -774,7 +748,7 @@ __global__ __launch_bounds__(256) void select_matches_kernel(const ChainFrameDev
     for (int q = 0; q < 7; q++) j.pose[q] = fr.pose[q];
     j.pad_ = 0.0;
     jobs[blockIdx.x] = j;
-    n_obs_out[blockIdx.x] = size;
+    in.n_obs[blockIdx.x] = size;
   }
 }
 
@@ -974,12 +948,9 @@ int sdvl_search_launch_device(sdvl_ctx *ctx, int n_slots, const SearchReqDev *d_
   return SDVL_OK;
 }
 
-int sdvl_select_matches_launch(sdvl_ctx *ctx, int n_frames, const ChainFrameDev *d_frames, const int32_t *d_cand_req,
-                               const int32_t *d_cand_first, const sdvl_search_res *d_res, const double *d_req_point,
-                               const sdvl_camera *cam, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs, int32_t *d_nobs, int32_t *d_match_cand) {
+int sdvl_select_matches_launch(sdvl_ctx *ctx, int n_frames, const PoseChainIn &in, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs) {
   if (n_frames <= 0) return SDVL_OK;
-  SDVL_LAUNCH(ctx, "select_matches", select_matches_kernel, dim3(n_frames), dim3(256), d_frames, d_cand_req, d_cand_first, d_res, d_req_point,
-              cam_of(*cam), d_jobs, d_obs, d_nobs, d_match_cand);
+  SDVL_LAUNCH(ctx, "select_matches", select_matches_kernel, dim3(n_frames), dim3(256), in, d_jobs, d_obs);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   return SDVL_OK;
 }
@@ -1200,10 +1171,12 @@ int sdvl_search_run_chain(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
   rc = sdvl_ensure_nits_table(ctx, pp->max_ransac_points, pp->max_ransac_its, max_size);
   if (rc) return rc;
   // behind the search's parts — device: jobs | obs | hypotheses | results | n_obs | lists ; host: results | n_obs | lists
+  // (jobs and hypotheses are records between the separate launches of a set of <= 4 trackers: empty parts otherwise)
+  const bool separate = sdvl_pose_separate_launches(n_frames);
   SearchOut so(n);
-  const sdvl_part<PoseJobDev> jobs = so.d.take<PoseJobDev>(n_frames);
+  const sdvl_part<PoseJobDev> jobs = so.d.take<PoseJobDev>(separate ? n_frames : 0);
   const sdvl_part<sdvl_pose_obs> obs = so.d.take<sdvl_pose_obs>(obs_total);
-  const sdvl_part<uint8_t> hyp = so.d.take<uint8_t>(sdvl_pose_hyp_bytes() * static_cast<size_t>(n_frames) * pp->max_ransac_its);
+  const sdvl_part<uint8_t> hyp = so.d.take<uint8_t>(separate ? sdvl_pose_hyp_bytes() * static_cast<size_t>(n_frames) * pp->max_ransac_its : 0);
   const auto take_back = [&](sdvl_layout &L) { return sdvl_ctx::ChainBack{L.take<sdvl_pose_result>(n_frames), L.take<int32_t>(n_frames), L.take<int32_t>(obs_total)}; };
   const sdvl_ctx::ChainBack back = take_back(so.d), h_back = take_back(so.h);
   rc = search_enqueue(ctx, n, cam, p, so);
@@ -1239,13 +1212,12 @@ int sdvl_search_run_chain(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
   if (n_rand) memcpy(st_rand.in(hs), rand_raw, st_rand.bytes());
   SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
   void *const dx = ctx->d_out;
-  rc = sdvl_select_matches_launch(ctx, n_frames, st_frames.cin(dsx), st_cand_req.cin(dsx), st_cand_first.cin(dsx), so.res.cin(dx), st_req_point.cin(dsx),
-                                  cam, jobs.in(dx), obs.in(dx), back.n_obs.in(dx), nullptr);
-  if (rc) return rc;
+  const PoseChainIn chain = {st_frames.cin(dsx), st_cand_req.cin(dsx), st_cand_first.cin(dsx), so.res.cin(dx), st_req_point.cin(dsx), cam_of(*cam),
+                             back.n_obs.in(dx), nullptr};
   sdvl_pose_params prm = *pp;
-  prm.pad_ = 1;  // raw rand() values: the kernel reduces them modulo the match count it finds in the job
-  rc = sdvl_pose_enqueue_device(ctx, n_frames, jobs.in(dx), obs.in(dx), st_rand.cin(dsx), static_cast<const int32_t *>(ctx->d_nits), &prm, hyp.in(dx),
-                                back.res.in(dx), back.lists.in(dx), max_size, n_frames);
+  prm.pad_ = 1;  // raw rand() values: the kernel reduces them modulo the match count it finds
+  rc = sdvl_pose_enqueue_device(ctx, n_frames, &chain, separate ? jobs.in(dx) : nullptr, obs.in(dx), st_rand.cin(dsx), static_cast<const int32_t *>(ctx->d_nits),
+                                &prm, separate ? hyp.in(dx) : nullptr, back.res.in(dx), back.lists.in(dx), max_size, n_frames);
   if (rc) return rc;
   // results | n_obs | lists are the tail of both layouts, part for part the same sizes: one copy
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(h_back.res.in(ctx->h_out), back.res.in(dx), so.h.bytes() - h_back.res.off, hipMemcpyDeviceToHost, ctx->stream));

@@ -97,6 +97,62 @@ struct ChainFrameDev {
   double pad2_;
 };
 
+// ---- second half of FeatureAlign::SelectPoints (feature_align.cc:105-149): candidates come cell by cell in the reference's order; a
+// cell's first found candidate is a match; the first max_matches matches are kept.  Two kernels run it — select_matches_kernel
+// (sdvl_search.hip: sets of <= 4 trackers) and wave 0 of pose_refine_kernel (sdvl_pose.hip) — with the statements below.
+constexpr int kChainMaxCand = 16384;  // candidates of one tracker whose found flags fit the kernels' LDS words (bit k & 63 of word k >> 6)
+
+// what the selection reads and writes besides the observations; frames == nullptr: no selection, the pose jobs come ready-made
+struct PoseChainIn {
+  const ChainFrameDev *frames;
+  const int32_t *cand_req;    // null: candidate k of a tracker was searched with request cand_begin + k (batches built on the device)
+  const int32_t *cand_first;  // first candidate of candidate k's cell
+  const sdvl_search_res *res;
+  const double *req_point;
+  sdvl::Cam cam;
+  int32_t *n_obs;             // matches kept, per tracker
+  int32_t *match_cand;        // may be null: per kept match its candidate index relative to cand_begin, at obs_begin + rank
+};
+
+__device__ __forceinline__ int select_request(const PoseChainIn &in, const ChainFrameDev &fr, int k) {
+  return in.cand_req ? in.cand_req[fr.cand_begin + k] : fr.cand_begin + k;
+}
+
+__device__ __forceinline__ bool select_found(const PoseChainIn &in, const ChainFrameDev &fr, int k) {
+  const int r = select_request(in, fr, k);
+  return r >= 0 && in.res[r].found != 0;
+}
+
+// candidate k (found) is a match when no candidate first..k-1 of its cell has been found
+__device__ __forceinline__ bool select_first_of_cell(const unsigned long long *found_words, int first, int k) {
+  if (first < 0) first = 0;
+  for (int w = first >> 6; w <= (k >> 6); w++) {
+    unsigned long long m = found_words[w];
+    if (w == (first >> 6)) m &= ~0ull << (first & 63);
+    if (w == (k >> 6)) m &= ~(~0ull << (k & 63));
+    if (m) return false;
+  }
+  return true;
+}
+
+// the match of candidate k leaves as pose observation `rank` of its tracker (feature_align.cc:132 creates the Feature — bearing =
+// Camera::Unproject(px) — SelectInliers reads bearing/z, the point and 1/2^level)
+__device__ __forceinline__ void select_emit(const PoseChainIn &in, const ChainFrameDev &fr, int k, int rank, sdvl_pose_obs *obs) {
+  const int req = select_request(in, fr, k);
+  const sdvl_search_res &r = in.res[req];
+  if (in.match_cand) in.match_cand[fr.obs_begin + rank] = k;
+  const sdvl::V3 v = sdvl::cam_unproject(in.cam, {r.px[0], r.px[1]});
+  sdvl_pose_obs o;
+  o.ax = v.x / v.z;
+  o.ay = v.y / v.z;
+  const double *P = in.req_point + 3 * static_cast<size_t>(req);
+  o.px = P[0];
+  o.py = P[1];
+  o.pz = P[2];
+  o.inv_cov = 1.0 / (1 << r.level);
+  obs[fr.obs_begin + rank] = o;
+}
+
 // ---- rows of the device-resident tracking tables (sdvl_track.hip); the depth filter (sdvl_search.hip) patches them in place
 constexpr int kDeleted = 0x100;                 // sdvl_track_point_stat::status bit
 constexpr int kTrash = 0x200;                   // deleted by the mapper: becomes kDeleted at the end of the next step's commit
@@ -151,12 +207,9 @@ extern "C" TrackPoint *sdvl_track_points_device(sdvl_track_set *set, int *max_po
 int sdvl_search_launch_device(sdvl_ctx *ctx, int n_slots, const SearchReqDev *d_reqs, const SearchFramePose *d_table,
                               const SearchBlock *d_blocks, int n_blocks, const sdvl_camera *cam, const sdvl_search_params *p,
                               SearchPrep *d_prep, sdvl_search_res *d_res, sdvl_search_res *h_res, bool prepared = false, bool binned = true);
-// second half of SelectPoints for n_frames trackers (feature_align.cc:105-149): d_cand_req may be null (candidate k of a
-// tracker = request cand_begin + k); d_match_cand (may be null) receives, per selected match, its candidate index
-// relative to cand_begin, at obs_begin + rank
-int sdvl_select_matches_launch(sdvl_ctx *ctx, int n_frames, const ChainFrameDev *d_frames, const int32_t *d_cand_req,
-                               const int32_t *d_cand_first, const sdvl_search_res *d_res, const double *d_req_point,
-                               const sdvl_camera *cam, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs, int32_t *d_nobs, int32_t *d_match_cand);
+// second half of SelectPoints for n_frames trackers as a launch of its own (sdvl_pose_enqueue_device queues it for sets of <= 4
+// trackers; larger sets select inside pose_refine): fills d_jobs and the observations
+int sdvl_select_matches_launch(sdvl_ctx *ctx, int n_frames, const PoseChainIn &in, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs);
 // sdvl_image_align.hip: the image alignment of a tracked step, features straight from the tracking tables (no records, no wait)
 int sdvl_image_align_track_enqueue(sdvl_ctx *ctx, int n_jobs, const TrackJobDev *d_jobs, const TrackPoint *d_points, const TrackFeat *d_feats0,
                                    const TrackFeat *d_feats1, int np, int nfeat_cap, int max_nf, int levels, const sdvl_camera *cam,

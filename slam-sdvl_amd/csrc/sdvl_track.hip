@@ -482,9 +482,11 @@ int sdvl_track_create(sdvl_ctx *ctx, int n, int max_points, int max_features, in
   s->cfeat = L.take<int32_t>(NF);
   s->blocks = L.take<SearchBlock>(NF / kWavesPerBlock);
   s->chain = L.take<ChainFrameDev>(N);
-  s->pjobs = L.take<PoseJobDev>(N);
+  // job and hypothesis records lie between the separate launches of a set of <= 4 trackers; larger sets' pose stage is one launch
+  const bool separate = sdvl_pose_separate_launches(n);
+  s->pjobs = L.take<PoseJobDev>(separate ? N : 0);
   s->obs = L.take<sdvl_pose_obs>(N * s->mm);
-  s->hyp = L.take<uint8_t>(sdvl_pose_hyp_bytes() * N * s->max_its);
+  s->hyp = L.take<uint8_t>(separate ? sdvl_pose_hyp_bytes() * N * s->max_its : 0);
   s->pres = L.take<sdvl_pose_result>(N);
   s->lists = L.take<int32_t>(N * s->mm);
   s->nobs = L.take<int32_t>(N);
@@ -763,13 +765,12 @@ int sdvl_track_search(sdvl_ctx *ctx, sdvl_track_set *s) {
                                      &s->prm.search, s->prep.in(D), s->res.in(D), nullptr, /*prepared*/ true);
   if (rc) return rc;
   // match ranks are not needed separately: track_commit derives them again from the same flags
-  rc = sdvl_select_matches_launch(ctx, n_jobs, s->chain.in(D), nullptr, s->cfirst.in(D), s->res.in(D), s->reqpt.in(D), &s->cam, s->pjobs.in(D),
-                                  s->obs.in(D), s->nobs.in(D), nullptr);
-  if (rc) return rc;
+  const PoseChainIn chain = {s->chain.cin(D), nullptr, s->cfirst.cin(D), s->res.cin(D), s->reqpt.cin(D), c, s->nobs.in(D), nullptr};
+  const bool separate = sdvl_pose_separate_launches(s->n);
   sdvl_pose_params pp = s->prm.pose;
-  pp.pad_ = 1;  // raw rand() values: the kernel reduces them modulo the match count it finds in the job
-  rc = sdvl_pose_enqueue_device(ctx, n_jobs, s->pjobs.in(D), s->obs.in(D), s->rand.in(D), static_cast<const int32_t *>(ctx->d_nits), &pp, s->hyp.in(D),
-                                s->pres.in(D), s->lists.in(D), s->mm, s->n);
+  pp.pad_ = 1;  // raw rand() values: the kernel reduces them modulo the match count it finds
+  rc = sdvl_pose_enqueue_device(ctx, n_jobs, &chain, separate ? s->pjobs.in(D) : nullptr, s->obs.in(D), s->rand.in(D), static_cast<const int32_t *>(ctx->d_nits),
+                                &pp, separate ? s->hyp.in(D) : nullptr, s->pres.in(D), s->lists.in(D), s->mm, s->n);
   if (rc) return rc;
   SDVL_LAUNCH_LDS(ctx, "track_commit", track_commit_kernel, dim3(n_jobs), dim3(256), CommitLds(stride, s->mm).bytes, s->djobs.cin(D), s->d_points,
                   static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->d_feats[0], s->d_feats[1], s->np,

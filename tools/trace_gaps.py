@@ -9,7 +9,8 @@ from collections import defaultdict
 rows = []
 with open(sys.argv[1]) as fh:
     for r in csv.DictReader(fh):
-        name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0]
+        # "void (anonymous namespace)::pose_refine_kernel<1>(PoseJobDev const*, ...)" -> "pose_refine_kernel"
+        name = r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0].split("<")[0]
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name, r.get("Stream_Id", "0"), r.get("Queue_Id", "0")))
 rows.sort()
 skip = float(sys.argv[2]) if len(sys.argv) > 2 else 0.5
@@ -25,7 +26,8 @@ for r in rows:
 print("streams %d, hardware queues %d (streams per queue: %s)" % (len(by_stream), len(queues), sorted(len(v) for v in queues.values())))
 pairs = [("pyr_down_kernel", "pyr_down_kernel"), ("pyr_down_kernel", "image_align_lds_kernel"), ("fast_cells_wave_kernel", "select_cells_kernel"),
          ("select_cells_kernel", "select_pack_kernel"), ("search_prepare_kernel", "search_points_kernel"),
-         ("select_matches_kernel", "pose_hypotheses_kernel"), ("pose_hypotheses_kernel", "pose_refine_kernel"),
+         ("search_points_kernel", "pose_refine_kernel"), ("pose_refine_kernel", "track_commit_kernel"),   # sets of more than 4 trackers
+         ("select_matches_kernel", "pose_hypotheses_wave_kernel"), ("pose_hypotheses_wave_kernel", "pose_refine_kernel"),   # sets of <= 4
          ("shi_tomasi_kernel", "orb_describe_kernel"), ("orb_describe_kernel", "filter_gather_kernel"), ("shi_tomasi_kernel", "filter_gather_kernel")]
 gaps = defaultdict(list)
 for s, lst in by_stream.items():
