@@ -348,6 +348,116 @@ class BundleResult(C.Structure):
     _fields_ = [("stage", BundleStage * 2), ("status", C.c_int32), ("n_level1", C.c_int32), ("n_free", C.c_int32), ("pad_", C.c_int32)]
 
 
+class TrackPoint(C.Structure):
+    """sdvl_track_point: what the tracked step reads of one Point; ref is the handle of a registered Frame"""
+    _fields_ = [("position", C.c_double * 3), ("px", C.c_double * 2), ("bearing", C.c_double * 3), ("idepth", C.c_double),
+                ("idepth_std", C.c_double), ("ref", C.c_void_p), ("level", C.c_int32), ("fixed", C.c_int32), ("score", C.c_int32),
+                ("n_failed", C.c_int32), ("last_frame", C.c_int32), ("status", C.c_int32), ("desc", C.c_uint8 * 32)]
+
+
+class TrackFeature(C.Structure):
+    """sdvl_track_feature: one feature of last_frame; point = row of its point, -1 = none, | TRACK_DUPLICATE = seen earlier in the list"""
+    _fields_ = [("px", C.c_double * 2), ("bearing", C.c_double * 3), ("level", C.c_int32), ("point", C.c_int32)]
+
+
+TRACK_DUPLICATE = 0x40000000
+
+
+class TrackParams(C.Structure):
+    _fields_ = [("align", AlignParams), ("search", SearchParams), ("pose", PoseParams), ("cell_size", C.c_int32), ("patch_size", C.c_int32),
+                ("max_failed", C.c_int32), ("pad_", C.c_int32)]
+
+
+class TrackJob(C.Structure):
+    _fields_ = [("tracker", C.c_int32), ("feat_buf", C.c_int32), ("last", C.c_void_p), ("cur", C.c_void_p), ("T", C.c_double * 7),
+                ("last_pose", C.c_double * 7), ("frame_id", C.c_int32), ("max_matches", C.c_int32)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 7), ("align_error", C.c_double), ("scene_depth", C.c_double)] + [(n, C.c_int32) for n in (
+        "align_meas", "align_iters", "n_features", "n_requests", "matches", "attempts", "n_draws", "n_inliers", "n_outliers", "refined",
+        "n_points", "n_deleted", "lk_iters", "n_corners", "status")]
+
+
+class TrackFeatureOut(C.Structure):
+    _fields_ = [("px", C.c_double * 2), ("level", C.c_int32), ("point", C.c_int32)]
+
+
+class TrackPointStat(C.Structure):
+    _fields_ = [("score", C.c_int32), ("n_failed", C.c_int32), ("last_frame", C.c_int32), ("status", C.c_int32)]
+
+
+class TrackSet:
+    """sdvl_track_set: the device-resident tracking tables of n trackers and the tracked step on them (include/sdvl_hip.h)"""
+
+    def __init__(self, ctx, n_trackers, max_points, max_features, grid_cells, max_matches, max_ransac_its):
+        self.ctx = ctx
+        self.n, self.cells, self.max_ransac_its = int(n_trackers), int(grid_cells), int(max_ransac_its)
+        h = C.c_void_p()
+        ctx._check(ctx.lib.sdvl_track_create(ctx.h, self.n, int(max_points), int(max_features), self.cells, int(max_matches),
+                                             self.max_ransac_its, C.byref(h)))
+        self.h = h
+        self.n_points = {}      # tracker -> point rows its table holds (sdvl_track_stats returns that many)
+        ctx.lib.sdvl_track_features.restype = C.POINTER(TrackFeatureOut)
+        ctx.lib.sdvl_track_features.argtypes = [C.c_void_p, C.c_int]
+        ctx.lib.sdvl_track_stats.restype = C.POINTER(TrackPointStat)
+        ctx.lib.sdvl_track_stats.argtypes = [C.c_void_p, C.c_int]
+
+    def _rows(self, fn, trackers, feat_buf, points, features):
+        """points / features: per named tracker a list (or ctypes array) of TrackPoint / TrackFeature rows"""
+        n = len(trackers)
+        assert len(feat_buf) == len(points) == len(features) == n
+        tr, fb = np.asarray(trackers, np.int32), np.asarray(feat_buf, np.int32)
+        npt, nft = np.asarray([len(p) for p in points], np.int32), np.asarray([len(f) for f in features], np.int32)
+        pa = (TrackPoint * max(int(npt.sum()), 1))(*[r for p in points for r in p])
+        fa = (TrackFeature * max(int(nft.sum()), 1))(*[r for f in features for r in f])
+        # (the rows are staged before the call returns: nothing has to outlive it)
+        self.ctx._check(fn(self.ctx.h, self.h, n, _ptr(tr, i32p), _ptr(fb, i32p), _ptr(npt, i32p), pa, _ptr(nft, i32p), fa))
+        return tr.tolist(), npt.tolist()
+
+    def upload(self, trackers, feat_buf, points, features):
+        """sdvl_track_upload: the tables of the named trackers are replaced"""
+        for t, k in zip(*self._rows(self.ctx.lib.sdvl_track_upload, trackers, feat_buf, points, features)):
+            self.n_points[t] = k
+
+    def append(self, trackers, feat_buf, points, features):
+        """sdvl_track_append: the rows go behind the rows the tables hold"""
+        for t, k in zip(*self._rows(self.ctx.lib.sdvl_track_append, trackers, feat_buf, points, features)):
+            self.n_points[t] = self.n_points.get(t, 0) + k
+
+    def step(self, jobs, cell_rank, rand_raw, cam, params, between=None):
+        """sdvl_track_align, the `between` callable (corners of the new frames: detect or set them there), sdvl_track_search and
+        sdvl_track_collect.  jobs: TrackJob array; cell_rank [n_jobs][grid_cells]; rand_raw [n_jobs][max_ransac_its].
+        -> (TrackResult array, per job the new frame's features [matches] and the point statistics [n_points], as numpy copies)"""
+        n = len(jobs)
+        lib = self.ctx.lib
+        rank = np.ascontiguousarray(cell_rank, np.uint16).reshape(n, self.cells)
+        raw = np.ascontiguousarray(rand_raw, np.int32).reshape(n, self.max_ransac_its)
+        n_points = [self.n_points.get(jobs[j].tracker, 0) for j in range(n)]
+        self.ctx._check(lib.sdvl_track_align(self.ctx.h, self.h, n, jobs, _ptr(rank, C.POINTER(C.c_uint16)), _ptr(raw, i32p), C.byref(cam),
+                                             C.byref(params)))
+        if between is not None:
+            between()
+        self.ctx._check(lib.sdvl_track_search(self.ctx.h, self.h))
+        res = (TrackResult * n)()
+        self.ctx._check(lib.sdvl_track_collect(self.ctx.h, self.h, n, res))
+        feat_t = np.dtype([("px", "<f8", 2), ("level", "<i4"), ("point", "<i4")])
+        stat_t = np.dtype([("score", "<i4"), ("n_failed", "<i4"), ("last_frame", "<i4"), ("status", "<i4")])
+        feats, stats = [], []
+        for j in range(n):
+            fp, sp = lib.sdvl_track_features(self.h, j), lib.sdvl_track_stats(self.h, j)
+            feats.append(np.ctypeslib.as_array(C.cast(fp, u8p), (res[j].matches * C.sizeof(TrackFeatureOut),)).view(feat_t).copy()
+                         if res[j].matches else np.zeros(0, feat_t))
+            stats.append(np.ctypeslib.as_array(C.cast(sp, u8p), (n_points[j] * C.sizeof(TrackPointStat),)).view(stat_t).copy()
+                         if n_points[j] else np.zeros(0, stat_t))
+        return res, feats, stats
+
+    def close(self):
+        if self.h:
+            self.ctx._check(self.ctx.lib.sdvl_track_destroy(self.ctx.h, self.h))
+            self.h = None
+
+
 BUNDLE_MAX_FREE = 16
 BUNDLE_OK, BUNDLE_EMPTY, BUNDLE_NO_EDGES, BUNDLE_NONFINITE = 0, 1, 2, 3
 
@@ -707,6 +817,17 @@ class Context:
                             inliers=lists[b:b + res[k].n_inliers].copy(),
                             outliers=lists[b + res[k].n_inliers:b + res[k].n_inliers + res[k].n_outliers].copy()))
         return out
+
+    def track_set(self, n_trackers, max_points, max_features, grid_cells, max_matches, max_ransac_its):
+        """sdvl_track_create: device-resident tracking tables for n_trackers (TrackSet)"""
+        return TrackSet(self, n_trackers, max_points, max_features, grid_cells, max_matches, max_ransac_its)
+
+    def register(self, frames, poses):
+        """sdvl_frames_register: (frame, pose [7]) pairs become addressable by the points of tracking tables"""
+        n = len(frames)
+        arr = (C.c_void_p * max(n, 1))(*[f.h for f in frames])
+        p7 = np.ascontiguousarray(poses, np.float64).reshape(n, 7)
+        self._check(self.lib.sdvl_frames_register(self.h, n, arr, _ptr(p7, f64p)))
 
     def klt_track(self, jobs, win_size=30, max_level=4, max_its=30, eps=0.001, min_eig_threshold=1e-4):
         """cv::calcOpticalFlowPyrLK as HomographyInit::TrackSecondFrame calls it (homography_init.cc:195-198), all jobs in one launch.

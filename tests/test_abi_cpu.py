@@ -40,6 +40,45 @@ def test_struct_layouts_match_header(sdvl):
     assert C.sizeof(sdvl.AlignResult) == 56 + 16 + 4 + 32 + 4 + 8
 
 
+TRACK_STRUCTS = {"sdvl_track_point": "TrackPoint", "sdvl_track_feature": "TrackFeature", "sdvl_track_params": "TrackParams",
+                 "sdvl_track_job": "TrackJob", "sdvl_track_result": "TrackResult", "sdvl_track_feature_out": "TrackFeatureOut",
+                 "sdvl_track_point_stat": "TrackPointStat"}
+
+
+def test_track_struct_layouts_match_the_compiled_header(sdvl, tmp_path):
+    """the structures of the tracked step, field for field: a program that includes include/sdvl_hip.h prints sizeof and every
+    field's offsetof; the ctypes classes must say the same, under the same field names and in the same order"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "the host compiler that builds libsdvl_synth.so is missing"
+    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "sdvl_hip.h"', 'int main() {']
+    for c_name, py_name in TRACK_STRUCTS.items():
+        cls = getattr(sdvl, py_name)
+        src.append('  printf("%s %%zu", sizeof(%s));' % (c_name, c_name))
+        for field in cls._fields_:
+            src.append('  printf(" %s:%%zu", offsetof(%s, %s));' % (field[0], c_name, field[0]))
+        src.append('  printf("\\n");')
+    src += ['  return 0;', '}']
+    path = tmp_path / "track_abi.cc"
+    path.write_text("\n".join(src) + "\n")
+    exe = str(tmp_path / "track_abi")
+    subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Werror", "-Wno-invalid-offsetof", "-I", os.path.join(ROOT, "include"), str(path), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()
+    assert len(out) == len(TRACK_STRUCTS)
+    for line, (c_name, py_name) in zip(out, TRACK_STRUCTS.items()):
+        cls = getattr(sdvl, py_name)
+        words = line.split()
+        assert words[0] == c_name and int(words[1]) == C.sizeof(cls), line
+        want = ["%s:%d" % (f[0], getattr(cls, f[0]).offset) for f in cls._fields_]
+        assert words[2:] == want, (c_name, words[2:], want)
+        # no field of the header is missing from the class: its declared fields fill the structure up to its alignment padding
+        last = cls._fields_[-1]
+        assert getattr(cls, last[0]).offset + C.sizeof(last[1]) + 8 > C.sizeof(cls), c_name
+    assert C.sizeof(sdvl.TrackPoint) == 144 and C.sizeof(sdvl.TrackFeature) == 48       # csrc/sdvl_search_types.h asserts the same
+    assert sdvl.TRACK_DUPLICATE == 0x40000000
+
+
 def test_no_cpu_fallback_without_gpu(sdvl):
     import torch
     if torch.cuda.is_available():
