@@ -367,8 +367,10 @@ int sdvl_search_run(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_sea
  * and returns the point's new filter state.  With a tracking table set, the row of a point that a tracker follows
  * (track_row >= 0) is patched in place — position, inverse depth and its deviation, fixed, n_failed, and "deleted after the next
  * step" (Map::DeletePoint takes effect in the next frame's EmptyTrash, sdvl.cc:127) — so the table stays valid across the
- * mapper's update.  acos / sin / exp are the device library's: results agree with the host arithmetic to the last bits, not
- * bit for bit (tolerance class of the poses, 1e-4). */
+ * mapper's update.  Everything in front of the first acos (pose products, triangulation, parallax, the guards) is the host's
+ * arithmetic bit for bit; acos / sin / exp are the device library's, so the new state agrees with host arithmetic to the last bits,
+ * not bit for bit.  Measured against a plain restatement on 53 designed cases (tests/test_gpu_depth_filter.py): 51 bit-equal, the
+ * others at most 3.8e-13 relative in sigma2 and 5.1e-15 elsewhere, an eighth of the per-case bound. */
 struct sdvl_track_set; /* the tracking tables, below */
 typedef struct sdvl_depth_state { /* the Point behind a request (point.h:136-150) */
   double rho, sigma2, a, b, z_range;
@@ -401,8 +403,8 @@ typedef struct sdvl_depth_out {
   int32_t outcome;
   int32_t n_failed;
   double rho, sigma2, a, b;
-  double cos_alpha, last_distance; /* valid when UPDATED / CONVERGED */
-  double position[3];              /* Point::GetPosition() after the update (UPDATED / CONVERGED) */
+  double cos_alpha, last_distance; /* valid when UPDATED / CONVERGED; FIXED_STALE: the state's own, unchanged */
+  double position[3];              /* Point::GetPosition() after the update (UPDATED / CONVERGED / FIXED_STALE) */
 } sdvl_depth_out;
 
 /* requests as for sdvl_search_points; state[n]; set may be NULL (no table to patch); out[n], fout[n] */
@@ -412,6 +414,13 @@ int sdvl_search_points_filter(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs,
 /* the same behind sdvl_search_begin / sdvl_search_slot */
 int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
                            const sdvl_depth_params *fp, struct sdvl_track_set *set, sdvl_search_res *out, sdvl_depth_out *fout);
+/* The depth filter alone, on search results the caller states (what sdvl_align_patches is to the search): item i has the world ->
+ * camera poses cur_pose7[i] and ref_pose7[i] of the current frame and of the candidate's keyframe, the bearing of its first
+ * observation, and found[i] / px[i] as a search would have returned them.  state, fp, set and fout as above, with the same checks
+ * (track_row inside the tables or -1, sigma2 > 0, z_range > 0); blocking. */
+int sdvl_depth_filter(sdvl_ctx *ctx, int n, const double *cur_pose7, const double *ref_pose7, const double *bearing3, const int32_t *found,
+                      const double *px2, const sdvl_camera *cam, const sdvl_depth_state *state, const sdvl_depth_params *fp,
+                      struct sdvl_track_set *set, sdvl_depth_out *fout);
 
 /* Matcher::AlignPatch alone, matcher.cc:359-445: n patches against level images of frames.
  * border[n][100], patch[n][64], uv_io[n][2] (level coordinates), converged[n], its[n] (may be NULL) */

@@ -593,8 +593,8 @@ struct Tracker {
     return result;
   }
 
-  // Point::Update, point.cc:64-100
-  void PointUpdate(RPoint *pt, const RFrame &frame, double depth, double px_error_angle) {
+  // Point::Update, point.cc:64-100; -> false when it returned early (norm_scale is NaN, :74) and left the point as it was
+  bool PointUpdate(RPoint *pt, const RFrame &frame, double depth, double px_error_angle) {
     const RFrame &f0 = *pt->init_feature->frame;
     const SE3 pose = f0.pose * frame.pose.Inverse();
     const double tau = ComputeTau(pose, pt->init_feature->v, depth, px_error_angle);
@@ -602,7 +602,7 @@ struct Tracker {
     const double tau2 = tau_inverse * tau_inverse;
     const double x = 1. / depth;
     const double norm_scale = std::sqrt(pt->sigma2 + tau2);
-    if (std::isnan(norm_scale)) return;
+    if (std::isnan(norm_scale)) return false;
     const double s2 = 1. / (1. / pt->sigma2 + 1. / tau2);
     const double m = s2 * (pt->rho / pt->sigma2 + x / tau2);
     double C1 = pt->a / (pt->a + pt->b) * PDFNormal(pt->rho, norm_scale, x);
@@ -623,6 +623,7 @@ struct Tracker {
     pt->cos_alpha = Parallax(f0.WorldPosition(), frame.WorldPosition(), pos);
     pt->last_distance = frame.DistanceTo(pos);
     pt->n_failed = 0;
+    return true;
   }
 
   // Point::HasConverged, point.cc:164-178

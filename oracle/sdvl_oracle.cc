@@ -360,8 +360,10 @@ int sdvl_ref_depth_filter(void *t, const double *cur_pose7, const double *ref_po
     }
     if (go && (depth < tr->map_scale * tr->scale_min_dist || depth < depth_mean * tr->scale_min_dist)) go = false;
     if (go) {
-      tr->PointUpdate(&point, cur_frame, depth, px_error_angle);
-      outcome = Tracker::PointHasConverged(&point) ? 3 : 2;
+      // the outcome as include/sdvl_hip.h numbers it: an Update that returned early leaves FIXED_STALE (4) or SKIPPED (1)
+      const bool updated = tr->PointUpdate(&point, cur_frame, depth, px_error_angle);
+      const bool converged = Tracker::PointHasConverged(&point);
+      outcome = updated ? (converged ? 3 : 2) : (converged ? 4 : 1);
     }
   }
   st[0] = point.rho; st[1] = point.sigma2; st[2] = point.a; st[3] = point.b; st[4] = point.z_range;

@@ -148,7 +148,7 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
@@ -700,13 +700,39 @@ class Context:
         im = (C.c_void_p * n)(*[int(a) for a in addresses])
         self._check(self.lib.sdvl_frames_upload(self.h, n, fr, im, int(stride)))
 
-    def search_points_filter(self, reqs, cam, sp, states, fparams):
-        """sdvl_search_points_filter without tracking tables: (search results, depth-filter outcomes)"""
+    def search_points_filter(self, reqs, cam, sp, states, fparams, track_set=None):
+        """sdvl_search_points_filter: (search results, depth-filter outcomes); with track_set (a TrackSet) the rows the states name
+        are patched in its tables"""
         n = len(reqs)
         res = (SearchRes * n)()
         fout = (DepthOut * n)()
-        self._check(self.lib.sdvl_search_points_filter(self.h, n, reqs, C.byref(cam), C.byref(sp), states, C.byref(fparams), None, res, fout))
+        self._check(self.lib.sdvl_search_points_filter(self.h, n, reqs, C.byref(cam), C.byref(sp), states, C.byref(fparams),
+                                                       track_set.h if track_set is not None else None, res, fout))
         return res, fout
+
+    def depth_filter(self, cur_poses, ref_poses, bearings, found, px, cam, states, fparams, track_set=None):
+        """sdvl_depth_filter: the mapper's depth filter alone.  cur_poses / ref_poses [n][7], bearings [n][3], found [n], px [n][2];
+        states: DepthState array -> DepthOut array"""
+        n = len(states)
+        cp = np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7)
+        rp = np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7)
+        bv = np.ascontiguousarray(bearings, np.float64).reshape(n, 3)
+        fd = np.ascontiguousarray(found, np.int32).reshape(n)
+        pp = np.ascontiguousarray(px, np.float64).reshape(n, 2)
+        fout = (DepthOut * n)()
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.sdvl_depth_filter(self.h, n, _ptr(cp, dp), _ptr(rp, dp), _ptr(bv, dp), _ptr(fd, i32p), _ptr(pp, dp), C.byref(cam),
+                                               states, C.byref(fparams), track_set.h if track_set is not None else None, fout))
+        return fout
+
+    def track_points_download(self, track_set):
+        """the point rows of every tracker of a TrackSet as the device holds them: uint8 [n_trackers * max_points][144]"""
+        self.lib.sdvl_track_points_device.restype = C.c_void_p
+        self.lib.sdvl_track_points_device.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        np_, nt = C.c_int(0), C.c_int(0)
+        p = self.lib.sdvl_track_points_device(track_set.h, C.byref(np_), C.byref(nt))
+        rows = np_.value * nt.value
+        return self.device_download(p, rows * C.sizeof(TrackPoint)).reshape(rows, C.sizeof(TrackPoint))
 
     def search_chain(self, reqs, cam, sp, trackers, req_points, fx, max_ransac_points=5, max_ransac_its=100, max_optim_pose_its=10,
                      inlier_error_threshold=2.0):

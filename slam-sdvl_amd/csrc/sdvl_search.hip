@@ -1271,11 +1271,8 @@ int sdvl_search_points(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs, const 
   return sdvl_search_run(ctx, n, cam, p, out);
 }
 
-// ---- search + depth filter (Map::UpdateCandidates, map.cc:402-498): one submission, one wait
-int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
-                           const sdvl_depth_params *fp, sdvl_track_set *set, sdvl_search_res *out, sdvl_depth_out *fout) {
-  if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout))) return SDVL_ERR_INVALID;
-  if (n == 0) return SDVL_OK;
+// what every entry to depth_filter_kernel requires of the states; -> the rows the kernel may patch (none without a set)
+static int depth_filter_check(sdvl_ctx *ctx, int n, const sdvl_depth_state *state, sdvl_track_set *set, TrackPoint **rows_out, int *n_rows_out) {
   TrackPoint *rows = nullptr;
   int n_rows = 0;
   if (set) {
@@ -1287,11 +1284,25 @@ int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const s
     SDVL_REQUIRE(ctx, state[i].track_row >= -1 && (state[i].track_row < n_rows || !set), "depth filter: track_row outside the tables");
     SDVL_REQUIRE(ctx, state[i].sigma2 > 0.0 && state[i].z_range > 0.0, "depth filter: sigma2 and z_range must be positive");
   }
+  *rows_out = rows;
+  *n_rows_out = n_rows;
+  return SDVL_OK;
+}
+
+// ---- search + depth filter (Map::UpdateCandidates, map.cc:402-498): one submission, one wait
+int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
+                           const sdvl_depth_params *fp, sdvl_track_set *set, sdvl_search_res *out, sdvl_depth_out *fout) {
+  if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout))) return SDVL_ERR_INVALID;
+  if (n == 0) return SDVL_OK;
+  TrackPoint *rows = nullptr;
+  int n_rows = 0;
+  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
+  if (rc) return rc;
   SearchOut so(n);
   const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
   const SearchReqDev *d_reqs = nullptr;
   const SearchFramePose *d_table = nullptr;
-  int rc = search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
+  rc = search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
   if (rc) return rc;
   const size_t state_bytes = sizeof(sdvl_depth_state) * static_cast<size_t>(n);  // staged: the states alone
   void *hs = nullptr, *dsx = nullptr;
@@ -1316,6 +1327,54 @@ int sdvl_search_points_filter(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs,
   const int rc = pack_requests(ctx, n, reqs);
   if (rc) return rc;
   return sdvl_search_run_filter(ctx, n, cam, p, state, fp, set, out, fout);
+}
+
+// ---- the depth filter alone: depth_filter_kernel on search results the caller states
+int sdvl_depth_filter(sdvl_ctx *ctx, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
+                      const double *px, const sdvl_camera *cam, const sdvl_depth_state *state, const sdvl_depth_params *fp,
+                      sdvl_track_set *set, sdvl_depth_out *fout) {
+  if (!ctx || !cam || !fp || n < 0 || (n > 0 && (!cur_pose || !ref_pose || !bearing || !found || !px || !state || !fout))) return SDVL_ERR_INVALID;
+  if (n == 0) return SDVL_OK;
+  TrackPoint *rows = nullptr;
+  int n_rows = 0;
+  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
+  if (rc) return rc;
+  // staging: requests | frame table (entry 2i: item i's current pose, 2i + 1: its reference pose) | search results | states;
+  // d_out and h_out: the outcomes.  Of a request the kernel reads the two slots and the bearing, of a table entry the pose, of a
+  // result `found` and `px`: everything else stays zero.
+  sdvl_layout st, o;
+  const sdvl_part<SearchReqDev> st_reqs = st.take<SearchReqDev>(n);
+  const sdvl_part<SearchFramePose> st_tab = st.take<SearchFramePose>(2 * static_cast<size_t>(n));
+  const sdvl_part<sdvl_search_res> st_res = st.take<sdvl_search_res>(n);
+  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
+  const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
+  void *hs = nullptr, *ds = nullptr;
+  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
+  if (rc) return rc;
+  memset(hs, 0, st.bytes());
+  SearchReqDev *hreq = st_reqs.in(hs);
+  SearchFramePose *htab = st_tab.in(hs);
+  sdvl_search_res *hres = st_res.in(hs);
+  for (int i = 0; i < n; i++) {
+    hreq[i].cur = 2 * i;
+    hreq[i].ref = 2 * i + 1;
+    memcpy(hreq[i].bearing, bearing + 3 * static_cast<size_t>(i), sizeof(double) * 3);
+    memcpy(htab[2 * i].pose, cur_pose + 7 * static_cast<size_t>(i), sizeof(double) * 7);
+    memcpy(htab[2 * i + 1].pose, ref_pose + 7 * static_cast<size_t>(i), sizeof(double) * 7);
+    hres[i].found = found[i] ? 1 : 0;
+    hres[i].px[0] = px[2 * static_cast<size_t>(i)];
+    hres[i].px[1] = px[2 * static_cast<size_t>(i) + 1];
+  }
+  memcpy(st_state.in(hs), state, st_state.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), st_reqs.cin(ds), st_tab.cin(ds), st_res.cin(ds),
+              st_state.cin(ds), n, cam_of(*cam), *fp, rows, n_rows, o_fout.in(ctx->d_out), o_fout.in(ctx->h_out));
+  SDVL_HIP_CHECK(ctx, hipGetLastError());
+  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
+  memcpy(fout, o_fout.in(ctx->h_out), o_fout.bytes());
+  return SDVL_OK;
 }
 
 int sdvl_align_patches(sdvl_ctx *ctx, int n, const sdvl_frame *const *frames, const int32_t *levels, const uint8_t *border,
