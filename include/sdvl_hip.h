@@ -472,8 +472,28 @@ int sdvl_frames_upload_undistorted(sdvl_ctx *ctx, int n, sdvl_frame *const *fram
  * format, a source stride below width x channels, null pointers or in-place conversion. */
 enum sdvl_pixel_format { SDVL_GRAY8 = 0, SDVL_RGB8 = 1, SDVL_BGR8 = 2, SDVL_RGBA8 = 3, SDVL_BGRA8 = 4 };
 
-/* n interleaved colour images src[i] (host pointers — pinned ones are read in place, pageable ones are staged — or device pointers
- * if src_on_device) -> n gray images dst_dev[i] (device).  Up to 16384 pixels a side.  Asynchronous on the context's stream. */
+/* RAW camera formats, what sensors put on the wire; accepted wherever a `format` argument takes the values above (codes 5-15 and every
+ * other value stay unknown).  The arithmetic is exact integer arithmetic stated by this project (tests/raw_restatement.py is its
+ * specification), not pinned to OpenCV:
+ *   Bayer, 1 byte per pixel.  The name states the 2x2 tile at the image's TOP-LEFT corner in reading order (RGGB: R G / G B).  OpenCV's
+ *     CV_Bayer??2GRAY names follow a different convention (they name another position of the tile), and no OpenCV Bayer parity is
+ *     claimed.  Bilinear demosaic times 4 over the mosaic reflected at the edges without repeating them (-1 -> 1, n -> n - 2), then
+ *     Y = (4899 R4 + 9617 G4 + 1868 B4 + 2^15) >> 16: a mosaic of one flat colour gives the luma above of that colour at every pixel.
+ *     Width and height at least 2, odd sizes allowed.  A Bayer source in host memory, pinned or not, is staged in device memory first.
+ *   YUYV / UYVY, 2 bytes per pixel (Y0 U Y1 V / U Y0 V Y1), even width: gray is the Y byte (cv::cvtColor COLOR_YUV2GRAY_YUY2 / _UYVY).
+ *   16-bit gray, 2 bytes per pixel, little-endian, 10 / 12 / 16 significant bits: Y = min(255, (v + (1 << (bits - 9))) >> (bits - 8)),
+ *     rounding half up; values above the nominal depth saturate.
+ * Not built: planar / semi-planar YUV (the Y plane of NV12 / I420 already is a SDVL_GRAY8 image of the first `height` rows), packed
+ * 10 / 12-bit (MIPI), big-endian 16-bit, MJPEG, white balance or colour correction ahead of the luma. */
+enum sdvl_raw_format {
+  SDVL_BAYER_RGGB8 = 16, SDVL_BAYER_GRBG8 = 17, SDVL_BAYER_GBRG8 = 18, SDVL_BAYER_BGGR8 = 19,
+  SDVL_YUYV8 = 20, SDVL_UYVY8 = 21,
+  SDVL_GRAY10_16 = 22, SDVL_GRAY12_16 = 23, SDVL_GRAY16 = 24
+};
+
+/* n interleaved colour (or raw) images src[i] (host pointers — pinned ones are read in place, pageable ones are staged — or device pointers
+ * if src_on_device) -> n gray images dst_dev[i] (device).  Up to 16384 pixels a side.  Asynchronous on the context's stream.  The source
+ * stride is at least width x bytes per pixel. */
 int sdvl_convert_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int width, int height, int format,
                       void *const *dst_dev, int dst_stride);
 /* the fused form video_source.cc:63 + main.cc:133 need: colour camera images -> level 0 of the frames = undistort(gray(raw)), the

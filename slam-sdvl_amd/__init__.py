@@ -24,6 +24,20 @@ HOST_LIB_PATH = os.path.join(_HERE, "host", "libsdvl_host.so")
 
 # enum sdvl_pixel_format
 SDVL_GRAY8, SDVL_RGB8, SDVL_BGR8, SDVL_RGBA8, SDVL_BGRA8 = 0, 1, 2, 3, 4
+# enum sdvl_raw_format: Bayer mosaics (1 byte per pixel), YUV 4:2:2 and little-endian 16-bit gray (2 bytes per pixel)
+SDVL_BAYER_RGGB8, SDVL_BAYER_GRBG8, SDVL_BAYER_GBRG8, SDVL_BAYER_BGGR8 = 16, 17, 18, 19
+SDVL_YUYV8, SDVL_UYVY8 = 20, 21
+SDVL_GRAY10_16, SDVL_GRAY12_16, SDVL_GRAY16 = 22, 23, 24
+
+
+def _raw_bytes(im):
+    """a camera image as its bytes [h, w, bytes per pixel]: uint8 [h, w] (gray, Bayer) or [h, w, c] (colour, YUYV / UYVY), or uint16
+    [h, w] (16-bit gray, stored little-endian)"""
+    im = np.asarray(im)
+    if im.dtype == np.uint16:
+        im = np.ascontiguousarray(im.astype("<u2", copy=False)).view(np.uint8).reshape(im.shape + (2,))
+    im = np.ascontiguousarray(im, np.uint8)
+    return im[..., None] if im.ndim == 2 else im
 
 MAX_LEVELS = 8
 MAX_CORNERS = 6144
@@ -980,9 +994,9 @@ class Context:
 
     def convert_gray(self, imgs, fmt):
         """cv::cvtColor(img, CV_*2GRAY) on the device for a batch of host colour images (numpy u8 [h, w, 3 or 4]; fmt = SDVL_* value)
-        -> numpy gray images"""
+        -> numpy gray images.  Raw formats: u8 [h, w] (Bayer), u8 [h, w, 2] (YUYV / UYVY) or u16 [h, w] (16-bit gray)"""
         n = len(imgs)
-        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        imgs = [_raw_bytes(im) for im in imgs]
         h, w, ch = imgs[0].shape
         src = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
         buf = self.device_malloc(n * w * h)
@@ -996,10 +1010,10 @@ class Context:
         return [out[i].copy() for i in range(n)]
 
     def upload_color(self, frames, imgs, fmt, cam=None, dist=None):
-        """host colour images (numpy u8 [h, w, 3 or 4]) -> level 0 of `frames` = undistort(gray(img)) (no lens without cam / dist);
-        follow with pyramid_build"""
+        """host colour images (numpy u8 [h, w, 3 or 4]; raw formats as for convert_gray) -> level 0 of `frames` = undistort(gray(img))
+        (no lens without cam / dist); follow with pyramid_build"""
         n = len(imgs)
-        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        imgs = [_raw_bytes(im) for im in imgs]
         h, w, ch = imgs[0].shape
         src = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
         arr = (C.c_void_p * n)(*[f.h for f in frames])
@@ -1007,6 +1021,8 @@ class Context:
         self.lib.sdvl_frames_upload_color.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         self._check(self.lib.sdvl_frames_upload_color(self.h, n, arr, src, w * ch, 0, int(fmt), C.byref(cam) if cam is not None else None,
                                                       C.byref(d) if d is not None else None))
+
+    frames_upload_color = upload_color   # (the C entry's name)
 
     # ---- synthetic frames in HBM
     def device_malloc(self, nbytes):

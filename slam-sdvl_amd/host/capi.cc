@@ -85,7 +85,8 @@ int sdvlh_batch_set_distortion(void *bp, const double *dist5) {
   return Guarded([&] { AsGroup(bp)->SetDistortion(dist5); });
 }
 
-// TrackerGroup::SetColor: the images of every later step are COLOUR camera frames of `format` (enum sdvl_pixel_format)
+// TrackerGroup::SetColor: the images of every later step are COLOUR camera frames of `format` (enum sdvl_pixel_format, or a raw camera
+// format of enum sdvl_raw_format)
 int sdvlh_batch_set_color(void *bp, int format) {
   if (!bp) return -1;
   return Guarded([&] { AsGroup(bp)->SetColor(format); });

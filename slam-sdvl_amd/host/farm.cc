@@ -68,7 +68,7 @@ void TrackerGroup::SetDistortion(const double *dist5) {
 }
 
 void TrackerGroup::SetColor(int format) {
-  if (format < PIX_GRAY8 || format > PIX_BGRA8) throw std::invalid_argument("TrackerGroup::SetColor: unknown pixel format " + std::to_string(format));
+  if (PixelFormatBytes(format) == 0) throw std::invalid_argument("TrackerGroup::SetColor: unknown pixel format " + std::to_string(format));
   format_ = format;
 }
 
@@ -433,7 +433,8 @@ void TrackerFarm::WriteTimeline(const char *path) const {
 // and run ~6 % slower (80.0k vs 75.6k tracked frames/s at 120 steps); creating 16 threads costs well under a millisecond.
 void TrackerFarm::Run(int n_steps, const void *const *frames, int stride, FrameStats *out, int workers) {
   const int W = workers > 0 ? (workers < G_ ? workers : G_) : G_;
-  if (host_input_ && format_ != PIX_GRAY8)
+  // one byte per pixel rides the host input: gray, and the Bayer mosaics, which are converted inside the step like any colour frame
+  if (host_input_ && PixelFormatBytes(format_) != 1)
     throw std::runtime_error("TrackerFarm::Run: colour frames need frames resident in HBM; the host input and its input ring carry gray images only");
   if (UsesRing()) {
     for (int g = 0; g < G_; g++)

@@ -52,7 +52,8 @@ class TrackerGroup {
   void SetDistortion(const double *dist5);
   // The images of every later step are COLOUR camera frames of `format` (enum sdvl_pixel_format; row strides in bytes): cv::cvtColor
   // (video_source.cc:63) runs on the device inside the step, fused into the frames' upload, before the undistortion of a lens.  SDVL_RGB8
-  // is what main.cc computes on cv::VideoCapture's bytes; SDVL_GRAY8 (0) turns it off again.  Throws on an unknown format.
+  // is what main.cc computes on cv::VideoCapture's bytes; SDVL_GRAY8 (0) turns it off again.  RAW camera formats (enum sdvl_raw_format:
+  // Bayer mosaics, YUYV / UYVY, 16-bit gray) are converted the same way; row strides are width x bytes per pixel.  Throws on an unknown format.
   void SetColor(int format);
 
   Device *device() const { return dev_; }
@@ -95,8 +96,10 @@ class TrackerFarm {
   void SetHostInput(bool on);
   // the input ring of host-fed runs on (default) / off (every step uploads its own frames on its own stream before it computes)
   void SetInputRing(bool on) { input_ring_ = on; }
-  // every group's frames are colour camera frames of `format` (TrackerGroup::SetColor).  Colour frames must be resident in HBM: the host
-  // input and its input ring (sdvl_feed_*) carry gray images only, and Run refuses the combination.
+  // every group's frames are colour or raw camera frames of `format` (TrackerGroup::SetColor).  Formats of more than one byte per pixel
+  // must be resident in HBM: the host input and its input ring (sdvl_feed_*) carry one byte per pixel, and Run refuses the combination.
+  // The four Bayer formats are one byte per pixel: they ride the ring and the ring-less host path as the gray bytes they are, and are
+  // converted inside the step.
   void SetColor(int format);
 
   // Runs n_steps steps with `workers` host threads (0 = one per group).  frames[(step * G*Bg) + g*Bg + i] = pointer to the frame of

@@ -5,6 +5,10 @@
 //   track_sequence --synthetic N [--seed S]                      N frames of the S-A scene, rendered on the host
 //   track_sequence --list frames.txt                             one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB: converted to gray on the
 //                                                                device, SDVL_RGB8) path per line, e.g. a TUM / EuRoC list
+//   track_sequence --list frames.txt --raw-format NAME           the P5 files are RAW camera frames of that format (raw Bayer is commonly stored as PGM), converted
+//                                                                to gray on the device: bayer_rggb | bayer_grbg | bayer_gbrg | bayer_bggr (a mosaic, named by its
+//                                                                top-left 2x2 tile), yuyv | uyvy, gray10 | gray12 | gray16 (little-endian).  With a two-byte format
+//                                                                a P5 of width 2 W carries a W-pixel frame.  16-bit PGM (maxval > 255) is big-endian: unsupported
 //   track_sequence --synthetic N --scene shelf                   N frames of a scene with depth (csrc/sdvl_synth_scene.h: several surfaces, nearest hit) instead of
 //                                                                the one plane; the map still bootstraps from --plane (the default is the scene's wall)
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
@@ -69,6 +73,36 @@ bool ReadPNM(const std::string &path, int *w, int *h, std::vector<uint8_t> *px, 
   return static_cast<size_t>(f.gcount()) == px->size();
 }
 
+// --raw-format NAME -> PIX_* (0: no such name)
+int RawFormatByName(const std::string &name) {
+  static const char *const names[] = {"bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr", "yuyv", "uyvy", "gray10", "gray12", "gray16"};
+  for (int i = 0; i < 9; i++)
+    if (name == names[i]) return PIX_BAYER_RGGB8 + i;
+  return 0;
+}
+
+const char kUsage[] =
+    "track_sequence --synthetic N [--seed S] [--scene NAME] | --list frames.txt [--raw-format NAME]\n"
+    "  --list: one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB) path per line\n"
+    "  --raw-format NAME: the P5 files are raw camera frames, converted to gray on the device:\n"
+    "      bayer_rggb | bayer_grbg | bayer_gbrg | bayer_bggr   a Bayer mosaic, named by the 2x2 tile at its top-left corner\n"
+    "      yuyv | uyvy                                         YUV 4:2:2; the P5 is 2 W bytes wide for a W-pixel frame\n"
+    "      gray10 | gray12 | gray16                            little-endian 16-bit gray; the P5 is 2 W bytes wide\n"
+    "    16-bit PGM (maxval above 255) is big-endian and is not supported\n"
+    "  common: [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle]\n"
+    "          [--init plane|two-frame] [--trackers N] [--batch] [--lookahead] [--prerender] [--pageable] [--set SDVL.key value]\n"
+    "          [--quiet] [--json] [--profile]\n";
+
+// the frame of a --list file as an Image: a P6 is RGB, a P5 is gray or, with --raw-format, the bytes of that format (file_w = W x bytes per
+// pixel of it); false if the file's width does not fit
+bool WrapListFrame(const uint8_t *data, int file_w, int W, int H, int format, int raw_format, Image *img) {
+  if (format == PIX_GRAY8 && raw_format) format = raw_format;
+  const int row = W * PixelFormatBytes(format);
+  if (file_w != (format == PIX_RGB8 ? W : row)) return false;
+  *img = Image::Wrap(data, W, H, row, format);
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -78,7 +112,7 @@ int main(int argc, char **argv) {
   std::string list, cfg, scene_name;
   bool mapper = false, bundle = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
   bool prerender = false, pageable = false, quiet = false, json = false, profile = false, batch = false, lookahead = false;
-  int n_trackers = 1;
+  int n_trackers = 1, raw_format = 0;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
   unsigned texture = SDVL_TEXTURE_PLANE_NOISE;
   for (int i = 1; i < argc; i++) {
@@ -87,6 +121,8 @@ int main(int argc, char **argv) {
     if (a == "--synthetic") { need(1); n_synth = std::atoi(argv[++i]); }
     else if (a == "--seed") { need(1); seed = static_cast<unsigned>(std::strtoul(argv[++i], nullptr, 10)); }
     else if (a == "--list") { need(1); list = argv[++i]; }
+    else if (a == "--raw-format") { need(1); raw_format = RawFormatByName(argv[++i]); if (!raw_format) { std::cerr << "unknown --raw-format " << argv[i] << "\n" << kUsage; return 2; } }
+    else if (a == "--help" || a == "-h") { std::cout << kUsage; return 0; }
     else if (a == "--config") { need(1); cfg = argv[++i]; }
     else if (a == "--size") { need(2); W = std::atoi(argv[++i]); H = std::atoi(argv[++i]); size_given = true; }
     else if (a == "--cam") { need(4); for (int k = 0; k < 4; k++) cam4[k] = std::atof(argv[++i]); cam_given = true; }
@@ -109,6 +145,7 @@ int main(int argc, char **argv) {
     else { std::cerr << "unknown argument " << a << std::endl; return 2; }
   }
   if ((n_synth > 0) == !list.empty()) { std::cerr << "give either --synthetic N or --list file" << std::endl; return 2; }
+  if (raw_format && list.empty()) { std::cerr << "--raw-format says what the P5 files of a --list hold: give --list file" << std::endl; return 2; }
   sdvl_synth_scene scene_surfaces = {};  // --scene: n_surfaces and surfaces of the preset
   if (!scene_name.empty()) {
     if (n_synth <= 0) { std::cerr << "--scene renders the synthetic sequence: give --synthetic N" << std::endl; return 2; }
@@ -244,20 +281,25 @@ int main(int argc, char **argv) {
         }
         for (int k = 0; k < n_frames; k++) {
           uint8_t *data = px.data();
-          int format = PIX_GRAY8;
+          int format = PIX_GRAY8, file_w = W;
           if (pool) {
             data = pool + frame_bytes * k;
           } else if (n_synth > 0) {
             render_host(k, px.data());
           } else {
             int w = 0, h = 0;
-            if (!ReadPNM(files[k], &w, &h, &px, &format) || w != W || h != H) {
+            if (!ReadPNM(files[k], &w, &h, &px, &format) || h != H) {
               me.err = "cannot read " + files[k] + " as a binary PGM / PPM of the configured size";
               return;
             }
             data = px.data();
+            file_w = w;
           }
-          Image img = Image::Wrap(data, W, H, format == PIX_RGB8 ? 3 * W : W, format);  // a P6 frame: cvtColor on the device (video_source.cc:63)
+          Image img;  // a P6 frame, or a raw P5 frame: converted to gray on the device (video_source.cc:63)
+          if (!WrapListFrame(data, file_w, W, H, format, raw_format, &img)) {
+            me.err = "cannot read " + files[k] + " as a binary PGM / PPM of the configured size";
+            return;
+          }
           Image imgu;
           if (lookahead && pool && ahead_valid) {
             imgu = ahead;                                          // undistorted one iteration ago
@@ -335,9 +377,10 @@ int main(int argc, char **argv) {
             uint8_t *data = px.data();
             if (pool) data = pool + frame_bytes * k;
             else if (n_synth > 0) render_host(k, px.data());
-            int format = PIX_GRAY8;
-            if (!pool && n_synth == 0) { int w = 0, h = 0; if (!ReadPNM(files[k], &w, &h, &px, &format) || w != W || h != H) { me.err = "cannot read " + files[k]; return; } data = px.data(); }
-            Image img = Image::Wrap(data, W, H, format == PIX_RGB8 ? 3 * W : W, format);
+            int format = PIX_GRAY8, file_w = W;
+            if (!pool && n_synth == 0) { int w = 0, h = 0; if (!ReadPNM(files[k], &w, &h, &px, &format) || h != H) { me.err = "cannot read " + files[k]; return; } data = px.data(); file_w = w; }
+            Image img;
+            if (!WrapListFrame(data, file_w, W, H, format, raw_format, &img)) { me.err = "cannot read " + files[k]; return; }
             std::vector<Image> imgs(n_trackers);
             for (int i = 0; i < n_trackers; i++) camera.UndistortImage(img, &imgs[i]);  // every camera its own frame in HBM (main.cc:133, outside the window)
             const auto t0 = std::chrono::steady_clock::now();

@@ -68,8 +68,20 @@ enum { CV_8UC1 = 0 };  // the only cv::Mat type the tracking front-end sees (fra
 
 // Pixel layout of an Image (= enum sdvl_pixel_format of include/sdvl_hip.h).  A colour image is a RAW camera frame: the Frame built from it
 // takes cv::cvtColor(frame, img, CV_*2GRAY) (video_source.cc:63) as its image, converted on the device inside the upload.
-enum PixelFormat { PIX_GRAY8 = 0, PIX_RGB8 = 1, PIX_BGR8 = 2, PIX_RGBA8 = 3, PIX_BGRA8 = 4 };
-enum { SDVL_CV_8UC3 = 16, SDVL_CV_8UC4 = 24 };  // the cv::Mat type codes of 8-bit 3- and 4-channel images (CV_8UC3, CV_8UC4)
+// From 16 on (= enum sdvl_raw_format): RAW camera formats, converted the same way.  A Bayer mosaic is named by the 2x2 tile at its top-left
+// corner; YUYV / UYVY and the 16-bit grays (little-endian, 10 / 12 / 16 significant bits) take two bytes per pixel.
+enum PixelFormat {
+  PIX_GRAY8 = 0, PIX_RGB8 = 1, PIX_BGR8 = 2, PIX_RGBA8 = 3, PIX_BGRA8 = 4,
+  PIX_BAYER_RGGB8 = 16, PIX_BAYER_GRBG8 = 17, PIX_BAYER_GBRG8 = 18, PIX_BAYER_BGGR8 = 19,
+  PIX_YUYV8 = 20, PIX_UYVY8 = 21, PIX_GRAY10_16 = 22, PIX_GRAY12_16 = 23, PIX_GRAY16 = 24
+};
+// the cv::Mat type codes of 8-bit 3- and 4-channel images (CV_8UC3, CV_8UC4) and of 16-bit gray (CV_16UC1)
+enum { SDVL_CV_8UC3 = 16, SDVL_CV_8UC4 = 24, SDVL_CV_16UC1 = 2 };
+// bytes per pixel of a PixelFormat, 0 for a value that is none
+inline int PixelFormatBytes(int format) {
+  return format == PIX_GRAY8 ? 1 : (format == PIX_RGB8 || format == PIX_BGR8) ? 3 : (format == PIX_RGBA8 || format == PIX_BGRA8) ? 4
+       : (format >= PIX_BAYER_RGGB8 && format <= PIX_BAYER_BGGR8) ? 1 : (format >= PIX_YUYV8 && format <= PIX_GRAY16) ? 2 : 0;
+}
 
 struct Image {
   const uint8_t *data = nullptr;
@@ -81,16 +93,25 @@ struct Image {
   // cv::Mat(rows, cols, type, data, step): a header over caller-owned pixels; type CV_8UC3 / CV_8UC4 = a colour frame
   Image(int rows_, int cols_, int type, const void *pixels, size_t step_ = 0)
       : data(static_cast<const uint8_t *>(pixels)), cols(cols_), rows(rows_),
-        format(type == SDVL_CV_8UC3 ? PIX_RGB8 : type == SDVL_CV_8UC4 ? PIX_RGBA8 : PIX_GRAY8) {
-    step = step_ ? static_cast<int>(step_) : cols_ * channels();
+        format(type == SDVL_CV_8UC3 ? PIX_RGB8 : type == SDVL_CV_8UC4 ? PIX_RGBA8 : type == SDVL_CV_16UC1 ? PIX_GRAY16 : PIX_GRAY8) {
+    step = step_ ? static_cast<int>(step_) : cols_ * bytes_per_pixel();
   }
-  int channels() const { return format == PIX_GRAY8 ? 1 : (format == PIX_RGB8 || format == PIX_BGR8) ? 3 : 4; }
+  // colour channels of a pixel (raw formats: 1), and the bytes it takes in a row
+  int channels() const { return (format == PIX_RGB8 || format == PIX_BGR8) ? 3 : (format == PIX_RGBA8 || format == PIX_BGRA8) ? 4 : 1; }
+  int bytes_per_pixel() const { return PixelFormatBytes(format); }
   bool color() const { return format != PIX_GRAY8; }
   // the same pixels, converted as CV_BGR2GRAY (the R weight on byte 2); a gray image stays as it is
   Image bgr() const {
     Image r = *this;
     if (format == PIX_RGB8) r.format = PIX_BGR8;
     if (format == PIX_RGBA8) r.format = PIX_BGRA8;
+    return r;
+  }
+  // the same bytes as a Bayer mosaic of `order` (PIX_BAYER_*: the tile at the top-left corner), for a one-byte image (what a camera SDK
+  // or a PGM file hands over as "gray"); any other image, or a value that is no Bayer order, stays as it is
+  Image bayer(int order) const {
+    Image r = *this;
+    if (bytes_per_pixel() == 1 && order >= PIX_BAYER_RGGB8 && order <= PIX_BAYER_BGGR8) r.format = order;
     return r;
   }
   sdvl_frame *dev = nullptr;
@@ -100,7 +121,7 @@ struct Image {
   Image clone() const {
     Image r = *this;
     if (data) {
-      const int row = cols * channels();
+      const int row = cols * bytes_per_pixel();
       r.owner = std::make_shared<std::vector<uint8_t>>(static_cast<size_t>(row) * rows);
       for (int y = 0; y < rows; y++)
         for (int x = 0; x < row; x++) (*r.owner)[static_cast<size_t>(y) * row + x] = data[static_cast<size_t>(y) * step + x];
@@ -114,8 +135,8 @@ struct Image {
   // 4-channel Mat (type 16 = CV_8UC3, 24 = CV_8UC4) is a colour frame in the reference's order (see `format`).
   Image(const cv::Mat &m) {
     const int t = m.empty() ? -1 : m.type();
-    if (t == CV_8UC1 || t == SDVL_CV_8UC3 || t == SDVL_CV_8UC4) {
-      format = t == SDVL_CV_8UC3 ? PIX_RGB8 : t == SDVL_CV_8UC4 ? PIX_RGBA8 : PIX_GRAY8;
+    if (t == CV_8UC1 || t == SDVL_CV_8UC3 || t == SDVL_CV_8UC4 || t == SDVL_CV_16UC1) {
+      format = t == SDVL_CV_8UC3 ? PIX_RGB8 : t == SDVL_CV_8UC4 ? PIX_RGBA8 : t == SDVL_CV_16UC1 ? PIX_GRAY16 : PIX_GRAY8;
       auto keep = std::make_shared<cv::Mat>(m);
       mat_owner = keep;
       data = keep->data;
@@ -126,7 +147,7 @@ struct Image {
   }
   // the host mirror as a cv::Mat header (GetPyramid() users: homography_init.cc:196, ui/drawimage.cc); empty while only the HBM copy exists
   operator cv::Mat() const {
-    const int t = channels() == 1 ? CV_8UC1 : channels() == 3 ? SDVL_CV_8UC3 : SDVL_CV_8UC4;
+    const int t = bytes_per_pixel() == 2 ? SDVL_CV_16UC1 : channels() == 1 ? CV_8UC1 : channels() == 3 ? SDVL_CV_8UC3 : SDVL_CV_8UC4;
     return data ? cv::Mat(rows, cols, t, const_cast<uint8_t *>(data), static_cast<size_t>(step)) : cv::Mat();
   }
   std::shared_ptr<void> mat_owner;

@@ -122,8 +122,11 @@ class HostDevice:
 
 
 # enum sdvl_pixel_format (include/sdvl_hip.h) and the bytes per pixel of each
-PIXEL_FORMATS = {"gray": 0, "rgb": 1, "bgr": 2, "rgba": 3, "bgra": 4}
-PIXEL_CHANNELS = {0: 1, 1: 3, 2: 3, 3: 4, 4: 4}
+# and enum sdvl_raw_format (16 ..): Bayer mosaics named by their top-left 2x2 tile, YUV 4:2:2, little-endian 16-bit gray
+PIXEL_FORMATS = {"gray": 0, "rgb": 1, "bgr": 2, "rgba": 3, "bgra": 4,
+                 "bayer_rggb": 16, "bayer_grbg": 17, "bayer_gbrg": 18, "bayer_bggr": 19,
+                 "yuyv": 20, "uyvy": 21, "gray10": 22, "gray12": 23, "gray16": 24}
+PIXEL_CHANNELS = {0: 1, 1: 3, 2: 3, 3: 4, 4: 4, 16: 1, 17: 1, 18: 1, 19: 1, 20: 2, 21: 2, 22: 2, 23: 2, 24: 2}   # bytes per pixel
 
 
 def pixel_format(fmt):
@@ -151,7 +154,8 @@ class TrackerBatch:
         self._stats = (FrameStats * B)()
 
     def step_host(self, imgs):
-        imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+        # (16-bit gray frames go as their little-endian bytes)
+        imgs = [np.ascontiguousarray(im, "<u2").view(np.uint8) if np.asarray(im).dtype == np.uint16 else np.ascontiguousarray(im, np.uint8) for im in imgs]
         ptrs = (C.c_void_p * self.B)(*[im.ctypes.data for im in imgs])
         if self.lib.sdvlh_batch_step_host(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
@@ -182,7 +186,10 @@ class TrackerBatch:
     def set_color(self, fmt):
         """the images of every later step are COLOUR camera frames (h x w x channels, interleaved) of pixel format `fmt` ("gray", "rgb",
         "bgr", "rgba", "bgra" or the SDVL_* value): cv::cvtColor (video_source.cc:63) runs on the device inside the step, before the
-        undistortion of set_distortion.  "rgb" puts the R weight on byte 0 — what main.cc computes on cv::VideoCapture's BGR bytes"""
+        undistortion of set_distortion.  "rgb" puts the R weight on byte 0 — what main.cc computes on cv::VideoCapture's BGR bytes.
+        RAW camera formats (enum sdvl_raw_format) go the same way: "bayer_rggb" / "bayer_grbg" / "bayer_gbrg" / "bayer_bggr" (h x w bytes,
+        named by the 2x2 tile at the top-left corner), "yuyv" / "uyvy" (h x w x 2 bytes, even w), "gray10" / "gray12" / "gray16" (h x w
+        little-endian uint16).  Row strides are w x bytes per pixel"""
         code = pixel_format(fmt)
         self.lib.sdvlh_batch_set_color.argtypes = [C.c_void_p, C.c_int]
         if self.lib.sdvlh_batch_set_color(self.h, code) != 0:
@@ -320,8 +327,10 @@ class TrackerFarm:
                 raise RuntimeError("sdvlh_batch_set_distortion")
 
     def set_color(self, fmt):
-        """every group's frames are COLOUR camera frames of `fmt` (TrackerBatch.set_color).  They must be resident in HBM: run() refuses
-        colour frames together with set_host_input (the host input and its input ring carry gray images only)"""
+        """every group's frames are COLOUR or RAW camera frames of `fmt` (TrackerBatch.set_color).  Formats of more than one byte per pixel
+        must be resident in HBM: run() refuses them together with set_host_input (the host input and its input ring carry one byte per
+        pixel).  The four Bayer formats are one byte per pixel: they ride the host input, with or without the ring, as gray does, and are
+        converted inside the step"""
         code = pixel_format(fmt)
         self.lib.sdvlh_farm_set_color.argtypes = [C.c_void_p, C.c_int]
         if self.lib.sdvlh_farm_set_color(self.h, code) != 0:
