@@ -823,7 +823,7 @@ int sdvl_device_free(sdvl_ctx *ctx, void *p);
 int sdvl_device_download(sdvl_ctx *ctx, const void *dev, int64_t bytes, void *host);
 /* Fork / join inside one context (round 5).  Work queued between _fork_begin and _fork_end runs on a side stream that starts behind
  * the point of the main stream _fork_mark recorded and is joined into the main stream by _fork_end: everything queued afterwards waits
- * for both.  A lone camera's tracked frame uses it (host/standalone.cc): Frame::CreateCorners' FAST + selection (frame.cc:122-131,
+ * for both.  A lone camera's tracked frame uses it (host/batch_tracked.cc): Frame::CreateCorners' FAST + selection (frame.cc:122-131,
  * reached from the Frame constructor, sdvl.cc:59) needs the pyramid only, so it runs beside ImageAlign::ComputePose (sdvl.cc:189)
  * instead of behind it.  One fork at a time; results are identical (the same kernels on the same inputs). */
 int sdvl_ctx_fork_mark(sdvl_ctx *ctx);

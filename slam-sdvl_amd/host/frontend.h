@@ -2,7 +2,7 @@
 // FastDetector (extra/fast_detector.h), ORBDetector (extra/orb_detector.h), ImageAlign (image_align.h), Matcher (matcher.h),
 // FeatureAlign (feature_align.h), with the reference's names, argument meaning and return conventions, implemented in frontend.cc on top
 // of the C-ABI (include/sdvl_hip.h).  Camera, Point and Map come from frontend_deps.h (the reference tree's own classes); SDVL, the map
-// stand-ins and the batch driver are in sdvl_host.h / standalone.cc.
+// stand-ins are in sdvl_host.h / standalone.cc, the batch driver in batch.h / batch*.cc.
 #ifndef SDVL_FRONTEND_H_
 #define SDVL_FRONTEND_H_
 

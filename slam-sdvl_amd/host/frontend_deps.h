@@ -4,7 +4,7 @@
 // second, independent implementation of exactly the members frontend.cc leaves undefined —
 //     Camera::Project, Camera::Unproject, Point::GetPosition, Point::GetStd, Point::Promote, Point::Unpromote
 // (all six are members of the reference's classes with the reference's signatures) — against which `make frontend_link_check` links
-// frontend.o without standalone.cc (tests/test_frontend_split.py keeps the list honest with nm).
+// frontend.o without standalone.cc or the batch driver's batch*.cc (tests/test_frontend_split.py keeps the list honest with nm).
 #ifndef SDVL_FRONTEND_DEPS_H_
 #define SDVL_FRONTEND_DEPS_H_
 

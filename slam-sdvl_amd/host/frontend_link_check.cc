@@ -1,6 +1,6 @@
 // frontend_link_check.cc — the hot path's classes WITHOUT the rest of the host layer.  Includes frontend.h only and is linked as
 //     frontend.cc + minimal_deps.cc + config.cc + this file  (+ libsdvl_hip.so, libsdvl_synth.so)
-// — no standalone.cc (Camera / Point / Map / SDVL / SDVLBatch), no mapper.cc, no capi.cc: what INTEGRATION.md route A puts next to
+// — no standalone.cc (Camera / Point / Map / SDVL), no batch*.cc (SDVLBatch), no mapper.cc, no capi.cc: what INTEGRATION.md route A puts next to
 // the reference's own sdvl.cc / map.cc / point.cc / camera.cc / config.cc.  That the link succeeds is the proof that the front end
 // has no hidden dependency; on a GPU the program also tracks one frame through the reference's per-object calls with the minimal
 // Camera / Point (Frame ctor -> FilterCorners -> ImageAlign::ComputePose -> Matcher::SearchPoint -> FeatureAlign::Reproject +

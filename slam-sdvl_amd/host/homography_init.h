@@ -5,7 +5,7 @@
 // HomographyMath is its arithmetic on plain arrays: ComputeHomography, CheckInliers, DecomposeHomography, ChooseBestDecomposition,
 // CheckDecompositionInliers and the map scaling of InitSecondFrame (:111-121), statement by statement.  No Eigen and no OpenCV here: the
 // DLT refit of H on the RANSAC inliers and the 3x3 SVD are small Jacobi routines; OpenCV's Levenberg-Marquardt polish of H is left
-// out.  Part of the reference-side file set (standalone.cc, mapper.cc), not of frontend.cc.
+// out.  Part of the reference-side file set (standalone.cc, mapper.cc; batch.cc calls it for a batch), not of frontend.cc.
 #ifndef SDVL_HOMOGRAPHY_INIT_H_
 #define SDVL_HOMOGRAPHY_INIT_H_
 

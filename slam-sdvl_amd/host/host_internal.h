@@ -1,8 +1,8 @@
-// host_internal.h — what the two translation units of the host layer share besides sdvl_host.h (not installed):
+// host_internal.h — what the translation units of the host layer share besides sdvl_host.h (not installed):
 //   frontend.cc    Device, Frame, Feature, FastDetector, ORBDetector, ImageAlign, Matcher, FeatureAlign — the hot path's classes
 //   standalone.cc  Camera, Point, Map / PlaneMap, SDVL — what the reference's own camera.cc / point.cc / map.cc / sdvl.cc provide in
-//                  its tree (INTEGRATION.md route A) — and SDVLBatch: tables, shared pieces of a step, relocalisation, the tabled step,
-//                  the host-driven step, epilogue and mappers
+//                  its tree (INTEGRATION.md route A)
+//   batch*.cc      SDVLBatch, one file per job (batch.h names them); what only they share is in batch_internal.h
 #ifndef SDVL_HOST_INTERNAL_H_
 #define SDVL_HOST_INTERNAL_H_
 

@@ -1,7 +1,7 @@
 // minimal_deps.cc — a SECOND, independent implementation of what frontend.cc leaves undefined (frontend_deps.h): the six members of
 // the reference's Camera and Point that the hot path's classes call out to, plus the constructors a program needs to make the
 // objects.  It shares no code with standalone.cc; `make frontend_link_check` links frontend.o against THIS file only — no
-// standalone.cc, no mapper.cc, no capi.cc — which proves that the front end has no hidden dependency on the rest of the host layer
+// standalone.cc, no batch*.cc, no mapper.cc, no capi.cc — which proves that the front end has no hidden dependency on the rest of the host layer
 // (INTEGRATION.md route A: in the reference's tree camera.cc and point.cc take this file's place).
 //   Camera::Project / Unproject     camera.cc:69-79
 //   Point::GetPosition              point.cc:128-142

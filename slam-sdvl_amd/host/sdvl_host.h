@@ -14,7 +14,8 @@
 // Error convention: the reference returns bool/int and prints to cerr; so does this layer.  A failing device call
 // is fatal (std::runtime_error carrying sdvl_last_error) — there is no CPU fallback.
 // Round 4: the header is in three parts — frontend_deps.h (Camera, Point, Map: the reference tree's own classes), frontend.h (the hot
-// path's classes) and, below, what only the standalone build needs: the map stand-ins, SDVL and the batch driver.
+// path's classes) and, below, what only the standalone build needs: the map stand-ins and SDVL.  The batch driver, SDVLBatch, has a
+// header of its own, batch.h, which this one includes at its end.
 #ifndef SDVL_HOST_H_
 #define SDVL_HOST_H_
 
@@ -274,114 +275,8 @@ class SDVL {
   } reloc_;
 };
 
-// B independent trackers stepping together, one launch per kernel per stage (MI355X-first driver)
-class SDVLBatch {
- public:
-  SDVLBatch(Device *dev, const std::vector<SDVL *> &trackers, int host_threads);
-  ~SDVLBatch();
-  // imgs[i] feeds tracker i; stats[i] receives its FrameStats
-  void HandleFrames(const std::vector<Image> &imgs, FrameStats *stats);
-  // Round 4: a caller that already holds the images of the NEXT step (a sequence from disk, frames resident in HBM) names them before
-  // the current step: their pyramids and corner detection — all that depends on the image alone, 45 % of a step's vector instructions —
-  // are queued right behind the current step's search / pose chain and run while the host waits for that chain and does its keyframe
-  // bookkeeping; the next HandleFrames with these images picks the frames up.  Same kernels on the same inputs: same results.
-  // The images must stay valid until that call (device images are aliased).  An unused look-ahead is dropped.
-  void SetNextImages(const std::vector<Image> &next);
-  // pose stage (RANSAC + refinement) on the device (default) or with the host implementation; process-wide switch,
-  // also set by SDVL_POSE_HOST=1 in the environment.  Both produce the same decisions (tests/test_gpu_tracker.py).
-  static void SetDevicePose(bool on);
-  static bool DevicePose();
-  // Device-resident tracking tables (the default): last_frame's features and points
-  // stay in HBM, a step is ONE submission and ONE wait, the host keeps rand(), the motion model and the keyframe logic.
-  // Off (SDVL_NO_TRACK_TABLES=1 or SetTrackTables(false)): the host assembles every request as before.  Same results.
-  static void SetTrackTables(bool on);
-  static bool TrackTables();
-  // Point objects / Feature lists catch up with the device (called on its own whenever the batch leaves the tracked path)
-  void SyncHostState();
-
- private:
-  void ParallelFor(int n, const std::function<void(int)> &fn);
- public:
-  StageTimes stage_times;
- private:
-  friend class SDVL;
-  Device *dev_;
-  std::vector<SDVL *> trk_;
-  int threads_;
-  // ParallelFor as Frame's batched calls take it (CreateBatch hands the body over by value, FilterCornersEnd by reference)
-  std::function<void(int, std::function<void(int)>)> pfor_;
-  std::function<void(int, const std::function<void(int)> &)> pfor_ref_;
-  std::vector<sdvl_search_req> scratch_reqs_;  // per-step request / pose batches, reused so that they never reallocate
-  FeatureAlign::PoseBatch scratch_pose_;
-  std::vector<double> scratch_points_;  // sdvl_search_run_chain inputs, same idea
-  std::vector<int32_t> chain_cand_req_, chain_cand_first_, chain_rand_;
-  // ---- what every form of a step shares
-  struct Step;      // what the stages of one step hand to each other (defined in standalone.cc)
-  struct HostStep;  // Step + the requests and pose jobs of the host-driven form
-  enum FrameStart { kFirstFrame, kLost, kRunning };
-  FrameStart BeginFrame(int i, const std::shared_ptr<Frame> &frame, FrameStats &st);
-  // the two-frame initialisation of every tracker of the step that is in its first-frame or second-frame state: ONE sdvl_klt_track
-  // call and ONE sdvl_homography_ransac call for all of them
-  void InitializeTrackers(Step &s);
-  void DetectOnSideStream(const std::vector<std::shared_ptr<Frame>> &frames, bool fork);
-  void FetchCornerCounts(const std::vector<std::shared_ptr<Frame>> &frames, FrameStats *stats);
-  void CollectKeyframes(Step &s, bool fetch_counts);
-  void GatherRows(const std::vector<int> &up, bool own_buf);
-  void SyncStats(SDVL &t);
-  void EpilogueAndMapper(Step &s);
-  void FinishKeyframes(Step &s);
-  void RunMappers();
-  // ---- the step on the device-resident tables
-  bool HandleFramesTracked(const std::vector<Image> &imgs, FrameStats *stats);  // false: not applicable this step
-  bool TrackedStepApplies();
-  bool EnsureTrackSet();
-  void TakeLookAhead(Step &s);
-  void QueueLookAhead(const Step &s);
-  void RelocalizeIntoStep(Step &s);
-  sdvl_track_params AssembleTrackJobs(const Step &s);
-  void SubmitTracked(Step &s);
-  void ReplayTracked(Step &s);
-  void SaveTrackedFrames(Step &s);
-  void InvalidateStaleTables();
-  int TrackOnHost(SDVL &t, FrameStats *st);
-  bool BuildTable(SDVL &t);
-  bool UploadTables(const std::vector<int> &need, std::vector<char> *built);
-  bool AppendSeeds(SDVL &t, const std::shared_ptr<Frame> &kf);  // rows of the points seeded on kf -> track_.up_points / up_feats
-  std::vector<Image> next_imgs_;                        // SetNextImages: what the next step will be given
-  std::vector<std::shared_ptr<Frame>> ahead_frames_;    // their frames, pyramids and detection queued
-  std::vector<const void *> ahead_src_;                 // the images they were made from
-  sdvl_track_set *track_ = nullptr;
-  int track_cells_ = 0, track_cap_ = 0;
-  std::vector<sdvl_track_job> tr_jobs_;
-  std::vector<uint16_t> tr_rank_;
-  std::vector<int32_t> tr_rand_;
-  std::vector<sdvl_track_result> tr_res_;
-  std::vector<sdvl_track_point> tr_up_points_;
-  std::vector<sdvl_track_feature> tr_up_feats_;
-  std::vector<int32_t> tr_up_trk_, tr_up_buf_, tr_up_np_, tr_up_nf_;  // whose rows those are, for which buffer, how many
-  // ---- relocalisation inside the tabled step
-  void RelocalizeLost(const std::vector<int> &lost, FrameStats *stats, std::vector<char> *found);
-  void PackRelocCache(SDVL &t, std::vector<sdvl_align_feature> *packed);
-  void RefreshRelocStore(const std::vector<int> &lost);
-  void RelocAlignKeyframes(const std::vector<int> &lost, std::vector<int> *first, std::vector<sdvl_align_result> *res);
-  void RelocAlign(const std::vector<sdvl_align_job> &jobs, const sdvl_align_params &ap, std::vector<sdvl_align_result> *res);
-  // keyframe feature records of the trackers that are relocalising (SDVL::RelocCache): one bump-allocated store per batch
-  sdvl_align_store *reloc_store_ = nullptr;
-  int reloc_cap_ = 0, reloc_used_ = 0;
-  unsigned long long reloc_epoch_ = 0;  // 0: no store yet
-  // ---- the host-driven step
-  void HandleFramesGeneric(const std::vector<Image> &imgs, FrameStats *stats);
-  bool RelocalizeOnHost(SDVL &t, FrameStats &st);
-  void AlignImages(HostStep &s);
-  void PackRequests(HostStep &s);
-  void PackChain(HostStep &s);
-  void CollectRequests(HostStep &s);
-  void LaunchSearch(HostStep &s);
-  void ReplaySelect(HostStep &s);
-  void LaunchPose(HostStep &s);
-  void CommitAndSave(HostStep &s);
-};
-
 }  // namespace sdvl
+
+#include "batch.h"  // SDVLBatch, the batch driver SDVL::HandleFrame steps through
 
 #endif  // SDVL_HOST_H_
