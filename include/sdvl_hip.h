@@ -502,6 +502,54 @@ int sdvl_convert_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stri
 int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
                              int format, const sdvl_camera *cam, const sdvl_distortion *dist);
 
+/* ---- input stage, depth cameras: the depth of a keyframe's corners from a REGISTERED depth image --------------------------------------
+ * Map::InitCandidates carries a branch that makes a candidate a fixed point at a known depth (`bool fixed`, map.cc:269,385-389) and
+ * never takes it; a depth camera is what it is for.  The rule below is stated by this project (tests/depth_seed_restatement.py is its
+ * specification), not pinned to the reference.
+ * A job is one depth image of width x height samples on the pixel grid of the camera image AS DELIVERED (the raw grid), rows `stride`
+ * bytes apart, and a range of the corner list.  SDVL_DEPTH_F32: metres as float; SDVL_DEPTH_U16: uint16 in the machine's byte order times
+ * `scale` metres per unit (TUM: 1 / 5000; millimetres: 0.001), `scale` is ignored for F32.  A source in HBM (on_device) or in pinned /
+ * registered host memory is read where it lies — a keyframe touches ~2.3 k samples of a 1.2 MB image; a pageable host source is staged
+ * like sdvl_convert_gray's.  Corners are (x, y, level) in level coordinates as sdvl_frame_download_corners returns them.  Per corner:
+ *   centre   s = 1 << level, (X, Y) = (x s, y s).  Without a lens (dist null or d[0] == 0) (cx, cy) = (X, Y).  With one the gray image
+ *            was undistorted, so the centre is the raw pixel the corner's ray lands on: xn = (X - u0) / fx, yn = (Y - v0) / fy, the
+ *            forward model of cv::undistort with (k1, k2, p1, p2, k3) as sdvl_undistort evaluates it, cx = floor(fx xd + u0 + 0.5), cy alike
+ *   window   the nine samples at (cx + i s, cy + j s), i, j in {-1, 0, 1}
+ *   valid    a sample inside the image that is finite, > 0 (U16: nonzero), >= min_depth and <= max_depth (max_depth <= 0: no limit)
+ *   status   the first that applies: OUTSIDE the centre is off the image; HOLE the centre is not valid; FEW fewer than min_valid valid
+ *            samples; EDGE max - min over the valid samples exceeds edge_ratio x the centre's depth; else OK
+ *   out_z    the centre sample in metres, unfiltered (a seed on a rendered surface is exact); 0 unless OK
+ * Fields of `p` that are 0 (or p null) take the defaults: min_depth 0.05, no max_depth, edge_ratio 0.05, min_valid 6.  out_ok_per_job[j] =
+ * OK corners of job j.  Job ranges do not overlap; a corner no job names comes back HOLE.  All jobs of a call take ONE launch, one
+ * push up and one copy back; blocking, like sdvl_depth_filter.  SDVL_ERR_INVALID (with a message) for null pointers, an unknown
+ * format, a stride below width x bytes per sample, scale <= 0 with U16, edge_ratio < 0, min_valid outside 1 .. 9, c_begin > c_end or a
+ * range outside the corner list, a level outside 0 .. SDVL_MAX_LEVELS - 1.  n_jobs == 0 or n_corners == 0: nothing to do, 0. */
+enum sdvl_depth_format { SDVL_DEPTH_F32 = 0, SDVL_DEPTH_U16 = 1 };
+#define SDVL_DEPTH_SEED_OK 0
+#define SDVL_DEPTH_SEED_HOLE 1
+#define SDVL_DEPTH_SEED_FEW 2
+#define SDVL_DEPTH_SEED_EDGE 3
+#define SDVL_DEPTH_SEED_OUTSIDE 4
+typedef struct sdvl_depth_job {
+  const void *depth;
+  int32_t on_device;     /* the pointer is a device pointer */
+  int32_t stride;        /* bytes between rows */
+  int32_t format;        /* enum sdvl_depth_format */
+  int32_t pad_;
+  double scale;          /* metres per unit (U16) */
+  int32_t c_begin, c_end; /* range in xyl */
+} sdvl_depth_job;
+
+typedef struct sdvl_depth_seed_params {
+  double min_depth, max_depth, edge_ratio;
+  int32_t min_valid;
+  int32_t pad_;
+} sdvl_depth_seed_params;
+
+int sdvl_depth_seed(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n_corners, const int32_t *xyl,
+                    const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
+                    int32_t *out_ok_per_job);
+
 /* ---- pose from matches: FeatureAlign::SelectInliers + OptimizePose (feature_align.cc:73-82,152-243,258-283,341-431) --
  * One job per frame.  obs[] are the frame's matched features in found order: ax, ay = feature bearing x/z, y/z
  * (feature_align.cc:268), p = 3D point position, inv_cov = 1 / (1 << level).  The reference draws rand() % size once

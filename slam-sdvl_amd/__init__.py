@@ -127,6 +127,22 @@ class DepthOut(C.Structure):
                 ("b", C.c_double), ("cos_alpha", C.c_double), ("last_distance", C.c_double), ("position", C.c_double * 3)]
 
 
+# enum sdvl_depth_format and sdvl_depth_seed's status codes
+SDVL_DEPTH_F32, SDVL_DEPTH_U16 = 0, 1
+DEPTH_SEED_OK, DEPTH_SEED_HOLE, DEPTH_SEED_FEW, DEPTH_SEED_EDGE, DEPTH_SEED_OUTSIDE = 0, 1, 2, 3, 4
+
+
+class DepthJob(C.Structure):
+    """sdvl_depth_job: one registered depth image and the range of the corner list it answers for"""
+    _fields_ = [("depth", C.c_void_p), ("on_device", C.c_int32), ("stride", C.c_int32), ("format", C.c_int32), ("pad_", C.c_int32),
+                ("scale", C.c_double), ("c_begin", C.c_int32), ("c_end", C.c_int32)]
+
+
+class DepthSeedParams(C.Structure):
+    """sdvl_depth_seed_params: a field that is 0 takes its default (0.05 m, no upper limit, 0.05, 6)"""
+    _fields_ = [("min_depth", C.c_double), ("max_depth", C.c_double), ("edge_ratio", C.c_double), ("min_valid", C.c_int32), ("pad_", C.c_int32)]
+
+
 class SynthView(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("u0", C.c_double), ("v0", C.c_double),
                 ("R", C.c_double * 9), ("t", C.c_double * 3), ("plane", C.c_double * 4),
@@ -162,7 +178,7 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
@@ -738,6 +754,36 @@ class Context:
         self._check(self.lib.sdvl_depth_filter(self.h, n, _ptr(cp, dp), _ptr(rp, dp), _ptr(bv, dp), _ptr(fd, i32p), _ptr(pp, dp), C.byref(cam),
                                                states, C.byref(fparams), track_set.h if track_set is not None else None, fout))
         return fout
+
+    def depth_seed(self, jobs, width, height, xyl, cam, dist=None, **rule):
+        """sdvl_depth_seed: the depth of corners from registered depth images.  jobs: (depth, c_begin, c_end) or (depth, c_begin, c_end,
+        scale) each, depth a numpy [height, width] float32 (metres) or uint16 (units of `scale` metres) image — read where it lies in host
+        memory, padded rows allowed — or a DepthJob made by the caller (device pointers, pinned memory).  xyl [n][3] level coordinates and
+        level; cam a Camera; dist (k1, k2, p1, p2, k3) or None; rule: min_depth, max_depth, edge_ratio, min_valid (0: the default)
+        -> (z float64 [n], status uint8 [n], ok per job int32)"""
+        keep, arr = [], (DepthJob * max(len(jobs), 1))()
+        for j, job in enumerate(jobs):
+            if isinstance(job, DepthJob):
+                arr[j] = job
+                continue
+            d = job[0]
+            assert d.dtype in (np.float32, np.uint16) and d.ndim == 2 and d.strides[1] == d.itemsize and d.shape == (height, width)
+            keep.append(d)
+            arr[j] = DepthJob(d.ctypes.data, 0, d.strides[0], SDVL_DEPTH_U16 if d.dtype == np.uint16 else SDVL_DEPTH_F32, 0,
+                              float(job[3]) if len(job) > 3 else 1.0, int(job[1]), int(job[2]))
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3)
+        n = len(xyl)
+        z, status, ok = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8), np.zeros(max(len(jobs), 1), np.int32)
+        d5 = Distortion((C.c_double * 5)(*[float(x) for x in dist])) if dist is not None else None
+        p = DepthSeedParams(float(rule.pop("min_depth", 0.0)), float(rule.pop("max_depth", 0.0)), float(rule.pop("edge_ratio", 0.0)),
+                            int(rule.pop("min_valid", 0)), 0)
+        assert not rule, "unknown rule field %s" % list(rule)
+        self.lib.sdvl_depth_seed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_depth_seed(self.h, len(jobs), arr, width, height, n, xyl.ctypes.data, C.addressof(cam),
+                                             C.addressof(d5) if d5 is not None else None, C.addressof(p), z.ctypes.data, status.ctypes.data,
+                                             ok.ctypes.data))
+        return z[:n], status[:n], ok[:len(jobs)]
 
     def track_points_download(self, track_set):
         """the point rows of every tracker of a TrackSet as the device holds them: uint8 [n_trackers * max_points][144]"""

@@ -171,7 +171,17 @@ SDVLBatch::FrameStart SDVLBatch::BeginFrame(int i, const shared_ptr<Frame> &fram
   t.current_frame_ = frame;
   t.current_frame_->SetID(t.frame_counter_++);
   if (t.state_ != SDVL::STATE_RUNNING) {
-    if (!t.two_frame_init_) t.SaveFirstFrame(st);  // otherwise InitializeTrackers, once every tracker's frame is known
+    if (t.depth_seeding_) {  // the frame becomes the first keyframe in FinishKeyframes, if enough of its corners have a depth
+      t.init_failed_ = false;
+      if (DepthOf(i)) {
+        t.PrepareFirstFrame();
+      } else {  // no depth image: the frame is not kept, the next one starts over
+        if (PlaneMap *pm = dynamic_cast<PlaneMap *>(t.map_)) pm->CountNoDepth();
+        t.init_failed_ = true;
+      }
+    } else if (!t.two_frame_init_) {
+      t.SaveFirstFrame(st);  // otherwise InitializeTrackers, once every tracker's frame is known
+    }
     return kFirstFrame;
   }
   st.state = 2;
@@ -293,10 +303,26 @@ void SDVLBatch::CollectKeyframes(Step &s, bool fetch_counts) {
   s.filter_begun = true;
 }
 
+const DepthImage *SDVLBatch::DepthOf(int i) const {
+  if (!step_depths_ || step_depths_->empty() || (*step_depths_)[i].empty()) return nullptr;
+  return &(*step_depths_)[i];
+}
+
+void SDVLBatch::HandleFrames(const vector<Image> &imgs, FrameStats *stats) { HandleFrames(imgs, vector<DepthImage>(), stats); }
+
 // SDVL::HandleFrame (sdvl.cc:55-130) for B trackers
-void SDVLBatch::HandleFrames(const vector<Image> &imgs, FrameStats *stats) {
+void SDVLBatch::HandleFrames(const vector<Image> &imgs, const vector<DepthImage> &depths, FrameStats *stats) {
   const int B = static_cast<int>(trk_.size());
   if (static_cast<int>(imgs.size()) != B) throw std::runtime_error("SDVLBatch::HandleFrames: one image per tracker");
+  if (!depths.empty() && static_cast<int>(depths.size()) != B) throw std::runtime_error("SDVLBatch::HandleFrames: one depth image per tracker, or none");
+  for (int i = 0; i < B && !depths.empty(); i++)
+    if (!depths[i].empty() && (depths[i].cols != imgs[i].cols || depths[i].rows != imgs[i].rows))
+      throw std::runtime_error("SDVLBatch::HandleFrames: a depth image has the size of its camera image");
+  struct DepthScope {  // the step's depth images are named for the step alone, however it ends
+    SDVLBatch *b;
+    ~DepthScope() { b->step_depths_ = nullptr; }
+  } depth_scope{this};
+  step_depths_ = &depths;
   Device::SetCurrent(dev_);
   StageTimes::Active() = &stage_times;
   stage_times.steps++;
@@ -341,16 +367,92 @@ void SDVLBatch::HandleFrames(const vector<Image> &imgs, FrameStats *stats) {
 }
 
 // --------------------------------------------------------------------------------- SDVLBatch: what follows the decisions
+// Depth cameras: the filtered corners of the step's keyframes whose tracker seeds from depth (SDVL::SetDepthSeeding) are looked up in
+// their frames' depth images by ONE sdvl_depth_seed call.  (*z)[k] / (*status)[k]: keyframe k's results, null for a keyframe that is not
+// seeded from depth.  A keyframe that came without a depth image seeds nothing and is counted.  A first frame becomes the first keyframe
+// here if at least SDVL.min_init_corners of its corners have a depth; otherwise it is not kept (its entry of s.kfs becomes null).
+void SDVLBatch::SeedKeyframesFromDepth(Step &s, vector<const double *> *z, vector<const uint8_t *> *status) {
+  const size_t K = s.kfs.size();
+  z->assign(K, nullptr);
+  status->assign(K, nullptr);
+  bool any = false;
+  for (size_t k = 0; k < K; k++) any = any || trk_[s.kf_owner[k]]->depth_seeding_;
+  if (!any) return;
+  vector<sdvl_depth_job> jobs;
+  vector<size_t> whose;
+  vector<int32_t> xyl;
+  const sdvl_depth_seed_params *rule = nullptr;
+  for (size_t k = 0; k < K; k++) {
+    SDVL &t = *trk_[s.kf_owner[k]];
+    if (!t.depth_seeding_) continue;
+    const DepthImage *d = DepthOf(s.kf_owner[k]);
+    if (!d) continue;  // (counted below)
+    if (rule && std::memcmp(rule, &t.depth_rule_, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
+    rule = &t.depth_rule_;
+    const int begin = static_cast<int>(xyl.size() / 3), n = s.kfs[k]->NumFiltered();
+    for (int c = 0; c < n; c++) {
+      const Vector3i corner = s.kfs[k]->FilteredCorner(c);
+      xyl.insert(xyl.end(), {corner(0), corner(1), corner(2)});
+    }
+    jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, begin, begin + n});
+    whose.push_back(k);
+  }
+  const int n_corners = static_cast<int>(xyl.size() / 3);
+  depth_z_.assign(std::max(n_corners, 1), 0.0);
+  depth_status_.assign(std::max(n_corners, 1), 0);
+  vector<int32_t> ok(std::max<size_t>(jobs.size(), 1), 0);
+  if (!jobs.empty()) {
+    const Camera &camera = *trk_[0]->camera_;
+    const sdvl_camera cam = camera.abi();
+    const sdvl_distortion dist = camera.distortion();
+    dev_->Check(sdvl_depth_seed(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), s.kfs[whose[0]]->GetWidth(), s.kfs[whose[0]]->GetHeight(), n_corners,
+                                xyl.data(), &cam, camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
+                "sdvl_depth_seed");
+  }
+  for (size_t j = 0; j < jobs.size(); j++) {
+    (*z)[whose[j]] = depth_z_.data() + jobs[j].c_begin;
+    (*status)[whose[j]] = depth_status_.data() + jobs[j].c_begin;
+  }
+  size_t j = 0;
+  for (size_t k = 0; k < K; k++) {
+    SDVL &t = *trk_[s.kf_owner[k]];
+    if (!t.depth_seeding_) continue;
+    const bool looked_up = j < whose.size() && whose[j] == k;
+    if (!looked_up)
+      if (PlaneMap *pm = dynamic_cast<PlaneMap *>(t.map_)) pm->CountNoDepth();
+    if (t.first_frame_waiting_) {
+      if (looked_up && ok[j] >= Config::MinInitCorners()) {
+        t.CommitFirstFrame(s.stats[s.kf_owner[k]]);
+      } else {  // too few corners with a depth: the frame is not kept, the next one starts over
+        t.first_frame_waiting_ = false;
+        t.init_failed_ = true;
+        t.pending_kf_ = nullptr;
+        s.kfs[k] = nullptr;
+      }
+    }
+    if (looked_up) j++;
+  }
+}
+
 // stage 4, the mapper stand-in for the step's keyframes (sequential mode, main.cc:148-149): the second half of their FilterCorners round
-// trip, the seeding from the scene plane, and the seeds' rows behind the tables that stayed on the device
+// trip, the seeding from the scene plane or from the frames' depth images, and the seeds' rows behind the tables that stayed on the device
 void SDVLBatch::FinishKeyframes(Step &s) {
   if (s.kfs.empty()) return;
   Frame::FilterCornersEnd(s.kfs, &pfor_ref_);
+  vector<const double *> depth_z;
+  vector<const uint8_t *> depth_status;
+  SeedKeyframesFromDepth(s, &depth_z, &depth_status);
   vector<char> appended(s.kfs.size(), 0);
   ParallelFor(static_cast<int>(s.kfs.size()), [&](int k) {
+    if (!s.kfs[k]) return;  // a first frame that was not kept
     SDVL &t = *trk_[s.kf_owner[k]];
     PlaneMap *pm = dynamic_cast<PlaneMap *>(t.map_);
-    if (pm) pm->SeedFromFiltered(s.kfs[k]);  // other Map implementations run their own mapper on AddKeyframe
+    // other Map implementations run their own mapper on AddKeyframe
+    if (pm && t.depth_seeding_) {
+      if (depth_status[k]) pm->SeedFromDepth(s.kfs[k], depth_z[k], depth_status[k]);  // (without a depth image: no seeds)
+    } else if (pm) {
+      pm->SeedFromFiltered(s.kfs[k]);
+    }
     t.pending_kf_ = nullptr;
     if (t.track_.append_pending) {
       t.track_.append_pending = false;

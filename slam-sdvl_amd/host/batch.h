@@ -16,6 +16,10 @@ class SDVLBatch {
   ~SDVLBatch();
   // imgs[i] feeds tracker i; stats[i] receives its FrameStats
   void HandleFrames(const std::vector<Image> &imgs, FrameStats *stats);
+  // the same with the frames' registered depth images for the trackers that seed from depth (SDVL::SetDepthSeeding): depths is empty or
+  // has one entry per tracker, and single entries may be empty.  A depth image is read inside the step's ONE sdvl_depth_seed call only
+  // (FinishKeyframes); nothing is copied or kept, and the look-ahead does not need it.
+  void HandleFrames(const std::vector<Image> &imgs, const std::vector<DepthImage> &depths, FrameStats *stats);
   // Round 4: a caller that already holds the images of the NEXT step (a sequence from disk, frames resident in HBM) names them before
   // the current step: their pyramids and corner detection — all that depends on the image alone, 45 % of a step's vector instructions —
   // are queued right behind the current step's search / pose chain and run while the host waits for that chain and does its keyframe
@@ -59,7 +63,12 @@ class SDVLBatch {
   void CollectKeyframes(Step &s, bool fetch_counts);
   void EpilogueAndMapper(Step &s);
   void FinishKeyframes(Step &s);
+  void SeedKeyframesFromDepth(Step &s, std::vector<const double *> *z, std::vector<const uint8_t *> *status);
   void RunMappers();
+  const std::vector<DepthImage> *step_depths_ = nullptr;  // the depth images of the step in flight (HandleFrames)
+  const DepthImage *DepthOf(int i) const;                  // tracker i's, null: none
+  std::vector<double> depth_z_;                            // sdvl_depth_seed's results for the step's keyframes
+  std::vector<uint8_t> depth_status_;
   // ---- batch_tables.cc: the device-resident tracking tables.  The set and the rows on their way to it; besides the table functions
   // the tabled step (batch_tracked.cc) uses them, and batch.cc where it releases the set, appends a keyframe's seeds (FinishKeyframes)
   // and lets the mapper's depth filter patch the rows (RunMappers)

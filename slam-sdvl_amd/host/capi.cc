@@ -245,6 +245,55 @@ int sdvlh_batch_set_next_device(void *bp, const void *const *dev_imgs, int strid
   return Guarded([&] { AsGroup(bp)->SetNextImages(dev_imgs, stride); });
 }
 
+// ---- depth cameras (SDVL::SetDepthSeeding, TrackerGroup::SetDepth)
+// the trackers of the batch seed their keyframes from the depth images handed to the *_depth step calls: format = enum sdvl_depth_format,
+// scale = metres per unit of a 16-bit image; the rule's fields as sdvl_depth_seed_params (0: the default)
+int sdvlh_batch_set_depth(void *bp, int on, int format, double scale, double edge_ratio, int min_valid, double min_depth, double max_depth) {
+  if (!bp) return -1;
+  return Guarded([&] { AsGroup(bp)->SetDepth(on != 0, format, scale, sdvl_depth_seed_params{min_depth, max_depth, edge_ratio, min_valid, 0}); });
+}
+// the step calls with B depth pointers beside the B images (host pointers with _host, device pointers otherwise; dense rows; `depths` or
+// single entries may be null)
+int sdvlh_batch_step_host_depth(void *bp, const uint8_t *const *imgs, int stride, const void *const *depths, sdvlh_frame_stats *out) {
+  return Guarded([&] { AsGroup(bp)->Step(TrackerGroup::Frames::kHost, reinterpret_cast<const void *const *>(imgs), stride, depths, out); });
+}
+int sdvlh_batch_step_device_depth(void *bp, const void *const *dev_imgs, int stride, const void *const *dev_depths, sdvlh_frame_stats *out) {
+  return Guarded([&] { AsGroup(bp)->Step(TrackerGroup::Frames::kResident, dev_imgs, stride, dev_depths, out); });
+}
+int sdvlh_batch_step_device_transient_depth(void *bp, const void *const *dev_imgs, int stride, const void *const *dev_depths, sdvlh_frame_stats *out) {
+  return Guarded([&] { AsGroup(bp)->Step(TrackerGroup::Frames::kTransient, dev_imgs, stride, dev_depths, out); });
+}
+// the live points tracker i seeded from depth (PlaneMap::GetSeededPoints, after SyncHostState): out7 = x y z keyframe_id u v level per
+// point.  Returns how many there are (at most cap rows are written; out7 may be null with cap 0)
+int sdvlh_batch_seeded_points(void *bp, int i, int cap, double *out7) {
+  TrackerGroup *b = AsGroup(bp);
+  if (!b || i < 0 || i >= b->size()) return -1;
+  int n = -1;
+  const int rc = Guarded([&] {
+    Device::SetCurrent(b->device());
+    b->batch().SyncHostState();
+    const std::vector<PlaneMap::SeededPoint> pts = b->map(i).GetSeededPoints();
+    n = static_cast<int>(pts.size());
+    for (int k = 0; k < n && k < cap && out7; k++) {
+      const double row[7] = {pts[k].x, pts[k].y, pts[k].z, static_cast<double>(pts[k].keyframe_id), static_cast<double>(pts[k].u),
+                             static_cast<double>(pts[k].v), static_cast<double>(pts[k].level)};
+      std::memcpy(out7 + 7 * k, row, sizeof(row));
+    }
+  });
+  return rc ? -2 : n;
+}
+// tracker i's depth seeding so far: out8 = keyframes seeded, seeds, corners by status (OK, HOLE, FEW, EDGE, OUTSIDE), keyframes or first
+// frames that came without a depth image
+int sdvlh_batch_depth_stats(void *bp, int i, long long *out8) {
+  TrackerGroup *b = AsGroup(bp);
+  if (!b || i < 0 || i >= b->size() || !out8) return -1;
+  const PlaneMap::DepthStats &s = b->map(i).GetDepthStats();
+  out8[0] = s.keyframes; out8[1] = s.seeds;
+  for (int k = 0; k < 5; k++) out8[2 + k] = s.by_status[k];
+  out8[7] = s.no_depth;
+  return 0;
+}
+
 // ---- TrackerFarm (farm.h): G groups x Bg sequences on ONE GPU
 void *sdvlh_farm_create(int gpu, int G, int Bg, int w, int h, const double *cam4, const double *plane4, const double *first_poses7,
                         int host_threads_per_group) {

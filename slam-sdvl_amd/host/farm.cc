@@ -58,6 +58,25 @@ void TrackerGroup::Step(Frames where, const void *const *imgs, int stride, Frame
   batch_->HandleFrames(Wrap(where, imgs, stride), out);
 }
 
+void TrackerGroup::Step(Frames where, const void *const *imgs, int stride, const void *const *depths, FrameStats *out) {
+  for (size_t i = 0; i < trackers_.size(); i++) out[i] = FrameStats();
+  std::vector<DepthImage> d;
+  if (depths) {
+    const int bps = depth_format_ == DEPTH_U16 ? 2 : 4;
+    for (size_t i = 0; i < trackers_.size(); i++)
+      d.push_back(depths[i] ? DepthImage::Wrap(depths[i], w_, h_, w_ * bps, depth_format_, depth_scale_, where != Frames::kHost) : DepthImage());
+  }
+  batch_->HandleFrames(Wrap(where, imgs, stride), d, out);
+}
+
+void TrackerGroup::SetDepth(bool on, int format, double scale, const sdvl_depth_seed_params &rule) {
+  if (format != DEPTH_F32 && format != DEPTH_U16) throw std::invalid_argument("TrackerGroup::SetDepth: unknown depth format " + std::to_string(format));
+  if (format == DEPTH_U16 && !(scale > 0.0)) throw std::invalid_argument("TrackerGroup::SetDepth: a 16-bit depth image needs scale > 0 (metres per unit)");
+  for (auto &t : trackers_) t->SetDepthSeeding(on, rule);
+  depth_format_ = format;
+  depth_scale_ = scale;
+}
+
 void TrackerGroup::SetNextImages(const void *const *dev_imgs, int stride) {
   batch_->SetNextImages(dev_imgs ? Wrap(Frames::kResident, dev_imgs, stride) : std::vector<Image>());
 }

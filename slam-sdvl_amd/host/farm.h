@@ -39,6 +39,9 @@ class TrackerGroup {
 
   // imgs[i] (row stride `stride`, in bytes) feeds tracker i; out[i] receives its FrameStats
   void Step(Frames where, const void *const *imgs, int stride, FrameStats *out);
+  // the same with the frames' registered depth images (SetDepth): depths[i] feeds tracker i — host pointers with kHost, device pointers
+  // otherwise, dense rows of the format SetDepth named; depths or single entries may be null
+  void Step(Frames where, const void *const *imgs, int stride, const void *const *depths, FrameStats *out);
   // Look-ahead (SDVLBatch::SetNextImages): the device images the NEXT Step(kResident) will be given (null: none); their pyramids and corner
   // detection are queued behind the coming step's search / pose chain.  They must stay valid AND UNCHANGED until that call: the look-ahead
   // is matched to the next step's images by device address alone, so a buffer that is rewritten in between would be tracked from pyramids
@@ -55,6 +58,10 @@ class TrackerGroup {
   // is what main.cc computes on cv::VideoCapture's bytes; SDVL_GRAY8 (0) turns it off again.  RAW camera formats (enum sdvl_raw_format:
   // Bayer mosaics, YUYV / UYVY, 16-bit gray) are converted the same way; row strides are width x bytes per pixel.  Throws on an unknown format.
   void SetColor(int format);
+  // Depth cameras (SDVL::SetDepthSeeding for every tracker): keyframes are seeded from the depth images handed to Step, which are of
+  // `format` (DEPTH_F32 / DEPTH_U16) with `scale` metres per unit.  Throws what SDVL::SetDepthSeeding throws, and on an unknown format
+  // or a scale <= 0 with DEPTH_U16.
+  void SetDepth(bool on, int format, double scale, const sdvl_depth_seed_params &rule);
 
   Device *device() const { return dev_; }
   int size() const { return static_cast<int>(trackers_.size()); }
@@ -73,6 +80,8 @@ class TrackerGroup {
   std::unique_ptr<SDVLBatch> batch_;
   bool raw_input_ = false;  // SetDistortion: the images of a step are RAW camera frames (Image::raw)
   int format_ = PIX_GRAY8;  // SetColor: the pixel format of the images of a step
+  int depth_format_ = DEPTH_F32;  // SetDepth: the depth images of a step
+  double depth_scale_ = 1.0;
 };
 
 class TrackerFarm {

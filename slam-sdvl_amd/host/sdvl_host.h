@@ -32,6 +32,19 @@ class PlaneMap : public Map {
   void InitCandidates(const std::shared_ptr<Frame> &kf) override;
   void SeedFromFiltered(const std::shared_ptr<Frame> &kf);  // after Frame::FilterCorners()
   void SetPlane(const Vector3d &n, double d) { n_ = n; d_ = d; }
+  // Depth cameras: the sibling of SeedFromFiltered for a keyframe whose filtered corners have been looked up in a registered depth image
+  // (sdvl_depth_seed: z[k] metres along the optical axis and status[k] of filtered corner k).  Every corner with status OK gets the feature
+  // and the descriptor SeedFromFiltered gives it and a FIXED point at s = z / v_z along its bearing v — the same variance (0.05 / s)^2 and
+  // the same bookkeeping, so the tracking tables take its rows unchanged; every other corner gets no point.  The plane is not read.
+  void SeedFromDepth(const std::shared_ptr<Frame> &kf, const double *z, const uint8_t *status);
+  // what depth seeding did so far: keyframes seeded, points seeded, the corners by status (sdvl_depth_seed's codes, [0] = OK), and the
+  // keyframes (or first frames) of a depth-seeding tracker that arrived without a depth image
+  struct DepthStats { long keyframes = 0, seeds = 0, by_status[5] = {0, 0, 0, 0, 0}, no_depth = 0; };
+  const DepthStats &GetDepthStats() const { return depth_stats_; }
+  void CountNoDepth() { depth_stats_.no_depth++; }
+  // the live points seeded from depth, oldest first: position, the frame id of their keyframe, their corner (level coordinates, level)
+  struct SeededPoint { double x, y, z; int keyframe_id, u, v, level; };
+  std::vector<SeededPoint> GetSeededPoints() const;
   // Round 5: the stub honours SDVL.max_keyframes like the reference's map (map.cc:190-205,692-706: once the list is full, the
   // keyframe furthest from the new one goes to the trash) — and, being the owner of the points it seeded there, deletes the points
   // whose FIRST observation lies in the culled keyframe with it (the reference keeps a culled keyframe's image alive for as long as
@@ -44,6 +57,9 @@ class PlaneMap : public Map {
   Vector3d n_;
   double d_;
   std::vector<std::shared_ptr<Frame>> culled_;
+  struct DepthSeedRec { std::weak_ptr<Point> point; int keyframe_id, u, v, level; };
+  std::vector<DepthSeedRec> depth_seeds_;  // SeedFromDepth drops the records of points that are gone
+  DepthStats depth_stats_;
 };
 
 // map.h:44-139 — the reference's mapper in SEQUENTIAL mode (main.cc:148-149: SDVL::Mapping() = Map::UpdateMap() after every
@@ -180,6 +196,16 @@ class SDVL {
   // where the reference stays stuck) makes HandleFrame return false and starts over with the next frame as first frame.
   void SetTwoFrameInit(bool on);
   bool TwoFrameInit() const { return two_frame_init_; }
+  // Depth cameras (an addition): every keyframe this tracker's map would seed from the scene plane — each one with the plane map, the
+  // bootstrap keyframe with the reference's mapper, which carries on as after the plane bootstrap — is seeded from the registered depth
+  // image handed over with its frame instead (HandleFrame(img, depth), SDVLBatch::HandleFrames(imgs, depths, stats)): metric scale, no
+  // plane, any scene geometry.  `rule`: sdvl_depth_seed_params, zero fields take the defaults; the trackers of one batch share it.
+  // A keyframe that arrives without a depth image seeds nothing and is counted (PlaneMap::GetDepthStats).  A first frame without a depth
+  // image, or with fewer OK seeds than SDVL.min_init_corners, is not kept: HandleFrame returns false and the next frame starts over (the
+  // deviation SetTwoFrameInit documents).  Throws std::runtime_error together with the two-frame initialisation — the two answer the same
+  // question — and with a map that is neither PlaneMap nor MapperMap; std::invalid_argument for a rule sdvl_depth_seed would refuse.
+  void SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule = sdvl_depth_seed_params{0.0, 0.0, 0.0, 0, 0});
+  bool DepthSeeding() const { return depth_seeding_; }
   // Map::BundleAdjustment after every keyframe update of a map with more than two keyframes (map.cc:130-137), on the device
   // (sdvl_bundle_adjust).  Off by default.  Needs the reference's mapper in sequential mode: throws std::runtime_error with any other map
   // and while the mapper thread runs.
@@ -193,6 +219,7 @@ class SDVL {
   void Stop() { map_->Stop(); }
   void Mapping();
   bool HandleFrame(const Image &img);
+  bool HandleFrame(const Image &img, const DepthImage &depth);  // SetDepthSeeding: the frame's registered depth image (empty: none)
   // Round 5, an addition for callers that READ a sequence (main.cc's Video.type 1: images from disk are there before they are needed):
   // name the image the NEXT HandleFrame call will be given (a device image, e.g. what Camera::UndistortImage returns, kept alive and
   // unchanged until that call).  Its pyramid and corner detection are queued behind the coming call's chain and run while the host
@@ -214,6 +241,12 @@ class SDVL {
   void GetMotionModel();
   void ResetMotionModel();
   void SaveFirstFrame(FrameStats &st);
+  // SaveFirstFrame in two halves for a depth-seeding tracker: the frame takes the first pose and waits for its corners' depth lookup;
+  // it becomes the first keyframe once enough of them have a depth (SDVLBatch::FinishKeyframes)
+  void PrepareFirstFrame();
+  void CommitFirstFrame(FrameStats &st);
+  bool depth_seeding_ = false, first_frame_waiting_ = false;
+  sdvl_depth_seed_params depth_rule_ = {0.0, 0.0, 0.0, 0, 0};
   bool InitFirstFrame(FrameStats &st);                       // sdvl.cc:132-148 (two-frame initialisation)
   void SecondFrameDone(bool initialised, FrameStats &st);    // sdvl.cc:154-176 behind HomographyInit::InitSecondFrame
   bool two_frame_init_ = false, init_failed_ = false;

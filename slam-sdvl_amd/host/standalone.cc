@@ -281,6 +281,48 @@ void PlaneMap::SeedFromFiltered(const shared_ptr<Frame> &kf) {
   }
 }
 
+// Depth cameras: SeedFromFiltered with the scale from a registered depth image.  z is the camera-frame depth (along the optical axis), the
+// bearing v is a unit vector, so the point lies at s = z / v_z along it; on a fronto-parallel plane seen from the identity pose that is the
+// plane's (d - n.t) / (n.ray) with the same operands.  The `fixed` branch of Map::InitCandidates (map.cc:269,385-389) is what this feeds.
+void PlaneMap::SeedFromDepth(const shared_ptr<Frame> &kf, const double *z, const uint8_t *status) {
+  const SE3 world = kf->GetWorldPose();
+  const int n_filtered = kf->NumFiltered();
+  depth_seeds_.erase(std::remove_if(depth_seeds_.begin(), depth_seeds_.end(), [](const DepthSeedRec &r) { return r.point.expired(); }),
+                     depth_seeds_.end());
+  depth_stats_.keyframes++;
+  for (int k = 0; k < n_filtered; k++) {
+    depth_stats_.by_status[status[k] <= SDVL_DEPTH_SEED_OUTSIDE ? status[k] : SDVL_DEPTH_SEED_HOLE]++;
+    if (status[k] != SDVL_DEPTH_SEED_OK) continue;
+    const Vector3i corner = kf->FilteredCorner(k);
+    const int scale = (1 << corner(2));
+    shared_ptr<Feature> feature = kf->NewFeature(Vector2d(corner(0) * scale, corner(1) * scale), corner(2));
+    if (Config::UseORB()) feature->SetDescriptor(kf->FilteredDescriptor(k));
+    const Vector3d &v = feature->GetVector();
+    const double s = z[k] / v(2);
+    if (!(s > 0.05)) continue;
+    shared_ptr<Point> pt = kf->NewPoint();
+    const double rho = 1.0 / s;
+    pt->InitFixed(feature, s, (0.05 * rho) * (0.05 * rho), world * Vector3d(s * v(0), s * v(1), s * v(2)));
+    version_++;
+    feature->SetPoint(pt);
+    kf->AddFeature(feature);
+    pt->AddFeature(feature);
+    depth_seeds_.push_back(DepthSeedRec{pt, kf->GetID(), corner(0), corner(1), corner(2)});
+    depth_stats_.seeds++;
+  }
+}
+
+vector<PlaneMap::SeededPoint> PlaneMap::GetSeededPoints() const {
+  vector<SeededPoint> out;
+  for (const DepthSeedRec &r : depth_seeds_) {
+    const shared_ptr<Point> p = r.point.lock();
+    if (!p || p->ToDelete()) continue;
+    const Vector3d pos = p->GetPosition();
+    out.push_back(SeededPoint{pos(0), pos(1), pos(2), r.keyframe_id, r.u, r.v, r.level});
+  }
+  return out;
+}
+
 // ----------------------------------------------------------------------------------------------------------- SDVL
 SDVL::SDVL(Camera *camera, Map *map, const SE3 &first_pose)
     : camera_(camera), map_(map), rng_(1), feature_align_(map, camera, Config::MaxMatches(), &rng_), first_pose_(first_pose) {}
@@ -423,6 +465,35 @@ void SDVL::SaveFirstFrame(FrameStats &st) {
   st.keyframe = 1;
 }
 
+// SaveFirstFrame for a tracker that seeds from depth: whether the frame becomes the first keyframe is known once its filtered corners have
+// been looked up in the depth image (SDVLBatch::FinishKeyframes)
+void SDVL::PrepareFirstFrame() {
+  current_frame_->SetPose(first_pose_);
+  pending_kf_ = current_frame_;
+  first_frame_waiting_ = true;
+}
+
+void SDVL::CommitFirstFrame(FrameStats &st) {
+  first_frame_waiting_ = false;
+  current_frame_->SetKeyframe();
+  map_->AddKeyframe(current_frame_, false);
+  last_frame_ = current_frame_;
+  last_kf_ = current_frame_;
+  state_ = STATE_RUNNING;
+  track_.valid = false;
+  st.state = 0;
+  st.keyframe = 1;
+}
+
+void SDVL::SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule) {
+  if (on && two_frame_init_) throw std::runtime_error("SDVL::SetDepthSeeding: the tracker takes the two-frame initialisation; the two answer the same question");
+  if (on && !dynamic_cast<PlaneMap *>(map_)) throw std::runtime_error("SDVL::SetDepthSeeding needs a PlaneMap or the reference's mapper (MapperMap)");
+  if (on && (rule.edge_ratio < 0.0 || rule.min_valid < 0 || rule.min_valid > 9))
+    throw std::invalid_argument("SDVL::SetDepthSeeding: edge_ratio is negative or min_valid lies outside 1 .. 9");
+  depth_seeding_ = on;
+  depth_rule_ = rule;
+}
+
 void SDVL::SetBundleAdjustment(bool on) {
   MapperMap *m = AsMapperMap(map_);
   if (!m) throw std::runtime_error("SDVL::SetBundleAdjustment needs the reference's mapper (MapperMap)");
@@ -431,6 +502,7 @@ void SDVL::SetBundleAdjustment(bool on) {
 
 void SDVL::SetTwoFrameInit(bool on) {
   if (on && !AsMapperMap(map_)) throw std::runtime_error("SDVL::SetTwoFrameInit needs the reference's mapper (MapperMap)");
+  if (on && depth_seeding_) throw std::runtime_error("SDVL::SetTwoFrameInit: the tracker seeds from depth (SetDepthSeeding); the two answer the same question");
   two_frame_init_ = on;
   if (on && !h_init_) h_init_.reset(new HomographyInit(map_, Config::MinAvgShift()));
 }
@@ -525,7 +597,9 @@ void SDVL::SetNextImage(const Image &next) {
   next_image_.assign(1, next);
 }
 
-bool SDVL::HandleFrame(const Image &img) {
+bool SDVL::HandleFrame(const Image &img) { return HandleFrame(img, DepthImage()); }
+
+bool SDVL::HandleFrame(const Image &img, const DepthImage &depth) {
   std::unique_lock<std::mutex> lock(map_->GetMutex());  // the mapper thread of threaded mode stays out meanwhile
   FrameStats st;
   Device *dev = Device::Current();
@@ -539,7 +613,7 @@ bool SDVL::HandleFrame(const Image &img) {
     next_image_.clear();
   }
   try {
-    self_batch_->HandleFrames({img}, &st);
+    self_batch_->HandleFrames({img}, depth.empty() ? std::vector<DepthImage>() : std::vector<DepthImage>{depth}, &st);
   } catch (...) {
     // a step that failed half way leaves the set's tables and its own bookkeeping in an unknown state: the next call starts with a
     // fresh batch and rebuilds the table from the host objects

@@ -11,6 +11,10 @@
 //                                                                a P5 of width 2 W carries a W-pixel frame.  16-bit PGM (maxval > 255) is big-endian: unsupported
 //   track_sequence --synthetic N --scene shelf                   N frames of a scene with depth (csrc/sdvl_synth_scene.h: several surfaces, nearest hit) instead of
 //                                                                the one plane; the map still bootstraps from --plane (the default is the scene's wall)
+//   track_sequence --synthetic N --scene shelf --depth           a depth camera: every frame comes with the renderer's registered depth image and the
+//                                                                keyframes' points are seeded from it (SDVL::SetDepthSeeding) — no plane; a --plane is ignored
+//   track_sequence --list frames.txt --depth-list depth.txt --depth-scale S   the same from disk: one 16-bit binary PGM (P5, maxval above 255; netpbm's samples are
+//                                                                big-endian and are swapped here) per frame, S metres per unit (TUM: 0.0002)
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
 //   round 5 (bench.py's latency legs):  [--texture plane|camera]  [--trackers N]  N cameras = N host threads, each with its own Device
 //            (= HIP stream), Camera, Map and SDVL, all fed the same frames;  [--batch]  with --trackers N: the N cameras step together through
@@ -73,6 +77,30 @@ bool ReadPNM(const std::string &path, int *w, int *h, std::vector<uint8_t> *px, 
   return static_cast<size_t>(f.gcount()) == px->size();
 }
 
+// a depth image: binary PGM (P5) with 16-bit samples (maxval above 255), which netpbm stores big-endian: swapped to the machine's order
+bool ReadDepthPGM(const std::string &path, int *w, int *h, std::vector<uint16_t> *px) {
+  std::ifstream f(path, std::ios::binary);
+  std::string magic;
+  if (!(f >> magic) || magic != "P5") return false;
+  int vals[3], n = 0;
+  while (n < 3) {
+    f >> std::ws;
+    if (f.peek() == '#') { std::string skip; std::getline(f, skip); continue; }
+    if (!(f >> vals[n])) return false;
+    n++;
+  }
+  if (vals[2] <= 255 || vals[2] > 65535 || vals[0] <= 0 || vals[1] <= 0) return false;
+  f.get();
+  *w = vals[0];
+  *h = vals[1];
+  std::vector<uint8_t> bytes(static_cast<size_t>(vals[0]) * vals[1] * 2);
+  f.read(reinterpret_cast<char *>(bytes.data()), static_cast<std::streamsize>(bytes.size()));
+  if (static_cast<size_t>(f.gcount()) != bytes.size()) return false;
+  px->resize(bytes.size() / 2);
+  for (size_t i = 0; i < px->size(); i++) (*px)[i] = static_cast<uint16_t>((bytes[2 * i] << 8) | bytes[2 * i + 1]);
+  return true;
+}
+
 // --raw-format NAME -> PIX_* (0: no such name)
 int RawFormatByName(const std::string &name) {
   static const char *const names[] = {"bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr", "yuyv", "uyvy", "gray10", "gray12", "gray16"};
@@ -82,13 +110,15 @@ int RawFormatByName(const std::string &name) {
 }
 
 const char kUsage[] =
-    "track_sequence --synthetic N [--seed S] [--scene NAME] | --list frames.txt [--raw-format NAME]\n"
+    "track_sequence --synthetic N [--seed S] [--scene NAME [--depth]] | --list frames.txt [--raw-format NAME] [--depth-list depth.txt --depth-scale S]\n"
     "  --list: one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB) path per line\n"
     "  --raw-format NAME: the P5 files are raw camera frames, converted to gray on the device:\n"
     "      bayer_rggb | bayer_grbg | bayer_gbrg | bayer_bggr   a Bayer mosaic, named by the 2x2 tile at its top-left corner\n"
     "      yuyv | uyvy                                         YUV 4:2:2; the P5 is 2 W bytes wide for a W-pixel frame\n"
     "      gray10 | gray12 | gray16                            little-endian 16-bit gray; the P5 is 2 W bytes wide\n"
     "    16-bit PGM (maxval above 255) is big-endian and is not supported\n"
+    "  --depth: with --synthetic N --scene NAME, the keyframes' points are seeded from the renderer's registered depth image (no plane)\n"
+    "  --depth-list FILE --depth-scale S: one 16-bit P5 depth image (big-endian samples, S metres per unit) per frame of --list\n"
     "  common: [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle]\n"
     "          [--init plane|two-frame] [--trackers N] [--batch] [--lookahead] [--prerender] [--pageable] [--set SDVL.key value]\n"
     "          [--quiet] [--json] [--profile]\n";
@@ -113,6 +143,9 @@ int main(int argc, char **argv) {
   bool mapper = false, bundle = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
   bool prerender = false, pageable = false, quiet = false, json = false, profile = false, batch = false, lookahead = false;
   int n_trackers = 1, raw_format = 0;
+  bool depth = false, plane_given = false;
+  std::string depth_list;
+  double depth_scale = 0.0;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
   unsigned texture = SDVL_TEXTURE_PLANE_NOISE;
   for (int i = 1; i < argc; i++) {
@@ -127,7 +160,10 @@ int main(int argc, char **argv) {
     else if (a == "--size") { need(2); W = std::atoi(argv[++i]); H = std::atoi(argv[++i]); size_given = true; }
     else if (a == "--cam") { need(4); for (int k = 0; k < 4; k++) cam4[k] = std::atof(argv[++i]); cam_given = true; }
     else if (a == "--dist") { need(5); for (int k = 0; k < 5; k++) dist[k] = std::atof(argv[++i]); dist_given = true; }
-    else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) plane[k] = std::atof(argv[++i]); }
+    else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) plane[k] = std::atof(argv[++i]); plane_given = true; }
+    else if (a == "--depth") depth = true;
+    else if (a == "--depth-list") { need(1); depth_list = argv[++i]; depth = true; }
+    else if (a == "--depth-scale") { need(1); depth_scale = std::atof(argv[++i]); }
     else if (a == "--mapper") mapper = true;
     else if (a == "--bundle") { bundle = true; mapper = true; }  // local bundle adjustment of every new keyframe (SDVL::SetBundleAdjustment; implies --mapper)
     else if (a == "--init") { need(1); const std::string t = argv[++i]; if (t == "two-frame") { two_frame = true; mapper = true; } else if (t != "plane") { std::cerr << "unknown --init " << t << std::endl; return 2; } }
@@ -155,6 +191,12 @@ int main(int argc, char **argv) {
     }
   }
   const bool use_scene = !scene_name.empty();
+  if (depth) {
+    if (depth_list.empty() && !use_scene) { std::cerr << "--depth tracks on the renderer's depth: give --synthetic N --scene NAME, or --depth-list FILE with --list" << std::endl; return 2; }
+    if (!depth_list.empty() && (list.empty() || !(depth_scale > 0.0))) { std::cerr << "--depth-list goes with --list and --depth-scale S (metres per unit, above 0)" << std::endl; return 2; }
+    if (batch || prerender || n_trackers > 1) { std::cerr << "--depth runs one camera on frames made inside the loop: not with --batch, --trackers or --prerender" << std::endl; return 2; }
+    if (plane_given) std::cerr << "note: --plane is ignored, the keyframes' points are seeded from depth" << std::endl;
+  }
 
   // main.cc:60-75: configuration file, then the TUM overrides the reference's config_tum_f1.cfg carries
   Config &c = Config::GetInstance();
@@ -179,6 +221,13 @@ int main(int argc, char **argv) {
     for (std::string line; std::getline(lf, line);)
       if (!line.empty() && line[0] != '#') files.push_back(line);
     if (files.empty()) { std::cerr << "no frames in " << list << std::endl; return 2; }
+  }
+  std::vector<std::string> depth_files;
+  if (!depth_list.empty()) {
+    std::ifstream lf(depth_list);
+    for (std::string line; std::getline(lf, line);)
+      if (!line.empty() && line[0] != '#') depth_files.push_back(line);
+    if (depth_files.size() != files.size()) { std::cerr << depth_list << " names " << depth_files.size() << " depth images for " << files.size() << " frames" << std::endl; return 2; }
   }
   const int n_frames = n_synth > 0 ? n_synth : static_cast<int>(files.size());
 
@@ -253,7 +302,7 @@ int main(int argc, char **argv) {
       render_dev->Check(sdvl_device_free(rc, dbuf), "sdvl_device_free");
     }
 
-    struct PerTracker { double busy = 0.0; int tracked = 0; std::vector<float> ms; std::string err; };
+    struct PerTracker { double busy = 0.0; int tracked = 0; std::vector<float> ms; std::string err; PlaneMap::DepthStats depth; };
     std::vector<PerTracker> per(n_trackers);
     std::atomic<int> ready{0};
     std::atomic<bool> go{false};
@@ -271,6 +320,9 @@ int main(int argc, char **argv) {
         SDVL sdvl(&camera, map.get());
         if (two_frame) sdvl.SetTwoFrameInit(true);
         if (bundle) sdvl.SetBundleAdjustment(true);
+        if (depth) sdvl.SetDepthSeeding(true);
+        std::vector<float> depth_f32(depth && depth_list.empty() ? frame_bytes : 0);
+        std::vector<uint16_t> depth_u16;
         std::vector<uint8_t> px(pool ? 0 : frame_bytes);
         me.ms.reserve(n_frames);
         Image ahead;
@@ -284,6 +336,9 @@ int main(int argc, char **argv) {
           int format = PIX_GRAY8, file_w = W;
           if (pool) {
             data = pool + frame_bytes * k;
+          } else if (n_synth > 0 && depth) {  // the image and its registered depth (through the lens of --dist: both on the raw grid)
+            const sdvl_synth_scene sc = scene_of(k);
+            sdvl_synth_render_scene_host(&sc, W, H, px.data(), W, depth_f32.data(), nullptr);
           } else if (n_synth > 0) {
             render_host(k, px.data());
           } else {
@@ -315,8 +370,19 @@ int main(int argc, char **argv) {
             if (k > 0) sdvl.SetNextImage(ahead);                   // (frame 0 is the bootstrap: no tracked step to queue behind)
           }
           if (k == 1 && profile) dev.Check(sdvl_ctx_timing_enable(dev.ctx(), 1), "sdvl_ctx_timing_enable");
+          DepthImage dimg;
+          if (depth && depth_list.empty()) {
+            dimg = DepthImage::Wrap(depth_f32.data(), W, H, W * 4, DEPTH_F32, 1.0, false);
+          } else if (depth) {
+            int w = 0, h = 0;
+            if (!ReadDepthPGM(depth_files[k], &w, &h, &depth_u16) || w != W || h != H) {
+              me.err = "cannot read " + depth_files[k] + " as a 16-bit binary PGM of the configured size";
+              return;
+            }
+            dimg = DepthImage::Wrap(depth_u16.data(), W, H, W * 2, DEPTH_U16, depth_scale, false);
+          }
           const auto t0 = std::chrono::steady_clock::now();
-          sdvl.HandleFrame(imgu);                                 // main.cc:136-138
+          sdvl.HandleFrame(imgu, dimg);                           // main.cc:136-138
           if (mapper) sdvl.Mapping();                             // sequential mode, main.cc:148-149
           const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
           const FrameStats &st = sdvl.LastStats();
@@ -325,6 +391,7 @@ int main(int argc, char **argv) {
             std::printf("%d %d %d %d %d %d  %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", k, st.state, st.quality, st.matches, st.attempts, st.inliers,
                         st.pose[0], st.pose[1], st.pose[2], st.pose[3], st.pose[4], st.pose[5], st.pose[6]);
         }
+        if (depth) me.depth = dynamic_cast<PlaneMap *>(map.get())->GetDepthStats();
         if (profile && id == 0) {
           char names[32][32];
           double ms[32];
@@ -448,6 +515,11 @@ int main(int argc, char **argv) {
     const double per_camera = batch ? total / n_trackers : (busy_sum > 0 ? tracked / busy_sum : 0.0);
     std::fprintf(stderr, "%d tracked frames in %.3f s of HandleFrame = %.1f tracked frames/s (%d sequence(s), one stream each; per camera %.1f)\n", tracked,
                  busy_max, total, n_trackers, per_camera);
+    if (depth) {
+      const PlaneMap::DepthStats &d = per[0].depth;
+      std::fprintf(stderr, "depth seeding: %ld keyframes, %ld seeds; corners OK %ld HOLE %ld FEW %ld EDGE %ld OUTSIDE %ld; %ld frames without depth\n", d.keyframes, d.seeds,
+                   d.by_status[0], d.by_status[1], d.by_status[2], d.by_status[3], d.by_status[4], d.no_depth);
+    }
     if (json)
       std::printf("{\"trackers\": %d, \"frames\": %d, \"tracked\": %d, \"frames_per_s\": %.2f, \"frames_per_s_per_camera\": %.2f, \"ms_per_frame_p50\": %.4f, "
                   "\"ms_per_frame_p95\": %.4f, \"ms_per_frame_max\": %.4f, \"wall_s\": %.3f, \"input\": \"%s\", \"texture\": \"%s\", \"width\": %d, \"height\": %d, "

@@ -186,6 +186,24 @@ struct Image {
   }
 };
 
+// (an addition) A depth image REGISTERED to the camera image as delivered (the raw pixel grid): a header over caller-owned samples, host or
+// HBM.  DEPTH_F32: metres; DEPTH_U16: units of `scale` metres (TUM 1 / 5000, millimetres 0.001) — enum sdvl_depth_format of
+// include/sdvl_hip.h.  Read only while a keyframe's points are seeded (sdvl_depth_seed), never copied or kept.  Empty means none.
+enum DepthFormat { DEPTH_F32 = 0, DEPTH_U16 = 1 };
+struct DepthImage {
+  const void *data = nullptr;
+  int cols = 0, rows = 0, step = 0;  // step: bytes between rows
+  int format = DEPTH_F32;
+  double scale = 1.0;
+  bool on_device = false;
+  bool empty() const { return !data || cols == 0 || rows == 0; }
+  static DepthImage Wrap(const void *p, int w, int h, int stride, int depth_format, double metres_per_unit, bool device) {
+    DepthImage r;
+    r.data = p; r.cols = w; r.rows = h; r.step = stride; r.format = depth_format; r.scale = metres_per_unit; r.on_device = device;
+    return r;
+  }
+};
+
 }  // namespace sdvl
 
 #endif  // SDVL_HOST_TYPES_H_

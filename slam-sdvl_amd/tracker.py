@@ -143,6 +143,7 @@ class TrackerBatch:
         self.dev = dev
         self.B, self.w, self.h_img = B, w, h
         self.channels = 1   # set_color
+        self.depth_dtype = np.float32   # set_depth
         cam4 = np.ascontiguousarray(cam4, np.float64)
         plane4 = np.ascontiguousarray(plane4, np.float64)
         if first_poses is None:
@@ -153,19 +154,71 @@ class TrackerBatch:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         self._stats = (FrameStats * B)()
 
-    def step_host(self, imgs):
+    def _step_depth(self, name, ptrs, depth_ptrs):
+        """a step call with the B depth pointers beside the images (None entries: no depth image for that tracker)"""
+        fn = getattr(self.lib, name)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        assert len(depth_ptrs) == self.B, "one depth image per tracker (None: none)"
+        dptrs = (C.c_void_p * self.B)(*[None if p is None else int(p) for p in depth_ptrs])
+        if fn(self.h, ptrs, self.w * self.channels, dptrs, self._stats) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        return self._stats
+
+    def step_host(self, imgs, depths=None):
+        """depths (set_depth): per tracker the frame's registered depth image, numpy [h, w] float32 or uint16 as set_depth named it, or None"""
         # (16-bit gray frames go as their little-endian bytes)
         imgs = [np.ascontiguousarray(im, "<u2").view(np.uint8) if np.asarray(im).dtype == np.uint16 else np.ascontiguousarray(im, np.uint8) for im in imgs]
         ptrs = (C.c_void_p * self.B)(*[im.ctypes.data for im in imgs])
+        if depths is not None:
+            depths = [None if d is None else np.ascontiguousarray(d, self.depth_dtype).reshape(self.h_img, self.w) for d in depths]
+            return self._step_depth("sdvlh_batch_step_host_depth", ptrs, [None if d is None else d.ctypes.data for d in depths])
         if self.lib.sdvlh_batch_step_host(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
 
-    def step_device(self, dev_ptrs):
+    def step_device(self, dev_ptrs, depth_ptrs=None):
+        """depth_ptrs (set_depth): per tracker the device pointer of the frame's registered depth image (dense rows), or None"""
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs])
+        if depth_ptrs is not None:
+            return self._step_depth("sdvlh_batch_step_device_depth", ptrs, depth_ptrs)
         if self.lib.sdvlh_batch_step_device(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
+
+    def set_depth(self, on=True, format="f32", scale=1.0, edge_ratio=0.0, min_valid=0, min_depth=0.0, max_depth=0.0):
+        """depth cameras: the trackers seed their keyframes' points from the registered depth image handed over with each frame (depths= /
+        depth_ptrs= of the step calls) instead of the scene plane — every keyframe on the plane map, the bootstrap keyframe with the
+        reference's mapper.  format "f32" (metres) or "u16" (units of `scale` metres: TUM 1 / 5000, millimetres 0.001); the rule's fields
+        as sdvl_depth_seed_params (0: the default — edge_ratio 0.05, min_valid 6, min_depth 0.05, no max_depth).  A first frame without a
+        depth image, or with fewer usable corners than SDVL.min_init_corners, is not kept (state 0) and the next frame starts over.
+        Raises together with set_two_frame_init(True)"""
+        code = {"f32": 0, "u16": 1}.get(format.lower() if isinstance(format, str) else None)
+        if code is None:
+            raise ValueError("unknown depth format %r (f32 or u16)" % (format,))
+        self.lib.sdvlh_batch_set_depth.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]
+        if self.lib.sdvlh_batch_set_depth(self.h, int(bool(on)), code, float(scale), float(edge_ratio), int(min_valid), float(min_depth),
+                                          float(max_depth)) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        self.depth_dtype = np.uint16 if code == 1 else np.float32
+
+    def seeded_points(self, i):
+        """the live points tracker i seeded from depth, oldest first: rows of x y z keyframe_id u v level (float64; u, v in level coordinates)"""
+        self.lib.sdvlh_batch_seeded_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        n = self.lib.sdvlh_batch_seeded_points(self.h, int(i), 0, None)
+        if n < 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode() if n == -2 else "no tracker %d" % i)
+        out = np.zeros((max(n, 1), 7), np.float64)
+        n = self.lib.sdvlh_batch_seeded_points(self.h, int(i), n, out.ctypes.data)
+        return out[:n].copy()
+
+    def depth_stats(self, i):
+        """tracker i's depth seeding so far: dict(keyframes, seeds, ok, hole, few, edge, outside, no_depth) — keyframes seeded, points
+        seeded, the keyframes' filtered corners by status, keyframes or first frames that came without a depth image"""
+        out = (C.c_longlong * 8)()
+        self.lib.sdvlh_batch_depth_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        if self.lib.sdvlh_batch_depth_stats(self.h, int(i), out) != 0:
+            raise RuntimeError("no tracker %d" % i)
+        return dict(zip(("keyframes", "seeds", "ok", "hole", "few", "edge", "outside", "no_depth"), [int(v) for v in out]))
 
     def set_next_device(self, dev_ptrs):
         """look-ahead: the device images the NEXT step_device call will be given (None: none); their pyramids and corner detection
@@ -236,10 +289,12 @@ class TrackerBatch:
         n = self.lib.sdvlh_batch_keyframe_poses(self.h, int(i), n, poses.ctypes.data, ids.ctypes.data)
         return ids[:n].copy(), poses[:n].copy()
 
-    def step_device_transient(self, dev_ptrs):
+    def step_device_transient(self, dev_ptrs, depth_ptrs=None):
         """frames in HBM that stay valid for THIS step only (a slot of an input ring): aliased while tracked, frames that become
-        keyframes take a copy at the end of the step"""
+        keyframes take a copy at the end of the step.  depth_ptrs as for step_device: a depth image is read inside the step only"""
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs])
+        if depth_ptrs is not None:
+            return self._step_depth("sdvlh_batch_step_device_transient_depth", ptrs, depth_ptrs)
         if self.lib.sdvlh_batch_step_device_transient(self.h, ptrs, self.w * self.channels, self._stats) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats

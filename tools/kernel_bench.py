@@ -143,6 +143,23 @@ ctx.synchronize()
 t_d = ctx.timing_get().get("search_points", (0.0, 0))
 print("search_points, LK sums as a wave butterfly (tolerance class): %.1f us/launch; found flags that differ from the sequential sums: %d of %d" %
       ((t_d[0] - t_c[0]) / max(1, t_d[1] - t_c[1]) * 1e3, sum(a.found != b.found for a, b in zip(sres2, sres3)), nreq))
+# depth cameras: sdvl_depth_seed for up to 300 corners of every frame (a keyframe's filtered corners are ~265), one job per frame over a
+# float depth image in HBM, all n jobs in ONE call: the entry blocks, so the kernel's dispatch time is a small part of what a caller waits for
+import torch
+dmap = torch.full((n, H, W), 2.0, dtype=torch.float32, device="cuda")
+torch.cuda.synchronize()
+dxyl = np.concatenate([c0s[j][:300] for j in range(n)]).astype(np.int32)
+djobs, at = [], 0
+for j in range(n):
+    m = min(300, len(c0s[j]))
+    djobs.append(sdvl.DepthJob(dmap.data_ptr() + 4 * j * W * H, 1, 4 * W, sdvl.SDVL_DEPTH_F32, 0, 1.0, at, at + m))
+    at += m
+import time
+t0 = time.perf_counter()
+for _ in range(reps):
+    dz, dstatus, dok = ctx.depth_seed(djobs, W, H, dxyl, cam)
+print("depth_seed: %d corners of %d frames per call, %d OK; %.1f us per blocking call (host wall, push + launch + copy back + wait)" %
+      (len(dxyl), n, int(dok.sum()), (time.perf_counter() - t0) / reps * 1e6))
 # pose stage: n jobs of 190 matches (20 % gross outliers) of a small camera motion; rand() draws from numpy (timing only)
 prng = np.random.default_rng(7)
 pose_jobs = []
@@ -172,7 +189,7 @@ P = [(W >> l) * (H >> l) for l in range(5)]
 alg = {"pyr_down": (sum(P[:4]) + sum(P[1:])) / 4.0, "fast_cells": sum(P[:3]) + 16 * nc, "select_cells": 4 * 10000 + 6 * nc + 1600, "select_pack": 1600 + 30 * nc,
        "orb_describe": 993 * nc, "image_align": 147 * nf + 25 * nf * i_ia, "pose_hypotheses": 48 * nf + 6400, "undistort": 2 * W * H,
        "search_points": 12 * nc + nf * (121 + 164 + lk * 81), "search_prepare": nf * (120 + 80),
-       "pose_refine": 52 * nf + 6480}
+       "pose_refine": 52 * nf + 6480, "depth_seed": min(300.0, nc) * (9 * 4 + 12 + 9)}
 print("n_frames=%d reps=%d corners/frame=%.0f GN evaluations/job=%.1f" % (n, reps, nc, i_ia))
 for k, (ms, launches) in sorted(t.items()):
     us = ms / launches * 1e3
