@@ -549,6 +549,43 @@ typedef struct sdvl_depth_seed_params {
 int sdvl_depth_seed(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n_corners, const int32_t *xyl,
                     const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
                     int32_t *out_ok_per_job);
+/* A pageable depth image is copied to the device by the call that is given it.  Between these two calls (one step of a caller that hands the
+ * same images to sdvl_depth_seed and to the measured depth filter below) an image staged once — same pointer, stride, format and size — is
+ * not staged again; the caller leaves its contents alone meanwhile.  The copies live in buffers of their own, not in scratch a search uses. */
+int sdvl_depth_stage_begin(sdvl_ctx *ctx);
+int sdvl_depth_stage_end(sdvl_ctx *ctx);
+
+/* ---- the mapper's depth filter with a MEASURED depth (this project's rule; tests/depth_measure_restatement.py is its specification) -----
+ * sdvl_depth_filter / sdvl_search_run_filter for a depth camera.  jobs[]: the depth image of the CURRENT frame of the requests
+ * c_begin .. c_end (sdvl_depth_job as above, c_* indexing the requests); a request in no job has no image.  Per request:
+ *   miss                       Unpromote, as sdvl_depth_filter
+ *   hit at px on level l       the lookup of sdvl_depth_seed at the found pixel: centre floor(px + 0.5) (with a lens: of the raw pixel px's
+ *                              ray lands on), nine samples at stride 1 << l, the same validity and status order
+ *   status not OK, no image    the triangulated update of sdvl_depth_filter: the same bits
+ *   status OK, sample z_c      P_c = unproject(px) z_c / unproject(px).z, P_r = (ref cur^-1) P_c, depth = P_r . bearing (the range along the
+ *                              candidate's ray); depth <= 0 or either minimum-depth test (map.cc:476-479) -> SKIPPED; else Point::Update and
+ *                              HasConverged with x = 1 / depth and tau = noise_abs + noise_quad z_c^2 in ComputeTau's place (tau_inverse as
+ *                              in point.cc:69, clamp included).  No triangulation is made, so neither it nor its parallax test applies; a
+ *                              depth that belongs to another surface is the business of the mixture's outlier weight.
+ * out_status[n]: SDVL_DEPTH_SEED_* of a request that looked a depth up, 255 for one that did not (a miss, no image).  noise_abs /
+ * noise_quad 0 (or mp null): 0.001 m and 0.0015 per metre, the order of magnitude of a structured-light sensor, not measured against one.
+ * One launch (depth_filter_measured: one lane per request, FP64); images are read where they lie as for sdvl_depth_seed.  Refused with a
+ * message: what sdvl_depth_filter and sdvl_depth_seed refuse (format, stride, scale, a range outside n, a level outside the pyramid),
+ * negative noise. */
+typedef struct sdvl_depth_measure_params {
+  sdvl_depth_seed_params rule;
+  double noise_abs, noise_quad;
+} sdvl_depth_measure_params;
+int sdvl_depth_filter_measured(sdvl_ctx *ctx, int n, const double *cur_pose7, const double *ref_pose7, const double *bearing3, const int32_t *found,
+                               const double *px2, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state,
+                               const sdvl_depth_params *fp, struct sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width,
+                               int height, const sdvl_distortion *dist, const sdvl_depth_measure_params *mp, sdvl_depth_out *fout,
+                               uint8_t *out_status);
+/* the same behind sdvl_search_begin / sdvl_search_slot: px and level are the search's own */
+int sdvl_search_run_filter_measured(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
+                                    const sdvl_depth_params *fp, struct sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width,
+                                    int height, const sdvl_distortion *dist, const sdvl_depth_measure_params *mp, sdvl_search_res *out,
+                                    sdvl_depth_out *fout, uint8_t *out_status);
 
 /* ---- pose from matches: FeatureAlign::SelectInliers + OptimizePose (feature_align.cc:73-82,152-243,258-283,341-431) --
  * One job per frame.  obs[] are the frame's matched features in found order: ax, ay = feature bearing x/z, y/z

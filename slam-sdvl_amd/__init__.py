@@ -143,6 +143,11 @@ class DepthSeedParams(C.Structure):
     _fields_ = [("min_depth", C.c_double), ("max_depth", C.c_double), ("edge_ratio", C.c_double), ("min_valid", C.c_int32), ("pad_", C.c_int32)]
 
 
+class DepthMeasureParams(C.Structure):
+    """sdvl_depth_measure_params: the lookup's rule and the depth noise tau = noise_abs + noise_quad z^2 (0: 0.001 m, 0.0015 per metre)"""
+    _fields_ = [("rule", DepthSeedParams), ("noise_abs", C.c_double), ("noise_quad", C.c_double)]
+
+
 class SynthView(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("u0", C.c_double), ("v0", C.c_double),
                 ("R", C.c_double * 9), ("t", C.c_double * 3), ("plane", C.c_double * 4),
@@ -178,7 +183,7 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
@@ -784,6 +789,81 @@ class Context:
                                              C.addressof(d5) if d5 is not None else None, C.addressof(p), z.ctypes.data, status.ctypes.data,
                                              ok.ctypes.data))
         return z[:n], status[:n], ok[:len(jobs)]
+
+    def _depth_measure_args(self, jobs, width, height, dist, noise_abs, noise_quad, rule):
+        """the depth side of the two measured entries -> (objects to keep alive, job array, distortion or None, DepthMeasureParams)"""
+        keep, arr = [], (DepthJob * max(len(jobs), 1))()
+        for j, job in enumerate(jobs):
+            if isinstance(job, DepthJob):
+                arr[j] = job
+                continue
+            d = job[0]
+            assert d.dtype in (np.float32, np.uint16) and d.ndim == 2 and d.strides[1] == d.itemsize and d.shape == (height, width)
+            keep.append(d)
+            arr[j] = DepthJob(d.ctypes.data, 0, d.strides[0], SDVL_DEPTH_U16 if d.dtype == np.uint16 else SDVL_DEPTH_F32, 0,
+                              float(job[3]) if len(job) > 3 else 1.0, int(job[1]), int(job[2]))
+        mp = DepthMeasureParams(DepthSeedParams(float(rule.pop("min_depth", 0.0)), float(rule.pop("max_depth", 0.0)),
+                                                float(rule.pop("edge_ratio", 0.0)), int(rule.pop("min_valid", 0)), 0), float(noise_abs), float(noise_quad))
+        assert not rule, "unknown rule field %s" % list(rule)
+        d5 = Distortion((C.c_double * 5)(*[float(x) for x in dist])) if dist is not None else None
+        return keep, arr, d5, mp
+
+    def depth_filter_measured(self, cur_poses, ref_poses, bearings, found, px, levels, cam, states, fparams, jobs, width, height, dist=None,
+                              noise_abs=0.0, noise_quad=0.0, track_set=None, **rule):
+        """sdvl_depth_filter_measured: depth_filter's arguments and the found level of every item [n]; jobs as for depth_seed, each the depth
+        image of the current frame of the items c_begin .. c_end (an item in no job has no image); noise_abs / noise_quad and rule: 0 takes
+        the default -> (DepthOut array, status uint8 [n]: depth_seed's codes, 255 where no depth was looked up)"""
+        n = len(states)
+        cp = np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7)
+        rp = np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7)
+        bv = np.ascontiguousarray(bearings, np.float64).reshape(n, 3)
+        fd = np.ascontiguousarray(found, np.int32).reshape(n)
+        pp = np.ascontiguousarray(px, np.float64).reshape(n, 2)
+        lv = np.ascontiguousarray(levels, np.int32).reshape(n)
+        keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, noise_abs, noise_quad, rule)
+        fout, status = (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
+        vp = C.c_void_p
+        self.lib.sdvl_depth_filter_measured.argtypes = [vp, C.c_int] + [vp] * 10 + [C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        self._check(self.lib.sdvl_depth_filter_measured(
+            self.h, n, cp.ctypes.data, rp.ctypes.data, bv.ctypes.data, fd.ctypes.data, pp.ctypes.data, lv.ctypes.data, C.addressof(cam),
+            C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None, len(jobs), C.addressof(arr), width, height,
+            C.addressof(d5) if d5 is not None else None, C.addressof(mp), C.addressof(fout), status.ctypes.data))
+        del keep
+        return fout, status[:n]
+
+    def search_points_filter_measured(self, reqs, cam, sp, states, fparams, jobs, width, height, dist=None, noise_abs=0.0, noise_quad=0.0,
+                                      track_set=None, **rule):
+        """sdvl_search_begin / _slot / sdvl_search_run_filter_measured: search_points_filter's requests (frames by handle) with the depth
+        side of depth_filter_measured -> (SearchRes array, DepthOut array, status uint8 [n])"""
+        n = len(reqs)
+        lib = self.lib
+        lib.sdvl_search_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(SearchReqPacked))]
+        lib.sdvl_search_slot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        packed = C.POINTER(SearchReqPacked)()
+        self._check(lib.sdvl_search_begin(self.h, n, C.byref(packed)))
+        for i, r in enumerate(reqs):
+            d = packed[i]
+            d.cur = lib.sdvl_search_slot(self.h, r.cur, r.cur_pose)
+            d.ref = lib.sdvl_search_slot(self.h, r.ref, r.ref_pose)
+            assert d.cur >= 0 and d.ref >= 0
+            d.level, d.fixed = r.level, r.fixed
+            d.px[0], d.px[1] = r.px[0], r.px[1]
+            for k in range(3):
+                d.bearing[k] = r.bearing[k]
+            d.idepth, d.idepth_std = r.idepth, r.idepth_std
+            d.px0[0], d.px0[1] = r.px0[0], r.px0[1]
+            for k in range(32):
+                d.desc[k] = r.desc[k]
+        keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, noise_abs, noise_quad, rule)
+        res, fout, status = (SearchRes * n)(), (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
+        vp = C.c_void_p
+        lib.sdvl_search_run_filter_measured.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        self._check(lib.sdvl_search_run_filter_measured(
+            self.h, n, C.addressof(cam), C.addressof(sp), C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None,
+            len(jobs), C.addressof(arr), width, height, C.addressof(d5) if d5 is not None else None, C.addressof(mp), C.addressof(res),
+            C.addressof(fout), status.ctypes.data))
+        del keep
+        return res, fout, status[:n]
 
     def track_points_download(self, track_set):
         """the point rows of every tracker of a TrackSet as the device holds them: uint8 [n_trackers * max_points][144]"""

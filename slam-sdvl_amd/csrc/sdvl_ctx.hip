@@ -411,6 +411,7 @@ int sdvl_ctx_destroy(sdvl_ctx *ctx) {
   if (ctx->d_stage) (void)hipFree(ctx->d_stage);
   if (ctx->d_out) (void)hipFree(ctx->d_out);
   if (ctx->d_work) (void)hipFree(ctx->d_work);
+  for (sdvl_ctx::DepthStaged &e : ctx->depth_pool) (void)hipFree(e.d);
   if (ctx->d_detect) (void)hipFree(ctx->d_detect);
   if (ctx->d_counts) (void)hipFree(ctx->d_counts);
   for (void *sl : ctx->slabs) (void)hipFree(sl);

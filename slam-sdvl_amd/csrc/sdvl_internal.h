@@ -88,6 +88,10 @@ struct sdvl_ctx {
   void *h_out = nullptr;   size_t h_out_bytes = 0;
   void *d_out = nullptr;   size_t d_out_bytes = 0;
   void *d_work = nullptr;  size_t d_work_bytes = 0;
+  // copies of pageable depth images (sdvl_depth_jobs_resolve, sdvl_depth_device.h): one buffer per image of a step, apart from d_work
+  struct DepthStaged { void *d; size_t bytes; const void *host; long long stride; int format, width, height, live; };
+  std::vector<DepthStaged> depth_pool;
+  int depth_stage_open = 0;  // between sdvl_depth_stage_begin and _end: an image staged once is not staged again
   // detection scratch (sdvl_detect.hip): per batch slot the per-cell FAST lists, counts and the selection's intermediate lists;
   // dead once the batch's select_pack kernel has run
   void *d_detect = nullptr; size_t d_detect_bytes = 0;

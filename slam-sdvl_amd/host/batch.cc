@@ -169,6 +169,7 @@ SDVLBatch::FrameStart SDVLBatch::BeginFrame(int i, const shared_ptr<Frame> &fram
   SDVL &t = *trk_[i];
   st = FrameStats();
   t.current_frame_ = frame;
+  t.step_frame_ = frame.get();
   t.current_frame_->SetID(t.frame_counter_++);
   if (t.state_ != SDVL::STATE_RUNNING) {
     if (t.depth_seeding_) {  // the frame becomes the first keyframe in FinishKeyframes, if enough of its corners have a depth
@@ -320,10 +321,16 @@ void SDVLBatch::HandleFrames(const vector<Image> &imgs, const vector<DepthImage>
       throw std::runtime_error("SDVLBatch::HandleFrames: a depth image has the size of its camera image");
   struct DepthScope {  // the step's depth images are named for the step alone, however it ends
     SDVLBatch *b;
-    ~DepthScope() { b->step_depths_ = nullptr; }
-  } depth_scope{this};
+    bool staged;
+    ~DepthScope() {
+      b->step_depths_ = nullptr;
+      if (staged) (void)sdvl_depth_stage_end(b->dev_->ctx());
+    }
+  } depth_scope{this, !depths.empty()};
   step_depths_ = &depths;
   Device::SetCurrent(dev_);
+  // a pageable depth image is copied to the device once per step: the keyframes' lookup and the mapper's filter passes share the copy
+  if (!depths.empty()) dev_->Check(sdvl_depth_stage_begin(dev_->ctx()), "sdvl_depth_stage_begin");
   StageTimes::Active() = &stage_times;
   stage_times.steps++;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -495,15 +502,62 @@ void SDVLBatch::EpilogueAndMapper(Step &s) {
   s.clk.reset();
 }
 
+// Depth cameras inside the mapper: the filtered corners of all the step's new keyframes whose mapper measures, looked up in their frames'
+// depth images by ONE sdvl_depth_seed call (as SeedKeyframesFromDepth does for the keyframes the driver seeds) and handed to the mappers
+void SDVLBatch::MeasureKeyframeCorners(const vector<MapperMap *> &mm, const vector<int> &mm_trk, const vector<int> &kf_idx, const vector<char> &need,
+                                       const vector<const DepthImage *> &depth_of) {
+  vector<sdvl_depth_job> jobs;
+  vector<int> whose;
+  vector<int32_t> xyl;
+  const sdvl_depth_seed_params *rule = nullptr;
+  for (size_t q = 0; q < kf_idx.size(); q++) {
+    const int k = kf_idx[q];
+    if (!need[q] || !mm[k]->DepthMapping()) continue;
+    const DepthImage *d = depth_of[k];
+    if (!d) {
+      mm[k]->SetCornerDepths(nullptr, nullptr);
+      continue;
+    }
+    const sdvl_depth_seed_params *r = &trk_[mm_trk[k]]->depth_rule_;
+    if (rule && std::memcmp(rule, r, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
+    rule = r;
+    const shared_ptr<Frame> &kf = mm[k]->CurrentFrame();
+    const int first = static_cast<int>(xyl.size() / 3), n = kf->NumFiltered();
+    for (int c = 0; c < n; c++) {
+      const Vector3i corner = kf->FilteredCorner(c);
+      xyl.insert(xyl.end(), {corner(0), corner(1), corner(2)});
+    }
+    jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, first, first + n});
+    whose.push_back(k);
+  }
+  if (jobs.empty()) return;
+  const int n_corners = static_cast<int>(xyl.size() / 3);
+  depth_z_.assign(std::max(n_corners, 1), 0.0);
+  depth_status_.assign(std::max(n_corners, 1), 0);
+  vector<int32_t> ok(jobs.size(), 0);
+  const Camera &camera = *trk_[0]->camera_;
+  const sdvl_camera cam = camera.abi();
+  const sdvl_distortion dist = camera.distortion();
+  const shared_ptr<Frame> &kf0 = mm[whose[0]]->CurrentFrame();
+  dev_->Check(sdvl_depth_seed(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), kf0->GetWidth(), kf0->GetHeight(), n_corners, xyl.data(), &cam,
+                              camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
+              "sdvl_depth_seed");
+  for (size_t j = 0; j < jobs.size(); j++) mm[whose[j]]->SetCornerDepths(depth_z_.data() + jobs[j].c_begin, depth_status_.data() + jobs[j].c_begin);
+}
+
 // stage 5: SDVL::Mapping() of sequential mode (main.cc:148-149) for the trackers that own a real mapper: the phases of
 // Map::UpdateMap run in lock step, every phase's SearchPoint requests of ALL trackers in one K7 launch
 void SDVLBatch::RunMappers() {
   vector<MapperMap *> mm;
+  vector<int> mm_trk;  // whose mapper mm[k] is
   {
     StageClock begin_clk(ST_MAP_BEGIN);
-    for (SDVL *t : trk_) {
-      MapperMap *m = AsMapperMap(t->map_);
-      if (m && !m->IsThreaded() && m->BeginUpdate()) mm.push_back(m);  // a started mapper thread does its own UpdateMap
+    for (size_t i = 0; i < trk_.size(); i++) {
+      MapperMap *m = AsMapperMap(trk_[i]->map_);
+      if (m && !m->IsThreaded() && m->BeginUpdate()) {  // a started mapper thread does its own UpdateMap
+        mm.push_back(m);
+        mm_trk.push_back(static_cast<int>(i));
+      }
     }
   }
   const int M = static_cast<int>(mm.size());
@@ -518,6 +572,23 @@ void SDVLBatch::RunMappers() {
   vector<sdvl_depth_state> states;
   vector<sdvl_depth_out> fout;
   const sdvl_depth_params fparams = mm[0]->FilterParams();
+  // Depth cameras (SDVL::SetDepthMapping): when a mapper of the step has the switch on, the candidate passes go through the measured
+  // filter — still one launch for all trackers.  depth_of[k]: the depth image of the step's frame, for a mapper with the switch on whose
+  // update works on that very frame; the requests of every other mapper are in no job and take the triangulated rule.
+  vector<const DepthImage *> depth_of(M, nullptr);
+  const MapperMap *measuring = nullptr;
+  for (int k = 0; k < M; k++) {
+    if (!mm[k]->DepthMapping()) continue;
+    if (!dev_filter) throw std::runtime_error("mapper: depth mapping (SDVL::SetDepthMapping) needs the depth filter on the device");
+    const sdvl_depth_measure_params a = mm[k]->DepthMeasureParams(trk_[mm_trk[k]]->depth_rule_);
+    if (measuring) {
+      const sdvl_depth_measure_params b = measuring->DepthMeasureParams(trk_[mm_trk[k]]->depth_rule_);
+      if (a.noise_abs != b.noise_abs || a.noise_quad != b.noise_quad) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth noise parameters");
+    }
+    measuring = mm[k];
+    if (mm[k]->CurrentFrame().get() == trk_[mm_trk[k]]->step_frame_) depth_of[k] = DepthOf(mm_trk[k]);
+  }
+  vector<uint8_t> depth_status;  // per candidate request, with `measuring`
   auto launch = [&](bool filter = false) {  // search everything the maps emitted, leave the offsets in `begin`
     // the requests go from the maps' lists straight into the context's pinned batch (device layout, frames by slot)
     Concatenate(per, nullptr, &begin);
@@ -551,7 +622,31 @@ void SDVLBatch::RunMappers() {
     }
     const sdvl_camera c = trk_[0]->camera_->abi();
     const sdvl_search_params sp = SearchParams();
-    if (filter) {
+    if (filter && measuring) {
+      if (states.size() != total) throw std::runtime_error("mapper: one filter state per candidate request");
+      vector<sdvl_depth_job> jobs;
+      const sdvl_depth_seed_params *rule = nullptr;
+      int width = 0, height = 0;
+      for (int k = 0; k < M; k++) {
+        const DepthImage *d = depth_of[k];
+        if (!d || begin[k] == begin[k + 1]) continue;
+        const sdvl_depth_seed_params *r = &trk_[mm_trk[k]]->depth_rule_;
+        if (rule && std::memcmp(rule, r, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
+        rule = r;
+        width = mm[k]->CurrentFrame()->GetWidth();
+        height = mm[k]->CurrentFrame()->GetHeight();
+        jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, static_cast<int>(begin[k]), static_cast<int>(begin[k + 1])});
+      }
+      if (jobs.empty()) { width = 1; height = 1; }  // (no request has an image: nothing is looked up)
+      const sdvl_depth_measure_params mp = measuring->DepthMeasureParams(rule ? *rule : sdvl_depth_seed_params{0.0, 0.0, 0.0, 0, 0});
+      const Camera &camera = *trk_[0]->camera_;
+      const sdvl_distortion dist = camera.distortion();
+      depth_status.resize(total);
+      dev_->Check(sdvl_search_run_filter_measured(ctx, static_cast<int>(total), &c, &sp, states.data(), &fparams, tables_.set, static_cast<int>(jobs.size()),
+                                                  jobs.data(), width, height, camera.HasDistortion() ? &dist : nullptr, &mp, res.data(), fout.data(),
+                                                  depth_status.data()),
+                  "sdvl_search_run_filter_measured");
+    } else if (filter) {
       if (states.size() != total) throw std::runtime_error("mapper: one filter state per candidate request");
       dev_->Check(sdvl_search_run_filter(ctx, static_cast<int>(total), &c, &sp, states.data(), &fparams, tables_.set, res.data(), fout.data()),
                   "sdvl_search_run_filter");
@@ -572,7 +667,10 @@ void SDVLBatch::RunMappers() {
       launch(dev_filter);
     }
     StageClock c(ST_MAP_APPLY);
-    ParallelFor(M, [&](int k) { if (more[k]) mm[k]->ApplyCandidates(res.data() + begin[k], dev_filter ? fout.data() + begin[k] : nullptr); });
+    ParallelFor(M, [&](int k) {
+      if (more[k]) mm[k]->ApplyCandidates(res.data() + begin[k], dev_filter ? fout.data() + begin[k] : nullptr,
+                                          measuring && !depth_status.empty() ? depth_status.data() + begin[k] : nullptr);
+    });
   }
   vector<int> kf_idx;
   for (int k = 0; k < M; k++)
@@ -598,6 +696,7 @@ void SDVLBatch::RunMappers() {
       if (need[q]) to_filter.push_back(mm[kf_idx[q]]->CurrentFrame());
     if (!to_filter.empty()) {
       Frame::FilterCornersBatch(to_filter);
+      if (measuring) MeasureKeyframeCorners(mm, mm_trk, kf_idx, need, depth_of);
       ParallelFor(K, [&](int q) { if (need[q]) mm[kf_idx[q]]->EmitInitCandidates(&per[kf_idx[q]]); });
       launch();
       ParallelFor(K, [&](int q) { if (need[q]) mm[kf_idx[q]]->ApplyInitCandidates(res.data() + begin[kf_idx[q]]); });

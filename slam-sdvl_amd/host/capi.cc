@@ -293,6 +293,27 @@ int sdvlh_batch_depth_stats(void *bp, int i, long long *out8) {
   out8[7] = s.no_depth;
   return 0;
 }
+// Depth cameras inside the mappers of the batch (SDVL::SetDepthMapping): needs sdvlh_batch_set_depth and the reference's mapper; the
+// trackers share the noise parameters (0: the defaults)
+int sdvlh_batch_set_depth_mapping(void *bp, int on, double noise_abs, double noise_quad) {
+  if (!bp) return -1;
+  return Guarded([&] {
+    for (int i = 0; i < AsGroup(bp)->size(); i++) AsGroup(bp)->tracker(i).SetDepthMapping(on != 0, noise_abs, noise_quad);
+  });
+}
+// tracker i's depth mapping so far: out9 = candidate updates measured, fallen back by status (HOLE, FEW, EDGE, OUTSIDE), keyframes looked
+// up, corners fixed and matched, fixed and unmatched, linked
+int sdvlh_batch_depth_map_stats(void *bp, int i, long long *out9) {
+  TrackerGroup *b = AsGroup(bp);
+  if (!b || i < 0 || i >= b->size() || !out9) return -1;
+  MapperMap *m = dynamic_cast<MapperMap *>(&b->map(i));
+  if (!m) return -1;
+  const MapperMap::DepthMapStats &s = m->GetDepthMapStats();
+  out9[0] = s.measured;
+  for (int k = 0; k < 4; k++) out9[1 + k] = s.fallback[k];
+  out9[5] = s.keyframes; out9[6] = s.fixed_matched; out9[7] = s.fixed_unmatched; out9[8] = s.linked;
+  return 0;
+}
 
 // ---- TrackerFarm (farm.h): G groups x Bg sequences on ONE GPU
 void *sdvlh_farm_create(int gpu, int G, int Bg, int w, int h, const double *cam4, const double *plane4, const double *first_poses7,

@@ -356,6 +356,7 @@ bool MapperMap::BeginUpdate() {
   updates_++;
   version_++;  // the depth filter moves candidates, connections add features to keyframes
   depth_mean_ = cur_->GetSceneDepth();
+  ic_range_.clear();
   pass_ = 0;
   occurrence_.assign(candidates_.size(), 0);
   // the reference pushes every new candidate twice (map.cc:381,389): entry k is the occurrence_[k]-th of its point.  The two
@@ -472,10 +473,11 @@ bool MapperMap::EmitCandidates(vector<sdvl_search_req> *reqs, vector<sdvl_depth_
   return any;
 }
 
-void MapperMap::ApplyCandidates(const sdvl_search_res *res_all, const sdvl_depth_out *fout_all) {
+void MapperMap::ApplyCandidates(const sdvl_search_res *res_all, const sdvl_depth_out *fout_all, const uint8_t *status_all) {
   if (!cur_) return;
   const sdvl_search_res *res = res_all + req_base_;
   const sdvl_depth_out *fout = fout_all ? fout_all + req_base_ : nullptr;
+  const uint8_t *status = (fout_all && status_all) ? status_all + req_base_ : nullptr;
   const double px_error_angle = std::atan(1.0 / (2.0 * camera_->GetFx())) * 2.0;  // Camera::GetPixelErrorAngle, camera.h:104-107
   const int min_kf_id = last_kf_->GetKeyframeID() - 2 * Config::MaxSearchKeyframes();
   vector<char> erase(candidates_.size(), 0);
@@ -502,6 +504,8 @@ void MapperMap::ApplyCandidates(const sdvl_search_res *res_all, const sdvl_depth
     const sdvl_search_res &r = res[w.req];
     if (fout) {  // the loop body ran on the device (depth_filter_kernel): book what it decided
       const sdvl_depth_out &o = fout[w.req];
+      if (status && status[w.req] == SDVL_DEPTH_SEED_OK) depth_map_stats_.measured++;
+      else if (status && status[w.req] <= SDVL_DEPTH_SEED_OUTSIDE) depth_map_stats_.fallback[status[w.req] - 1]++;
       point->ApplyFilterOut(o);
       if (o.outcome & SDVL_DEPTH_DELETED) {
         if (point->TrackRow() >= 0) point->SetDeviceTrashed();  // its table row carries the deletion already
@@ -674,6 +678,10 @@ void MapperMap::EmitInitCandidates(vector<sdvl_search_req> *reqs) {
     const Vector3d bearing = camera_->Unproject(px);
     FillRequest(&ic_proto_[c], cur_.get(), cur_.get(), px, bearing, corner(2), Config::UseORB() ? cur_->FilteredDescriptor(c) : nullptr,
                 1.0 / depth_mean_, 1.0, false, Vector2d(0, 0));
+    if (CornerMeasured(c)) {  // the search looks where the measured depth says, as wide as the sensor's noise
+      ic_proto_[c].idepth = 1.0 / ic_range_[c];
+      ic_proto_[c].idepth_std = MeasuredTauInverse(ic_range_[c], ic_range_[c] * bearing(2));
+    }
   }
   for (size_t k = 0; k < best_kfs_.size(); k++) {
     Frame *cframe = best_kfs_[k].get();
@@ -700,6 +708,7 @@ void MapperMap::ApplyInitCandidates(const sdvl_search_res *res_all) {
   vector<int> &fcorners = cur_->GetFilteredCorners();
   const int nc = static_cast<int>(fcorners.size());
   vector<bool> imatches(fcorners.size(), false);
+  vector<bool> linked(fcorners.size(), false), too_close(fcorners.size(), false);  // of measured corners (SetDepthMapping)
   for (size_t k = 0; k < best_kfs_.size(); k++) {
     shared_ptr<Frame> cframe = best_kfs_[k];
     cframe->SetSelected(true);
@@ -748,12 +757,42 @@ void MapperMap::ApplyInitCandidates(const sdvl_search_res *res_all) {
           point->AddFeature(feature);
           mfound = true;
           stats_.linked++;
+          if (CornerMeasured(count)) {
+            linked[count] = true;
+            depth_map_stats_.linked++;
+          }
         }
       }
       if (mfound) continue;
       const SE3 pose = cframe->GetPose() * cur_->GetPose().Inverse();
       shared_ptr<Feature> feature2 = std::make_shared<Feature>(cframe, imgpos, level);
       double depth = 0.0;
+      if (CornerMeasured(count)) {
+        // the `fixed` branch of map.cc:383-389 for a candidate of known depth: the range the depth image measured along the corner's
+        // bearing stands where the triangulated depth would; no triangulation is made, so neither it nor its parallax test applies
+        depth = ic_range_[count];
+        if (depth < Config::MapScale() * Config::ScaleMinDist() || depth < depth_mean_ * Config::ScaleMinDist()) {
+          too_close[count] = true;
+          continue;
+        }
+        candidate->InitCandidate(feature, depth);
+        cur_->AddFeature(feature);
+        candidate->AddFeature(feature);
+        feature->SetPoint(candidate);
+        cframe->AddFeature(feature2);
+        kf_scan_.push_back(KfScan{feature2->GetPosition()(0), feature2->GetPosition()(1), true});
+        candidate->AddFeature(feature2);
+        feature2->SetPoint(candidate);
+        imatches[count] = true;
+        candidates_.push_back(candidate);  // ONCE (:383): the next update's HasConverged takes it off the list
+        const Vector3d pos = candidate->GetPosition();
+        candidate->SetFixed();
+        candidate->SetPosition(pos);
+        depth_seeds_.push_back(DepthSeedRec{candidate, cur_->GetID(), corner(0), corner(1), corner(2)});
+        stats_.initialized++;
+        depth_map_stats_.fixed_matched++;
+        continue;
+      }
       if (!GetDepthFromTriangulation(pose, feature->GetVector(), feature2->GetVector(), &depth)) continue;
       const Vector3d &fv = feature->GetVector();
       const Vector3d p3d = cur_->GetWorldPose() * Vector3d(depth * fv(0), depth * fv(1), depth * fv(2));
@@ -774,7 +813,64 @@ void MapperMap::ApplyInitCandidates(const sdvl_search_res *res_all) {
       stats_.initialized++;
     }
   }
+  // measured corners that no connected keyframe answered for: fixed points with their one observation on the new keyframe, made as
+  // PlaneMap::SeedFromDepth makes the bootstrap keyframe's, in corner order.  The map reaches a surface on the keyframe that first sees it.
+  if (!ic_range_.empty()) {
+    const SE3 world = cur_->GetWorldPose();
+    for (int c = 0; c < nc; c++) {
+      if (!CornerMeasured(c) || imatches[c] || linked[c] || too_close[c]) continue;
+      const double s = ic_range_[c];
+      if (!(s > 0.05)) continue;
+      const Vector3i corner = cur_->FilteredCorner(c);
+      const int scale = (1 << corner(2));
+      shared_ptr<Feature> feature = cur_->NewFeature(Vector2d(corner(0) * scale, corner(1) * scale), corner(2));
+      if (Config::UseORB()) feature->SetDescriptor(cur_->FilteredDescriptor(c));
+      const Vector3d &v = feature->GetVector();
+      shared_ptr<Point> pt = cur_->NewPoint();
+      const double rho = 1.0 / s;
+      pt->InitFixed(feature, s, (0.05 * rho) * (0.05 * rho), world * Vector3d(s * v(0), s * v(1), s * v(2)));
+      feature->SetPoint(pt);
+      cur_->AddFeature(feature);
+      pt->AddFeature(feature);
+      depth_seeds_.push_back(DepthSeedRec{pt, cur_->GetID(), corner(0), corner(1), corner(2)});
+      depth_map_stats_.fixed_unmatched++;
+    }
+    version_++;
+    ic_range_.clear();
+  }
   best_kfs_.clear();
+}
+
+// ---- depth cameras inside the mapper (sdvl_host.h)
+void MapperMap::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
+  if (on && running_) throw std::runtime_error("MapperMap::SetDepthMapping: depth mapping runs in sequential mode only, the mapper thread is started");
+  if (on && !DeviceFilter()) throw std::runtime_error("MapperMap::SetDepthMapping: the measured depth filter is a device kernel, the host depth filter is selected");
+  if (on && !(noise_abs >= 0.0 && noise_quad >= 0.0)) throw std::invalid_argument("MapperMap::SetDepthMapping: noise_abs and noise_quad must not be negative");
+  depth_mapping_ = on;
+  noise_abs_ = noise_abs;
+  noise_quad_ = noise_quad;
+}
+
+// the tau_inverse of depth_filter_measured_kernel (point.cc:69 with tau = noise_abs + noise_quad z^2) for a range and its sample z
+double MapperMap::MeasuredTauInverse(double range, double z) const {
+  const double tau = (noise_abs_ != 0.0 ? noise_abs_ : 0.001) + (noise_quad_ != 0.0 ? noise_quad_ : 0.0015) * (z * z);
+  return 0.5 * (1.0 / std::max(0.0000001, range - tau) - 1.0 / (range + tau));
+}
+
+void MapperMap::SetCornerDepths(const double *z, const uint8_t *status) {
+  ic_range_.clear();
+  if (!depth_mapping_ || !cur_ || !z || !status) return;
+  const int nc = cur_->NumFiltered();
+  ic_range_.assign(nc, 0.0);
+  depth_map_stats_.keyframes++;
+  for (int c = 0; c < nc; c++) {
+    if (status[c] != SDVL_DEPTH_SEED_OK) continue;
+    const Vector3i corner = cur_->FilteredCorner(c);
+    const int scale = (1 << corner(2));
+    const Vector3d bearing = camera_->Unproject(Vector2d(corner(0) * scale, corner(1) * scale));
+    const double range = z[c] / bearing(2);
+    if (range > 0.0) ic_range_[c] = range;
+  }
 }
 
 // Map::CheckRedundantKeyframes, map.cc:619-690
@@ -834,6 +930,7 @@ MapperMap::~MapperMap() { Stop(); }
 void MapperMap::Start() {
   if (running_) return;
   if (bundle_on_) throw std::runtime_error("MapperMap::Start: bundle adjustment is on and runs in sequential mode only");
+  if (depth_mapping_) throw std::runtime_error("MapperMap::Start: depth mapping is on and runs in sequential mode only");
   tracker_device_ = Device::CurrentOrNull();
   running_ = true;
   thread_ = std::thread(&MapperMap::Run, this);

@@ -53,12 +53,14 @@ class PlaneMap : public Map {
   void LimitKeyframes(const std::shared_ptr<Frame> &frame) override;
   void EmptyTrash() override;
 
+ protected:
+  struct DepthSeedRec { std::weak_ptr<Point> point; int keyframe_id, u, v, level; };
+  std::vector<DepthSeedRec> depth_seeds_;  // SeedFromDepth drops the records of points that are gone
+
  private:
   Vector3d n_;
   double d_;
   std::vector<std::shared_ptr<Frame>> culled_;
-  struct DepthSeedRec { std::weak_ptr<Point> point; int keyframe_id, u, v, level; };
-  std::vector<DepthSeedRec> depth_seeds_;  // SeedFromDepth drops the records of points that are gone
   DepthStats depth_stats_;
 };
 
@@ -85,7 +87,8 @@ class MapperMap : public PlaneMap {
   // UpdateCandidates, one pass; false = no more passes.  states / fout: the depth filter runs on the device behind the search
   // (sdvl_search_points_filter) and Apply only books its outcomes; without them Apply does the arithmetic itself
   bool EmitCandidates(std::vector<sdvl_search_req> *reqs, std::vector<sdvl_depth_state> *states = nullptr);
-  void ApplyCandidates(const sdvl_search_res *res, const sdvl_depth_out *fout = nullptr);
+  // status (with fout): the depth lookup's byte per request, from sdvl_search_run_filter_measured; counted into DepthMapStats
+  void ApplyCandidates(const sdvl_search_res *res, const sdvl_depth_out *fout = nullptr, const uint8_t *status = nullptr);
   static bool DeviceFilter();             // env SDVL_HOST_DEPTH_FILTER=1 turns it off
   static void SetDeviceFilter(bool on);
   sdvl_depth_params FilterParams() const;
@@ -98,6 +101,25 @@ class MapperMap : public PlaneMap {
   const std::shared_ptr<Frame> &CurrentFrame() const { return cur_; }
   void EmitInitCandidates(std::vector<sdvl_search_req> *reqs);   // after Frame::FilterCorners of CurrentFrame()
   void ApplyInitCandidates(const sdvl_search_res *res);
+  // ---- depth cameras inside the mapper (an addition; SDVL::SetDepthMapping).  The driver's side of it: UpdateCandidates goes through
+  // sdvl_search_run_filter_measured with the depth image of the step's frame, and between Frame::FilterCorners and EmitInitCandidates
+  // the filtered corners of the new keyframe are looked up in that image (sdvl_depth_seed) and handed over here: z[c] / status[c] of
+  // filtered corner c, null: no image.  A corner with status OK is MEASURED, at the range z / bearing.z along its bearing:
+  //   * its requests say so to the search: idepth = 1 / range, idepth_std = the tau_inverse of the measured filter for that range;
+  //   * found in a connected keyframe and not linked to a point there, it becomes a point at the measured range — no triangulation, no
+  //     parallax test, the two minimum-depth tests on the range — with both features, fixed at once (map.cc:385-389) and pushed ONCE;
+  //   * neither linked nor found in any connected keyframe, it becomes a fixed point with its one observation on the new keyframe, made
+  //     as PlaneMap::SeedFromDepth makes the bootstrap keyframe's, behind the loop over the connected keyframes, in corner order.
+  // Unmeasured corners go the reference's way.  Needs the depth filter on the device and the sequential mapper.
+  void SetDepthMapping(bool on, double noise_abs = 0.0, double noise_quad = 0.0);
+  bool DepthMapping() const { return depth_mapping_; }
+  sdvl_depth_measure_params DepthMeasureParams(const sdvl_depth_seed_params &rule) const { return sdvl_depth_measure_params{rule, noise_abs_, noise_quad_}; }
+  void SetCornerDepths(const double *z, const uint8_t *status);
+  // candidate updates that took the measured depth and those that fell back by the lookup's status (HOLE, FEW, EDGE, OUTSIDE); keyframes
+  // whose corners were looked up; corners fixed from depth and matched in a connected keyframe, fixed on the new keyframe alone, and
+  // measured corners that were linked to an existing point
+  struct DepthMapStats { long measured = 0, fallback[4] = {0, 0, 0, 0}, keyframes = 0, fixed_matched = 0, fixed_unmatched = 0, linked = 0; };
+  const DepthMapStats &GetDepthMapStats() const { return depth_map_stats_; }
   void FinishUpdate();                                           // CheckRedundantKeyframes + trash for ordinary frames
   // ---- local bundle adjustment, the end of Map::UpdateMap (map.cc:130-137) and Map::BundleAdjustment (map.cc:844-869); off by default.
   // Sequential mode only: throws while the mapper thread runs, and Start() throws while it is on.
@@ -136,6 +158,8 @@ class MapperMap : public PlaneMap {
 
  private:
   void CheckRedundantKeyframes();  // map.cc:619-690
+  bool CornerMeasured(int c) const { return static_cast<size_t>(c) < ic_range_.size() && ic_range_[c] > 0.0; }
+  double MeasuredTauInverse(double range, double z) const;
   Camera *camera_;
   std::vector<std::shared_ptr<Point>> candidates_;
   std::deque<std::shared_ptr<Frame>> frame_queue_, keyframe_queue_;
@@ -161,6 +185,10 @@ class MapperMap : public PlaneMap {
   struct KfScan { double x, y; bool live; };
   std::vector<KfScan> kf_scan_;                            // InitCandidates: a connected keyframe's features as the seed loop scans them
   std::vector<sdvl_search_req> ic_proto_;                  // InitCandidates: the request of filtered corner c without its keyframe
+  bool depth_mapping_ = false;
+  double noise_abs_ = 0.0, noise_quad_ = 0.0;              // SetDepthMapping: as given (0: sdvl_depth_measure_params' default)
+  std::vector<double> ic_range_;                           // SetCornerDepths: the measured range of filtered corner c, 0: not measured
+  DepthMapStats depth_map_stats_;
   std::thread thread_;
   std::atomic<bool> running_{false};
   std::atomic<long> updates_{0};
@@ -206,6 +234,12 @@ class SDVL {
   // question — and with a map that is neither PlaneMap nor MapperMap; std::invalid_argument for a rule sdvl_depth_seed would refuse.
   void SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule = sdvl_depth_seed_params{0.0, 0.0, 0.0, 0, 0});
   bool DepthSeeding() const { return depth_seeding_; }
+  // Depth cameras inside the reference's mapper (an addition, MapperMap::SetDepthMapping): the depth image of every tracked frame feeds
+  // the candidates' depth filter, and a new keyframe's corners become fixed points at their measured depth.  noise: the sensor's depth
+  // noise tau = noise_abs + noise_quad z^2 (0: 0.001 m and 0.0015 per metre); the trackers of a batch share it.  Needs SetDepthSeeding and
+  // the reference's mapper in sequential mode with the depth filter on the device: throws std::runtime_error without depth seeding, with
+  // any other map, while the mapper thread runs (and Start() throws while it is on), and with the host depth filter.
+  void SetDepthMapping(bool on, double noise_abs = 0.0, double noise_quad = 0.0);
   // Map::BundleAdjustment after every keyframe update of a map with more than two keyframes (map.cc:130-137), on the device
   // (sdvl_bundle_adjust).  Off by default.  Needs the reference's mapper in sequential mode: throws std::runtime_error with any other map
   // and while the mapper thread runs.
@@ -246,6 +280,7 @@ class SDVL {
   void PrepareFirstFrame();
   void CommitFirstFrame(FrameStats &st);
   bool depth_seeding_ = false, first_frame_waiting_ = false;
+  const Frame *step_frame_ = nullptr;  // the frame of the step in flight (BeginFrame): whose depth image the step's is
   sdvl_depth_seed_params depth_rule_ = {0.0, 0.0, 0.0, 0, 0};
   bool InitFirstFrame(FrameStats &st);                       // sdvl.cc:132-148 (two-frame initialisation)
   void SecondFrameDone(bool initialised, FrameStats &st);    // sdvl.cc:154-176 behind HomographyInit::InitSecondFrame

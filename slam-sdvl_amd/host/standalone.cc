@@ -494,6 +494,13 @@ void SDVL::SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule) {
   depth_rule_ = rule;
 }
 
+void SDVL::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
+  MapperMap *m = AsMapperMap(map_);
+  if (on && !m) throw std::runtime_error("SDVL::SetDepthMapping needs the reference's mapper (MapperMap)");
+  if (on && !depth_seeding_) throw std::runtime_error("SDVL::SetDepthMapping needs depth seeding (SetDepthSeeding): the bootstrap keyframe is seeded from depth too");
+  if (m) m->SetDepthMapping(on, noise_abs, noise_quad);
+}
+
 void SDVL::SetBundleAdjustment(bool on) {
   MapperMap *m = AsMapperMap(map_);
   if (!m) throw std::runtime_error("SDVL::SetBundleAdjustment needs the reference's mapper (MapperMap)");

@@ -13,6 +13,8 @@
 //                                                                the one plane; the map still bootstraps from --plane (the default is the scene's wall)
 //   track_sequence --synthetic N --scene shelf --depth           a depth camera: every frame comes with the renderer's registered depth image and the
 //                                                                keyframes' points are seeded from it (SDVL::SetDepthSeeding) — no plane; a --plane is ignored
+//   ... --depth --depth-mapping                                  the depth camera inside the reference's mapper too (SDVL::SetDepthMapping; implies --mapper): every tracked
+//                                                                frame's depth feeds the candidates' filter, new keyframes' corners become fixed points; beside --depth only
 //   track_sequence --list frames.txt --depth-list depth.txt --depth-scale S   the same from disk: one 16-bit binary PGM (P5, maxval above 255; netpbm's samples are
 //                                                                big-endian and are swapped here) per frame, S metres per unit (TUM: 0.0002)
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
@@ -143,7 +145,7 @@ int main(int argc, char **argv) {
   bool mapper = false, bundle = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
   bool prerender = false, pageable = false, quiet = false, json = false, profile = false, batch = false, lookahead = false;
   int n_trackers = 1, raw_format = 0;
-  bool depth = false, plane_given = false;
+  bool depth = false, depth_mapping = false, plane_given = false;
   std::string depth_list;
   double depth_scale = 0.0;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
@@ -162,6 +164,7 @@ int main(int argc, char **argv) {
     else if (a == "--dist") { need(5); for (int k = 0; k < 5; k++) dist[k] = std::atof(argv[++i]); dist_given = true; }
     else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) plane[k] = std::atof(argv[++i]); plane_given = true; }
     else if (a == "--depth") depth = true;
+    else if (a == "--depth-mapping") { depth_mapping = true; mapper = true; }
     else if (a == "--depth-list") { need(1); depth_list = argv[++i]; depth = true; }
     else if (a == "--depth-scale") { need(1); depth_scale = std::atof(argv[++i]); }
     else if (a == "--mapper") mapper = true;
@@ -191,6 +194,7 @@ int main(int argc, char **argv) {
     }
   }
   const bool use_scene = !scene_name.empty();
+  if (depth_mapping && !depth) { std::cerr << "--depth-mapping feeds the mapper from the frames' depth images: give --depth or --depth-list too" << std::endl; return 2; }
   if (depth) {
     if (depth_list.empty() && !use_scene) { std::cerr << "--depth tracks on the renderer's depth: give --synthetic N --scene NAME, or --depth-list FILE with --list" << std::endl; return 2; }
     if (!depth_list.empty() && (list.empty() || !(depth_scale > 0.0))) { std::cerr << "--depth-list goes with --list and --depth-scale S (metres per unit, above 0)" << std::endl; return 2; }
@@ -302,7 +306,7 @@ int main(int argc, char **argv) {
       render_dev->Check(sdvl_device_free(rc, dbuf), "sdvl_device_free");
     }
 
-    struct PerTracker { double busy = 0.0; int tracked = 0; std::vector<float> ms; std::string err; PlaneMap::DepthStats depth; };
+    struct PerTracker { double busy = 0.0; int tracked = 0; std::vector<float> ms; std::string err; PlaneMap::DepthStats depth; MapperMap::DepthMapStats depth_map; };
     std::vector<PerTracker> per(n_trackers);
     std::atomic<int> ready{0};
     std::atomic<bool> go{false};
@@ -321,6 +325,7 @@ int main(int argc, char **argv) {
         if (two_frame) sdvl.SetTwoFrameInit(true);
         if (bundle) sdvl.SetBundleAdjustment(true);
         if (depth) sdvl.SetDepthSeeding(true);
+        if (depth_mapping) sdvl.SetDepthMapping(true);
         std::vector<float> depth_f32(depth && depth_list.empty() ? frame_bytes : 0);
         std::vector<uint16_t> depth_u16;
         std::vector<uint8_t> px(pool ? 0 : frame_bytes);
@@ -392,6 +397,7 @@ int main(int argc, char **argv) {
                         st.pose[0], st.pose[1], st.pose[2], st.pose[3], st.pose[4], st.pose[5], st.pose[6]);
         }
         if (depth) me.depth = dynamic_cast<PlaneMap *>(map.get())->GetDepthStats();
+        if (depth_mapping) me.depth_map = dynamic_cast<MapperMap *>(map.get())->GetDepthMapStats();
         if (profile && id == 0) {
           char names[32][32];
           double ms[32];
@@ -520,16 +526,27 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "depth seeding: %ld keyframes, %ld seeds; corners OK %ld HOLE %ld FEW %ld EDGE %ld OUTSIDE %ld; %ld frames without depth\n", d.keyframes, d.seeds,
                    d.by_status[0], d.by_status[1], d.by_status[2], d.by_status[3], d.by_status[4], d.no_depth);
     }
+    char depth_map_json[256] = "";
+    if (depth_mapping) {
+      const MapperMap::DepthMapStats &d = per[0].depth_map;
+      std::fprintf(stderr, "depth mapping: %ld measured updates, fallen back HOLE %ld FEW %ld EDGE %ld OUTSIDE %ld; %ld keyframes looked up, corners fixed %ld matched + %ld unmatched, %ld linked\n",
+                   d.measured, d.fallback[0], d.fallback[1], d.fallback[2], d.fallback[3], d.keyframes, d.fixed_matched, d.fixed_unmatched, d.linked);
+      std::snprintf(depth_map_json, sizeof(depth_map_json),
+                    ", \"depth_mapping\": {\"measured\": %ld, \"hole\": %ld, \"few\": %ld, \"edge\": %ld, \"outside\": %ld, \"keyframes\": %ld, \"fixed_matched\": %ld, "
+                    "\"fixed_unmatched\": %ld, \"linked\": %ld}",
+                    d.measured, d.fallback[0], d.fallback[1], d.fallback[2], d.fallback[3], d.keyframes, d.fixed_matched, d.fixed_unmatched, d.linked);
+    }
     if (json)
       std::printf("{\"trackers\": %d, \"frames\": %d, \"tracked\": %d, \"frames_per_s\": %.2f, \"frames_per_s_per_camera\": %.2f, \"ms_per_frame_p50\": %.4f, "
                   "\"ms_per_frame_p95\": %.4f, \"ms_per_frame_max\": %.4f, \"wall_s\": %.3f, \"input\": \"%s\", \"texture\": \"%s\", \"width\": %d, \"height\": %d, "
-                  "\"mapper\": %s, \"api\": \"%s\"}\n",
+                  "\"mapper\": %s, \"api\": \"%s\"%s}\n",
                   n_trackers, n_frames, tracked, total, per_camera, pct(0.5), pct(0.95), all_ms.empty() ? 0.0 : static_cast<double>(all_ms.back()), wall,
                   pool ? (pool_pinned ? "page-locked host memory" : "pageable host memory") : "host memory of the loop (pageable)",
                   texture == SDVL_TEXTURE_CAMERA ? "camera" : "plane", W, H, mapper ? "true" : "false",
                   batch ? "sdvl::SDVLBatch::HandleFrames, one call per frame for all cameras (one thread, one stream)"
                   : lookahead ? "SDVL::SetNextImage + SDVL::HandleFrame per frame (the next frame of the sequence named one call ahead)"
-                        : "SDVL::HandleFrame per frame and camera (host/track_sequence.cc, the loop of main.cc:126-159; one thread and stream per camera)");
+                        : "SDVL::HandleFrame per frame and camera (host/track_sequence.cc, the loop of main.cc:126-159; one thread and stream per camera)",
+                  depth_map_json);
   } catch (const std::exception &e) {
     std::cerr << "track_sequence: " << e.what() << std::endl;
     return 1;

@@ -220,6 +220,27 @@ class TrackerBatch:
             raise RuntimeError("no tracker %d" % i)
         return dict(zip(("keyframes", "seeds", "ok", "hole", "few", "edge", "outside", "no_depth"), [int(v) for v in out]))
 
+    def set_depth_mapping(self, on=True, noise_abs=0.0, noise_quad=0.0):
+        """depth cameras inside the reference's mapper (SDVL::SetDepthMapping; needs set_depth and a mapper batch): the depth image of
+        every tracked frame feeds the candidates' depth filter as a measurement (sdvl_search_run_filter_measured), and the corners of a
+        new keyframe become fixed points at their measured depth — matched in a connected keyframe or on the new keyframe alone.  The
+        sensor's depth noise is tau = noise_abs + noise_quad z^2 (0: 0.001 m and 0.0015 per metre, an order of magnitude and not a
+        measurement); the trackers share it.  The points fixed from depth join seeded_points.  Raises RuntimeError without depth seeding,
+        without the mapper, with the mapper thread started and with the host depth filter."""
+        self.lib.sdvlh_batch_set_depth_mapping.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        if self.lib.sdvlh_batch_set_depth_mapping(self.h, int(bool(on)), float(noise_abs), float(noise_quad)) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+
+    def depth_map_stats(self, i):
+        """tracker i's depth mapping so far: dict(measured, hole, few, edge, outside, keyframes, fixed_matched, fixed_unmatched, linked) —
+        candidate updates that took the measured depth and those that fell back by the lookup's status, keyframes whose corners were looked
+        up, corners fixed and matched in a connected keyframe, fixed on the new keyframe alone, and measured corners linked to a point"""
+        out = (C.c_longlong * 9)()
+        self.lib.sdvlh_batch_depth_map_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        if self.lib.sdvlh_batch_depth_map_stats(self.h, int(i), out) != 0:
+            raise RuntimeError("no tracker %d, or not a mapper batch" % i)
+        return dict(zip(("measured", "hole", "few", "edge", "outside", "keyframes", "fixed_matched", "fixed_unmatched", "linked"), [int(v) for v in out]))
+
     def set_next_device(self, dev_ptrs):
         """look-ahead: the device images the NEXT step_device call will be given (None: none); their pyramids and corner detection
         are queued behind the coming step's search / pose chain (SDVLBatch::SetNextImages).  The buffers must keep their CONTENT until that

@@ -160,6 +160,31 @@ for _ in range(reps):
     dz, dstatus, dok = ctx.depth_seed(djobs, W, H, dxyl, cam)
 print("depth_seed: %d corners of %d frames per call, %d OK; %.1f us per blocking call (host wall, push + launch + copy back + wait)" %
       (len(dxyl), n, int(dok.sum()), (time.perf_counter() - t0) / reps * 1e6))
+# the mapper's depth filter on the search's own results, triangulated (depth_filter) and with a measured depth (depth_filter_measured): the
+# requests of frame pair j are one job over frame j's float depth image in HBM; both kernels appear in the table below
+fstates = (sdvl.DepthState * nreq)()
+for i in range(nreq):
+    s = fstates[i]
+    s.rho, s.sigma2, s.a, s.b, s.z_range = sreqs[i].idepth * 1.05, 0.05, 10.0, 10.0, 6.0
+    s.cos_alpha, s.last_distance, s.depth_mean, s.track_row = 1.0, 1.0 / sreqs[i].idepth, 2.0, -1
+fpar = sdvl.DepthParams()
+fpar.px_error_angle, fpar.min_depth, fpar.scale_min_dist, fpar.max_failed = 2.0 * np.arctan(1.0 / (2.0 * B.TUM_CAM[0])), 0.25, 0.25, 15
+f_cur = np.array([[sreqs[i].cur_pose[k] for k in range(7)] for i in range(nreq)])
+f_ref = np.array([[sreqs[i].ref_pose[k] for k in range(7)] for i in range(nreq)])
+f_bearing = np.array([[sreqs[i].bearing[k] for k in range(3)] for i in range(nreq)])
+f_found = np.array([r.found for r in sres], np.int32)
+f_px = np.array([tuple(r.px) for r in sres])
+f_level = np.array([r.level if r.found else 0 for r in sres], np.int32)
+fjobs, at = [], 0
+owner = {fr3[j].h.value: j for j in range(n)}
+counts_j = np.bincount([owner[sreqs[i].cur] for i in range(nreq)], minlength=n)
+for j in range(n):
+    fjobs.append(sdvl.DepthJob(dmap.data_ptr() + 4 * j * W * H, 1, 4 * W, sdvl.SDVL_DEPTH_F32, 0, 1.0, at, at + int(counts_j[j])))
+    at += int(counts_j[j])
+for _ in range(reps):
+    ctx.depth_filter(f_cur, f_ref, f_bearing, f_found, f_px, cam, fstates, fpar)
+    fm_out, fm_status = ctx.depth_filter_measured(f_cur, f_ref, f_bearing, f_found, f_px, f_level, cam, fstates, fpar, fjobs, W, H, None, 0.002, 0.001)
+print("depth filter: %d requests, %d found, %d measured (status OK)" % (nreq, int(f_found.sum()), int((fm_status == 0).sum())))
 # pose stage: n jobs of 190 matches (20 % gross outliers) of a small camera motion; rand() draws from numpy (timing only)
 prng = np.random.default_rng(7)
 pose_jobs = []
