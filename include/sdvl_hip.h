@@ -9,6 +9,10 @@
  * independent sequences, so that a single launch fills the 256 CUs.  Frames live in HBM behind opaque handles
  * (pyramid + corner list + ORB descriptors); only small records cross PCIe.
  *
+ * Depth cameras are an addition (the reference reads no depth image): sdvl_depth_seed / sdvl_depth_lookup read a registered depth image at
+ * a keyframe's corners / at tracked features, sdvl_depth_filter_measured feeds the mapper's depth filter, and sdvl_bundle_adjust_depth
+ * gives local bundle adjustment depth edges (g2o's EdgeStereoSE3ProjectXYZ).
+ *
  * Poses are 7 doubles (qw,qx,qy,qz,tx,ty,tz) of Frame::pose_ (world -> camera), extra/se3.h:32-78.
  * Threading: one sdvl_ctx per host thread (tracker / mapper); frames may be shared read-only across contexts
  * of the same device once the creating context has been synchronised. */
@@ -549,6 +553,15 @@ typedef struct sdvl_depth_seed_params {
 int sdvl_depth_seed(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n_corners, const int32_t *xyl,
                     const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
                     int32_t *out_ok_per_job);
+/* The same rule at positions of the caller's own: px2[n][2] are LEVEL-0 positions of the gray image (a tracked feature's found pixel,
+ * sub-pixel) and level[n] the pyramid level each was found on.  Per position the centre is floor(px + 0.5) (with a lens: of the raw
+ * pixel px's ray lands on), the window the nine samples at stride 1 << level around it, validity, status order and out_z as above:
+ * exactly what the measured depth filter below looks up at a found pixel.  Jobs (c_* indexing the positions), staging, checks, refusals
+ * and out_ok_per_job as for sdvl_depth_seed; a position no job names comes back HOLE; a position that is not finite is OUTSIDE.  One
+ * launch, one lane per position.  tests/depth_lookup_restatement.py is its specification. */
+int sdvl_depth_lookup(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n, const double *px2, const int32_t *level,
+                      const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
+                      int32_t *out_ok_per_job);
 /* A pageable depth image is copied to the device by the call that is given it.  Between these two calls (one step of a caller that hands the
  * same images to sdvl_depth_seed and to the measured depth filter below) an image staged once — same pointer, stride, format and size — is
  * not staged again; the caller leaves its contents alone meanwhile.  The copies live in buffers of their own, not in scratch a search uses. */
@@ -867,6 +880,27 @@ typedef struct sdvl_bundle_result {
 int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed,
                        int n_pt, double *points, int n_e, const sdvl_bundle_edge *edges, const sdvl_camera *cam, int32_t *edge_levels,
                        int32_t *pose_stages, int32_t *point_stages, sdvl_bundle_result *results);
+
+/* The same with depth edges: an observation of a depth camera carries the measured camera-frame z of its pixel, in metres.  An edge
+ * with depth > 0 is g2o's EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.cpp:150-234; the reference ships it and never uses it) with
+ * identity information: err = (u - u', v - v', (u - bf / depth) - (u' - bf / z)), Huber delta^2 and outlier threshold 7.815 (95 % of
+ * chi2 with three degrees of freedom); it goes to level 1 as a whole.  An edge with depth <= 0 is the edge of sdvl_bundle_adjust in
+ * every respect.  bf (pixel x metres) converts depth noise to pixels: one unit of the third residual is dz bf / z^2.  A depth is metric:
+ * it removes the scale gauge that a window with one fixed keyframe leaves to lambda.  tests/bundle_depth_restatement.py is the
+ * specification.  Contract, caps and statuses are those of sdvl_bundle_adjust; in addition a depth that is NaN or infinite, and a bf
+ * that is not finite and > 0 while any edge of a problem carries a depth, are SDVL_ERR_INVALID with a message and nothing written.
+ * A problem gives the same bits wherever it stands in a call, and a problem none of whose edges carries a depth gives the bytes
+ * sdvl_bundle_adjust gives for it, whatever its neighbours carry: such problems run the monocular kernel, the others the depth form
+ * in a second launch of the same call. */
+typedef struct sdvl_bundle_edge_depth {
+  int32_t point, keyframe;
+  double u, v;
+  double depth;             /* measured camera-frame z at (u, v), metres; <= 0: none, a monocular edge */
+} sdvl_bundle_edge_depth;
+
+int sdvl_bundle_adjust_depth(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed,
+                             int n_pt, double *points, int n_e, const sdvl_bundle_edge_depth *edges, const sdvl_camera *cam, double bf,
+                             int32_t *edge_levels, int32_t *pose_stages, int32_t *point_stages, sdvl_bundle_result *results);
 
 /* ---- synthetic sequence generator (no dataset ships with the repo) ------------------------------- */
 struct sdvl_synth_view;

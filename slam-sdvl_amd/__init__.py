@@ -183,13 +183,13 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_lookup", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
     "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
     "sdvl_frames_own_images", "sdvl_feed_create", "sdvl_feed_destroy", "sdvl_feed_last_error", "sdvl_feed_slot_arrived", "sdvl_feed_images", "sdvl_ctx_feed_acquire", "sdvl_ctx_feed_release", "sdvl_frame_footprint_cap", "sdvl_ctx_set_corner_capacity", "sdvl_frame_corner_capacity", "sdvl_detect_scratch_bytes",
-    "sdvl_klt_track", "sdvl_homography_ransac", "sdvl_bundle_adjust",
+    "sdvl_klt_track", "sdvl_homography_ransac", "sdvl_bundle_adjust", "sdvl_bundle_adjust_depth",
     "sdvl_ctx_set_wait_spin", "sdvl_ctx_fork_mark", "sdvl_ctx_fork_begin", "sdvl_ctx_fork_end", "sdvl_host_alloc_pinned", "sdvl_host_free_pinned", "sdvl_host_register", "sdvl_host_unregister",
 ]
 
@@ -210,6 +210,8 @@ def load_library():
         lib.sdvl_ctx_stream.argtypes = [C.c_void_p]
         lib.sdvl_bundle_adjust.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.sdvl_bundle_adjust_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.sdvl_synth_scene_preset.argtypes = [C.c_char_p, C.c_void_p]
         lib.sdvl_synth_scene_preset_names.restype = C.c_char_p
         lib.sdvl_synth_render_scene.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -372,6 +374,11 @@ class BundleProblem(C.Structure):
 
 class BundleEdge(C.Structure):
     _fields_ = [("point", C.c_int32), ("keyframe", C.c_int32), ("u", C.c_double), ("v", C.c_double)]
+
+
+class BundleEdgeDepth(C.Structure):
+    """sdvl_bundle_edge_depth: depth = the measured camera-frame z of the observation in metres, <= 0: none"""
+    _fields_ = [("point", C.c_int32), ("keyframe", C.c_int32), ("u", C.c_double), ("v", C.c_double), ("depth", C.c_double)]
 
 
 class BundleStage(C.Structure):
@@ -790,6 +797,22 @@ class Context:
                                              ok.ctypes.data))
         return z[:n], status[:n], ok[:len(jobs)]
 
+    def depth_lookup(self, jobs, width, height, px, levels, cam, dist=None, **rule):
+        """sdvl_depth_lookup: depth_seed's rule at level-0 positions px [n][2] (sub-pixel) with the window stride of levels [n]; jobs, cam,
+        dist and rule as for depth_seed, the jobs' ranges indexing the positions -> (z float64 [n], status uint8 [n], ok per job int32)"""
+        keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, 0.0, 0.0, rule)
+        px = np.ascontiguousarray(px, np.float64).reshape(-1, 2)
+        levels = np.ascontiguousarray(levels, np.int32).reshape(-1)
+        n = len(px)
+        assert len(levels) == n
+        z, status, ok = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8), np.zeros(max(len(jobs), 1), np.int32)
+        self.lib.sdvl_depth_lookup.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_depth_lookup(self.h, len(jobs), arr, width, height, n, px.ctypes.data, levels.ctypes.data, C.addressof(cam),
+                                               C.addressof(d5) if d5 is not None else None, C.addressof(mp.rule), z.ctypes.data, status.ctypes.data,
+                                               ok.ctypes.data))
+        return z[:n], status[:n], ok[:len(jobs)]
+
     def _depth_measure_args(self, jobs, width, height, dist, noise_abs, noise_quad, rule):
         """the depth side of the two measured entries -> (objects to keep alive, job array, distortion or None, DepthMeasureParams)"""
         keep, arr = [], (DepthJob * max(len(jobs), 1))()
@@ -1052,8 +1075,10 @@ class Context:
         return [dict(H=np.array(list(res[k].H)).reshape(3, 3), best_draw=res[k].best_draw, n_its=res[k].n_its,
                      inliers=lists[hj[k].m_begin:hj[k].m_begin + res[k].n_inliers].copy()) for k in range(n)]
 
-    def bundle_adjust(self, problems, cam):
+    def bundle_adjust(self, problems, cam, bf=None):
         """Bundle::Local (extra/bundle.cc:110-223) for every problem of the list in one launch.
+        With bf (pixel x metres) the problems' edge_d [n_e] (measured camera-frame z in metres, 0: none) makes depth edges of the
+        observations that carry one (sdvl_bundle_adjust_depth; a problem without edge_d has none); without bf edge_d is not looked at.
         problems: dicts with poses [n_kf][7] (free ones first), fixed [n_kf], points [n_pt][3], edge_pt [n_e], edge_kf [n_e] (indices
         inside the problem), edge_uv [n_e][2]; cam = (fx, fy, cx, cy).  The inputs are not modified.
         Returns per problem dict(status, poses, points, levels [n_e], pose_stages [n_kf], point_stages [n_pt], n_level1,
@@ -1062,8 +1087,9 @@ class Context:
         bp = (BundleProblem * max(n, 1))()
         poses_all, fixed_all, pts_all = [np.zeros((0, 7))], [np.zeros(0, np.int32)], [np.zeros((0, 3))]
         edge_n = sum(len(p["edge_pt"]) for p in problems)
-        be = np.zeros(max(edge_n, 1), np.dtype([("point", np.int32), ("keyframe", np.int32), ("u", np.float64), ("v", np.float64)]))
-        assert be.dtype.itemsize == C.sizeof(BundleEdge)
+        fields = [("point", np.int32), ("keyframe", np.int32), ("u", np.float64), ("v", np.float64)]
+        be = np.zeros(max(edge_n, 1), np.dtype(fields + ([("depth", np.float64)] if bf is not None else [])))
+        assert be.dtype.itemsize == C.sizeof(BundleEdge if bf is None else BundleEdgeDepth)
         k_at = p_at = e_at = 0
         for j, p in enumerate(problems):
             poses = np.asarray(p["poses"], np.float64).reshape(-1, 7)
@@ -1073,6 +1099,9 @@ class Context:
             bp[j] = BundleProblem(k_at, k_at + len(poses), p_at, p_at + len(pts), e_at, e_at + len(uv))
             sl = be[e_at:e_at + len(uv)]
             sl["point"], sl["keyframe"], sl["u"], sl["v"] = p["edge_pt"], p["edge_kf"], uv[:, 0], uv[:, 1]
+            if bf is not None and "edge_d" in p:
+                assert len(p["edge_d"]) == len(uv)
+                sl["depth"] = p["edge_d"]
             k_at += len(poses); p_at += len(pts); e_at += len(uv)
             poses_all.append(poses); fixed_all.append(np.asarray(p["fixed"], np.int32)); pts_all.append(pts)
         poses = np.ascontiguousarray(np.concatenate(poses_all), np.float64).copy()
@@ -1082,8 +1111,12 @@ class Context:
         kstage, pstage = np.zeros(max(k_at, 1), np.int32), np.zeros(max(p_at, 1), np.int32)
         res = (BundleResult * max(n, 1))()
         c = Camera(0.0, 0.0, float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]))
-        self._check(self.lib.sdvl_bundle_adjust(self.h, n, bp, k_at, poses.ctypes.data, fixed.ctypes.data, p_at, pts.ctypes.data, e_at, be.ctypes.data,
-                                                C.byref(c), levels.ctypes.data, kstage.ctypes.data, pstage.ctypes.data, res))
+        if bf is None:
+            self._check(self.lib.sdvl_bundle_adjust(self.h, n, bp, k_at, poses.ctypes.data, fixed.ctypes.data, p_at, pts.ctypes.data, e_at, be.ctypes.data,
+                                                    C.byref(c), levels.ctypes.data, kstage.ctypes.data, pstage.ctypes.data, res))
+        else:
+            self._check(self.lib.sdvl_bundle_adjust_depth(self.h, n, bp, k_at, poses.ctypes.data, fixed.ctypes.data, p_at, pts.ctypes.data, e_at,
+                                                          be.ctypes.data, C.byref(c), float(bf), levels.ctypes.data, kstage.ctypes.data, pstage.ctypes.data, res))
         out = []
         for j in range(n):
             b, r = bp[j], res[j]

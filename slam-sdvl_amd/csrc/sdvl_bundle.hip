@@ -2,6 +2,8 @@
 // does to a local window of keyframes and points (optimization_algorithm_levenberg.cpp:61-189, block_solver.hpp,
 // base_binary_edge.hpp:60-115, robust_kernel_impl.cpp:78-91, types_six_dof_expmap.cpp:103-147).  g2o is no dependency of this project:
 // tests/bundle_restatement.py states what is computed, DESIGN §2 what g2o leaves implicit.
+// The kernel is a template over the depth form (sdvl_bundle_adjust_depth, tests/bundle_depth_restatement.py): an edge that carries a
+// measured depth is EdgeStereoSE3ProjectXYZ (:150-234), three rows; bundle_adjust_kernel<false> is the monocular kernel as it was.
 //
 // One workgroup (256 threads) per problem; both stages, every iteration and every trial run inside the kernel.  Everything is FP64.
 // No floating-point atomics: a point's blocks are summed by its own thread over its CSR edges, a pose's blocks by its own 16 lanes over
@@ -19,6 +21,7 @@
 
 #include <algorithm>
 #include <numeric>
+#include <type_traits>
 
 #include "sdvl_internal.h"
 
@@ -32,7 +35,8 @@ constexpr int kTile = 48;                                 // per-edge slots (and
 // entries of the reduced system's lower triangle (36 per block pair a > b, 21 per diagonal block) and of its right-hand side
 constexpr int items_of(int nf) { return nf * (nf + 1) / 2 * 36 - 15 * nf + 6 * nf; }
 constexpr int kItems = (items_of(kMaxFree) + kThreads - 1) / kThreads;  // per thread: 19
-constexpr double kChi2Th = 5.991;
+constexpr double kChi2Th = 5.991;       // 95 % of chi2 with two degrees of freedom: the monocular edge
+constexpr double kChi2ThDepth = 7.815;  // with three: the depth edge
 constexpr int kMaxTrials = 10;
 
 struct EdgeDev {  // CSR (point-major) order
@@ -72,22 +76,51 @@ struct BundleArgs {
   double fx, fy, cx, cy;
 };
 
+// the depth form (sdvl_bundle_adjust_depth): EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.cpp:150-234) on the edges that carry a
+// measured depth; tests/bundle_depth_restatement.py states it.  The monocular form neither reads nor holds any of this.
+struct BundleArgsD : BundleArgs {
+  const double *edge_depth;  // [n_e] CSR order: measured camera-frame z, <= 0: a monocular edge
+  double bf;
+};
+template <bool kDepth>
+using ArgsOf = std::conditional_t<kDepth, BundleArgsD, BundleArgs>;
+
 struct Geo {
   double x, y, z, ex, ey;
+  double ez;  // depth form only: (u - bf / d) - (u' - bf / z), 0 on an edge without a depth
 };
 
-__device__ __forceinline__ Geo edge_geo(const double *__restrict__ rt, const double *__restrict__ X, double u, double v, const BundleArgs &A) {
+template <bool kDepth>
+__device__ __forceinline__ Geo edge_geo(const double *__restrict__ rt, const double *__restrict__ X, double u, double v, double d, const ArgsOf<kDepth> &A) {
   Geo g;
   g.x = ((rt[0] * X[0] + rt[1] * X[1]) + rt[2] * X[2]) + rt[9];
   g.y = ((rt[3] * X[0] + rt[4] * X[1]) + rt[5] * X[2]) + rt[10];
   g.z = ((rt[6] * X[0] + rt[7] * X[1]) + rt[8] * X[2]) + rt[11];
   g.ex = u - (A.fx * g.x / g.z + A.cx);
   g.ey = v - (A.fy * g.y / g.z + A.cy);
+  if constexpr (kDepth) g.ez = d > 0.0 ? (u - A.bf / d) - ((A.fx * g.x / g.z + A.cx) - A.bf / g.z) : 0.0;
   return g;
 }
 
-// linearizeOplus, types_six_dof_expmap.cpp:103-139
-__device__ __forceinline__ void edge_jacobians(const Geo &g, const double *__restrict__ rt, const BundleArgs &A, double Ji[2][3], double Jj[2][6]) {
+// err.err, rows summed ((r0 + r1) + r2)
+template <bool kDepth>
+__device__ __forceinline__ double edge_chi2(const Geo &g) {
+  double e = g.ex * g.ex + g.ey * g.ey;
+  if constexpr (kDepth) e = e + g.ez * g.ez;
+  return e;
+}
+
+// the edge's outlier threshold = its Huber delta^2
+template <bool kDepth>
+__device__ __forceinline__ double edge_threshold(double d) {
+  if constexpr (kDepth) return d > 0.0 ? kChi2ThDepth : kChi2Th;
+  return kChi2Th;
+}
+
+// linearizeOplus, types_six_dof_expmap.cpp:103-139; the depth form's row 2 is row 0 plus the bf terms of :210-212 and :228-233, and
+// zero on an edge without a depth
+template <bool kDepth>
+__device__ __forceinline__ void edge_jacobians(const Geo &g, const double *__restrict__ rt, double d, const ArgsOf<kDepth> &A, double (*Ji)[3], double (*Jj)[6]) {
   const double x = g.x, y = g.y, z = g.z, z2 = z * z;
   const double t02 = -x / z * A.fx, t12 = -y / z * A.fy, s = -1.0 / z;
   for (int c = 0; c < 3; c++) {
@@ -106,11 +139,35 @@ __device__ __forceinline__ void edge_jacobians(const Geo &g, const double *__res
   Jj[1][3] = 0.0;
   Jj[1][4] = -1.0 / z * A.fy;
   Jj[1][5] = y / z2 * A.fy;
+  if constexpr (kDepth) {
+    const bool has = d > 0.0;
+    for (int c = 0; c < 3; c++) Ji[2][c] = has ? Ji[0][c] - A.bf * rt[6 + c] / z2 : 0.0;
+    Jj[2][0] = has ? Jj[0][0] - A.bf * y / z2 : 0.0;
+    Jj[2][1] = has ? Jj[0][1] + A.bf * x / z2 : 0.0;
+    Jj[2][2] = has ? Jj[0][2] : 0.0;
+    Jj[2][3] = has ? Jj[0][3] : 0.0;
+    Jj[2][4] = 0.0;
+    Jj[2][5] = has ? Jj[0][5] - A.bf / z2 : 0.0;
+  }
+}
+
+// sum over the edge's rows of A[k][i] B[k][j] and of A[k][i] err[k], ((r0 + r1) + r2)
+template <bool kDepth, int NA, int NB>
+__device__ __forceinline__ double rows_jj(const double (*A)[NA], int i, const double (*B)[NB], int j) {
+  double s = A[0][i] * B[0][j] + A[1][i] * B[1][j];
+  if constexpr (kDepth) s = s + A[2][i] * B[2][j];
+  return s;
+}
+template <bool kDepth, int NA>
+__device__ __forceinline__ double rows_je(const double (*A)[NA], int i, const Geo &g) {
+  double s = A[0][i] * g.ex + A[1][i] * g.ey;
+  if constexpr (kDepth) s = s + A[2][i] * g.ez;
+  return s;
 }
 
 // RobustKernelHuber::robustify, robust_kernel_impl.cpp:78-91: rho[0] -> *cost, returns rho[1]
-__device__ __forceinline__ double huber(double e, bool robust, double *cost) {
-  const double delta = sqrt(kChi2Th), dsqr = delta * delta;
+__device__ __forceinline__ double huber(double e, bool robust, bool depth_edge, double *cost) {
+  const double delta = depth_edge ? sqrt(kChi2ThDepth) : sqrt(kChi2Th), dsqr = delta * delta;
   if (!robust || e <= dsqr) {
     *cost = e;
     return 1.0;
@@ -207,7 +264,9 @@ __device__ __forceinline__ double block_max(double v, double *red) {  // of non-
 
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
 
-__global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
+template <bool kDepth>
+__global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(ArgsOf<kDepth> A) {
+  constexpr int kRows = kDepth ? 3 : 2;
   __shared__ double S[kPacked];            // reduced system, lower triangle; then its Cholesky factor
   __shared__ double bp[kMaxN], xs[kMaxN], xsol[kMaxN];  // b of the poses; right-hand side (-> y of L y = rhs); the solution
   __shared__ double pose_lin[kMaxFree][7], pose_trial[kMaxFree][7];
@@ -236,6 +295,10 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
   double *hpp = A.hpp + static_cast<size_t>(blockIdx.x) * kMaxFree * 36;
   double *hpart = A.hpart + static_cast<size_t>(blockIdx.x) * kMaxFree * 16 * 27;
   int32_t *levels = A.levels;
+  auto edge_d = [&](int e) -> double {  // the measured depth of (absolute) edge e
+    if constexpr (kDepth) return A.edge_depth[e];
+    return 0.0;
+  };
   const int nf = P.n_free, n = 6 * nf;
   const int n_items = items_of(nf);
 
@@ -283,12 +346,13 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
   for (int stage = 0; stage < 2; stage++) {
     const bool robust = stage == 0;
     if (stage == 1) {
-      // bundle.cc:196-205 at the accepted estimates: chi2 > 5.991 or depth not positive -> level 1
+      // bundle.cc:196-205 at the accepted estimates: chi2 > 5.991 (a depth edge: 7.815) or depth not positive -> level 1
       double n1 = 0.0, n_free_active = 0.0;
       for (int e = tid; e < P.n_e; e += kThreads) {
         const EdgeDev ed = edges[P.e_begin + e];
-        const Geo g = edge_geo(rt_lin + 12 * ed.kf, points + 3 * ed.pt, ed.u, ed.v, A);
-        const bool bad = (g.ex * g.ex + g.ey * g.ey > kChi2Th) || !(g.z > 0.0);
+        const double dm = edge_d(P.e_begin + e);
+        const Geo g = edge_geo<kDepth>(rt_lin + 12 * ed.kf, points + 3 * ed.pt, ed.u, ed.v, dm, A);
+        const bool bad = (edge_chi2<kDepth>(g) > edge_threshold<kDepth>(dm)) || !(g.z > 0.0);
         levels[P.e_begin + e] = bad ? 1 : 0;
         n1 += bad ? 1.0 : 0.0;
         n_free_active += (!bad && ed.kf < nf) ? 1.0 : 0.0;
@@ -319,18 +383,19 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
           if (levels[e] != 0) continue;
           const EdgeDev ed = edges[e];
           const double *rt = rt_lin + 12 * ed.kf;
-          const Geo g = edge_geo(rt, points + 3 * p, ed.u, ed.v, A);
-          double Ji[2][3], Jj[2][6], cost;
-          edge_jacobians(g, rt, A, Ji, Jj);
-          const double w = huber(g.ex * g.ex + g.ey * g.ey, robust, &cost);
+          const double dm = edge_d(e);
+          const Geo g = edge_geo<kDepth>(rt, points + 3 * p, ed.u, ed.v, dm, A);
+          double Ji[kRows][3], Jj[kRows][6], cost;
+          edge_jacobians<kDepth>(g, rt, dm, A, Ji, Jj);
+          const double w = huber(edge_chi2<kDepth>(g), robust, dm > 0.0, &cost);
           chi_part += cost;
-          h[0] += w * (Ji[0][0] * Ji[0][0] + Ji[1][0] * Ji[1][0]);
-          h[1] += w * (Ji[0][0] * Ji[0][1] + Ji[1][0] * Ji[1][1]);
-          h[2] += w * (Ji[0][0] * Ji[0][2] + Ji[1][0] * Ji[1][2]);
-          h[3] += w * (Ji[0][1] * Ji[0][1] + Ji[1][1] * Ji[1][1]);
-          h[4] += w * (Ji[0][1] * Ji[0][2] + Ji[1][1] * Ji[1][2]);
-          h[5] += w * (Ji[0][2] * Ji[0][2] + Ji[1][2] * Ji[1][2]);
-          for (int c = 0; c < 3; c++) h[6 + c] += -w * (Ji[0][c] * g.ex + Ji[1][c] * g.ey);
+          h[0] += w * rows_jj<kDepth>(Ji, 0, Ji, 0);
+          h[1] += w * rows_jj<kDepth>(Ji, 0, Ji, 1);
+          h[2] += w * rows_jj<kDepth>(Ji, 0, Ji, 2);
+          h[3] += w * rows_jj<kDepth>(Ji, 1, Ji, 1);
+          h[4] += w * rows_jj<kDepth>(Ji, 1, Ji, 2);
+          h[5] += w * rows_jj<kDepth>(Ji, 2, Ji, 2);
+          for (int c = 0; c < 3; c++) h[6 + c] += -w * rows_je<kDepth>(Ji, c, g);
         }
         for (int i = 0; i < 9; i++) ptblk[9 * p + i] = h[i];
         diag_part = fmax(diag_part, fmax(fabs(h[0]), fmax(fabs(h[3]), fabs(h[5]))));
@@ -346,13 +411,14 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
           if (levels[e] != 0) continue;
           const EdgeDev ed = edges[e];
           const double *rt = rt_lin + 12 * a;
-          const Geo g = edge_geo(rt, points + 3 * ed.pt, ed.u, ed.v, A);
-          double Ji[2][3], Jj[2][6], cost;
-          edge_jacobians(g, rt, A, Ji, Jj);
-          const double w = huber(g.ex * g.ex + g.ey * g.ey, robust, &cost);
+          const double dm = edge_d(e);
+          const Geo g = edge_geo<kDepth>(rt, points + 3 * ed.pt, ed.u, ed.v, dm, A);
+          double Ji[kRows][3], Jj[kRows][6], cost;
+          edge_jacobians<kDepth>(g, rt, dm, A, Ji, Jj);
+          const double w = huber(edge_chi2<kDepth>(g), robust, dm > 0.0, &cost);
           for (int r = 0, k = 0; r < 6; r++) {
-            for (int c = 0; c <= r; c++, k++) acc[k] += w * (Jj[0][r] * Jj[0][c] + Jj[1][r] * Jj[1][c]);
-            acc[21 + r] += -w * (Jj[0][r] * g.ex + Jj[1][r] * g.ey);
+            for (int c = 0; c <= r; c++, k++) acc[k] += w * rows_jj<kDepth>(Jj, r, Jj, c);
+            acc[21 + r] += -w * rows_je<kDepth>(Jj, r, g);
           }
         }
         for (int k = 0; k < 27; k++) hpart[(a * 16 + l) * 27 + k] = acc[k];
@@ -416,15 +482,16 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
             const EdgeDev ed = edges[e];
             if (levels[e] == 0) {
               const double *rt = rt_lin + 12 * ed.kf;
-              const Geo g = edge_geo(rt, points + 3 * ed.pt, ed.u, ed.v, A);
-              double Ji[2][3], Jj[2][6], cost;
-              edge_jacobians(g, rt, A, Ji, Jj);
-              const double w = huber(g.ex * g.ex + g.ey * g.ey, robust, &cost);
+              const double dm = edge_d(e);
+              const Geo g = edge_geo<kDepth>(rt, points + 3 * ed.pt, ed.u, ed.v, dm, A);
+              double Ji[kRows][3], Jj[kRows][6], cost;
+              edge_jacobians<kDepth>(g, rt, dm, A, Ji, Jj);
+              const double w = huber(edge_chi2<kDepth>(g), robust, dm > 0.0, &cost);
               const double *hi = tHinv[ed.pt - p0];
               const double H3[3][3] = {{hi[0], hi[1], hi[2]}, {hi[1], hi[3], hi[4]}, {hi[2], hi[4], hi[5]}};
               for (int i = 0; i < 6; i++) {
                 double wr[3];
-                for (int c = 0; c < 3; c++) wr[c] = w * (Jj[0][i] * Ji[0][c] + Jj[1][i] * Ji[1][c]);
+                for (int c = 0; c < 3; c++) wr[c] = w * rows_jj<kDepth>(Jj, i, Ji, c);
                 for (int c = 0; c < 3; c++) {
                   tW[tid][3 * i + c] = wr[c];
                   tY[tid][3 * i + c] = (wr[0] * H3[0][c] + wr[1] * H3[1][c]) + wr[2] * H3[2][c];
@@ -517,14 +584,15 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
               if (levels[e] != 0) continue;
               const EdgeDev ed = edges[e];
               const double *rt = rt_lin + 12 * ed.kf;
-              const Geo g = edge_geo(rt, points + 3 * p, ed.u, ed.v, A);
-              double Ji[2][3], Jj[2][6], cost;
-              edge_jacobians(g, rt, A, Ji, Jj);
-              const double w = huber(g.ex * g.ex + g.ey * g.ey, robust, &cost);
+              const double dm = edge_d(e);
+              const Geo g = edge_geo<kDepth>(rt, points + 3 * p, ed.u, ed.v, dm, A);
+              double Ji[kRows][3], Jj[kRows][6], cost;
+              edge_jacobians<kDepth>(g, rt, dm, A, Ji, Jj);
+              const double w = huber(edge_chi2<kDepth>(g), robust, dm > 0.0, &cost);
               const double *xa = xsol + 6 * ed.kf;
               for (int c = 0; c < 3; c++) {
                 double s = 0.0;
-                for (int r = 0; r < 6; r++) s += w * (Jj[0][r] * Ji[0][c] + Jj[1][r] * Ji[1][c]) * xa[r];
+                for (int r = 0; r < 6; r++) s += w * rows_jj<kDepth>(Jj, r, Ji, c) * xa[r];
                 tv[c] -= s;
               }
             }
@@ -542,9 +610,10 @@ __global__ __launch_bounds__(kThreads) void bundle_adjust_kernel(BundleArgs A) {
             for (int e = pt_off[p]; e < pt_off[p + 1]; e++) {
               if (levels[e] != 0) continue;
               const EdgeDev ed = edges[e];
-              const Geo g = edge_geo(rt_trial + 12 * ed.kf, pts_trial + 3 * p, ed.u, ed.v, A);
+              const double dm = edge_d(e);
+              const Geo g = edge_geo<kDepth>(rt_trial + 12 * ed.kf, pts_trial + 3 * p, ed.u, ed.v, dm, A);
               double cost;
-              huber(g.ex * g.ex + g.ey * g.ey, robust, &cost);
+              huber(edge_chi2<kDepth>(g), robust, dm > 0.0, &cost);
               cpart += cost;
             }
           chi_new = block_sum(cpart, red);
@@ -588,19 +657,36 @@ done:
   if (tid == 0) A.results[blockIdx.x] = res;
 }
 
-}  // namespace
+inline double depth_of(const sdvl_bundle_edge &) { return 0.0; }
+inline double depth_of(const sdvl_bundle_edge_depth &e) { return e.depth; }
 
-extern "C" int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed,
-                                  int n_pt, double *points, int n_e, const sdvl_bundle_edge *edges, const sdvl_camera *cam, int32_t *edge_levels,
-                                  int32_t *pose_stages, int32_t *point_stages, sdvl_bundle_result *results) {
+// Both entry points.  Edge = sdvl_bundle_edge: the monocular kernel over every problem, one launch.  Edge = sdvl_bundle_edge_depth:
+// the problems none of whose edges carries a depth are listed first and go to the monocular kernel as they are, which is what gives
+// them the monocular call's bits whatever their neighbours carry; the others go to the depth form in a second launch.
+template <class Edge>
+int bundle_adjust_any(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed, int n_pt,
+                      double *points, int n_e, const Edge *edges, const sdvl_camera *cam, double bf, int32_t *edge_levels, int32_t *pose_stages,
+                      int32_t *point_stages, sdvl_bundle_result *results) {
+  constexpr bool kDepthCall = std::is_same<Edge, sdvl_bundle_edge_depth>::value;
   if (!ctx || !cam || n_problems < 0 || n_kf < 0 || n_pt < 0 || n_e < 0 || (n_problems > 0 && (!problems || !results)) ||
       (n_kf > 0 && (!poses || !fixed || !pose_stages)) || (n_pt > 0 && (!points || !point_stages)) || (n_e > 0 && (!edges || !edge_levels)))
     return SDVL_ERR_INVALID;
   if (n_problems == 0) return SDVL_OK;
   // ---- checks first: nothing is written before every problem has passed
   std::vector<ProblemDev> pd(n_problems);
+  std::vector<char> with_depth(n_problems, 0);
   size_t n_ptoff = 0, n_kfoff = 0, n_fe = 0;
   int prev_kf = 0, prev_pt = 0, prev_e = 0;
+  if (kDepthCall) {
+    bool any = false;
+    for (int j = 0; j < n_problems; j++)
+      for (int e = std::max(problems[j].edge_begin, 0); e < std::min(problems[j].edge_end, n_e); e++) {
+        const double d = depth_of(edges[e]);
+        SDVL_REQUIRE(ctx, std::isfinite(d), "an edge's depth is NaN or infinite (<= 0 means none)");
+        if (d > 0.0) with_depth[j] = 1, any = true;
+      }
+    SDVL_REQUIRE(ctx, !any || (std::isfinite(bf) && bf > 0.0), "bf must be finite and > 0 when an edge carries a depth");
+  }
   for (int j = 0; j < n_problems; j++) {
     const sdvl_bundle_problem &a = problems[j];
     SDVL_REQUIRE(ctx, a.kf_begin >= prev_kf && a.kf_end >= a.kf_begin && a.kf_end <= n_kf, "pose range out of bounds or overlapping");
@@ -683,6 +769,7 @@ extern "C" int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bund
   const sdvl_part<int32_t> st_ptoff = st.take<int32_t>(n_ptoff), st_ptfe = st.take<int32_t>(n_ptoff), st_kfoff = st.take<int32_t>(n_kfoff);
   const sdvl_part<int32_t> st_kfe = st.take<int32_t>(std::max<size_t>(n_csr, 1)), st_fe = st.take<int32_t>(fe.size()), st_tile = st.take<int32_t>(tile_pt.size());
   const sdvl_part<double> st_poses = st.take<double>(7 * static_cast<size_t>(std::max(n_kf, 1))), st_points = st.take<double>(3 * static_cast<size_t>(std::max(n_pt, 1)));
+  const sdvl_part<double> st_depth = kDepthCall ? st.take<double>(std::max<size_t>(n_csr, 1)) : sdvl_part<double>{};
   const sdvl_part<double> o_poses = o.take<double>(st_poses.count), o_points = o.take<double>(st_points.count);
   const sdvl_part<int32_t> o_levels = o.take<int32_t>(std::max<size_t>(n_csr, 1)), o_pstage = o.take<int32_t>(std::max(n_kf, 1)), o_qstage = o.take<int32_t>(std::max(n_pt, 1));
   const sdvl_part<sdvl_bundle_result> o_res = o.take<sdvl_bundle_result>(n_problems);
@@ -696,11 +783,18 @@ extern "C" int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bund
   if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
   if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
   if (rc) return rc;
-  memcpy(st_prob.in(hs), pd.data(), st_prob.bytes());
+  // the kernels' problem lists: the problems without a depth first (all of them in the monocular call), in the caller's order
+  std::vector<int32_t> perm;
+  for (int pass = 0; pass < 2; pass++)
+    for (int j = 0; j < n_problems; j++)
+      if (with_depth[j] == pass) perm.push_back(j);
+  const int n_mono = static_cast<int>(std::count(with_depth.begin(), with_depth.end(), 0));
+  for (int i = 0; i < n_problems; i++) st_prob.in(hs)[i] = pd[perm[i]];
   EdgeDev *he = st_edges.in(hs);
   for (size_t c = 0; c < n_csr; c++) {
-    const sdvl_bundle_edge &e = edges[order[c]];
+    const Edge &e = edges[order[c]];
     he[c] = EdgeDev{e.point, e.keyframe, e.u, e.v};
+    if (kDepthCall) st_depth.in(hs)[c] = depth_of(e);
   }
   memcpy(st_ptoff.in(hs), pt_off.data(), st_ptoff.bytes());
   memcpy(st_ptfe.in(hs), pt_fe_off.data(), st_ptfe.bytes());
@@ -738,7 +832,18 @@ extern "C" int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bund
   A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->u0; A.cy = cam->v0;
   // vertices and edges of no problem keep zeros
   SDVL_HIP_CHECK(ctx, hipMemsetAsync(o_levels.in(ctx->d_out), 0, o.bytes() - o_levels.off, ctx->stream));
-  SDVL_LAUNCH(ctx, "bundle_adjust", bundle_adjust_kernel, dim3(n_problems), dim3(kThreads), A);
+  if (n_mono > 0) SDVL_LAUNCH(ctx, "bundle_adjust", bundle_adjust_kernel<false>, dim3(n_mono), dim3(kThreads), A);
+  if (n_mono < n_problems) {  // blockIdx.x counts from the first problem with a depth
+    BundleArgsD D;
+    static_cast<BundleArgs &>(D) = A;
+    D.problems += n_mono;
+    D.results += n_mono;
+    D.hpp += static_cast<size_t>(n_mono) * kMaxFree * 36;
+    D.hpart += static_cast<size_t>(n_mono) * kMaxFree * 16 * 27;
+    D.edge_depth = st_depth.cin(dsx);
+    D.bf = bf;
+    SDVL_LAUNCH(ctx, "bundle_adjust_depth", bundle_adjust_kernel<true>, dim3(n_problems - n_mono), dim3(kThreads), D);
+  }
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
@@ -746,18 +851,32 @@ extern "C" int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bund
   const sdvl_bundle_result *hr = o_res.cin(ctx->h_out);
   const double *hp = o_poses.cin(ctx->h_out), *hq = o_points.cin(ctx->h_out);
   const int32_t *hl = o_levels.cin(ctx->h_out);
-  memcpy(results, hr, o_res.bytes());
+  for (int i = 0; i < n_problems; i++) results[perm[i]] = hr[i];
   for (int e = 0; e < n_e; e++) edge_levels[e] = 0;
   for (int k = 0; k < n_kf; k++) pose_stages[k] = 0;
   for (int q = 0; q < n_pt; q++) point_stages[q] = 0;
   for (int j = 0; j < n_problems; j++) {
-    if (hr[j].status != SDVL_BUNDLE_OK) continue;
+    if (results[j].status != SDVL_BUNDLE_OK) continue;
     const sdvl_bundle_problem &a = problems[j];
-    memcpy(poses + 7 * static_cast<size_t>(a.kf_begin), hp + 7 * static_cast<size_t>(a.kf_begin), sizeof(double) * 7 * static_cast<size_t>(hr[j].n_free));
+    memcpy(poses + 7 * static_cast<size_t>(a.kf_begin), hp + 7 * static_cast<size_t>(a.kf_begin), sizeof(double) * 7 * static_cast<size_t>(results[j].n_free));
     memcpy(points + 3 * static_cast<size_t>(a.pt_begin), hq + 3 * static_cast<size_t>(a.pt_begin), sizeof(double) * 3 * static_cast<size_t>(a.pt_end - a.pt_begin));
     for (int e = a.edge_begin; e < a.edge_end; e++) edge_levels[e] = hl[csr_of[e]];
     memcpy(pose_stages + a.kf_begin, o_pstage.cin(ctx->h_out) + a.kf_begin, sizeof(int32_t) * static_cast<size_t>(a.kf_end - a.kf_begin));
     memcpy(point_stages + a.pt_begin, o_qstage.cin(ctx->h_out) + a.pt_begin, sizeof(int32_t) * static_cast<size_t>(a.pt_end - a.pt_begin));
   }
   return SDVL_OK;
+}
+
+}  // namespace
+
+extern "C" int sdvl_bundle_adjust(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed,
+                                  int n_pt, double *points, int n_e, const sdvl_bundle_edge *edges, const sdvl_camera *cam, int32_t *edge_levels,
+                                  int32_t *pose_stages, int32_t *point_stages, sdvl_bundle_result *results) {
+  return bundle_adjust_any(ctx, n_problems, problems, n_kf, poses, fixed, n_pt, points, n_e, edges, cam, 0.0, edge_levels, pose_stages, point_stages, results);
+}
+
+extern "C" int sdvl_bundle_adjust_depth(sdvl_ctx *ctx, int n_problems, const sdvl_bundle_problem *problems, int n_kf, double *poses, const int32_t *fixed,
+                                        int n_pt, double *points, int n_e, const sdvl_bundle_edge_depth *edges, const sdvl_camera *cam, double bf,
+                                        int32_t *edge_levels, int32_t *pose_stages, int32_t *point_stages, sdvl_bundle_result *results) {
+  return bundle_adjust_any(ctx, n_problems, problems, n_kf, poses, fixed, n_pt, points, n_e, edges, cam, bf, edge_levels, pose_stages, point_stages, results);
 }

@@ -9,7 +9,8 @@
 //   status    the first that applies of OUTSIDE (centre off the image), HOLE (centre invalid), FEW (fewer than min_valid valid samples),
 //             EDGE (max - min over the valid samples > edge_ratio x the centre's depth); otherwise OK and z = the centre sample, unfiltered
 // depth_seed: one lane per corner, nine gathers, no LDS; all jobs of a call in one launch.  The lookup itself (depth_lookup,
-// sdvl_depth_device.h) is shared with the mapper's measured depth filter (sdvl_search.hip).  A keyframe reads ~2.3 k samples of a 1.2 MB
+// sdvl_depth_device.h) is shared with the mapper's measured depth filter (sdvl_search.hip) and with sdvl_depth_lookup below, which applies it
+// at the sub-pixel position a feature was found at (the depths bundle adjustment's depth edges carry).  A keyframe reads ~2.3 k samples of a 1.2 MB
 // image: a source in HBM or in pinned host memory is read where it lies; only a pageable source is copied, into buffers the context keeps
 // for depth images alone.  The file is built with -ffp-contract=off like every other: the centre is the restatement's operation order,
 // ties included.
@@ -36,6 +37,25 @@ __global__ __launch_bounds__(256) void depth_seed(const DepthJobDev *__restrict_
   const int l = xyl[3 * i + 2], s = 1 << l;
   double zc;
   const int status = depth_lookup(jobs[jb], static_cast<double>(xyl[3 * i]) * s, static_cast<double>(xyl[3 * i + 1]) * s, s, width, height, lens, rule, &zc);
+  out_z[i] = zc;
+  out_status[i] = static_cast<uint8_t>(status);
+}
+
+// sdvl_depth_lookup: the same rule at a position of its own, one lane per position — the level-0 pixel a feature was found at and the
+// stride of the level it was found on, as depth_filter_measured_kernel (sdvl_search.hip) applies it
+__global__ __launch_bounds__(256) void depth_lookup_kernel(const DepthJobDev *__restrict__ jobs, const double *__restrict__ px2, const int32_t *__restrict__ level,
+                                                           const int32_t *__restrict__ pos_job, int n, int width, int height, DepthLens lens, DepthRule rule,
+                                                           double *__restrict__ out_z, uint8_t *__restrict__ out_status) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int jb = pos_job[i];
+  if (jb < 0) {  // a position no job names
+    out_z[i] = 0.0;
+    out_status[i] = SDVL_DEPTH_SEED_HOLE;
+    return;
+  }
+  double zc;
+  const int status = depth_lookup(jobs[jb], px2[2 * i], px2[2 * i + 1], 1 << level[i], width, height, lens, rule, &zc);
   out_z[i] = zc;
   out_status[i] = static_cast<uint8_t>(status);
 }
@@ -178,6 +198,57 @@ int sdvl_depth_seed(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int w
   const DepthLens lens = sdvl_depth_lens_of(cam, dist);
   SDVL_LAUNCH(ctx, "depth_seed", depth_seed, dim3((n_corners + 255) / 256), dim3(256), st_jobs.cin(ds), st_xyl.cin(ds), st_cj.cin(ds), n_corners, width,
               height, lens, rule, o_z.in(ctx->d_out), o_status.in(ctx->d_out));
+  SDVL_HIP_CHECK(ctx, hipGetLastError());
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
+  memcpy(out_z, o_z.in(ctx->h_out), o_z.bytes());
+  memcpy(out_status, o_status.in(ctx->h_out), o_status.bytes());
+  for (int j = 0; j < n_jobs; j++) {
+    int ok = 0;
+    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) ok += out_status[i] == SDVL_DEPTH_SEED_OK ? 1 : 0;
+    out_ok_per_job[j] = ok;
+  }
+  return SDVL_OK;
+}
+
+int sdvl_depth_lookup(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n, const double *px2, const int32_t *level,
+                      const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
+                      int32_t *out_ok_per_job) {
+  if (!ctx) return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, n_jobs >= 0 && n >= 0, "sdvl_depth_lookup: negative count");
+  if (n_jobs == 0 || n == 0) {
+    for (int j = 0; j < n_jobs && out_ok_per_job; j++) out_ok_per_job[j] = 0;
+    return SDVL_OK;
+  }
+  SDVL_REQUIRE(ctx, jobs && px2 && level && cam && out_z && out_status && out_ok_per_job, "sdvl_depth_lookup: null pointer");
+  DepthRule rule;
+  int rc = sdvl_depth_rule_of(ctx, "sdvl_depth_lookup", p, &rule);
+  if (!rc) rc = sdvl_depth_jobs_check(ctx, "sdvl_depth_lookup", n_jobs, jobs, width, height, n);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) SDVL_REQUIRE(ctx, level[i] >= 0 && level[i] < SDVL_MAX_LEVELS, "sdvl_depth_lookup: level outside 0 .. SDVL_MAX_LEVELS - 1");
+  // staging: jobs | positions | levels | the job of every position (-1: none); d_out and h_out: z | status
+  sdvl_layout st, o;
+  const sdvl_part<DepthJobDev> st_jobs = st.take<DepthJobDev>(n_jobs);
+  const sdvl_part<double> st_px = st.take<double>(2 * static_cast<size_t>(n));
+  const sdvl_part<int32_t> st_level = st.take<int32_t>(n), st_pj = st.take<int32_t>(n);
+  const sdvl_part<double> o_z = o.take<double>(n);
+  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
+  void *hs = nullptr, *ds = nullptr;
+  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
+  if (!rc) rc = sdvl_depth_jobs_resolve(ctx, n_jobs, jobs, width, height, st_jobs.in(hs));
+  if (rc) return rc;
+  int32_t *hpj = st_pj.in(hs);
+  for (int i = 0; i < n; i++) hpj[i] = -1;
+  for (int j = 0; j < n_jobs; j++)
+    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) hpj[i] = j;
+  memcpy(st_px.in(hs), px2, st_px.bytes());
+  memcpy(st_level.in(hs), level, st_level.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  const DepthLens lens = sdvl_depth_lens_of(cam, dist);
+  SDVL_LAUNCH(ctx, "depth_lookup", depth_lookup_kernel, dim3((n + 255) / 256), dim3(256), st_jobs.cin(ds), st_px.cin(ds), st_level.cin(ds), st_pj.cin(ds), n,
+              width, height, lens, rule, o_z.in(ctx->d_out), o_status.in(ctx->d_out));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));

@@ -545,6 +545,46 @@ void SDVLBatch::MeasureKeyframeCorners(const vector<MapperMap *> &mm, const vect
   for (size_t j = 0; j < jobs.size(); j++) mm[whose[j]]->SetCornerDepths(depth_z_.data() + jobs[j].c_begin, depth_status_.data() + jobs[j].c_begin);
 }
 
+// Depth edges in bundle adjustment (SDVL::SetDepthBundle): the features the step's new keyframes hold when their mapper takes them up —
+// the tracked matches, at their found pixel and level — are looked up in their frames' depth images by ONE sdvl_depth_lookup call, inside
+// the step's sdvl_depth_stage_begin / _end bracket like the sdvl_depth_seed calls beside it.  A keyframe that is not the step's own frame
+// (or came without an image) is not looked up: its image is gone.
+void SDVLBatch::LookupKeyframeFeatures(const vector<MapperMap *> &mm, const vector<int> &mm_trk, const vector<int> &kf_idx) {
+  vector<sdvl_depth_job> jobs;
+  vector<int> whose;
+  vector<double> px2;
+  vector<int32_t> level;
+  const sdvl_depth_seed_params *rule = nullptr;
+  int width = 0, height = 0;
+  for (int k : kf_idx) {
+    if (!mm[k]->DepthBundleOn() || mm[k]->CurrentFrame().get() != trk_[mm_trk[k]]->step_frame_) continue;
+    const DepthImage *d = DepthOf(mm_trk[k]);
+    if (!d) continue;
+    const sdvl_depth_seed_params *r = &trk_[mm_trk[k]]->depth_rule_;
+    if (rule && std::memcmp(rule, r, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
+    rule = r;
+    const int first = static_cast<int>(level.size());
+    const int n = mm[k]->EmitDepthLookups(&px2, &level);
+    if (n == 0) continue;
+    width = mm[k]->CurrentFrame()->GetWidth();
+    height = mm[k]->CurrentFrame()->GetHeight();
+    jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, first, first + n});
+    whose.push_back(k);
+  }
+  if (jobs.empty()) return;
+  const int n = static_cast<int>(level.size());
+  depth_z_.assign(n, 0.0);
+  depth_status_.assign(n, 0);
+  vector<int32_t> ok(jobs.size(), 0);
+  const Camera &camera = *trk_[0]->camera_;
+  const sdvl_camera cam = camera.abi();
+  const sdvl_distortion dist = camera.distortion();
+  dev_->Check(sdvl_depth_lookup(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), width, height, n, px2.data(), level.data(), &cam,
+                                camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
+              "sdvl_depth_lookup");
+  for (size_t j = 0; j < jobs.size(); j++) mm[whose[j]]->ApplyDepthLookups(depth_z_.data() + jobs[j].c_begin, depth_status_.data() + jobs[j].c_begin);
+}
+
 // stage 5: SDVL::Mapping() of sequential mode (main.cc:148-149) for the trackers that own a real mapper: the phases of
 // Map::UpdateMap run in lock step, every phase's SearchPoint requests of ALL trackers in one K7 launch
 void SDVLBatch::RunMappers() {
@@ -677,6 +717,7 @@ void SDVLBatch::RunMappers() {
     if (mm[k]->IsKeyframeUpdate()) kf_idx.push_back(k);
   const int K = static_cast<int>(kf_idx.size());
   sub.reset(new StageClock(ST_MAP_CONNECTIONS));
+  if (K > 0) LookupKeyframeFeatures(mm, mm_trk, kf_idx);  // (returns at once unless a mapper has depth edges on)
   if (K > 0) {
     ParallelFor(K, [&](int q) {
       MapperMap *m = mm[kf_idx[q]];
@@ -722,7 +763,13 @@ void SDVLBatch::RunMappers() {
   if (problems.empty()) return;
   vector<sdvl_bundle_result> results;
   vector<vector<Frame *>> moved;
-  Bundle::Solve(dev_, *trk_[0]->camera_, problems, &results, &moved);
+  double bf = 0.0;  // depth edges: the windows of the mappers that have them on carry depths; the trackers of a batch share bf
+  for (int k : whose) {
+    if (!mm[k]->DepthBundleOn()) continue;
+    if (bf > 0.0 && bf != mm[k]->DepthBundleBf()) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth edges' bf");
+    bf = mm[k]->DepthBundleBf();
+  }
+  Bundle::Solve(dev_, *trk_[0]->camera_, problems, &results, &moved, bf);
   for (size_t j = 0; j < problems.size(); j++) mm[whose[j]]->FinishBundle(windows[whose[j]], results[j], moved[j]);
 }
 

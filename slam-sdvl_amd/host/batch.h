@@ -65,6 +65,7 @@ class SDVLBatch {
   void FinishKeyframes(Step &s);
   void SeedKeyframesFromDepth(Step &s, std::vector<const double *> *z, std::vector<const uint8_t *> *status);
   void RunMappers();
+  void LookupKeyframeFeatures(const std::vector<MapperMap *> &mm, const std::vector<int> &mm_trk, const std::vector<int> &kf_idx);
   void MeasureKeyframeCorners(const std::vector<MapperMap *> &mm, const std::vector<int> &mm_trk, const std::vector<int> &kf_idx, const std::vector<char> &need,
                               const std::vector<const DepthImage *> &depth_of);
   const std::vector<DepthImage> *step_depths_ = nullptr;  // the depth images of the step in flight (HandleFrames)

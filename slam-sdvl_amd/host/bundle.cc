@@ -15,12 +15,13 @@ int Bundle::NextId() {
   return counter++;
 }
 
-bool Bundle::Collect(const vector<shared_ptr<Frame>> &kfs, BundleProblem *out) {
+bool Bundle::Collect(const vector<shared_ptr<Frame>> &kfs, BundleProblem *out, bool with_depth) {
   const int id = NextId();
   out->kfs.clear();
   out->points.clear();
   out->edges.clear();
   out->n_free = 0;
+  out->n_depth_edges = out->n_depth_level1 = 0;
   // :72-87: all points involved.  (GetFeatures turns a tracked keyframe's flat records into Feature objects and links them to their points.)
   for (const shared_ptr<Frame> &kf : kfs) {
     kf->SetLastBA(id);
@@ -63,18 +64,20 @@ bool Bundle::Collect(const vector<shared_ptr<Frame>> &kfs, BundleProblem *out) {
       if (it == index.end()) continue;  // :167-168
       if (seen[it->second] == static_cast<int32_t>(q)) continue;
       seen[it->second] = static_cast<int32_t>(q);
-      sdvl_bundle_edge e;
+      sdvl_bundle_edge_depth e;
       e.point = static_cast<int32_t>(q);
       e.keyframe = it->second;
       e.u = ft->GetPosition()(0);
       e.v = ft->GetPosition()(1);
+      e.depth = with_depth ? ft->GetDepth() : 0.0;
+      if (e.depth > 0.0) out->n_depth_edges++;
       out->edges.push_back(e);
     }
   return true;
 }
 
 void Bundle::Solve(Device *dev, const Camera &camera, const vector<BundleProblem *> &problems, vector<sdvl_bundle_result> *results,
-                   vector<vector<Frame *>> *moved) {
+                   vector<vector<Frame *>> *moved, double bf) {
   const int J = static_cast<int>(problems.size());
   results->assign(J, sdvl_bundle_result{});
   moved->assign(J, vector<Frame *>());
@@ -82,7 +85,7 @@ void Bundle::Solve(Device *dev, const Camera &camera, const vector<BundleProblem
   vector<sdvl_bundle_problem> ranges(J);
   vector<double> poses, points;
   vector<int32_t> fixed;
-  vector<sdvl_bundle_edge> edges;
+  vector<sdvl_bundle_edge_depth> edges;
   for (int j = 0; j < J; j++) {
     const BundleProblem &p = *problems[j];
     sdvl_bundle_problem &r = ranges[j];
@@ -106,14 +109,25 @@ void Bundle::Solve(Device *dev, const Camera &camera, const vector<BundleProblem
   }
   vector<int32_t> levels(edges.size() + 1), pose_stages(fixed.size() + 1), point_stages(points.size() / 3 + 1);
   const sdvl_camera cam = camera.abi();  // :180-183
-  dev->Check(sdvl_bundle_adjust(dev->ctx(), J, ranges.data(), static_cast<int>(fixed.size()), poses.data(), fixed.data(), static_cast<int>(points.size() / 3),
-                                points.data(), static_cast<int>(edges.size()), edges.data(), &cam, levels.data(), pose_stages.data(), point_stages.data(),
-                                results->data()),
-             "sdvl_bundle_adjust");
+  if (bf > 0.0) {
+    dev->Check(sdvl_bundle_adjust_depth(dev->ctx(), J, ranges.data(), static_cast<int>(fixed.size()), poses.data(), fixed.data(),
+                                        static_cast<int>(points.size() / 3), points.data(), static_cast<int>(edges.size()), edges.data(), &cam, bf,
+                                        levels.data(), pose_stages.data(), point_stages.data(), results->data()),
+               "sdvl_bundle_adjust_depth");
+  } else {
+    vector<sdvl_bundle_edge> mono(edges.size());
+    for (size_t e = 0; e < edges.size(); e++) mono[e] = sdvl_bundle_edge{edges[e].point, edges[e].keyframe, edges[e].u, edges[e].v};
+    dev->Check(sdvl_bundle_adjust(dev->ctx(), J, ranges.data(), static_cast<int>(fixed.size()), poses.data(), fixed.data(), static_cast<int>(points.size() / 3),
+                                  points.data(), static_cast<int>(mono.size()), mono.data(), &cam, levels.data(), pose_stages.data(), point_stages.data(),
+                                  results->data()),
+               "sdvl_bundle_adjust");
+  }
   for (int j = 0; j < J; j++) {
     if ((*results)[j].status != SDVL_BUNDLE_OK) continue;  // the estimates stay as they were
-    const BundleProblem &p = *problems[j];
+    BundleProblem &p = *problems[j];
     const sdvl_bundle_problem &r = ranges[j];
+    p.n_depth_level1 = 0;
+    for (int e = r.edge_begin; e < r.edge_end && bf > 0.0; e++) p.n_depth_level1 += edges[e].depth > 0.0 && levels[e] != 0 ? 1 : 0;
     // :211-216 — poses first: a candidate point's position hangs off its first keyframe's pose (Point::SetPosition)
     for (int k = 0; k < p.n_free; k++) {
       if (!pose_stages[r.kf_begin + k]) continue;  // a vertex without an active edge was not optimised

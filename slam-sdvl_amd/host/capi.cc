@@ -315,6 +315,31 @@ int sdvlh_batch_depth_map_stats(void *bp, int i, long long *out9) {
   return 0;
 }
 
+// Depth edges in the mappers' bundle adjustment (SDVL::SetDepthBundle): needs sdvlh_batch_set_depth and sdvlh_batch_set_bundle_adjustment;
+// bf in pixel x metres, 0: the default; the trackers share it
+int sdvlh_batch_set_depth_bundle(void *bp, int on, double bf) {
+  if (!bp) return -1;
+  return Guarded([&] {
+    for (int i = 0; i < AsGroup(bp)->size(); i++) AsGroup(bp)->tracker(i).SetDepthBundle(on != 0, bf);
+  });
+}
+// tracker i's depth edges so far: out13 = lookups by status (OK, HOLE, FEW, EDGE, OUTSIDE), observations that got a depth stored, then
+// edges, edges with a depth and depth edges that ended on level 1 of the last window, the same three summed over all windows, and the
+// features that were handed to the lookup
+int sdvlh_batch_depth_bundle_stats(void *bp, int i, long long *out13) {
+  TrackerGroup *b = AsGroup(bp);
+  if (!b || i < 0 || i >= b->size() || !out13) return -1;
+  MapperMap *m = dynamic_cast<MapperMap *>(&b->map(i));
+  if (!m) return -1;
+  const DepthBundleStats &s = m->GetDepthBundleStats();
+  for (int k = 0; k < 5; k++) out13[k] = s.lookups[k];
+  out13[5] = s.stored;
+  out13[6] = s.last_edges; out13[7] = s.last_depth_edges; out13[8] = s.last_depth_level1;
+  out13[9] = s.total_edges; out13[10] = s.total_depth_edges; out13[11] = s.total_depth_level1;
+  out13[12] = s.features;
+  return 0;
+}
+
 // ---- TrackerFarm (farm.h): G groups x Bg sequences on ONE GPU
 void *sdvlh_farm_create(int gpu, int G, int Bg, int w, int h, const double *cam4, const double *plane4, const double *first_poses7,
                         int host_threads_per_group) {

@@ -1,5 +1,5 @@
 // mapper.cc — the reference's mapper (map.cc, point.cc depth filter) on top of the batched K7 search kernel: SURVEY §8f
-// row 3.  Sequential mode only (main.cc:148-149); bundle adjustment (extra/bundle.cc) is out of scope and not run.
+// row 3.  Sequential mode only (main.cc:148-149); local bundle adjustment (extra/bundle.cc) runs behind it when it is switched on (bundle.h).
 // Every function cites the reference lines it restates; arithmetic keeps the reference's expression order (the file is
 // built with -ffp-contract=off like the rest of the host layer).
 #include <algorithm>
@@ -231,6 +231,40 @@ void MapperMap::SetBundleAdjustment(bool on) {
   if (on && running_) throw std::runtime_error("MapperMap::SetBundleAdjustment: bundle adjustment runs in sequential mode only, the mapper thread is started");
   bundle_on_ = on;
   if (!on) ba_kf_.reset();
+  if (!on) depth_bundle_ = store_depths_ = false;  // depth edges live inside the adjustment
+}
+
+// ---- depth edges (sdvl_host.h)
+void MapperMap::SetDepthBundle(bool on, double bf) {
+  if (on && running_) throw std::runtime_error("MapperMap::SetDepthBundle: bundle adjustment runs in sequential mode only, the mapper thread is started");
+  if (on && !bundle_on_) throw std::runtime_error("MapperMap::SetDepthBundle: bundle adjustment is off (SetBundleAdjustment comes first)");
+  if (on && !(bf >= 0.0 && std::isfinite(bf))) throw std::invalid_argument("MapperMap::SetDepthBundle: bf must be finite and not negative (0: the default)");
+  depth_bundle_ = store_depths_ = on;
+  depth_bundle_bf_ = on ? bf : 0.0;
+}
+
+int MapperMap::EmitDepthLookups(vector<double> *px2, vector<int32_t> *level) {
+  lookup_features_.clear();
+  if (!depth_bundle_ || !cur_) return 0;
+  for (const shared_ptr<Feature> &ft : cur_->GetFeatures()) {
+    if (!ft || ft->GetDepth() > 0.0) continue;
+    px2->push_back(ft->GetPosition()(0));
+    px2->push_back(ft->GetPosition()(1));
+    level->push_back(std::min(std::max(ft->GetLevel(), 0), SDVL_MAX_LEVELS - 1));
+    lookup_features_.push_back(ft);
+  }
+  depth_bundle_stats_.features += static_cast<long>(lookup_features_.size());
+  return static_cast<int>(lookup_features_.size());
+}
+
+void MapperMap::ApplyDepthLookups(const double *z, const uint8_t *status) {
+  for (size_t i = 0; i < lookup_features_.size(); i++) {
+    depth_bundle_stats_.lookups[status[i] <= SDVL_DEPTH_SEED_OUTSIDE ? status[i] : SDVL_DEPTH_SEED_HOLE]++;
+    if (status[i] != SDVL_DEPTH_SEED_OK || !(z[i] > 0.0)) continue;
+    lookup_features_[i]->SetDepth(z[i]);
+    depth_bundle_stats_.stored++;
+  }
+  lookup_features_.clear();
 }
 
 bool MapperMap::PrepareBundle(BundleProblem *out, int min_keyframes) {
@@ -244,7 +278,7 @@ bool MapperMap::PrepareBundle(BundleProblem *out, int min_keyframes) {
   for (const shared_ptr<Frame> &kf : keyframes_)
     if (kf->HasFlatFeatures()) kf->GetFeatures();
   ba_kf_.reset();  // :868
-  if (!Bundle::Collect(fov_kfs, out)) return false;
+  if (!Bundle::Collect(fov_kfs, out, depth_bundle_)) return false;
   if (out->n_free > SDVL_BUNDLE_MAX_FREE) {  // more than the device solver takes (SDVL.max_search_keyframes above 7): this adjustment is left out
     bundle_stats_.skipped++;
     return false;
@@ -259,6 +293,15 @@ void MapperMap::FinishBundle(const BundleProblem &problem, const sdvl_bundle_res
   bundle_stats_.n_points = static_cast<int>(problem.points.size());
   bundle_stats_.n_edges = static_cast<int>(problem.edges.size());
   bundle_stats_.last = result;
+  if (depth_bundle_) {
+    DepthBundleStats &d = depth_bundle_stats_;
+    d.last_edges = static_cast<long>(problem.edges.size());
+    d.last_depth_edges = problem.n_depth_edges;
+    d.last_depth_level1 = result.status == SDVL_BUNDLE_OK ? problem.n_depth_level1 : 0;
+    d.total_edges += d.last_edges;
+    d.total_depth_edges += d.last_depth_edges;
+    d.total_depth_level1 += d.last_depth_level1;
+  }
   if (result.status != SDVL_BUNDLE_OK) return;  // nothing was written
   // what the device holds of the old estimates: the (frame, pose) registry entries of the keyframes that moved (registered again by the
   // next table that names them), the tracker's table rows (inverse depths and bearings of the points, rebuilt before the next step) and
@@ -273,7 +316,7 @@ void MapperMap::BundleAdjustment(int min_keyframes) {
   if (!PrepareBundle(&problem, min_keyframes)) return;
   vector<sdvl_bundle_result> results;
   vector<vector<Frame *>> moved;
-  Bundle::Solve(Device::Current(), *camera_, {&problem}, &results, &moved);
+  Bundle::Solve(Device::Current(), *camera_, {&problem}, &results, &moved, depth_bundle_ ? DepthBundleBf() : 0.0);
   FinishBundle(problem, results[0], moved[0]);
 }
 
@@ -760,6 +803,10 @@ void MapperMap::ApplyInitCandidates(const sdvl_search_res *res_all) {
           if (CornerMeasured(count)) {
             linked[count] = true;
             depth_map_stats_.linked++;
+            if (store_depths_) {
+              feature->SetDepth(ic_z_[count]);
+              depth_bundle_stats_.stored++;
+            }
           }
         }
       }
@@ -789,6 +836,10 @@ void MapperMap::ApplyInitCandidates(const sdvl_search_res *res_all) {
         candidate->SetFixed();
         candidate->SetPosition(pos);
         depth_seeds_.push_back(DepthSeedRec{candidate, cur_->GetID(), corner(0), corner(1), corner(2)});
+        if (store_depths_) {  // the new keyframe's corner keeps its sample; the partner feature in the older keyframe has none
+          feature->SetDepth(ic_z_[count]);
+          depth_bundle_stats_.stored++;
+        }
         stats_.initialized++;
         depth_map_stats_.fixed_matched++;
         continue;
@@ -833,6 +884,10 @@ void MapperMap::ApplyInitCandidates(const sdvl_search_res *res_all) {
       cur_->AddFeature(feature);
       pt->AddFeature(feature);
       depth_seeds_.push_back(DepthSeedRec{pt, cur_->GetID(), corner(0), corner(1), corner(2)});
+      if (store_depths_) {
+        feature->SetDepth(ic_z_[c]);
+        depth_bundle_stats_.stored++;
+      }
       depth_map_stats_.fixed_unmatched++;
     }
     version_++;
@@ -862,6 +917,7 @@ void MapperMap::SetCornerDepths(const double *z, const uint8_t *status) {
   if (!depth_mapping_ || !cur_ || !z || !status) return;
   const int nc = cur_->NumFiltered();
   ic_range_.assign(nc, 0.0);
+  ic_z_.assign(nc, 0.0);
   depth_map_stats_.keyframes++;
   for (int c = 0; c < nc; c++) {
     if (status[c] != SDVL_DEPTH_SEED_OK) continue;
@@ -869,7 +925,10 @@ void MapperMap::SetCornerDepths(const double *z, const uint8_t *status) {
     const int scale = (1 << corner(2));
     const Vector3d bearing = camera_->Unproject(Vector2d(corner(0) * scale, corner(1) * scale));
     const double range = z[c] / bearing(2);
-    if (range > 0.0) ic_range_[c] = range;
+    if (range > 0.0) {
+      ic_range_[c] = range;
+      ic_z_[c] = z[c];
+    }
   }
 }
 

@@ -56,6 +56,8 @@ class PlaneMap : public Map {
  protected:
   struct DepthSeedRec { std::weak_ptr<Point> point; int keyframe_id, u, v, level; };
   std::vector<DepthSeedRec> depth_seeds_;  // SeedFromDepth drops the records of points that are gone
+  bool store_depths_ = false;              // MapperMap::SetDepthBundle: a seeded corner's feature keeps its z (Feature::SetDepth)
+  DepthBundleStats depth_bundle_stats_;
 
  private:
   Vector3d n_;
@@ -134,6 +136,22 @@ class MapperMap : public PlaneMap {
   void FinishBundle(const BundleProblem &problem, const sdvl_bundle_result &result, const std::vector<Frame *> &moved);
   void BundleAdjustment(int min_keyframes = 2);  // the three for this map alone: one sdvl_bundle_adjust call
   const BundleStats &GetBundleStats() const { return bundle_stats_; }
+  // ---- depth edges in the adjustment (an addition; SDVL::SetDepthBundle, off by default).  An observation carries the camera-frame z its
+  // frame's depth image measured at it when the feature was made in a step that had the image: the corners a keyframe is seeded from
+  // (PlaneMap::SeedFromDepth, the measured corners of InitCandidates) keep sdvl_depth_seed's z, and the features a frame holds when it
+  // becomes a keyframe — its tracked matches — are looked up at their found pixel and level (sdvl_depth_lookup, by the driver: the
+  // two calls below).  Features added to a keyframe in a later step (AddConnectionsPoints, the partner feature of a new candidate in a
+  // connected keyframe) carry none and stay monocular edges.  bf (pixel x metres) turns depth noise into pixels; 0: 1 / noise_quad of
+  // SetDepthMapping (0.0015 when that is off or at its default, 666.7 px m): one pixel of the third residual is then one sigma of the
+  // quadratic noise term — an order of magnitude nobody has measured against a sensor, like that term.  Throws std::runtime_error
+  // without bundle adjustment on and while the mapper thread runs, std::invalid_argument for a negative or non-finite bf.
+  void SetDepthBundle(bool on, double bf = 0.0);
+  bool DepthBundleOn() const { return depth_bundle_; }
+  double DepthBundleBf() const { return depth_bundle_bf_ > 0.0 ? depth_bundle_bf_ : 1.0 / (noise_quad_ != 0.0 ? noise_quad_ : 0.0015); }
+  // the features of CurrentFrame() (a keyframe update) that have no depth yet, as level-0 positions and levels, appended to the lists
+  int EmitDepthLookups(std::vector<double> *px2, std::vector<int32_t> *level);
+  void ApplyDepthLookups(const double *z, const uint8_t *status);  // of the features EmitDepthLookups listed, in its order
+  const DepthBundleStats &GetDepthBundleStats() const { return depth_bundle_stats_; }
   // the whole of it for one tracker (one launch per phase)
   void UpdateMap() override;
   // map.cc:49-71: the mapper thread of threaded mode.  It works on a Device of its own (one sdvl_ctx = one HIP stream per
@@ -188,6 +206,10 @@ class MapperMap : public PlaneMap {
   bool depth_mapping_ = false;
   double noise_abs_ = 0.0, noise_quad_ = 0.0;              // SetDepthMapping: as given (0: sdvl_depth_measure_params' default)
   std::vector<double> ic_range_;                           // SetCornerDepths: the measured range of filtered corner c, 0: not measured
+  std::vector<double> ic_z_;                               // and the sample itself, for Feature::SetDepth
+  bool depth_bundle_ = false;
+  double depth_bundle_bf_ = 0.0;                           // SetDepthBundle: as given (0: the default)
+  std::vector<std::shared_ptr<Feature>> lookup_features_;  // EmitDepthLookups: whose depths ApplyDepthLookups gets
   DepthMapStats depth_map_stats_;
   std::thread thread_;
   std::atomic<bool> running_{false};
@@ -244,6 +266,12 @@ class SDVL {
   // (sdvl_bundle_adjust).  Off by default.  Needs the reference's mapper in sequential mode: throws std::runtime_error with any other map
   // and while the mapper thread runs.
   void SetBundleAdjustment(bool on);
+  // Depth edges in that adjustment (an addition, MapperMap::SetDepthBundle): the observations that carry a measured depth become
+  // EdgeStereoSE3ProjectXYZ edges (sdvl_bundle_adjust_depth), which fixes the scale that a window with one fixed keyframe leaves free.
+  // Off by default.  bf: pixel x metres, 0 takes 1 / noise_quad of the depth mapping.  Throws std::runtime_error without depth seeding,
+  // without bundle adjustment on, with any other map and while the mapper thread runs; std::invalid_argument for a negative or
+  // non-finite bf.  Depth mapping is not required.
+  void SetDepthBundle(bool on, double bf = 0.0);
   // sdvl.h:52-54 (the UI's queries)
   void GetCameraTrail(std::vector<std::pair<SE3, bool>> *positions);
   void GetPoints(std::vector<Vector3d> *positions);

@@ -309,6 +309,10 @@ void PlaneMap::SeedFromDepth(const shared_ptr<Frame> &kf, const double *z, const
     pt->AddFeature(feature);
     depth_seeds_.push_back(DepthSeedRec{pt, kf->GetID(), corner(0), corner(1), corner(2)});
     depth_stats_.seeds++;
+    if (store_depths_) {
+      feature->SetDepth(z[k]);
+      depth_bundle_stats_.stored++;
+    }
   }
 }
 
@@ -499,6 +503,13 @@ void SDVL::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
   if (on && !m) throw std::runtime_error("SDVL::SetDepthMapping needs the reference's mapper (MapperMap)");
   if (on && !depth_seeding_) throw std::runtime_error("SDVL::SetDepthMapping needs depth seeding (SetDepthSeeding): the bootstrap keyframe is seeded from depth too");
   if (m) m->SetDepthMapping(on, noise_abs, noise_quad);
+}
+
+void SDVL::SetDepthBundle(bool on, double bf) {
+  MapperMap *m = dynamic_cast<MapperMap *>(map_);
+  if (on && !m) throw std::runtime_error("SDVL::SetDepthBundle needs the reference's mapper (MapperMap)");
+  if (on && !depth_seeding_) throw std::runtime_error("SDVL::SetDepthBundle needs depth seeding (SetDepthSeeding): without it no observation carries a depth");
+  if (m) m->SetDepthBundle(on, bf);
 }
 
 void SDVL::SetBundleAdjustment(bool on) {

@@ -17,6 +17,8 @@
 //                                                                frame's depth feeds the candidates' filter, new keyframes' corners become fixed points; beside --depth only
 //   track_sequence --list frames.txt --depth-list depth.txt --depth-scale S   the same from disk: one 16-bit binary PGM (P5, maxval above 255; netpbm's samples are
 //                                                                big-endian and are swapped here) per frame, S metres per unit (TUM: 0.0002)
+//   track_sequence ... --depth --depth-bundle [--depth-bf X]   depth edges in the local bundle adjustment (SDVL::SetDepthBundle; implies --bundle): X in
+//                                                                pixel x metres, default 1 / noise_quad of the depth mapping = 666.7
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
 //   round 5 (bench.py's latency legs):  [--texture plane|camera]  [--trackers N]  N cameras = N host threads, each with its own Device
 //            (= HIP stream), Camera, Map and SDVL, all fed the same frames;  [--batch]  with --trackers N: the N cameras step together through
@@ -120,6 +122,7 @@ const char kUsage[] =
     "      gray10 | gray12 | gray16                            little-endian 16-bit gray; the P5 is 2 W bytes wide\n"
     "    16-bit PGM (maxval above 255) is big-endian and is not supported\n"
     "  --depth: with --synthetic N --scene NAME, the keyframes' points are seeded from the renderer's registered depth image (no plane)\n"
+    "  --depth-bundle [--depth-bf X]: with --depth, observations that carry a measured depth are depth edges of the bundle adjustment (implies --bundle)\n"
     "  --depth-list FILE --depth-scale S: one 16-bit P5 depth image (big-endian samples, S metres per unit) per frame of --list\n"
     "  common: [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle]\n"
     "          [--init plane|two-frame] [--trackers N] [--batch] [--lookahead] [--prerender] [--pageable] [--set SDVL.key value]\n"
@@ -145,7 +148,8 @@ int main(int argc, char **argv) {
   bool mapper = false, bundle = false, two_frame = false, size_given = false, cam_given = false, dist_given = false;
   bool prerender = false, pageable = false, quiet = false, json = false, profile = false, batch = false, lookahead = false;
   int n_trackers = 1, raw_format = 0;
-  bool depth = false, depth_mapping = false, plane_given = false;
+  bool depth = false, depth_mapping = false, plane_given = false, depth_bundle = false;
+  double depth_bf = 0.0;
   std::string depth_list;
   double depth_scale = 0.0;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
@@ -165,6 +169,8 @@ int main(int argc, char **argv) {
     else if (a == "--plane") { need(4); for (int k = 0; k < 4; k++) plane[k] = std::atof(argv[++i]); plane_given = true; }
     else if (a == "--depth") depth = true;
     else if (a == "--depth-mapping") { depth_mapping = true; mapper = true; }
+    else if (a == "--depth-bundle") { depth_bundle = true; bundle = true; mapper = true; }
+    else if (a == "--depth-bf") { need(1); depth_bf = std::atof(argv[++i]); }
     else if (a == "--depth-list") { need(1); depth_list = argv[++i]; depth = true; }
     else if (a == "--depth-scale") { need(1); depth_scale = std::atof(argv[++i]); }
     else if (a == "--mapper") mapper = true;
@@ -194,6 +200,7 @@ int main(int argc, char **argv) {
     }
   }
   const bool use_scene = !scene_name.empty();
+  if (depth_bundle && !depth) { std::cerr << "--depth-bundle takes its depths from the frames' depth images: give --depth or --depth-list too" << std::endl; return 2; }
   if (depth_mapping && !depth) { std::cerr << "--depth-mapping feeds the mapper from the frames' depth images: give --depth or --depth-list too" << std::endl; return 2; }
   if (depth) {
     if (depth_list.empty() && !use_scene) { std::cerr << "--depth tracks on the renderer's depth: give --synthetic N --scene NAME, or --depth-list FILE with --list" << std::endl; return 2; }
@@ -306,7 +313,7 @@ int main(int argc, char **argv) {
       render_dev->Check(sdvl_device_free(rc, dbuf), "sdvl_device_free");
     }
 
-    struct PerTracker { double busy = 0.0; int tracked = 0; std::vector<float> ms; std::string err; PlaneMap::DepthStats depth; MapperMap::DepthMapStats depth_map; };
+    struct PerTracker { double busy = 0.0; int tracked = 0; std::vector<float> ms; std::string err; PlaneMap::DepthStats depth; MapperMap::DepthMapStats depth_map; DepthBundleStats depth_bundle; };
     std::vector<PerTracker> per(n_trackers);
     std::atomic<int> ready{0};
     std::atomic<bool> go{false};
@@ -326,6 +333,7 @@ int main(int argc, char **argv) {
         if (bundle) sdvl.SetBundleAdjustment(true);
         if (depth) sdvl.SetDepthSeeding(true);
         if (depth_mapping) sdvl.SetDepthMapping(true);
+        if (depth_bundle) sdvl.SetDepthBundle(true, depth_bf);
         std::vector<float> depth_f32(depth && depth_list.empty() ? frame_bytes : 0);
         std::vector<uint16_t> depth_u16;
         std::vector<uint8_t> px(pool ? 0 : frame_bytes);
@@ -398,6 +406,7 @@ int main(int argc, char **argv) {
         }
         if (depth) me.depth = dynamic_cast<PlaneMap *>(map.get())->GetDepthStats();
         if (depth_mapping) me.depth_map = dynamic_cast<MapperMap *>(map.get())->GetDepthMapStats();
+        if (depth_bundle) me.depth_bundle = dynamic_cast<MapperMap *>(map.get())->GetDepthBundleStats();
         if (profile && id == 0) {
           char names[32][32];
           double ms[32];
@@ -536,17 +545,28 @@ int main(int argc, char **argv) {
                     "\"fixed_unmatched\": %ld, \"linked\": %ld}",
                     d.measured, d.fallback[0], d.fallback[1], d.fallback[2], d.fallback[3], d.keyframes, d.fixed_matched, d.fixed_unmatched, d.linked);
     }
+    char depth_bundle_json[320] = "";
+    if (depth_bundle) {
+      const DepthBundleStats &d = per[0].depth_bundle;
+      std::fprintf(stderr, "depth edges: lookups OK %ld HOLE %ld FEW %ld EDGE %ld OUTSIDE %ld, %ld observations with a depth; all windows: %ld edges, %ld with a depth, "
+                   "%ld of those on level 1\n", d.lookups[0], d.lookups[1], d.lookups[2], d.lookups[3], d.lookups[4], d.stored, d.total_edges, d.total_depth_edges,
+                   d.total_depth_level1);
+      std::snprintf(depth_bundle_json, sizeof(depth_bundle_json),
+                    ", \"depth_bundle\": {\"ok\": %ld, \"hole\": %ld, \"few\": %ld, \"edge\": %ld, \"outside\": %ld, \"stored\": %ld, \"edges\": %ld, "
+                    "\"depth_edges\": %ld, \"depth_level1\": %ld}",
+                    d.lookups[0], d.lookups[1], d.lookups[2], d.lookups[3], d.lookups[4], d.stored, d.total_edges, d.total_depth_edges, d.total_depth_level1);
+    }
     if (json)
       std::printf("{\"trackers\": %d, \"frames\": %d, \"tracked\": %d, \"frames_per_s\": %.2f, \"frames_per_s_per_camera\": %.2f, \"ms_per_frame_p50\": %.4f, "
                   "\"ms_per_frame_p95\": %.4f, \"ms_per_frame_max\": %.4f, \"wall_s\": %.3f, \"input\": \"%s\", \"texture\": \"%s\", \"width\": %d, \"height\": %d, "
-                  "\"mapper\": %s, \"api\": \"%s\"%s}\n",
+                  "\"mapper\": %s, \"api\": \"%s\"%s%s}\n",
                   n_trackers, n_frames, tracked, total, per_camera, pct(0.5), pct(0.95), all_ms.empty() ? 0.0 : static_cast<double>(all_ms.back()), wall,
                   pool ? (pool_pinned ? "page-locked host memory" : "pageable host memory") : "host memory of the loop (pageable)",
                   texture == SDVL_TEXTURE_CAMERA ? "camera" : "plane", W, H, mapper ? "true" : "false",
                   batch ? "sdvl::SDVLBatch::HandleFrames, one call per frame for all cameras (one thread, one stream)"
                   : lookahead ? "SDVL::SetNextImage + SDVL::HandleFrame per frame (the next frame of the sequence named one call ahead)"
                         : "SDVL::HandleFrame per frame and camera (host/track_sequence.cc, the loop of main.cc:126-159; one thread and stream per camera)",
-                  depth_map_json);
+                  depth_map_json, depth_bundle_json);
   } catch (const std::exception &e) {
     std::cerr << "track_sequence: " << e.what() << std::endl;
     return 1;

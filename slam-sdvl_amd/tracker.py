@@ -288,6 +288,33 @@ class TrackerBatch:
         if self.lib.sdvlh_batch_set_bundle_adjustment(self.h, int(bool(on))) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
 
+    def set_depth_bundle(self, on=True, bf=0.0):
+        """depth edges in the local bundle adjustment (SDVL::SetDepthBundle; needs set_depth and set_bundle_adjustment): an observation
+        that carries a measured depth — the corners a keyframe was seeded from, and the tracked features a frame held when it became a
+        keyframe in a step that was handed its depth image — becomes a three-row edge (sdvl_bundle_adjust_depth), which fixes the
+        scale a window with one fixed keyframe leaves free.  Features added to a keyframe in a later step stay monocular edges.  bf
+        (pixel x metres) turns depth noise into pixels; 0: 1 / noise_quad of set_depth_mapping (666.7 at its default), an order of
+        magnitude that nobody has measured against a sensor.  Off by default.  Raises RuntimeError without depth seeding, without bundle
+        adjustment on, with the mapper thread started and for a negative or non-finite bf."""
+        self.lib.sdvlh_batch_set_depth_bundle.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        if self.lib.sdvlh_batch_set_depth_bundle(self.h, int(bool(on)), float(bf)) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+
+    def depth_bundle_stats(self, i):
+        """tracker i's depth edges so far: dict(ok, hole, few, edge, outside: the lookups of new keyframes' features by status; stored:
+        observations that got a depth; features: the features handed to the lookup; last / total: dict(edges, depth_edges, depth_level1) of
+        the last window and of all windows)"""
+        out = (C.c_longlong * 13)()
+        self.lib.sdvlh_batch_depth_bundle_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        if self.lib.sdvlh_batch_depth_bundle_stats(self.h, int(i), out) != 0:
+            raise RuntimeError("no tracker %d, or not a mapper batch" % i)
+        v = [int(x) for x in out]
+        d = dict(zip(("ok", "hole", "few", "edge", "outside", "stored"), v[:6]))
+        d["last"] = dict(zip(("edges", "depth_edges", "depth_level1"), v[6:9]))
+        d["total"] = dict(zip(("edges", "depth_edges", "depth_level1"), v[9:12]))
+        d["features"] = v[12]
+        return d
+
     def bundle_stats(self, i):
         """mapper mode only: dict(runs, skipped, n_free, n_fixed, n_points, n_edges, last) of tracker i; `last` is the BundleResult
         (sdvl_bundle_result) of its last window, zeros before the first run"""
