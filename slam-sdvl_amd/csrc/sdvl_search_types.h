@@ -199,6 +199,13 @@ struct TrackJobDev {
 
 // the set's point rows and the row count per tracker (sdvl_track.hip)
 extern "C" TrackPoint *sdvl_track_points_device(sdvl_track_set *set, int *max_points, int *n_trackers);
+// for tests: the visiting order the collected step's reprojection left on the device.  Slot k of job j is entry j * stride + k of arrays
+// of `capacity` >= n_jobs * stride entries (px, px0: two doubles each): the candidates come first, in visiting order — cand_first (slot
+// of the first candidate of k's cell), cand_feat (row of last_frame's feature list), the request's level, px (the point's first
+// observation) and px0 (its projection); behind them req_level is -1 and the rest undefined.  One (block_first, block_count) per 4 slots
+extern "C" int sdvl_track_read_order(sdvl_ctx *ctx, const sdvl_track_set *set, int n_jobs, int capacity, int32_t *stride, int32_t *cand_first,
+                                     int32_t *cand_feat, int32_t *req_level, double *req_px, double *req_px0, int32_t *block_first,
+                                     int32_t *block_count);
 
 // ---- launch helpers of sdvl_search.hip for callers whose records already live in HBM (no copies, no wait) --------------
 // search_prepare + search_points over n_slots request records (a record with level < 0 is a dead slot) dealt to workgroups

@@ -22,6 +22,7 @@
 #include "sdvl_math.h"
 #include "sdvl_search_types.h"
 #include "sdvl_search_prepare.h"
+#include "sdvl_wave.h"
 
 namespace {
 
@@ -74,18 +75,48 @@ __global__ __launch_bounds__(256) void track_upload_kernel(const UploadRec *__re
 }
 
 constexpr int kProjThreads = 512;
+constexpr int kProjOneWaveStride = 512;  // a farm's sets project with one wave up to this stride (8 rounds of 64 features)
+// track_project orders a job's candidates through a histogram over the cell ranks (one bucket per cell and one, the last, for the rank
+// 0xFFFF of projections outside the grid) for grids of up to this many cells; larger grids (sdvl_track_create takes up to 65535 cells)
+// keep the quadratic count of smaller keys.  2048 cells: 4 KB of histogram, so that stride 2048 stays below the default LDS limit
+// (53312 + 4100 bytes); 640x480 at cell 32 has 300 cells, configuration C's 1280x960 1200, 1920x1080 2040
+constexpr int kProjBuckets = 2048;
 
-// dynamic LDS of track_project_kernel for `stride` feature slots — s_key [stride] 64-bit at 0 | s_px [stride][2] doubles | s_cell
-// [stride] 16-bit | 64 spare: byte offsets of the parts and the total
+// dynamic LDS of track_project_kernel for `stride` feature slots on a grid of `cells` cells — s_key [stride] 64-bit at 0 | s_px
+// [stride][2] doubles | s_cell [stride] 16-bit (the histogram form's s_seg lies there: it has no use for s_cell) | s_hist [cells + 1]
+// 16-bit in 32-bit words (none beyond kProjBuckets cells) | 64 spare: byte offsets of the parts and the total
 struct ProjLds {
-  size_t px, cell, bytes;
-  __host__ __device__ constexpr explicit ProjLds(size_t stride) : px(8 * stride), cell(px + 16 * stride), bytes(cell + 2 * stride + 64) {}
+  size_t px, cell, hist, bytes;
+  __host__ __device__ constexpr ProjLds(size_t stride, size_t cells)
+      : px(8 * stride), cell(px + 16 * stride), hist(cell + 2 * stride),
+        bytes(hist + (cells <= static_cast<size_t>(kProjBuckets) ? 4 * ((cells + 2) / 2) : 0) + 64) {}
 };
-constexpr size_t kProjLdsDefault = 60 * 1024, kProjLdsMax = ProjLds(4096).bytes;  // beyond the first the limit is raised, to the largest set's (<= 4096 features)
-static_assert(kProjLdsMax == 106560, "track_project at stride 4096");
+constexpr size_t kProjLdsDefault = 60 * 1024, kProjLdsMax = ProjLds(4096, kProjBuckets).bytes;  // beyond the first the limit is raised, to the largest set's (<= 4096 features)
+static_assert(kProjLdsMax == 110660, "track_project at stride 4096");
+static_assert(ProjLds(2048, kProjBuckets).bytes <= kProjLdsDefault, "stride 2048 (the alignment's limit) within the default");
 
-// ProjectPoints + the first half of SelectPoints (feature_align.cc:88-118,285-339)
-__global__ __launch_bounds__(kProjThreads) void track_project_kernel(const TrackJobDev *__restrict__ jobs, TrackPoint *__restrict__ points,
+// inclusive prefix sum over the 64 lanes (all active): wave_sum_i32's steps (sdvl_wave.h) without the final readlane — a scan inside the
+// 16-lane rows, then the two row broadcasts
+__device__ __forceinline__ int wave_scan_i32(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xe, false);  // row_shr:4, banks 1-3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xc, false);  // row_shr:8, banks 2-3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+// hand-off through LDS between the phases of track_project: a workgroup of one wave needs no s_barrier
+template <bool kOneWave>
+__device__ __forceinline__ void proj_sync() {
+  if constexpr (kOneWave) wave_sync();
+  else __syncthreads();
+}
+
+// ProjectPoints + the first half of SelectPoints (feature_align.cc:88-118,285-339).  kOneWave: launched with 64 threads (a farm's sets)
+template <bool kOneWave>
+__global__ __launch_bounds__(kOneWave ? 64 : kProjThreads) void track_project_kernel(const TrackJobDev *__restrict__ jobs, TrackPoint *__restrict__ points,
                                                                      const TrackFeat *__restrict__ feats0, const TrackFeat *__restrict__ feats1,
                                                                      int np, int nf, int stride, int mm, int max_its,
                                                                      const sdvl_align_result *__restrict__ ares,
@@ -96,18 +127,23 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
                                                                      SearchBlock *__restrict__ blocks, ChainFrameDev *__restrict__ chain,
                                                                      sdvl_search_params sprm, SearchPrep *__restrict__ prep) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-  const ProjLds lds(stride);
+  const ProjLds lds(stride, cells);
   unsigned long long *s_key = reinterpret_cast<unsigned long long *>(s_dyn);  // [stride] sort key of feature i, ~0 = not a candidate
   double *s_px = reinterpret_cast<double *>(s_dyn + lds.px);                   // [stride][2] its projection
-  uint16_t *s_cell = reinterpret_cast<uint16_t *>(s_dyn + lds.cell);           // [stride] cell of the candidate at sorted position k
+  uint16_t *s_cell = reinterpret_cast<uint16_t *>(s_dyn + lds.cell);           // [stride] cell of the candidate at sorted position k (quadratic form)
+  uint16_t *s_seg = s_cell;                                                    // [stride] histogram form: candidates bucket by bucket, any order inside one
+  unsigned *s_hist = reinterpret_cast<unsigned *>(s_dyn + lds.hist);           // [cells + 1] 16-bit, two to a word: count, then start, then end of a bucket
   __shared__ double s_pose[7];
   __shared__ int s_ncand;
-  const int j = blockIdx.x, tid = threadIdx.x;
+  const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int nthreads = kOneWave ? 64 : static_cast<int>(blockDim.x);
   const TrackJobDev &jb = jobs[j];
   const TrackFeat *F = (jb.feat_buf ? feats1 : feats0) + static_cast<size_t>(jb.tracker) * nf;
   TrackPoint *P = points + static_cast<size_t>(jb.tracker) * np;
   const int n_feat = jb.n_feat;
   const int base = j * stride;
+  const bool linear = cells <= kProjBuckets;     // visiting positions through the histogram
+  const int hist_words = linear ? (cells + 2) / 2 : 0;
   if (tid == 0) {
     // frame2.pose = T * frame1.pose (image_align.cc:79)
     const Rigid pose = se3_mul(se3_from7(ares[j].T), se3_from7(jb.last_pose));
@@ -119,51 +155,99 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
     e.pad_ = 0.0;
     registry[jb.cur_id] = e;
   }
-  __syncthreads();
+  for (int w = tid; w < hist_words; w += nthreads) s_hist[w] = 0u;
+  proj_sync<kOneWave>();
   const Rigid pose = se3_from7(s_pose);
   const M3 R = se3_rot(pose);
   // the FeatureAlign grid: cell ranks are 16-bit (sdvl_track_create: <= 65535 cells); 3840x2160 at cell 32 has 8160, at 8 px 130 k are refused there
   const int gw = static_cast<int>(ceil(cam.width / cell_size));
-  for (int i = tid; i < n_feat; i += static_cast<int>(blockDim.x)) {
+  int n_cand = 0;
+  for (int i0 = 0; i0 < n_feat; i0 += nthreads) {  // (whole waves go round: the ballot below)
+    const int i = i0 + tid;
     unsigned long long key = ~0ull;
-    const int praw = F[i].point;
-    if (praw >= 0 && !(praw & SDVL_TRACK_DUPLICATE)) {
-      TrackPoint &p = P[praw];
-      if (!(p.status & kDeleted) && p.last_frame != jb.frame_id) {
-        // ProjectPoint, feature_align.cc:317-339; Frame::Project, frame.cc:94-103
-        const V3 rel = vadd(mvec(R, {p.P[0], p.P[1], p.P[2]}), pose.t);
-        bool ok = !(rel.z < 0.0);
-        V2 px = {0.0, 0.0};
-        if (ok) {
-          px = cam_project(cam, rel);
-          ok = cam_inside(cam, static_cast<int>(px.x), static_cast<int>(px.y), patch);
+    if (i < n_feat) {
+      const int praw = F[i].point;
+      if (praw >= 0 && !(praw & SDVL_TRACK_DUPLICATE)) {
+        TrackPoint &p = P[praw];
+        if (!(p.status & kDeleted) && p.last_frame != jb.frame_id) {
+          // ProjectPoint, feature_align.cc:317-339; Frame::Project, frame.cc:94-103
+          const V3 rel = vadd(mvec(R, {p.P[0], p.P[1], p.P[2]}), pose.t);
+          bool ok = !(rel.z < 0.0);
+          V2 px = {0.0, 0.0};
+          if (ok) {
+            px = cam_project(cam, rel);
+            ok = cam_inside(cam, static_cast<int>(px.x), static_cast<int>(px.y), patch);
+          }
+          if (!ok) {
+            p.status = (p.status & kTrash) | kUnseen;
+          } else {
+            const int k = static_cast<int>(px.y / cell_size) * gw + static_cast<int>(px.x / cell_size);
+            const unsigned sc = static_cast<unsigned>(p.score < 0 ? 0 : (p.score > 0xFFFFFF ? 0xFFFFFF : p.score));
+            // cells in the shuffled order; inside a cell by descending score, ties in list order (std::list::sort is stable)
+            const unsigned rank = k < cells ? cell_rank[static_cast<size_t>(j) * cells + k] : 0xFFFFu;
+            key = (static_cast<unsigned long long>(rank) << 48) | (static_cast<unsigned long long>(0xFFFFFFu - sc) << 24) | static_cast<unsigned>(i);
+            if (linear) {
+              const unsigned b = rank == 0xFFFFu ? static_cast<unsigned>(cells) : rank;
+              atomicAdd(&s_hist[b >> 1], 1u << (16 * (b & 1)));  // (a count is at most stride <= 4096: nothing carries into the neighbour)
+            }
+            s_px[2 * i] = px.x;
+            s_px[2 * i + 1] = px.y;
+            p.status = (p.status & kTrash) | kSeen;
+          }
+          p.last_frame = jb.frame_id;  // not relocalising (the tables are only used for ordinary tracking)
         }
-        if (!ok) {
-          p.status = (p.status & kTrash) | kUnseen;
-        } else {
-          const int k = static_cast<int>(px.y / cell_size) * gw + static_cast<int>(px.x / cell_size);
-          const unsigned sc = static_cast<unsigned>(p.score < 0 ? 0 : (p.score > 0xFFFFFF ? 0xFFFFFF : p.score));
-          // cells in the shuffled order; inside a cell by descending score, ties in list order (std::list::sort is stable)
-          key = (static_cast<unsigned long long>(k < cells ? cell_rank[static_cast<size_t>(j) * cells + k] : 0xFFFFu) << 48) |
-                (static_cast<unsigned long long>(0xFFFFFFu - sc) << 24) | static_cast<unsigned>(i);
-          s_px[2 * i] = px.x;
-          s_px[2 * i + 1] = px.y;
-          p.status = (p.status & kTrash) | kSeen;
-        }
-        p.last_frame = jb.frame_id;  // not relocalising (the tables are only used for ordinary tracking)
+      }
+      s_key[i] = key;
+    }
+    const unsigned long long is_cand = __ballot(key != ~0ull);
+    if constexpr (kOneWave) n_cand += __popcll(is_cand);
+    else if (lane == 0 && is_cand) atomicAdd(&s_ncand, __popcll(is_cand));
+  }
+  proj_sync<kOneWave>();
+  if constexpr (!kOneWave) n_cand = s_ncand;
+  if (linear) {
+    // exclusive prefix over the buckets in bucket order, by the first wave: a lane takes a word (two buckets), 128 buckets a round
+    if (tid < 64) {
+      int carry = 0;
+      for (int w0 = 0; w0 < hist_words; w0 += 64) {
+        const int w = w0 + lane;
+        const unsigned word = w < hist_words ? s_hist[w] : 0u;
+        const int lo = static_cast<int>(word & 0xFFFFu), both = lo + static_cast<int>(word >> 16);
+        const int incl = wave_scan_i32(both);
+        const int start = carry + incl - both;
+        if (w < hist_words) s_hist[w] = static_cast<unsigned>(start) | (static_cast<unsigned>(start + lo) << 16);
+        carry += __builtin_amdgcn_readlane(incl, 63);
       }
     }
-    s_key[i] = key;
-    if (key != ~0ull) atomicAdd(&s_ncand, 1);
+    proj_sync<kOneWave>();
+    // every candidate into its bucket's segment; the bucket's start moves up to its end
+    for (int i = tid; i < n_feat; i += nthreads) {
+      const unsigned long long key = s_key[i];
+      if (key == ~0ull) continue;
+      const unsigned rank = static_cast<unsigned>(key >> 48), b = rank == 0xFFFFu ? static_cast<unsigned>(cells) : rank;
+      const unsigned before = atomicAdd(&s_hist[b >> 1], 1u << (16 * (b & 1)));
+      s_seg[(before >> (16 * (b & 1))) & 0xFFFFu] = static_cast<uint16_t>(i);
+    }
+    proj_sync<kOneWave>();
   }
-  __syncthreads();
-  const int n_cand = s_ncand;
   // position of every candidate in visiting order = number of smaller keys (keys are unique: they end in the feature index)
-  for (int i = tid; i < n_feat; i += static_cast<int>(blockDim.x)) {
+  for (int i = tid; i < n_feat; i += nthreads) {
     const unsigned long long key = s_key[i];
     if (key == ~0ull) continue;
     int r = 0;
-    for (int q = 0; q < n_feat; q++) r += s_key[q] < key ? 1 : 0;
+    if (linear) {
+      // = candidates in buckets of smaller rank + smaller keys of its own bucket
+      const unsigned rank = static_cast<unsigned>(key >> 48), b = rank == 0xFFFFu ? static_cast<unsigned>(cells) : rank;
+      const unsigned below = b ? b - 1 : 0;
+      const int first = b ? static_cast<int>((s_hist[below >> 1] >> (16 * (below & 1))) & 0xFFFFu) : 0;
+      const int end = static_cast<int>((s_hist[b >> 1] >> (16 * (b & 1))) & 0xFFFFu);
+      r = first;
+      for (int q = first; q < end; q++) r += s_key[s_seg[q]] < key ? 1 : 0;
+      cand_first[base + r] = base + first;
+    } else {
+      for (int q = 0; q < n_feat; q++) r += s_key[q] < key ? 1 : 0;
+      s_cell[r] = static_cast<uint16_t>(key >> 48);
+    }
     const TrackPoint &p = P[F[i].point];
     SearchReqDev rq;
     rq.cur = jb.cur_id;
@@ -184,15 +268,16 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
     double *rp = req_point + 3 * static_cast<size_t>(base + r);
     rp[0] = p.P[0]; rp[1] = p.P[1]; rp[2] = p.P[2];
     cand_feat[base + r] = i;
-    s_cell[r] = static_cast<uint16_t>(key >> 48);
   }
-  __syncthreads();
-  for (int k = tid; k < stride; k += static_cast<int>(blockDim.x)) {
+  if (!linear) proj_sync<kOneWave>();
+  for (int k = tid; k < stride; k += nthreads) {
     if (k < n_cand) {
-      int first = k;
-      const uint16_t c = s_cell[k];
-      while (first > 0 && s_cell[first - 1] == c) first--;
-      cand_first[base + k] = base + first;
+      if (!linear) {
+        int first = k;
+        const uint16_t c = s_cell[k];
+        while (first > 0 && s_cell[first - 1] == c) first--;
+        cand_first[base + k] = base + first;
+      }
     } else {
       reqs[base + k].level = -1;  // dead slot: search_prepare / search_points skip it
       if (prep) {
@@ -202,7 +287,7 @@ __global__ __launch_bounds__(kProjThreads) void track_project_kernel(const Track
     }
   }
   const int nblk = stride / kWavesPerBlock;
-  for (int b = tid; b < nblk; b += static_cast<int>(blockDim.x)) {
+  for (int b = tid; b < nblk; b += nthreads) {
     int cnt = n_cand - b * kWavesPerBlock;
     cnt = cnt < 0 ? 0 : (cnt > kWavesPerBlock ? kWavesPerBlock : cnt);
     blocks[j * nblk + b] = SearchBlock{base + b * kWavesPerBlock, cnt};
@@ -742,23 +827,30 @@ int sdvl_track_search(sdvl_ctx *ctx, sdvl_track_set *s) {
   // (The chain as a HIP graph was measured in rounds 4 and 5 — 2.69 k against 2.96 k frames/s for a lone camera, nothing for a farm:
   //  launches are not the cost — and removed in round 6.)
   // (one-time set-up calls stay outside a capture)
-  const size_t proj_lds = ProjLds(stride).bytes;
-  if (proj_lds > kProjLdsDefault) {  // track_project beyond the default dynamic LDS limit: raise it once per device
+  const size_t proj_lds = ProjLds(stride, s->cells).bytes;
+  if (proj_lds > kProjLdsDefault) {  // track_project beyond the default dynamic LDS limit (strides beyond 2000: only the wide form): raise it once per device
     static std::atomic<unsigned long long> attr_devices{0};
-    const int rc_a = sdvl_allow_dynamic_lds(ctx, reinterpret_cast<const void *>(track_project_kernel), kProjLdsMax, &attr_devices);
+    const int rc_a = sdvl_allow_dynamic_lds(ctx, reinterpret_cast<const void *>(track_project_kernel<false>), kProjLdsMax, &attr_devices);
     if (rc_a) return rc_a;
   }
   {
     // a lane per feature of last_frame: 256 lanes cover the ~190 features of the metric configuration, configuration C's ~850 take 512.
-    // Round 6: a farm's launches (sets of more than 32 trackers) take 128 — among the other streams' one-wave workgroups a workgroup
-    // is placed when ALL its waves find a slot on one CU at the same moment, and four are found far less often than two: the kernel's
-    // dispatch time in company is how long its workgroups wait to be placed (2.0 -> 1.5 ms per step of 16 groups, +3 % tracked frames/s;
-    // 64 threads: +1 % — the rank loop gets longer)
-    const int proj_threads = stride <= 256 ? (s->n > 32 ? 128 : 256) : kProjThreads;
-    SDVL_LAUNCH_LDS(ctx, "track_project", track_project_kernel, dim3(n_jobs), dim3(proj_threads), proj_lds, s->djobs.cin(D), s->d_points,
-                    static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->np, s->nf, stride, s->mm,
-                    s->max_its, s->ares.cin(D), s->cell_rank.cin(D), s->cells, c, s->prm.cell_size, s->prm.patch_size, registry, s->reqs.in(D),
-                    s->reqpt.in(D), s->cfirst.in(D), s->cfeat.in(D), s->blocks.in(D), s->chain.in(D), s->prm.search, s->prep.in(D));
+    // A farm's launches (sets of more than 32 trackers) are workgroups of ONE wave up to stride kProjOneWaveStride: among the other
+    // streams' one-wave workgroups a workgroup is placed when ALL its waves find a slot on one CU at the same moment, and the kernel's
+    // dispatch time in company is how long its workgroups wait to be placed.  (Round 6, with the quadratic count of smaller keys: 256 ->
+    // 128 threads 2.0 -> 1.5 ms per step of 16 groups; 64 threads gained less, the count's loop got longer.  The histogram has no such
+    // loop.  Round 7: the flagship's groups are above stride 256 in nine launches of ten, which took the 512-thread form; the one
+    // wave serves them too — figures in profiles/r07/track_project_one_wave.)
+    const bool one_wave = stride <= kProjOneWaveStride && s->n > 32;
+    const int proj_threads = one_wave ? 64 : (stride <= 256 ? 256 : kProjThreads);
+#define SDVL_TRACK_PROJECT(kernel)                                                                                                                  \
+  SDVL_LAUNCH_LDS(ctx, "track_project", kernel, dim3(n_jobs), dim3(proj_threads), proj_lds, s->djobs.cin(D), s->d_points,                          \
+                  static_cast<const TrackFeat *>(s->d_feats[0]), static_cast<const TrackFeat *>(s->d_feats[1]), s->np, s->nf, stride, s->mm,        \
+                  s->max_its, s->ares.cin(D), s->cell_rank.cin(D), s->cells, c, s->prm.cell_size, s->prm.patch_size, registry, s->reqs.in(D),      \
+                  s->reqpt.in(D), s->cfirst.in(D), s->cfeat.in(D), s->blocks.in(D), s->chain.in(D), s->prm.search, s->prep.in(D))
+    if (one_wave) SDVL_TRACK_PROJECT(track_project_kernel<true>);
+    else SDVL_TRACK_PROJECT(track_project_kernel<false>);
+#undef SDVL_TRACK_PROJECT
     SDVL_HIP_CHECK(ctx, hipGetLastError());
   }
   int rc = sdvl_search_launch_device(ctx, n_jobs * stride, s->reqs.in(D), registry, s->blocks.in(D), n_jobs * (stride / kWavesPerBlock), &s->cam,
@@ -803,6 +895,34 @@ const sdvl_track_feature_out *sdvl_track_features(const sdvl_track_set *s, int j
 
 const sdvl_track_point_stat *sdvl_track_stats(const sdvl_track_set *s, int job) {
   return (s && job >= 0 && job < s->n) ? s->h_stats + static_cast<size_t>(job) * s->np : nullptr;
+}
+
+int sdvl_track_read_order(sdvl_ctx *ctx, const sdvl_track_set *s, int n_jobs, int capacity, int32_t *stride, int32_t *cand_first,
+                          int32_t *cand_feat, int32_t *req_level, double *req_px, double *req_px0, int32_t *block_first, int32_t *block_count) {
+  if (!ctx || !s || s->ctx != ctx || !stride || !cand_first || !cand_feat || !req_level || !req_px || !req_px0 || !block_first || !block_count)
+    return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, s->phase == 0 && n_jobs >= 1 && n_jobs == static_cast<int>(s->jobs.size()), "sdvl_track_read_order without a collected step");
+  const size_t slots = static_cast<size_t>(n_jobs) * s->stride;
+  SDVL_REQUIRE(ctx, static_cast<size_t>(capacity) >= slots, "sdvl_track_read_order: arrays shorter than the step's slots");
+  SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
+  const uint8_t *D = s->d_scratch;
+  std::vector<SearchReqDev> reqs(slots);
+  std::vector<SearchBlock> blocks(slots / kWavesPerBlock);
+  SDVL_HIP_CHECK(ctx, hipMemcpy(cand_first, s->cfirst.cin(D), sizeof(int32_t) * slots, hipMemcpyDeviceToHost));
+  SDVL_HIP_CHECK(ctx, hipMemcpy(cand_feat, s->cfeat.cin(D), sizeof(int32_t) * slots, hipMemcpyDeviceToHost));
+  SDVL_HIP_CHECK(ctx, hipMemcpy(reqs.data(), s->reqs.cin(D), sizeof(SearchReqDev) * slots, hipMemcpyDeviceToHost));
+  SDVL_HIP_CHECK(ctx, hipMemcpy(blocks.data(), s->blocks.cin(D), sizeof(SearchBlock) * blocks.size(), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < slots; k++) {
+    req_level[k] = reqs[k].level;
+    req_px[2 * k] = reqs[k].px[0]; req_px[2 * k + 1] = reqs[k].px[1];
+    req_px0[2 * k] = reqs[k].px0[0]; req_px0[2 * k + 1] = reqs[k].px0[1];
+  }
+  for (size_t b = 0; b < blocks.size(); b++) {
+    block_first[b] = blocks[b].first;
+    block_count[b] = blocks[b].count;
+  }
+  *stride = s->stride;
+  return SDVL_OK;
 }
 
 }  // extern "C"
