@@ -589,6 +589,8 @@ typedef struct sdvl_depth_measure_params {
   sdvl_depth_seed_params rule;
   double noise_abs, noise_quad;
 } sdvl_depth_measure_params;
+#define SDVL_DEPTH_NOISE_ABS 0.001   /* metres: what noise_abs 0 stands for */
+#define SDVL_DEPTH_NOISE_QUAD 0.0015 /* per metre: what noise_quad 0 stands for */
 int sdvl_depth_filter_measured(sdvl_ctx *ctx, int n, const double *cur_pose7, const double *ref_pose7, const double *bearing3, const int32_t *found,
                                const double *px2, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state,
                                const sdvl_depth_params *fp, struct sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width,

@@ -752,15 +752,18 @@ class Context:
                                                        track_set.h if track_set is not None else None, res, fout))
         return res, fout
 
+    @staticmethod
+    def _stated_results(n, cur_poses, ref_poses, bearings, found, px):
+        """what the two depth_filter entries take in a search's place, as contiguous arrays [n][7], [n][7], [n][3], [n], [n][2]"""
+        return (np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7), np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7),
+                np.ascontiguousarray(bearings, np.float64).reshape(n, 3), np.ascontiguousarray(found, np.int32).reshape(n),
+                np.ascontiguousarray(px, np.float64).reshape(n, 2))
+
     def depth_filter(self, cur_poses, ref_poses, bearings, found, px, cam, states, fparams, track_set=None):
         """sdvl_depth_filter: the mapper's depth filter alone.  cur_poses / ref_poses [n][7], bearings [n][3], found [n], px [n][2];
         states: DepthState array -> DepthOut array"""
         n = len(states)
-        cp = np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7)
-        rp = np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7)
-        bv = np.ascontiguousarray(bearings, np.float64).reshape(n, 3)
-        fd = np.ascontiguousarray(found, np.int32).reshape(n)
-        pp = np.ascontiguousarray(px, np.float64).reshape(n, 2)
+        cp, rp, bv, fd, pp = self._stated_results(n, cur_poses, ref_poses, bearings, found, px)
         fout = (DepthOut * n)()
         dp = C.POINTER(C.c_double)
         self._check(self.lib.sdvl_depth_filter(self.h, n, _ptr(cp, dp), _ptr(rp, dp), _ptr(bv, dp), _ptr(fd, i32p), _ptr(pp, dp), C.byref(cam),
@@ -773,27 +776,14 @@ class Context:
         memory, padded rows allowed — or a DepthJob made by the caller (device pointers, pinned memory).  xyl [n][3] level coordinates and
         level; cam a Camera; dist (k1, k2, p1, p2, k3) or None; rule: min_depth, max_depth, edge_ratio, min_valid (0: the default)
         -> (z float64 [n], status uint8 [n], ok per job int32)"""
-        keep, arr = [], (DepthJob * max(len(jobs), 1))()
-        for j, job in enumerate(jobs):
-            if isinstance(job, DepthJob):
-                arr[j] = job
-                continue
-            d = job[0]
-            assert d.dtype in (np.float32, np.uint16) and d.ndim == 2 and d.strides[1] == d.itemsize and d.shape == (height, width)
-            keep.append(d)
-            arr[j] = DepthJob(d.ctypes.data, 0, d.strides[0], SDVL_DEPTH_U16 if d.dtype == np.uint16 else SDVL_DEPTH_F32, 0,
-                              float(job[3]) if len(job) > 3 else 1.0, int(job[1]), int(job[2]))
+        keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, 0.0, 0.0, rule)
         xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3)
         n = len(xyl)
         z, status, ok = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8), np.zeros(max(len(jobs), 1), np.int32)
-        d5 = Distortion((C.c_double * 5)(*[float(x) for x in dist])) if dist is not None else None
-        p = DepthSeedParams(float(rule.pop("min_depth", 0.0)), float(rule.pop("max_depth", 0.0)), float(rule.pop("edge_ratio", 0.0)),
-                            int(rule.pop("min_valid", 0)), 0)
-        assert not rule, "unknown rule field %s" % list(rule)
         self.lib.sdvl_depth_seed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(self.lib.sdvl_depth_seed(self.h, len(jobs), arr, width, height, n, xyl.ctypes.data, C.addressof(cam),
-                                             C.addressof(d5) if d5 is not None else None, C.addressof(p), z.ctypes.data, status.ctypes.data,
+                                             C.addressof(d5) if d5 is not None else None, C.addressof(mp.rule), z.ctypes.data, status.ctypes.data,
                                              ok.ctypes.data))
         return z[:n], status[:n], ok[:len(jobs)]
 
@@ -837,11 +827,7 @@ class Context:
         image of the current frame of the items c_begin .. c_end (an item in no job has no image); noise_abs / noise_quad and rule: 0 takes
         the default -> (DepthOut array, status uint8 [n]: depth_seed's codes, 255 where no depth was looked up)"""
         n = len(states)
-        cp = np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7)
-        rp = np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7)
-        bv = np.ascontiguousarray(bearings, np.float64).reshape(n, 3)
-        fd = np.ascontiguousarray(found, np.int32).reshape(n)
-        pp = np.ascontiguousarray(px, np.float64).reshape(n, 2)
+        cp, rp, bv, fd, pp = self._stated_results(n, cur_poses, ref_poses, bearings, found, px)
         lv = np.ascontiguousarray(levels, np.int32).reshape(n)
         keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, noise_abs, noise_quad, rule)
         fout, status = (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)

@@ -9,7 +9,7 @@
 //   status    the first that applies of OUTSIDE (centre off the image), HOLE (centre invalid), FEW (fewer than min_valid valid samples),
 //             EDGE (max - min over the valid samples > edge_ratio x the centre's depth); otherwise OK and z = the centre sample, unfiltered
 // depth_seed: one lane per corner, nine gathers, no LDS; all jobs of a call in one launch.  The lookup itself (depth_lookup,
-// sdvl_depth_device.h) is shared with the mapper's measured depth filter (sdvl_search.hip) and with sdvl_depth_lookup below, which applies it
+// sdvl_depth_device.h) is shared with the mapper's measured depth filter (sdvl_depth_filter.hip) and with sdvl_depth_lookup below, which applies it
 // at the sub-pixel position a feature was found at (the depths bundle adjustment's depth edges carry).  A keyframe reads ~2.3 k samples of a 1.2 MB
 // image: a source in HBM or in pinned host memory is read where it lies; only a pageable source is copied, into buffers the context keeps
 // for depth images alone.  The file is built with -ffp-contract=off like every other: the centre is the restatement's operation order,
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void depth_seed(const DepthJobDev *__restrict_
 }
 
 // sdvl_depth_lookup: the same rule at a position of its own, one lane per position — the level-0 pixel a feature was found at and the
-// stride of the level it was found on, as depth_filter_measured_kernel (sdvl_search.hip) applies it
+// stride of the level it was found on, as depth_filter_measured_kernel (sdvl_depth_filter.hip) applies it
 __global__ __launch_bounds__(256) void depth_lookup_kernel(const DepthJobDev *__restrict__ jobs, const double *__restrict__ px2, const int32_t *__restrict__ level,
                                                            const int32_t *__restrict__ pos_job, int n, int width, int height, DepthLens lens, DepthRule rule,
                                                            double *__restrict__ out_z, uint8_t *__restrict__ out_status) {

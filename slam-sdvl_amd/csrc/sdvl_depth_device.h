@@ -1,5 +1,5 @@
 // sdvl_depth_device.h — the depth lookup of include/sdvl_hip.h's "depth cameras" section, stated once for the two kernels that make it:
-// depth_seed (sdvl_depth.hip: a keyframe's corners) and depth_filter_measured_kernel (sdvl_search.hip: the pixel a candidate was found
+// depth_seed (sdvl_depth.hip: a keyframe's corners) and depth_filter_measured_kernel (sdvl_depth_filter.hip: the pixel a candidate was found
 // at); and what their host entries share: the checks of a job list, the rule's defaults, where an image is read.
 #ifndef SDVL_DEPTH_DEVICE_H_
 #define SDVL_DEPTH_DEVICE_H_

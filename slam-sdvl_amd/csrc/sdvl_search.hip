@@ -24,7 +24,6 @@
 #include "sdvl_orb_device.h"
 #include "sdvl_search_types.h"
 #include "sdvl_search_prepare.h"
-#include "sdvl_depth_device.h"
 
 namespace {
 
@@ -753,306 +752,6 @@ __global__ __launch_bounds__(256) void select_matches_kernel(PoseChainIn in, Pos
   }
 }
 
-
-// ---------------------------------------------------------------------------------------------- the mapper's depth filter
-// extra/utils.cc:193-205: A = [R v_ref | v_cur], depth2 = -(A^T A)^-1 A^T t, |depth2[0]|
-__device__ __forceinline__ bool depth_from_triangulation(const Rigid &pose, V3 v_ref, V3 v_cur, double *depth) {
-  const M3 R = se3_rot(pose);
-  const V3 a0 = mvec(R, v_ref);
-  const V3 a1 = v_cur;
-  const double m00 = vdot(a0, a0), m01 = vdot(a0, a1), m11 = vdot(a1, a1);
-  const double det = m00 * m11 - m01 * m01;
-  if (det < 0.000001) return false;
-  const double invdet = 1.0 / det;
-  const double i00 = m11 * invdet, i01 = -m01 * invdet;
-  const double n00 = -i00, n01 = -i01;
-  const double r0x = n00 * a0.x + n01 * a1.x, r0y = n00 * a0.y + n01 * a1.y, r0z = n00 * a0.z + n01 * a1.z;
-  const double d0 = r0x * pose.t.x + r0y * pose.t.y + r0z * pose.t.z;
-  *depth = fabs(d0);
-  return true;
-}
-
-// extra/utils.cc:207-213
-__device__ __forceinline__ double parallax_of(V3 src1, V3 src2, V3 p3d) {
-  V3 v1 = vsub(src1, p3d), v2 = vsub(src2, p3d);
-  const double n1 = vnorm(v1), n2 = vnorm(v2);
-  v1 = {v1.x / n1, v1.y / n1, v1.z / n1};
-  v2 = {v2.x / n2, v2.y / n2, v2.z / n2};
-  return vdot(v1, v2);
-}
-
-// point.cc:189-201
-__device__ __forceinline__ double compute_tau(const Rigid &pose, V3 v, double depth, double px_error_angle) {
-  const double PI = 3.14159265;
-  const V3 t = pose.t;
-  const V3 a = {v.x * depth - t.x, v.y * depth - t.y, v.z * depth - t.z};
-  const double t_norm = vnorm(t), a_norm = vnorm(a);
-  const double alpha = acos((v.x * t.x + v.y * t.y + v.z * t.z) / t_norm);
-  const double beta = acos((a.x * -t.x + a.y * -t.y + a.z * -t.z) / (t_norm * a_norm));
-  const double beta_plus = beta + px_error_angle;
-  const double gamma_plus = PI - alpha - beta_plus;
-  const double depth_plus = t_norm * sin(beta_plus) / sin(gamma_plus);
-  return depth_plus - depth;
-}
-
-// point.cc:203-217
-__device__ __forceinline__ double pdf_normal(double mean, double sd, double x) {
-  const double PI = 3.14159265;
-  double result = 0.0;
-  if (sd <= 0) return result;
-  double exponent = x - mean;
-  exponent *= -exponent;
-  exponent /= 2 * sd * sd;
-  result = exp(exponent);
-  result /= sd * sqrt(2.0 * PI);
-  return result;
-}
-
-// The body of Map::UpdateCandidates' loop behind SearchPoint (map.cc:454-497), one lane per request: Unpromote for a miss;
-// triangulation, parallax, the minimum-depth tests, Point::Update (point.cc:64-100) and Point::HasConverged (:164-178) for a
-// hit.  The point's row in the tracking tables (if it has one) receives what the tracker reads of it.
-__global__ __launch_bounds__(128) void depth_filter_kernel(const SearchReqDev *__restrict__ reqs, const SearchFramePose *__restrict__ table,
-                                                           const sdvl_search_res *__restrict__ res, const sdvl_depth_state *__restrict__ state,
-                                                           int n, Cam cam, sdvl_depth_params fp, TrackPoint *__restrict__ rows, int n_rows,
-                                                           sdvl_depth_out *__restrict__ out, sdvl_depth_out *__restrict__ out_host) {
-  const int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= n) return;
-  const SearchReqDev &rq = reqs[i];
-  const sdvl_depth_state st = state[i];
-  const sdvl_search_res r = res[i];
-  TrackPoint *row = (rows && st.track_row >= 0 && st.track_row < n_rows) ? rows + st.track_row : nullptr;
-  sdvl_depth_out o;
-  o.outcome = SDVL_DEPTH_SKIPPED;
-  o.n_failed = st.n_failed;
-  o.rho = st.rho; o.sigma2 = st.sigma2; o.a = st.a; o.b = st.b;
-  o.cos_alpha = 0.0; o.last_distance = 0.0;
-  o.position[0] = o.position[1] = o.position[2] = 0.0;
-  if (!r.found) {
-    // Point::Unpromote, point.cc:109-118
-    o.n_failed = st.n_failed + 1;
-    o.b = st.b + 1.0;
-    o.outcome = SDVL_DEPTH_NOT_FOUND | (o.n_failed > fp.max_failed ? SDVL_DEPTH_DELETED : 0);
-    if (row) {
-      row->n_failed = o.n_failed;
-      if (o.outcome & SDVL_DEPTH_DELETED) row->status |= kTrash;
-    }
-  } else {
-    const Rigid cur = se3_from7(table[rq.cur].pose), ref = se3_from7(table[rq.ref].pose);
-    const V3 fv = {rq.bearing[0], rq.bearing[1], rq.bearing[2]};
-    const Rigid pose = se3_mul(cur, se3_inverse(ref));  // map.cc:459
-    const V3 v3d = cam_unproject(cam, {r.px[0], r.px[1]});
-    double depth = 0.0;
-    bool go = depth_from_triangulation(pose, fv, v3d, &depth);
-    const Rigid ref_world = se3_inverse(ref), cur_world = se3_inverse(cur);  // Frame::GetWorldPose
-    if (go) {
-      const V3 p3d = se3_apply(ref_world, {depth * fv.x, depth * fv.y, depth * fv.z});
-      const double cos_alpha = parallax_of(ref_world.t, cur_world.t, p3d);
-      if (cos_alpha >= 0.999999) go = false;
-    }
-    if (go && (depth < fp.min_depth || depth < st.depth_mean * fp.scale_min_dist)) go = false;
-    if (go) {
-      // Point::Update, point.cc:64-100
-      const Rigid pose2 = se3_mul(ref, se3_inverse(cur));
-      const double tau = compute_tau(pose2, fv, depth, fp.px_error_angle);
-      const double tau_inverse = 0.5 * (1.0 / fmax(0.0000001, depth - tau) - 1.0 / (depth + tau));
-      const double tau2 = tau_inverse * tau_inverse;
-      const double x = 1. / depth;
-      const double norm_scale = sqrt(st.sigma2 + tau2);
-      if (norm_scale != norm_scale) {
-        // std::isnan(norm_scale) -> Update returns with the point untouched (point.cc:76); HasConverged still runs
-        const double std_d = sqrt(st.sigma2) / (st.rho * st.rho);
-        const double l = 4 * std_d * st.cos_alpha / st.last_distance;
-        if (st.fixed || l < 0.1) {
-          const double sc = 1.0 / st.rho;
-          const V3 pos = st.fixed ? V3{st.position[0], st.position[1], st.position[2]} : se3_apply(ref_world, {sc * fv.x, sc * fv.y, sc * fv.z});
-          o.position[0] = pos.x; o.position[1] = pos.y; o.position[2] = pos.z;
-          o.cos_alpha = st.cos_alpha; o.last_distance = st.last_distance;
-          o.outcome = SDVL_DEPTH_FIXED_STALE;
-          if (row) {
-            row->P[0] = pos.x; row->P[1] = pos.y; row->P[2] = pos.z;
-            row->fixed = 1;
-          }
-        }
-      } else {
-        const double s2 = 1. / (1. / st.sigma2 + 1. / tau2);
-        const double m = s2 * (st.rho / st.sigma2 + x / tau2);
-        double C1 = st.a / (st.a + st.b) * pdf_normal(st.rho, norm_scale, x);
-        double C2 = st.b / (st.a + st.b) * 1. / st.z_range;
-        const double normalization_constant = C1 + C2;
-        C1 /= normalization_constant;
-        C2 /= normalization_constant;
-        const double f = C1 * (st.a + 1.) / (st.a + st.b + 1.) + C2 * st.a / (st.a + st.b + 1.);
-        const double e = C1 * (st.a + 1.) * (st.a + 2.) / ((st.a + st.b + 1.) * (st.a + st.b + 2.)) +
-                         C2 * st.a * (st.a + 1.0) / ((st.a + st.b + 1.0) * (st.a + st.b + 2.0));
-        const double rho_new = C1 * m + C2 * st.rho;
-        o.sigma2 = C1 * (s2 + m * m) + C2 * (st.sigma2 + st.rho * st.rho) - rho_new * rho_new;
-        o.rho = rho_new;
-        o.a = (e - f) / (f - e / f);
-        o.b = o.a * (1.0 - f) / f;
-        // Point::GetPosition (point.cc:128-142) of the candidate: the first observation's ray at the new inverse depth
-        const double sc = 1.0 / o.rho;
-        const V3 pos = st.fixed ? V3{st.position[0], st.position[1], st.position[2]} : se3_apply(ref_world, {sc * fv.x, sc * fv.y, sc * fv.z});
-        o.cos_alpha = parallax_of(ref_world.t, cur_world.t, pos);
-        o.last_distance = vnorm(vsub(cur_world.t, pos));  // Frame::DistanceTo, frame.h:133-136
-        o.n_failed = 0;
-        o.position[0] = pos.x; o.position[1] = pos.y; o.position[2] = pos.z;
-        o.outcome = SDVL_DEPTH_UPDATED;
-        // Point::HasConverged, point.cc:164-178
-        const double std_d = sqrt(o.sigma2) / (o.rho * o.rho);
-        const double l = 4 * std_d * o.cos_alpha / o.last_distance;
-        if (st.fixed || l < 0.1) o.outcome = SDVL_DEPTH_CONVERGED;
-        if (row) {
-          row->P[0] = pos.x; row->P[1] = pos.y; row->P[2] = pos.z;
-          row->idepth = o.rho;
-          row->idepth_std = sqrt(o.sigma2);  // Point::GetStd
-          row->n_failed = 0;
-          if (o.outcome == SDVL_DEPTH_CONVERGED) row->fixed = 1;
-        }
-      }
-    }
-  }
-  out[i] = o;
-  if (out_host) out_host[i] = o;
-}
-
-// The same loop body for a depth camera (this project's rule; tests/depth_measure_restatement.py is its specification): a hit whose
-// request names a depth image of its CURRENT frame looks the depth up at the found pixel by depth_seed's rule (depth_lookup, stride
-// 1 << the found level).  Status OK: the sample z_c, carried along the found pixel's ray and into the reference frame, gives the range
-// along the candidate's ray; that range goes through the two minimum-depth tests, Point::Update and HasConverged with
-// tau = noise_abs + noise_quad z_c^2 in ComputeTau's place — no triangulation is made, so neither it nor the parallax test that guards it
-// applies.  Any other status, or no image: depth_filter_kernel's triangulated update, the same expressions and so the same bits.  A
-// miss is Unpromote as there.  status: the lookup's, 255 for a request that made none.  One lane per request, no LDS, no atomics.
-struct DepthMeasure {
-  sdvl_depth::DepthLens lens;
-  sdvl_depth::DepthRule rule;
-  double noise_abs, noise_quad;
-  int32_t width, height;
-};
-
-__global__ __launch_bounds__(128) void depth_filter_measured_kernel(const SearchReqDev *__restrict__ reqs, const SearchFramePose *__restrict__ table,
-                                                                    const sdvl_search_res *__restrict__ res, const sdvl_depth_state *__restrict__ state,
-                                                                    int n, Cam cam, sdvl_depth_params fp, const sdvl_depth::DepthJobDev *__restrict__ jobs,
-                                                                    const int32_t *__restrict__ req_job, DepthMeasure dm, TrackPoint *__restrict__ rows,
-                                                                    int n_rows, sdvl_depth_out *__restrict__ out, sdvl_depth_out *__restrict__ out_host,
-                                                                    uint8_t *__restrict__ status_out, uint8_t *__restrict__ status_host) {
-  const int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= n) return;
-  const SearchReqDev &rq = reqs[i];
-  const sdvl_depth_state st = state[i];
-  const sdvl_search_res r = res[i];
-  TrackPoint *row = (rows && st.track_row >= 0 && st.track_row < n_rows) ? rows + st.track_row : nullptr;
-  sdvl_depth_out o;
-  o.outcome = SDVL_DEPTH_SKIPPED;
-  o.n_failed = st.n_failed;
-  o.rho = st.rho; o.sigma2 = st.sigma2; o.a = st.a; o.b = st.b;
-  o.cos_alpha = 0.0; o.last_distance = 0.0;
-  o.position[0] = o.position[1] = o.position[2] = 0.0;
-  int status = 255;
-  if (!r.found) {
-    // Point::Unpromote, point.cc:109-118
-    o.n_failed = st.n_failed + 1;
-    o.b = st.b + 1.0;
-    o.outcome = SDVL_DEPTH_NOT_FOUND | (o.n_failed > fp.max_failed ? SDVL_DEPTH_DELETED : 0);
-    if (row) {
-      row->n_failed = o.n_failed;
-      if (o.outcome & SDVL_DEPTH_DELETED) row->status |= kTrash;
-    }
-  } else {
-    const Rigid cur = se3_from7(table[rq.cur].pose), ref = se3_from7(table[rq.ref].pose);
-    const V3 fv = {rq.bearing[0], rq.bearing[1], rq.bearing[2]};
-    const V3 v3d = cam_unproject(cam, {r.px[0], r.px[1]});
-    const Rigid ref_world = se3_inverse(ref), cur_world = se3_inverse(cur);  // Frame::GetWorldPose
-    const Rigid pose2 = se3_mul(ref, se3_inverse(cur));
-    double zc = 0.0;
-    const int jb = req_job[i];
-    if (jb >= 0) {
-      const int l = r.level < 0 ? 0 : (r.level >= SDVL_MAX_LEVELS ? SDVL_MAX_LEVELS - 1 : r.level);
-      status = sdvl_depth::depth_lookup(jobs[jb], r.px[0], r.px[1], 1 << l, dm.width, dm.height, dm.lens, dm.rule, &zc);
-    }
-    const bool measured = status == SDVL_DEPTH_SEED_OK;
-    double depth = 0.0, tau = 0.0;
-    bool go;
-    if (measured) {
-      const double k = zc / v3d.z;
-      const V3 p_r = se3_apply(pose2, {v3d.x * k, v3d.y * k, v3d.z * k});
-      depth = vdot(p_r, fv);  // the range along the candidate's ray
-      go = depth > 0.0;
-      tau = dm.noise_abs + dm.noise_quad * (zc * zc);
-    } else {
-      const Rigid pose = se3_mul(cur, se3_inverse(ref));  // map.cc:459
-      go = depth_from_triangulation(pose, fv, v3d, &depth);
-      if (go) {
-        const V3 p3d = se3_apply(ref_world, {depth * fv.x, depth * fv.y, depth * fv.z});
-        const double cos_alpha = parallax_of(ref_world.t, cur_world.t, p3d);
-        if (cos_alpha >= 0.999999) go = false;
-      }
-    }
-    if (go && (depth < fp.min_depth || depth < st.depth_mean * fp.scale_min_dist)) go = false;
-    if (go) {
-      // Point::Update, point.cc:64-100
-      if (!measured) tau = compute_tau(pose2, fv, depth, fp.px_error_angle);
-      const double tau_inverse = 0.5 * (1.0 / fmax(0.0000001, depth - tau) - 1.0 / (depth + tau));
-      const double tau2 = tau_inverse * tau_inverse;
-      const double x = 1. / depth;
-      const double norm_scale = sqrt(st.sigma2 + tau2);
-      if (norm_scale != norm_scale) {
-        // std::isnan(norm_scale) -> Update returns with the point untouched (point.cc:76); HasConverged still runs
-        const double std_d = sqrt(st.sigma2) / (st.rho * st.rho);
-        const double l = 4 * std_d * st.cos_alpha / st.last_distance;
-        if (st.fixed || l < 0.1) {
-          const double sc = 1.0 / st.rho;
-          const V3 pos = st.fixed ? V3{st.position[0], st.position[1], st.position[2]} : se3_apply(ref_world, {sc * fv.x, sc * fv.y, sc * fv.z});
-          o.position[0] = pos.x; o.position[1] = pos.y; o.position[2] = pos.z;
-          o.cos_alpha = st.cos_alpha; o.last_distance = st.last_distance;
-          o.outcome = SDVL_DEPTH_FIXED_STALE;
-          if (row) {
-            row->P[0] = pos.x; row->P[1] = pos.y; row->P[2] = pos.z;
-            row->fixed = 1;
-          }
-        }
-      } else {
-        const double s2 = 1. / (1. / st.sigma2 + 1. / tau2);
-        const double m = s2 * (st.rho / st.sigma2 + x / tau2);
-        double C1 = st.a / (st.a + st.b) * pdf_normal(st.rho, norm_scale, x);
-        double C2 = st.b / (st.a + st.b) * 1. / st.z_range;
-        const double normalization_constant = C1 + C2;
-        C1 /= normalization_constant;
-        C2 /= normalization_constant;
-        const double f = C1 * (st.a + 1.) / (st.a + st.b + 1.) + C2 * st.a / (st.a + st.b + 1.);
-        const double e = C1 * (st.a + 1.) * (st.a + 2.) / ((st.a + st.b + 1.) * (st.a + st.b + 2.)) +
-                         C2 * st.a * (st.a + 1.0) / ((st.a + st.b + 1.0) * (st.a + st.b + 2.0));
-        const double rho_new = C1 * m + C2 * st.rho;
-        o.sigma2 = C1 * (s2 + m * m) + C2 * (st.sigma2 + st.rho * st.rho) - rho_new * rho_new;
-        o.rho = rho_new;
-        o.a = (e - f) / (f - e / f);
-        o.b = o.a * (1.0 - f) / f;
-        const double sc = 1.0 / o.rho;  // Point::GetPosition, point.cc:128-142
-        const V3 pos = st.fixed ? V3{st.position[0], st.position[1], st.position[2]} : se3_apply(ref_world, {sc * fv.x, sc * fv.y, sc * fv.z});
-        o.cos_alpha = parallax_of(ref_world.t, cur_world.t, pos);
-        o.last_distance = vnorm(vsub(cur_world.t, pos));  // Frame::DistanceTo, frame.h:133-136
-        o.n_failed = 0;
-        o.position[0] = pos.x; o.position[1] = pos.y; o.position[2] = pos.z;
-        o.outcome = SDVL_DEPTH_UPDATED;
-        // Point::HasConverged, point.cc:164-178
-        const double std_d = sqrt(o.sigma2) / (o.rho * o.rho);
-        const double l = 4 * std_d * o.cos_alpha / o.last_distance;
-        if (st.fixed || l < 0.1) o.outcome = SDVL_DEPTH_CONVERGED;
-        if (row) {
-          row->P[0] = pos.x; row->P[1] = pos.y; row->P[2] = pos.z;
-          row->idepth = o.rho;
-          row->idepth_std = sqrt(o.sigma2);  // Point::GetStd
-          row->n_failed = 0;
-          if (o.outcome == SDVL_DEPTH_CONVERGED) row->fixed = 1;
-        }
-      }
-    }
-  }
-  out[i] = o;
-  if (out_host) out_host[i] = o;
-  status_out[i] = static_cast<uint8_t>(status);
-  if (status_host) status_host[i] = static_cast<uint8_t>(status);
-}
-
 }  // namespace
 
 int sdvl_search_launch_device(sdvl_ctx *ctx, int n_slots, const SearchReqDev *d_reqs, const SearchFramePose *d_table,
@@ -1168,18 +867,9 @@ int sdvl_search_slot(sdvl_ctx *ctx, const sdvl_frame *f, const double *pose) {
   return B.last;
 }
 
-// What a search of n requests keeps in the context's result buffers — d_out: results | per-request records of the scalar phase;
-// h_out: results — each at the head, so a caller takes the parts it wants behind them from `d` / `h` before search_enqueue.
-struct SearchOut {
-  sdvl_layout d, h;
-  sdvl_part<sdvl_search_res> res, h_res;
-  sdvl_part<SearchPrep> prep;
-  explicit SearchOut(int n) : res(d.take<sdvl_search_res>(n)), h_res(h.take<sdvl_search_res>(n)), prep(d.take<SearchPrep>(n)) {}
-};
-
-// everything of sdvl_search_run up to and including the queued copy of the results into h_out (so.h_res); the caller waits.
-static int search_enqueue(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const SearchOut &so,
-                          const SearchReqDev **d_reqs_out = nullptr, const SearchFramePose **d_table_out = nullptr) {
+// (sdvl_search_types.h; the mapper's depth filter queues its kernel behind this one: sdvl_depth_filter.hip)
+int sdvl_search_enqueue(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const SearchOut &so, const SearchReqDev **d_reqs_out,
+                        const SearchFramePose **d_table_out) {
   SearchBatch &B = batch_of(ctx);
   SDVL_REQUIRE(ctx, B.hs && n <= B.cap, "sdvl_search_run without a matching sdvl_search_begin");
   int rc = sdvl_check_search_params(ctx, p);
@@ -1236,7 +926,7 @@ int sdvl_search_run(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_sea
   if (!ctx || !cam || !p || n < 0 || (n > 0 && !out)) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
   const SearchOut so(n);
-  const int rc = search_enqueue(ctx, n, cam, p, so);
+  const int rc = sdvl_search_enqueue(ctx, n, cam, p, so);
   if (rc) return rc;
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
   memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
@@ -1318,7 +1008,7 @@ int sdvl_search_run_chain(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sd
   const sdvl_part<uint8_t> hyp = so.d.take<uint8_t>(separate ? sdvl_pose_hyp_bytes() * static_cast<size_t>(n_frames) * pp->max_ransac_its : 0);
   const auto take_back = [&](sdvl_layout &L) { return sdvl_ctx::ChainBack{L.take<sdvl_pose_result>(n_frames), L.take<int32_t>(n_frames), L.take<int32_t>(obs_total)}; };
   const sdvl_ctx::ChainBack back = take_back(so.d), h_back = take_back(so.h);
-  rc = search_enqueue(ctx, n, cam, p, so);
+  rc = sdvl_search_enqueue(ctx, n, cam, p, so);
   if (rc) return rc;
   SDVL_HIP_CHECK(ctx, sdvl_mark_record(ctx, SDVL_MARK_CHAIN, &ctx->chain_ticket));  // the search results are on the host from here on
   // inputs of the selection + pose stage: one staged copy
@@ -1379,8 +1069,7 @@ int sdvl_search_chain_end(sdvl_ctx *ctx, int n_frames, sdvl_pose_result *results
   return SDVL_OK;
 }
 
-
-static int pack_requests(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs) {
+int sdvl_search_pack_requests(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs) {
   sdvl_search_req_packed *packed = nullptr;
   int rc = sdvl_search_begin(ctx, n, &packed);
   if (rc) return rc;
@@ -1405,250 +1094,9 @@ int sdvl_search_points(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs, const 
                        const sdvl_search_params *p, sdvl_search_res *out) {
   if (!ctx || !cam || !p || n < 0 || (n > 0 && (!reqs || !out))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  const int rc = pack_requests(ctx, n, reqs);
+  const int rc = sdvl_search_pack_requests(ctx, n, reqs);
   if (rc) return rc;
   return sdvl_search_run(ctx, n, cam, p, out);
-}
-
-// what every entry to depth_filter_kernel requires of the states; -> the rows the kernel may patch (none without a set)
-static int depth_filter_check(sdvl_ctx *ctx, int n, const sdvl_depth_state *state, sdvl_track_set *set, TrackPoint **rows_out, int *n_rows_out) {
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  if (set) {
-    int np = 0, nt = 0;
-    rows = sdvl_track_points_device(set, &np, &nt);
-    n_rows = np * nt;
-  }
-  for (int i = 0; i < n; i++) {
-    SDVL_REQUIRE(ctx, state[i].track_row >= -1 && (state[i].track_row < n_rows || !set), "depth filter: track_row outside the tables");
-    SDVL_REQUIRE(ctx, state[i].sigma2 > 0.0 && state[i].z_range > 0.0, "depth filter: sigma2 and z_range must be positive");
-  }
-  *rows_out = rows;
-  *n_rows_out = n_rows;
-  return SDVL_OK;
-}
-
-// ---- search + depth filter (Map::UpdateCandidates, map.cc:402-498): one submission, one wait
-int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
-                           const sdvl_depth_params *fp, sdvl_track_set *set, sdvl_search_res *out, sdvl_depth_out *fout) {
-  if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout))) return SDVL_ERR_INVALID;
-  if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (rc) return rc;
-  SearchOut so(n);
-  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
-  const SearchReqDev *d_reqs = nullptr;
-  const SearchFramePose *d_table = nullptr;
-  rc = search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
-  if (rc) return rc;
-  const size_t state_bytes = sizeof(sdvl_depth_state) * static_cast<size_t>(n);  // staged: the states alone
-  void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, state_bytes, &hs, &dsx);
-  if (rc) return rc;
-  memcpy(hs, state, state_bytes);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, state_bytes));
-  SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table, so.res.cin(ctx->d_out),
-              static_cast<const sdvl_depth_state *>(dsx), n, cam_of(*cam), *fp, rows, n_rows, d_fout.in(ctx->d_out), h_fout.in(ctx->h_out));
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
-  memcpy(fout, h_fout.in(ctx->h_out), h_fout.bytes());
-  return SDVL_OK;
-}
-
-int sdvl_search_points_filter(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs, const sdvl_camera *cam, const sdvl_search_params *p,
-                              const sdvl_depth_state *state, const sdvl_depth_params *fp, sdvl_track_set *set, sdvl_search_res *out,
-                              sdvl_depth_out *fout) {
-  if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!reqs || !state || !out || !fout))) return SDVL_ERR_INVALID;
-  if (n == 0) return SDVL_OK;
-  const int rc = pack_requests(ctx, n, reqs);
-  if (rc) return rc;
-  return sdvl_search_run_filter(ctx, n, cam, p, state, fp, set, out, fout);
-}
-
-// ---- the depth filter alone: depth_filter_kernel on search results the caller states
-int sdvl_depth_filter(sdvl_ctx *ctx, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
-                      const double *px, const sdvl_camera *cam, const sdvl_depth_state *state, const sdvl_depth_params *fp,
-                      sdvl_track_set *set, sdvl_depth_out *fout) {
-  if (!ctx || !cam || !fp || n < 0 || (n > 0 && (!cur_pose || !ref_pose || !bearing || !found || !px || !state || !fout))) return SDVL_ERR_INVALID;
-  if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (rc) return rc;
-  // staging: requests | frame table (entry 2i: item i's current pose, 2i + 1: its reference pose) | search results | states;
-  // d_out and h_out: the outcomes.  Of a request the kernel reads the two slots and the bearing, of a table entry the pose, of a
-  // result `found` and `px`: everything else stays zero.
-  sdvl_layout st, o;
-  const sdvl_part<SearchReqDev> st_reqs = st.take<SearchReqDev>(n);
-  const sdvl_part<SearchFramePose> st_tab = st.take<SearchFramePose>(2 * static_cast<size_t>(n));
-  const sdvl_part<sdvl_search_res> st_res = st.take<sdvl_search_res>(n);
-  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
-  const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
-  if (rc) return rc;
-  memset(hs, 0, st.bytes());
-  SearchReqDev *hreq = st_reqs.in(hs);
-  SearchFramePose *htab = st_tab.in(hs);
-  sdvl_search_res *hres = st_res.in(hs);
-  for (int i = 0; i < n; i++) {
-    hreq[i].cur = 2 * i;
-    hreq[i].ref = 2 * i + 1;
-    memcpy(hreq[i].bearing, bearing + 3 * static_cast<size_t>(i), sizeof(double) * 3);
-    memcpy(htab[2 * i].pose, cur_pose + 7 * static_cast<size_t>(i), sizeof(double) * 7);
-    memcpy(htab[2 * i + 1].pose, ref_pose + 7 * static_cast<size_t>(i), sizeof(double) * 7);
-    hres[i].found = found[i] ? 1 : 0;
-    hres[i].px[0] = px[2 * static_cast<size_t>(i)];
-    hres[i].px[1] = px[2 * static_cast<size_t>(i) + 1];
-  }
-  memcpy(st_state.in(hs), state, st_state.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), st_reqs.cin(ds), st_tab.cin(ds), st_res.cin(ds),
-              st_state.cin(ds), n, cam_of(*cam), *fp, rows, n_rows, o_fout.in(ctx->d_out), o_fout.in(ctx->h_out));
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(fout, o_fout.in(ctx->h_out), o_fout.bytes());
-  return SDVL_OK;
-}
-
-// ---- the same two entries for a depth camera: depth_filter_measured_kernel
-// what both require of the depth side; -> the kernel's record
-static int depth_measure_check(sdvl_ctx *ctx, const char *who, int n, int n_jobs, const sdvl_depth_job *jobs, int width, int height, const sdvl_camera *cam,
-                               const sdvl_distortion *dist, const sdvl_depth_measure_params *mp, DepthMeasure *dm) {
-  const std::string w(who);
-  SDVL_REQUIRE(ctx, n_jobs >= 0 && (n_jobs == 0 || jobs), w + ": bad job list");
-  int rc = sdvl_depth_rule_of(ctx, who, mp ? &mp->rule : nullptr, &dm->rule);
-  if (!rc) rc = sdvl_depth_jobs_check(ctx, who, n_jobs, jobs, width, height, n);
-  if (rc) return rc;
-  dm->noise_abs = 0.001;   // metres; with noise_quad the order of magnitude of a structured-light sensor, not measured against one
-  dm->noise_quad = 0.0015; // per metre
-  if (mp) {
-    SDVL_REQUIRE(ctx, mp->noise_abs >= 0.0 && mp->noise_quad >= 0.0, w + ": noise_abs and noise_quad must not be negative");
-    if (mp->noise_abs != 0.0) dm->noise_abs = mp->noise_abs;
-    if (mp->noise_quad != 0.0) dm->noise_quad = mp->noise_quad;
-  }
-  dm->lens = sdvl_depth_lens_of(cam, dist);
-  dm->width = width;
-  dm->height = height;
-  return SDVL_OK;
-}
-
-// jobs | the job of every request (-1: none) as one staged record
-struct DepthMeasureStage {
-  sdvl_part<sdvl_depth::DepthJobDev> jobs;
-  sdvl_part<int32_t> req_job;
-  DepthMeasureStage(sdvl_layout &st, int n, int n_jobs) : jobs(st.take<sdvl_depth::DepthJobDev>(n_jobs > 0 ? n_jobs : 1)), req_job(st.take<int32_t>(n)) {}
-  int fill(sdvl_ctx *ctx, void *hs, int n, int n_jobs, const sdvl_depth_job *in, int width, int height) const {
-    const int rc = n_jobs > 0 ? sdvl_depth_jobs_resolve(ctx, n_jobs, in, width, height, jobs.in(hs)) : SDVL_OK;
-    if (rc) return rc;
-    int32_t *rj = req_job.in(hs);
-    for (int i = 0; i < n; i++) rj[i] = -1;
-    for (int j = 0; j < n_jobs; j++)
-      for (int i = in[j].c_begin; i < in[j].c_end; i++) rj[i] = j;
-    return SDVL_OK;
-  }
-};
-
-int sdvl_search_run_filter_measured(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
-                                    const sdvl_depth_params *fp, sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width, int height,
-                                    const sdvl_distortion *dist, const sdvl_depth_measure_params *mp, sdvl_search_res *out, sdvl_depth_out *fout,
-                                    uint8_t *out_status) {
-  if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout || !out_status))) return SDVL_ERR_INVALID;
-  if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  DepthMeasure dm;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (!rc) rc = depth_measure_check(ctx, "sdvl_search_run_filter_measured", n, n_jobs, jobs, width, height, cam, dist, mp, &dm);
-  if (rc) return rc;
-  SearchOut so(n);
-  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
-  const sdvl_part<uint8_t> d_status = so.d.take<uint8_t>(n), h_status = so.h.take<uint8_t>(n);
-  const SearchReqDev *d_reqs = nullptr;
-  const SearchFramePose *d_table = nullptr;
-  rc = search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
-  if (rc) return rc;
-  sdvl_layout st;  // staged: states | jobs | the job of every request
-  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
-  const DepthMeasureStage st_depth(st, n, n_jobs);
-  void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
-  if (!rc) rc = st_depth.fill(ctx, hs, n, n_jobs, jobs, width, height);
-  if (rc) return rc;
-  memcpy(st_state.in(hs), state, st_state.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
-  SDVL_LAUNCH(ctx, "depth_filter_measured", depth_filter_measured_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table, so.res.cin(ctx->d_out),
-              st_state.cin(dsx), n, cam_of(*cam), *fp, st_depth.jobs.cin(dsx), st_depth.req_job.cin(dsx), dm, rows, n_rows, d_fout.in(ctx->d_out),
-              h_fout.in(ctx->h_out), d_status.in(ctx->d_out), h_status.in(ctx->h_out));
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
-  memcpy(fout, h_fout.in(ctx->h_out), h_fout.bytes());
-  memcpy(out_status, h_status.in(ctx->h_out), h_status.bytes());
-  return SDVL_OK;
-}
-
-int sdvl_depth_filter_measured(sdvl_ctx *ctx, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
-                               const double *px, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state,
-                               const sdvl_depth_params *fp, sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width, int height,
-                               const sdvl_distortion *dist, const sdvl_depth_measure_params *mp, sdvl_depth_out *fout, uint8_t *out_status) {
-  if (!ctx || !cam || !fp || n < 0 || (n > 0 && (!cur_pose || !ref_pose || !bearing || !found || !px || !level || !state || !fout || !out_status)))
-    return SDVL_ERR_INVALID;
-  if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  DepthMeasure dm;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (!rc) rc = depth_measure_check(ctx, "sdvl_depth_filter_measured", n, n_jobs, jobs, width, height, cam, dist, mp, &dm);
-  if (rc) return rc;
-  for (int i = 0; i < n; i++)
-    SDVL_REQUIRE(ctx, level[i] >= 0 && level[i] < SDVL_MAX_LEVELS, "sdvl_depth_filter_measured: found level outside 0 .. SDVL_MAX_LEVELS - 1");
-  // staging as sdvl_depth_filter's, then jobs | the job of every request; d_out and h_out: the outcomes | the status bytes
-  sdvl_layout st, o;
-  const sdvl_part<SearchReqDev> st_reqs = st.take<SearchReqDev>(n);
-  const sdvl_part<SearchFramePose> st_tab = st.take<SearchFramePose>(2 * static_cast<size_t>(n));
-  const sdvl_part<sdvl_search_res> st_res = st.take<sdvl_search_res>(n);
-  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
-  const DepthMeasureStage st_depth(st, n, n_jobs);
-  const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
-  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
-  if (rc) return rc;
-  memset(hs, 0, st.bytes());
-  rc = st_depth.fill(ctx, hs, n, n_jobs, jobs, width, height);
-  if (rc) return rc;
-  SearchReqDev *hreq = st_reqs.in(hs);
-  SearchFramePose *htab = st_tab.in(hs);
-  sdvl_search_res *hres = st_res.in(hs);
-  for (int i = 0; i < n; i++) {
-    hreq[i].cur = 2 * i;
-    hreq[i].ref = 2 * i + 1;
-    memcpy(hreq[i].bearing, bearing + 3 * static_cast<size_t>(i), sizeof(double) * 3);
-    memcpy(htab[2 * i].pose, cur_pose + 7 * static_cast<size_t>(i), sizeof(double) * 7);
-    memcpy(htab[2 * i + 1].pose, ref_pose + 7 * static_cast<size_t>(i), sizeof(double) * 7);
-    hres[i].found = found[i] ? 1 : 0;
-    hres[i].level = level[i];
-    hres[i].px[0] = px[2 * static_cast<size_t>(i)];
-    hres[i].px[1] = px[2 * static_cast<size_t>(i) + 1];
-  }
-  memcpy(st_state.in(hs), state, st_state.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  SDVL_LAUNCH(ctx, "depth_filter_measured", depth_filter_measured_kernel, dim3((n + 127) / 128), dim3(128), st_reqs.cin(ds), st_tab.cin(ds), st_res.cin(ds),
-              st_state.cin(ds), n, cam_of(*cam), *fp, st_depth.jobs.cin(ds), st_depth.req_job.cin(ds), dm, rows, n_rows, o_fout.in(ctx->d_out),
-              o_fout.in(ctx->h_out), o_status.in(ctx->d_out), o_status.in(ctx->h_out));
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(fout, o_fout.in(ctx->h_out), o_fout.bytes());
-  memcpy(out_status, o_status.in(ctx->h_out), o_status.bytes());
-  return SDVL_OK;
 }
 
 int sdvl_align_patches(sdvl_ctx *ctx, int n, const sdvl_frame *const *frames, const int32_t *levels, const uint8_t *border,

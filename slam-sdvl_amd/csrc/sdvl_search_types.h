@@ -153,7 +153,7 @@ __device__ __forceinline__ void select_emit(const PoseChainIn &in, const ChainFr
   obs[fr.obs_begin + rank] = o;
 }
 
-// ---- rows of the device-resident tracking tables (sdvl_track.hip); the depth filter (sdvl_search.hip) patches them in place
+// ---- rows of the device-resident tracking tables (sdvl_track.hip); the depth filter (sdvl_depth_filter.hip) patches them in place
 constexpr int kDeleted = 0x100;                 // sdvl_track_point_stat::status bit
 constexpr int kTrash = 0x200;                   // deleted by the mapper: becomes kDeleted at the end of the next step's commit
 constexpr int kKeepBits = kDeleted | kTrash;
@@ -217,6 +217,21 @@ int sdvl_search_launch_device(sdvl_ctx *ctx, int n_slots, const SearchReqDev *d_
 // second half of SelectPoints for n_frames trackers as a launch of its own (sdvl_pose_enqueue_device queues it for sets of <= 4
 // trackers; larger sets select inside pose_refine): fills d_jobs and the observations
 int sdvl_select_matches_launch(sdvl_ctx *ctx, int n_frames, const PoseChainIn &in, PoseJobDev *d_jobs, sdvl_pose_obs *d_obs);
+// ---- and for the entries that queue a kernel of their own behind a search of host requests (sdvl_depth_filter.hip)
+// What a search of n requests keeps in the context's result buffers — d_out: results | per-request records of the scalar phase;
+// h_out: results — each at the head, so a caller takes the parts it wants behind them from `d` / `h` before sdvl_search_enqueue.
+struct SearchOut {
+  sdvl_layout d, h;
+  sdvl_part<sdvl_search_res> res, h_res;
+  sdvl_part<SearchPrep> prep;
+  explicit SearchOut(int n) : res(d.take<sdvl_search_res>(n)), h_res(h.take<sdvl_search_res>(n)), prep(d.take<SearchPrep>(n)) {}
+};
+// everything of sdvl_search_run up to and including the queued copy of the results into h_out (so.h_res); the caller waits.  -> where
+// the batch's requests and frame table lie in HBM
+extern "C" int sdvl_search_enqueue(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const SearchOut &so,
+                                   const SearchReqDev **d_reqs_out = nullptr, const SearchFramePose **d_table_out = nullptr);
+// sdvl_search_begin + one sdvl_search_slot pair per request: the batch of sdvl_search_points
+extern "C" int sdvl_search_pack_requests(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs);
 // sdvl_image_align.hip: the image alignment of a tracked step, features straight from the tracking tables (no records, no wait)
 int sdvl_image_align_track_enqueue(sdvl_ctx *ctx, int n_jobs, const TrackJobDev *d_jobs, const TrackPoint *d_points, const TrackFeat *d_feats0,
                                    const TrackFeat *d_feats1, int np, int nfeat_cap, int max_nf, int levels, const sdvl_camera *cam,

@@ -126,8 +126,6 @@ class Point {
   int GetLastBA() const { return last_ba_; }
   void SetLastBA(int id) { last_ba_ = id; }
   static void ConsumeId();  // what constructing and discarding a Point does to the id counter
-  static double ComputeTau(const SE3 &pose, const Vector3d &v, double depth, double px_error_angle);
-  static double PDFNormal(double mean, double sd, double x);
 
  private:
   // the fields the per-frame loops touch (ProjectPoints, SelectPoints) first, so that they share a cache line

@@ -8,6 +8,7 @@
 #include <map>
 #include <set>
 
+#include "../csrc/sdvl_depth_filter.h"
 #include "config.h"
 #include "sdvl_host.h"
 
@@ -21,32 +22,16 @@ using std::vector;
 
 namespace {
 
-// extra/utils.cc:193-205: A = [R v_ref | v_cur], depth2 = -(A^T A)^-1 A^T t, |depth2[0]|
+// The depth filter's arithmetic is csrc/sdvl_depth_filter.h's, the statements the device kernels run; here the reference's signatures
+V3 v3(const Vector3d &v) { return {v(0), v(1), v(2)}; }
+
+// extra/utils.cc:193-205
 bool GetDepthFromTriangulation(const SE3 &pose, const Vector3d &v_ref, const Vector3d &v_cur, double *depth) {
-  const M3 R = pose.GetRotation();
-  const V3 a0 = mvec(R, {v_ref(0), v_ref(1), v_ref(2)});
-  const V3 a1 = {v_cur(0), v_cur(1), v_cur(2)};
-  const double m00 = vdot(a0, a0), m01 = vdot(a0, a1), m11 = vdot(a1, a1);
-  const double det = m00 * m11 - m01 * m01;
-  if (det < 0.000001) return false;
-  const double invdet = 1.0 / det;
-  const double i00 = m11 * invdet, i01 = -m01 * invdet;
-  const double n00 = -i00, n01 = -i01;
-  const double r0x = n00 * a0.x + n01 * a1.x, r0y = n00 * a0.y + n01 * a1.y, r0z = n00 * a0.z + n01 * a1.z;
-  const Vector3d t = pose.GetTranslation();
-  const double d0 = r0x * t(0) + r0y * t(1) + r0z * t(2);
-  *depth = std::fabs(d0);
-  return true;
+  return depth_from_triangulation(pose.pod(), v3(v_ref), v3(v_cur), depth);
 }
 
 // extra/utils.cc:207-213
-double GetParallax(const Vector3d &src1, const Vector3d &src2, const Vector3d &p3d) {
-  V3 v1 = {src1(0) - p3d(0), src1(1) - p3d(1), src1(2) - p3d(2)}, v2 = {src2(0) - p3d(0), src2(1) - p3d(1), src2(2) - p3d(2)};
-  const double n1 = vnorm(v1), n2 = vnorm(v2);
-  v1 = {v1.x / n1, v1.y / n1, v1.z / n1};
-  v2 = {v2.x / n2, v2.y / n2, v2.z / n2};
-  return vdot(v1, v2);
-}
+double GetParallax(const Vector3d &src1, const Vector3d &src2, const Vector3d &p3d) { return parallax_of(v3(src1), v3(src2), v3(p3d)); }
 
 void FillRequest(sdvl_search_req *rq, Frame *cur, Frame *ref, const Vector2d &px, const Vector3d &bearing, int level, const uchar *desc,
                  double idepth, double idepth_std, bool fixed, const Vector2d &px0) {
@@ -74,58 +59,14 @@ void FillRequestFromFeature(sdvl_search_req *rq, Frame *cur, Feature *feature, F
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------- Point (depth filter)
-// point.cc:189-201
-double Point::ComputeTau(const SE3 &pose, const Vector3d &v, double depth, double px_error_angle) {
-  const double PI = 3.14159265;
-  const Vector3d t = pose.GetTranslation();
-  const V3 tt = {t(0), t(1), t(2)};
-  const V3 a = {v(0) * depth - t(0), v(1) * depth - t(1), v(2) * depth - t(2)};
-  const double t_norm = vnorm(tt), a_norm = vnorm(a);
-  const double alpha = std::acos((v(0) * t(0) + v(1) * t(1) + v(2) * t(2)) / t_norm);
-  const double beta = std::acos((a.x * -t(0) + a.y * -t(1) + a.z * -t(2)) / (t_norm * a_norm));
-  const double beta_plus = beta + px_error_angle;
-  const double gamma_plus = PI - alpha - beta_plus;
-  const double depth_plus = t_norm * std::sin(beta_plus) / std::sin(gamma_plus);
-  return depth_plus - depth;
-}
-
-// point.cc:203-217
-double Point::PDFNormal(double mean, double sd, double x) {
-  const double PI = 3.14159265;
-  double result = 0.0;
-  if (sd <= 0) return result;
-  double exponent = x - mean;
-  exponent *= -exponent;
-  exponent /= 2 * sd * sd;
-  result = std::exp(exponent);
-  result /= sd * std::sqrt(2.0 * PI);
-  return result;
-}
-
-// point.cc:64-100
+// point.cc:64-100; ComputeTau (:189-201) and PDFNormal (:203-217) are the shared header's compute_tau and pdf_normal
 void Point::Update(const shared_ptr<Frame> &frame, double depth, double px_error_angle) {
   Frame *f0 = feature_->GetFrameRaw();
   const SE3 pose = f0->GetPose() * frame->GetPose().Inverse();
-  const double tau = ComputeTau(pose, feature_->GetVector(), depth, px_error_angle);
-  const double tau_inverse = 0.5 * (1.0 / std::max(0.0000001, depth - tau) - 1.0 / (depth + tau));
-  const double tau2 = tau_inverse * tau_inverse;
-  const double x = 1. / depth;
-  const double norm_scale = std::sqrt(sigma2_ + tau2);
-  if (std::isnan(norm_scale)) return;
-  const double s2 = 1. / (1. / sigma2_ + 1. / tau2);
-  const double m = s2 * (rho_ / sigma2_ + x / tau2);
-  double C1 = a_ / (a_ + b_) * PDFNormal(rho_, norm_scale, x);
-  double C2 = b_ / (a_ + b_) * 1. / z_range_;
-  const double normalization_constant = C1 + C2;
-  C1 /= normalization_constant;
-  C2 /= normalization_constant;
-  const double f = C1 * (a_ + 1.) / (a_ + b_ + 1.) + C2 * a_ / (a_ + b_ + 1.);
-  const double e = C1 * (a_ + 1.) * (a_ + 2.) / ((a_ + b_ + 1.) * (a_ + b_ + 2.)) + C2 * a_ * (a_ + 1.0) / ((a_ + b_ + 1.0) * (a_ + b_ + 2.0));
-  const double rho_new = C1 * m + C2 * rho_;
-  sigma2_ = C1 * (s2 + m * m) + C2 * (sigma2_ + rho_ * rho_) - rho_new * rho_new;
-  rho_ = rho_new;
-  a_ = (e - f) / (f - e / f);
-  b_ = a_ * (1.0 - f) / f;
+  const double tau = compute_tau(pose.pod(), v3(feature_->GetVector()), depth, px_error_angle);
+  DepthPosterior q;
+  if (!posterior_update({rho_, sigma2_, a_, b_}, z_range_, 1. / depth, tau_inverse(depth, tau), &q)) return;
+  rho_ = q.rho; sigma2_ = q.sigma2; a_ = q.a; b_ = q.b;
   const Vector3d pos = GetPosition();
   cos_alpha_ = GetParallax(f0->GetWorldPosition(), frame->GetWorldPosition(), pos);
   last_distance_ = frame->DistanceTo(pos);
@@ -135,9 +76,7 @@ void Point::Update(const shared_ptr<Frame> &frame, double depth, double px_error
 // point.cc:164-178
 bool Point::HasConverged() {
   if (fixed_) return true;
-  const double std_d = std::sqrt(sigma2_) / (rho_ * rho_);
-  const double l = 4 * std_d * cos_alpha_ / last_distance_;
-  if (l < 0.1) {
+  if (has_converged(false, rho_, sigma2_, cos_alpha_, last_distance_)) {
     p3d_ = GetPosition();
     fixed_ = true;
     return true;
@@ -906,10 +845,10 @@ void MapperMap::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
   noise_quad_ = noise_quad;
 }
 
-// the tau_inverse of depth_filter_measured_kernel (point.cc:69 with tau = noise_abs + noise_quad z^2) for a range and its sample z
+// the tau_inverse of the measured depth filter (point.cc:69 with tau = noise_abs + noise_quad z^2) for a range and its sample z
 double MapperMap::MeasuredTauInverse(double range, double z) const {
-  const double tau = (noise_abs_ != 0.0 ? noise_abs_ : 0.001) + (noise_quad_ != 0.0 ? noise_quad_ : 0.0015) * (z * z);
-  return 0.5 * (1.0 / std::max(0.0000001, range - tau) - 1.0 / (range + tau));
+  const double tau = (noise_abs_ != 0.0 ? noise_abs_ : SDVL_DEPTH_NOISE_ABS) + (noise_quad_ != 0.0 ? noise_quad_ : SDVL_DEPTH_NOISE_QUAD) * (z * z);
+  return tau_inverse(range, tau);
 }
 
 void MapperMap::SetCornerDepths(const double *z, const uint8_t *status) {

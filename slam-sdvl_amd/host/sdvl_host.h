@@ -147,7 +147,7 @@ class MapperMap : public PlaneMap {
   // without bundle adjustment on and while the mapper thread runs, std::invalid_argument for a negative or non-finite bf.
   void SetDepthBundle(bool on, double bf = 0.0);
   bool DepthBundleOn() const { return depth_bundle_; }
-  double DepthBundleBf() const { return depth_bundle_bf_ > 0.0 ? depth_bundle_bf_ : 1.0 / (noise_quad_ != 0.0 ? noise_quad_ : 0.0015); }
+  double DepthBundleBf() const { return depth_bundle_bf_ > 0.0 ? depth_bundle_bf_ : 1.0 / (noise_quad_ != 0.0 ? noise_quad_ : SDVL_DEPTH_NOISE_QUAD); }
   // the features of CurrentFrame() (a keyframe update) that have no depth yet, as level-0 positions and levels, appended to the lists
   int EmitDepthLookups(std::vector<double> *px2, std::vector<int32_t> *level);
   void ApplyDepthLookups(const double *z, const uint8_t *status);  // of the features EmitDepthLookups listed, in its order

@@ -1,5 +1,5 @@
 """The mapper's depth filter with a MEASURED depth (sdvl_depth_filter_measured, include/sdvl_hip.h) restated one candidate at a time in
-plain Python floats, in the device's operation order: the SPECIFICATION of depth_filter_measured_kernel (csrc/sdvl_search.hip).  The rule is
+plain Python floats, in the device's operation order: the SPECIFICATION of depth_filter_measured_kernel (csrc/sdvl_depth_filter.hip).  The rule is
 this project's own.  It is composed of the two restatements it stands on, which are imported and not edited: depth_restatement (the loop
 body of Map::UpdateCandidates, Point::Update, HasConverged and the SE3 arithmetic) and depth_seed_restatement (the validity of a depth
 sample, the status codes, the rule's defaults).

@@ -1,4 +1,4 @@
-"""depth_filter_kernel (csrc/sdvl_search.hip) alone, through sdvl_depth_filter, against the pure-Python restatement of
+"""depth_filter_kernel (csrc/sdvl_depth_filter.hip) alone, through sdvl_depth_filter, against the pure-Python restatement of
 Map::UpdateCandidates' loop body (tests/depth_restatement.py) on the named cases of tests/depth_cases.py: misses around max_failed,
 det, cos_alpha, the two depth tests and l on both sides of their thresholds, negative tau, the clamp, regular updates over the range of
 states a candidate passes through (sigma2 down to 1e-9, a + b up to 600), the early return of Point::Update, a sequence of twelve

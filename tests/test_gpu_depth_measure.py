@@ -1,4 +1,4 @@
-"""depth_filter_measured_kernel (csrc/sdvl_search.hip) through sdvl_depth_filter_measured, against its specification
+"""depth_filter_measured_kernel (csrc/sdvl_depth_filter.hip) through sdvl_depth_filter_measured, against its specification
 tests/depth_measure_restatement.py on the cases of tests/depth_measure_cases.py: float and 16-bit images (16-bit at an odd address and with
 rows wider than their samples, both in HBM; tight images in pageable memory), with and without a lens, found levels 0 to 4 on 24 x 16,
 every status, a request in no job, misses, a fixed point, the early return of Point::Update, a converging update, rows patched in a

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 T_ID = np.array([1, 0, 0, 0, 0, 0, 0], np.float64)
 K_LDS_MAX_F = 384          # csrc/sdvl_image_align.hip:26 (one wave per job up to this many features)
 MAX_ALIGN_FEATURES = 2048  # SDVL_MAX_ALIGN_FEATURES, include/sdvl_hip.h:37
-SEARCH_TAB_CAP = 2048      # kSearchTabCap, csrc/sdvl_search.hip:1014
+SEARCH_TAB_CAP = 2048      # kSearchTabCap, csrc/sdvl_search.hip
 WAVES_PER_BLOCK = 4        # kWavesPerBlock: requests per search workgroup, patch jobs per align-patches workgroup
 BIN_CELLS_SMALL, BIN_CORNERS_SMALL, BIN_CELLS = 512, 2048, 2048   # csrc/sdvl_orb.hip:234-235
 REMAP_FRAMES = 4           # kRemapFrames, csrc/sdvl_undistort.hip:194
@@ -296,8 +296,8 @@ def test_align_store_equals_image_align(ctx, sdvl, ia):
 
 # ------------------------------------------------------------------------------------------------ search
 def search_table_size(reqs):
-    """entries of the batch's frame table: sdvl_search_slot (csrc/sdvl_search.hip:1046-1067) for the current then the reference
-    (frame, pose) of every request, in request order (pack_requests, :1292-1293)"""
+    """entries of the batch's frame table: sdvl_search_slot (csrc/sdvl_search.hip) for the current then the reference
+    (frame, pose) of every request, in request order (sdvl_search_pack_requests)"""
     table, where, last, last2 = [], {}, -1, -1
     for r in reqs:
         for f, pose in ((r.cur, tuple(r.cur_pose)), (r.ref, tuple(r.ref_pose))):
@@ -361,7 +361,7 @@ SEARCH_FIRST_RUN = {}   # n_req -> the result bytes of the module's first run at
 @pytest.mark.parametrize("n_req", [SEARCH_TAB_CAP - 1, SEARCH_TAB_CAP, 2100, 1, 32, 33, 64, 65, pytest.param(32, id="32-again")])
 def test_search_points_frame_table_over_the_staging_cap(ctx, sdvl, many, n_req):
     """a frame table of 2048, 2049 and 2101 (frame, pose) entries: up to kSearchTabCap it rides in the staging copy, beyond it goes
-    through the work buffer with a copy of its own (csrc/sdvl_search.hip:1112-1123).  Found, level and offsets bit-equal to the
+    through the work buffer with a copy of its own (sdvl_search_enqueue, csrc/sdvl_search.hip).  Found, level and offsets bit-equal to the
     oracle; the chosen corner equals that of the same requests run in batches whose tables stay under the cap.
     Behind the large batches, in buffers that have grown: 1 request, and 32 / 33 and 64 / 65, where the packed requests (120 B:
     32 are 15 x 256) and the results (40 B: 32 are 5 x 256) fill their part of a buffer to the last byte and run one record over;
@@ -436,8 +436,8 @@ def check_search_points_filter(ctx, sdvl, orc, many, n):
 
 
 def test_search_points_filter_frame_table_over_the_staging_cap(ctx, sdvl, orc, many):
-    """sdvl_search_points_filter with 2101 table entries: depth_filter_kernel reads the frame table where the search left it, in
-    the work buffer.  Outcomes and counters exact, filter state within 1e-11 relative, as test_depth_filter_behind_the_search"""
+    """sdvl_search_points_filter with 2101 table entries: depth_filter_kernel (csrc/sdvl_depth_filter.hip) reads the frame table
+    where the search left it, in the work buffer.  Outcomes and counters exact, filter state within 1e-11 relative, as test_depth_filter_behind_the_search"""
     assert search_table_size(many["reqs"]) > SEARCH_TAB_CAP
     outcomes = check_search_points_filter(ctx, sdvl, orc, many, len(many["reqs"]))
     assert len(outcomes) >= 3, outcomes
@@ -451,7 +451,7 @@ def test_search_points_filter_states_that_fill_their_part(ctx, sdvl, orc, many, 
 
 
 def search_blocks(cur_of_request):
-    """the search's workgroups: runs of up to kWavesPerBlock consecutive requests of one current frame (csrc/sdvl_search.hip:1102-1109)"""
+    """the search's workgroups: runs of up to kWavesPerBlock consecutive requests of one current frame (sdvl_search_enqueue, csrc/sdvl_search.hip)"""
     blocks, i, n = [], 0, len(cur_of_request)
     while i < n:
         cnt = 1
@@ -466,7 +466,7 @@ def search_blocks(cur_of_request):
 def test_search_points_workgroups_of_every_run_length(ctx, sdvl, orc, synth, binned):
     """requests in runs of 1..9 of one current frame, alternating between two current frames: workgroups of 1..4 requests, runs
     split across workgroups.  Every frame from sdvl_detect_corners (binned): search_points_kernel<false, 1>; frames with
-    set_corners: <true, kWavesPerBlock> (csrc/sdvl_search.hip:947-956).  Results equal the oracle's and those of the same
+    set_corners: <true, kWavesPerBlock> (sdvl_search_launch_device, csrc/sdvl_search.hip).  Results equal the oracle's and those of the same
     requests in sorted order"""
     imgs = frames_of(synth, orc, TUM_CAM, 640, 480, [0, 4, 7])
     T = [trajectory_pose(orc, k) for k in (0, 4, 7)]
@@ -608,7 +608,7 @@ def patch_scene(orc, synth):
 
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 9, 8, 16, 17, 64, 65])
 def test_align_patches_workgroup_tails(ctx, orc, patch_scene, n):
-    """kWavesPerBlock patch jobs per workgroup (csrc/sdvl_search.hip:1389): a lone job, a partial, a full, one over and two full
+    """kWavesPerBlock patch jobs per workgroup (sdvl_align_patches, csrc/sdvl_search.hip): a lone job, a partial, a full, one over and two full
     workgroups plus one; each job on its own frame and pyramid level, bit-exact against the oracle.  Then the counts at which a part
     of the staged block or of the results is a whole number of 256-byte units, and one job more: 8 job records (32 B), 16 start
     points (16 B), 64 borders (100 B: 25 x 256)"""
