@@ -528,7 +528,8 @@ int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, co
  * push up and one copy back; blocking, like sdvl_depth_filter.  SDVL_ERR_INVALID (with a message) for null pointers, an unknown
  * format, a stride below width x bytes per sample, scale <= 0 with U16, edge_ratio < 0, min_valid outside 1 .. 9, c_begin > c_end or a
  * range outside the corner list, a level outside 0 .. SDVL_MAX_LEVELS - 1.  n_jobs == 0 or n_corners == 0: nothing to do, 0. */
-enum sdvl_depth_format { SDVL_DEPTH_F32 = 0, SDVL_DEPTH_U16 = 1 };
+enum sdvl_depth_format { SDVL_DEPTH_F32 = 0, SDVL_DEPTH_U16 = 1,
+                         SDVL_DEPTH_RIGHT8 = 2 /* no depth image: a stereo pair's right image, 8-bit gray (sdvl_stereo_depth); refused here */ };
 #define SDVL_DEPTH_SEED_OK 0
 #define SDVL_DEPTH_SEED_HOLE 1
 #define SDVL_DEPTH_SEED_FEW 2
@@ -567,6 +568,58 @@ int sdvl_depth_lookup(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int
  * not staged again; the caller leaves its contents alone meanwhile.  The copies live in buffers of their own, not in scratch a search uses. */
 int sdvl_depth_stage_begin(sdvl_ctx *ctx);
 int sdvl_depth_stage_end(sdvl_ctx *ctx);
+
+/* ---- input stage, stereo cameras: the depth of a keyframe's corners from a RECTIFIED right image -----------------------------------------
+ * The producer of sdvl_depth_seed's `z` / `status` contract for a rig without a depth sensor: a sparse matcher at the corners only, never
+ * a dense disparity image.  The rule below is stated by this project (tests/stereo_restatement.py is its specification), not pinned to the
+ * reference or to OpenCV.
+ * A job is a left frame (level 0 is read as it stands), a right image — 8-bit gray of the left frame's width and height, rows `stride`
+ * bytes apart, the same intrinsics, rectified so that rows correspond, the right camera `baseline` metres along the left camera's x
+ * axis — and a range of the corner list.  Corners are (x, y, level) in level coordinates as for sdvl_depth_seed.  Per corner:
+ *   window   s = 1 << level, (X, Y) = (x s, y s); the 9 x 9 samples at (X + i s, Y + j s), i, j in -4 .. 4, of level 0 of both images
+ *   range    d_lo = max_depth > 0 ? floor(fx baseline / max_depth) : 0;  d_hi = min(max_disparity, floor(fx baseline / min_depth),
+ *            X - 4 s): the right window at X - d lies inside the image for every d of the range
+ *   cost     S(d) = the sum of |L - R| over the 81 samples, an integer <= 20 655.  d0 is its argmin, ties to the smallest d.  Four
+ *            half-window costs come from the same absolute differences: sample columns 0 - 4, columns 4 - 8, rows 0 - 4, rows 4 - 8
+ *   status   the first that applies: OUTSIDE the left window leaves the image, or fewer than 3 disparities are in the range; NOMATCH
+ *            S(d0) > 81 max_sad, or d0 is an end of the range (no neighbour on one side); AMBIGUOUS 100 S(d0) > uniqueness S2 with
+ *            S2 = min S(d) over |d - d0| > 1 (no such d: not ambiguous); EDGE some half window's argmin (same tie rule) differs from d0
+ *            by more than 1 — FAST fires on occlusion edges, where the window straddles two depths; else OK
+ *   result   delta = 0.5 (S(d0 - 1) - S(d0 + 1)) / (S(d0 - 1) - 2 S(d0) + S(d0 + 1)) if the denominator is positive, else 0, in double;
+ *            out_disparity = d0 + delta, out_z = fx baseline / out_disparity; both 0 unless OK
+ * Fields of `p` that are 0 take the defaults: min_depth 0.3 m, no max_depth, max_disparity 192, max_sad 20 per sample, uniqueness 80;
+ * the baseline has none.  out_ok_per_job[j] = OK corners of job j.  Job ranges do not overlap; a corner no job names comes back NOMATCH.
+ * A right image in HBM (on_device) is read where it lies; one in host memory, pinned or pageable, is copied to HBM first (a keyframe's
+ * corners read its rows many times over) into the buffers that sdvl_depth_stage_begin / _end govern.  All jobs of a call take ONE launch
+ * (stereo_depth: one wave per corner, lane per disparity), one push up and one copy back; blocking.  SDVL_ERR_INVALID (with a message) for
+ * null pointers, a baseline that is not positive and finite, max_disparity > 511, uniqueness outside 1 .. 100, max_sad outside 1 .. 255,
+ * negative depths, a stride below the width, a level outside the left frame's pyramid, c_begin > c_end, a range outside the corner list,
+ * overlapping ranges, a left frame of another context, a lens (p->dist with d[0] != 0: rectified pairs only).  n_jobs == 0 or
+ * n_corners == 0: nothing to do, 0.  The status codes are 0 .. 4 like sdvl_depth_seed's: counters by status carry either. */
+#define SDVL_STEREO_OK 0
+#define SDVL_STEREO_NOMATCH 1
+#define SDVL_STEREO_AMBIGUOUS 2
+#define SDVL_STEREO_EDGE 3
+#define SDVL_STEREO_OUTSIDE 4
+#define SDVL_STEREO_MAX_DISPARITY 511
+typedef struct sdvl_stereo_job {
+  const sdvl_frame *left;
+  const void *right;
+  int32_t on_device;      /* `right` is a device pointer */
+  int32_t stride;         /* bytes between the right image's rows */
+  int32_t c_begin, c_end; /* range in xyl */
+} sdvl_stereo_job;
+
+typedef struct sdvl_stereo_params {
+  double baseline;              /* metres */
+  double min_depth, max_depth;  /* metres */
+  int32_t max_disparity, max_sad, uniqueness;
+  int32_t pad_;
+  const sdvl_distortion *dist;  /* the pair's lens, if the caller has one to declare: refused unless null or d[0] == 0 */
+} sdvl_stereo_params;
+
+int sdvl_stereo_depth(sdvl_ctx *ctx, int n_jobs, const sdvl_stereo_job *jobs, int n_corners, const int32_t *xyl, const sdvl_camera *cam,
+                      const sdvl_stereo_params *p, double *out_z, double *out_disparity, uint8_t *out_status, int32_t *out_ok_per_job);
 
 /* ---- the mapper's depth filter with a MEASURED depth (this project's rule; tests/depth_measure_restatement.py is its specification) -----
  * sdvl_depth_filter / sdvl_search_run_filter for a depth camera.  jobs[]: the depth image of the CURRENT frame of the requests

@@ -148,6 +148,23 @@ class DepthMeasureParams(C.Structure):
     _fields_ = [("rule", DepthSeedParams), ("noise_abs", C.c_double), ("noise_quad", C.c_double)]
 
 
+# sdvl_stereo_depth's status codes (0 .. 4, as depth seeding's) and the format of a right image in the depth image's slot
+STEREO_OK, STEREO_NOMATCH, STEREO_AMBIGUOUS, STEREO_EDGE, STEREO_OUTSIDE = 0, 1, 2, 3, 4
+SDVL_DEPTH_RIGHT8 = 2
+
+
+class StereoJob(C.Structure):
+    """sdvl_stereo_job: a left frame, the rectified right image of the pair and the range of the corner list they answer for"""
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("on_device", C.c_int32), ("stride", C.c_int32), ("c_begin", C.c_int32),
+                ("c_end", C.c_int32)]
+
+
+class StereoParams(C.Structure):
+    """sdvl_stereo_params: the baseline, and the rule — a field that is 0 takes its default (0.3 m, no upper limit, 192, 20, 80)"""
+    _fields_ = [("baseline", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double), ("max_disparity", C.c_int32),
+                ("max_sad", C.c_int32), ("uniqueness", C.c_int32), ("pad_", C.c_int32), ("dist", C.c_void_p)]
+
+
 class SynthView(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("u0", C.c_double), ("v0", C.c_double),
                 ("R", C.c_double * 9), ("t", C.c_double * 3), ("plane", C.c_double * 4),
@@ -183,7 +200,7 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_lookup", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_lookup", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_stereo_depth", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
@@ -786,6 +803,35 @@ class Context:
                                              C.addressof(d5) if d5 is not None else None, C.addressof(mp.rule), z.ctypes.data, status.ctypes.data,
                                              ok.ctypes.data))
         return z[:n], status[:n], ok[:len(jobs)]
+
+    def stereo_depth(self, jobs, xyl, cam, baseline, dist=None, **rule):
+        """sdvl_stereo_depth: the depth of corners from rectified stereo pairs.  jobs: (left Frame, right, c_begin, c_end) each, right a
+        numpy [height, width] uint8 image — host memory, padded rows allowed, copied to HBM by the call — or a StereoJob made by the caller
+        (device pointers, pinned memory).  xyl [n][3] level coordinates and level; cam a Camera; baseline in metres; dist (k1, k2, p1, p2,
+        k3) or None: a lens is refused; rule: min_depth, max_depth, max_disparity, max_sad, uniqueness (0: the default)
+        -> (z float64 [n], disparity float64 [n], status uint8 [n], ok per job int32)"""
+        keep, arr = [], (StereoJob * max(len(jobs), 1))()
+        for j, job in enumerate(jobs):
+            if isinstance(job, StereoJob):
+                arr[j] = job
+                continue
+            left, r = job[0], job[1]
+            assert r.dtype == np.uint8 and r.ndim == 2 and r.strides[1] == 1 and r.shape == (left.height, left.width)
+            keep.append(r)
+            arr[j] = StereoJob(left.h, r.ctypes.data, 0, r.strides[0], int(job[2]), int(job[3]))
+        d5 = Distortion((C.c_double * 5)(*[float(x) for x in dist])) if dist is not None else None
+        p = StereoParams(float(baseline), float(rule.pop("min_depth", 0.0)), float(rule.pop("max_depth", 0.0)), int(rule.pop("max_disparity", 0)),
+                         int(rule.pop("max_sad", 0)), int(rule.pop("uniqueness", 0)), 0, C.addressof(d5) if d5 is not None else None)
+        assert not rule, "unknown rule field %s" % list(rule)
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3)
+        n = len(xyl)
+        z, disparity, status = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8)
+        ok = np.zeros(max(len(jobs), 1), np.int32)
+        self.lib.sdvl_stereo_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        self._check(self.lib.sdvl_stereo_depth(self.h, len(jobs), C.addressof(arr), n, xyl.ctypes.data, C.addressof(cam), C.addressof(p),
+                                               z.ctypes.data, disparity.ctypes.data, status.ctypes.data, ok.ctypes.data))
+        del keep
+        return z[:n], disparity[:n], status[:n], ok[:len(jobs)]
 
     def depth_lookup(self, jobs, width, height, px, levels, cam, dist=None, **rule):
         """sdvl_depth_lookup: depth_seed's rule at level-0 positions px [n][2] (sub-pixel) with the window stride of levels [n]; jobs, cam,

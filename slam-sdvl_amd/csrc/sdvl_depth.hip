@@ -82,6 +82,7 @@ int sdvl_depth_jobs_check(sdvl_ctx *ctx, const char *who, int n_jobs, const sdvl
   for (int j = 0; j < n_jobs; j++) {
     const sdvl_depth_job &jb = jobs[j];
     SDVL_REQUIRE(ctx, jb.depth != nullptr, w + ": null depth image");
+    SDVL_REQUIRE(ctx, jb.format != SDVL_DEPTH_RIGHT8, w + ": unknown depth format: a right image (SDVL_DEPTH_RIGHT8) is no depth image, sdvl_stereo_depth reads it");
     SDVL_REQUIRE(ctx, jb.format == SDVL_DEPTH_F32 || jb.format == SDVL_DEPTH_U16, w + ": unknown depth format");
     const long long bps = jb.format == SDVL_DEPTH_U16 ? 2 : 4;
     SDVL_REQUIRE(ctx, static_cast<long long>(jb.stride) >= width * bps, w + ": stride smaller than width x bytes per sample");
@@ -118,29 +119,36 @@ int sdvl_depth_jobs_resolve(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *job
       continue;
     }
     (void)hipGetLastError();  // an unregistered pointer is not an error here
-    const size_t row = static_cast<size_t>(width) * (jb.format == SDVL_DEPTH_U16 ? 2 : 4), bytes = row * height;
-    int hit = -1, spare = -1;
-    for (size_t k = 0; k < ctx->depth_pool.size(); k++) {
-      const sdvl_ctx::DepthStaged &e = ctx->depth_pool[k];
-      if (e.live && e.host == jb.depth && e.stride == jb.stride && e.format == jb.format && e.width == width && e.height == height) hit = static_cast<int>(k);
-      if (!e.live && e.bytes >= bytes && (spare < 0 || e.bytes < ctx->depth_pool[spare].bytes)) spare = static_cast<int>(k);
-    }
-    if (hit < 0) {
-      if (spare < 0) {
-        void *d = nullptr;
-        SDVL_HIP_CHECK(ctx, hipMalloc(&d, bytes));
-        ctx->depth_pool.push_back(sdvl_ctx::DepthStaged{d, bytes, nullptr, 0, 0, 0, 0, 0});
-        spare = static_cast<int>(ctx->depth_pool.size()) - 1;
-      }
-      sdvl_ctx::DepthStaged &e = ctx->depth_pool[spare];
-      SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(e.d, row, jb.depth, jb.stride, row, height, hipMemcpyHostToDevice, ctx->stream));
-      e.host = jb.depth; e.stride = jb.stride; e.format = jb.format; e.width = width; e.height = height;
-      e.live = 1;
-      hit = spare;
-    }
-    out[j].img = static_cast<const uint8_t *>(ctx->depth_pool[hit].d);
+    const size_t row = static_cast<size_t>(width) * (jb.format == SDVL_DEPTH_U16 ? 2 : 4);
+    const int rc = sdvl_depth_stage_image(ctx, jb.depth, jb.stride, jb.format, width, height, row, &out[j].img);
+    if (rc) return rc;
     out[j].stride = static_cast<long long>(row);
   }
+  return SDVL_OK;
+}
+
+int sdvl_depth_stage_image(sdvl_ctx *ctx, const void *host, long long stride, int format, int width, int height, size_t row, const uint8_t **staged) {
+  const size_t bytes = row * height;
+  int hit = -1, spare = -1;
+  for (size_t k = 0; k < ctx->depth_pool.size(); k++) {
+    const sdvl_ctx::DepthStaged &e = ctx->depth_pool[k];
+    if (e.live && e.host == host && e.stride == stride && e.format == format && e.width == width && e.height == height) hit = static_cast<int>(k);
+    if (!e.live && e.bytes >= bytes && (spare < 0 || e.bytes < ctx->depth_pool[spare].bytes)) spare = static_cast<int>(k);
+  }
+  if (hit < 0) {
+    if (spare < 0) {
+      void *d = nullptr;
+      SDVL_HIP_CHECK(ctx, hipMalloc(&d, bytes));
+      ctx->depth_pool.push_back(sdvl_ctx::DepthStaged{d, bytes, nullptr, 0, 0, 0, 0, 0});
+      spare = static_cast<int>(ctx->depth_pool.size()) - 1;
+    }
+    sdvl_ctx::DepthStaged &e = ctx->depth_pool[spare];
+    SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(e.d, row, host, stride, row, height, hipMemcpyHostToDevice, ctx->stream));
+    e.host = host; e.stride = stride; e.format = format; e.width = width; e.height = height;
+    e.live = 1;
+    hit = spare;
+  }
+  *staged = static_cast<const uint8_t *>(ctx->depth_pool[hit].d);
   return SDVL_OK;
 }
 

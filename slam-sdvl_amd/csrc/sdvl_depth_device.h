@@ -101,6 +101,9 @@ int sdvl_depth_jobs_check(sdvl_ctx *ctx, const char *who, int n_jobs, const sdvl
 // where each image is read: HBM and pinned host memory in place; a pageable image as a tight copy in a buffer the context keeps for depth
 // images alone (queued on the stream).  Between sdvl_depth_stage_begin and _end an image staged once is not staged again
 int sdvl_depth_jobs_resolve(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, sdvl_depth::DepthJobDev *out);
+// the copy itself: `height` rows of `row` bytes, `stride` apart at `host`, into one of those buffers (or the one that holds it already);
+// sdvl_stereo_depth stages a right image in host memory through it (format SDVL_DEPTH_RIGHT8)
+int sdvl_depth_stage_image(sdvl_ctx *ctx, const void *host, long long stride, int format, int width, int height, size_t row, const uint8_t **staged);
 sdvl_depth::DepthLens sdvl_depth_lens_of(const sdvl_camera *cam, const sdvl_distortion *dist);
 
 #endif  // SDVL_DEPTH_DEVICE_H_

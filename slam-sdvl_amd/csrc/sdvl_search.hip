@@ -80,21 +80,6 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   return v;
 }
 
-// minimum over the 64 lanes (all active) in every lane: DPP steps inside the 16-lane rows, two row broadcasts, one readlane
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  const auto step = [](uint32_t x, auto ctrl, auto rows) {
-    const uint32_t o = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(-1, static_cast<int>(x), decltype(ctrl)::value, decltype(rows)::value, 0xf, false));
-    return o < x ? o : x;
-  };
-  v = step(v, std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});  // row_shr:1
-  v = step(v, std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});  // row_shr:2
-  v = step(v, std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});  // row_shr:4
-  v = step(v, std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});  // row_shr:8: lane 15 of a row holds the row's minimum
-  v = step(v, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});  // row_bcast:15 into rows 1 and 3
-  v = step(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});  // row_bcast:31 into rows 2 and 3
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
-}
-
 // Matcher::AlignPatch, matcher.cc:359-445.  border/patch in this wave's LDS.  Returns converged; *u,*v updated.
 __device__ __forceinline__ float wave_sum_f32(float v) {
 #pragma unroll

@@ -385,23 +385,35 @@ void SDVLBatch::SeedKeyframesFromDepth(Step &s, vector<const double *> *z, vecto
   bool any = false;
   for (size_t k = 0; k < K; k++) any = any || trk_[s.kf_owner[k]]->depth_seeding_;
   if (!any) return;
+  // (a stereo tracker's second image is the pair's right image, SDVL::SetStereoSeeding: the same jobs with sdvl_stereo_depth as the producer)
   vector<sdvl_depth_job> jobs;
+  vector<sdvl_stereo_job> pairs;
   vector<size_t> whose;
   vector<int32_t> xyl;
   const sdvl_depth_seed_params *rule = nullptr;
+  const sdvl_stereo_params *stereo = nullptr;
   for (size_t k = 0; k < K; k++) {
     SDVL &t = *trk_[s.kf_owner[k]];
     if (!t.depth_seeding_) continue;
     const DepthImage *d = DepthOf(s.kf_owner[k]);
     if (!d) continue;  // (counted below)
-    if (rule && std::memcmp(rule, &t.depth_rule_, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
-    rule = &t.depth_rule_;
+    if (t.stereo_seeding_) {
+      if (rule || (stereo && std::memcmp(stereo, &t.stereo_rule_, sizeof(*stereo)) != 0))
+        throw std::runtime_error("SDVLBatch: the trackers of a batch share the stereo baseline and rule");
+      if (d->format != DEPTH_RIGHT8) throw std::runtime_error("SDVLBatch: a tracker that seeds from a stereo pair takes a right image (DEPTH_RIGHT8), not a depth image");
+      stereo = &t.stereo_rule_;
+    } else {
+      if (stereo || (rule && std::memcmp(rule, &t.depth_rule_, sizeof(*rule)) != 0))
+        throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
+      rule = &t.depth_rule_;
+    }
     const int begin = static_cast<int>(xyl.size() / 3), n = s.kfs[k]->NumFiltered();
     for (int c = 0; c < n; c++) {
       const Vector3i corner = s.kfs[k]->FilteredCorner(c);
       xyl.insert(xyl.end(), {corner(0), corner(1), corner(2)});
     }
     jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, begin, begin + n});
+    pairs.push_back(sdvl_stereo_job{s.kfs[k]->device(), d->data, d->on_device ? 1 : 0, d->step, begin, begin + n});
     whose.push_back(k);
   }
   const int n_corners = static_cast<int>(xyl.size() / 3);
@@ -412,9 +424,18 @@ void SDVLBatch::SeedKeyframesFromDepth(Step &s, vector<const double *> *z, vecto
     const Camera &camera = *trk_[0]->camera_;
     const sdvl_camera cam = camera.abi();
     const sdvl_distortion dist = camera.distortion();
-    dev_->Check(sdvl_depth_seed(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), s.kfs[whose[0]]->GetWidth(), s.kfs[whose[0]]->GetHeight(), n_corners,
-                                xyl.data(), &cam, camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
-                "sdvl_depth_seed");
+    if (stereo) {
+      sdvl_stereo_params sp = *stereo;
+      sp.dist = camera.HasDistortion() ? &dist : nullptr;  // (refused: rectified pairs only)
+      stereo_disparity_.assign(n_corners, 0.0);
+      dev_->Check(sdvl_stereo_depth(dev_->ctx(), static_cast<int>(pairs.size()), pairs.data(), n_corners, xyl.data(), &cam, &sp, depth_z_.data(),
+                                    stereo_disparity_.data(), depth_status_.data(), ok.data()),
+                  "sdvl_stereo_depth");
+    } else {
+      dev_->Check(sdvl_depth_seed(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), s.kfs[whose[0]]->GetWidth(), s.kfs[whose[0]]->GetHeight(), n_corners,
+                                  xyl.data(), &cam, camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
+                  "sdvl_depth_seed");
+    }
   }
   for (size_t j = 0; j < jobs.size(); j++) {
     (*z)[whose[j]] = depth_z_.data() + jobs[j].c_begin;

@@ -17,7 +17,8 @@ class SDVLBatch {
   // imgs[i] feeds tracker i; stats[i] receives its FrameStats
   void HandleFrames(const std::vector<Image> &imgs, FrameStats *stats);
   // the same with the frames' registered depth images for the trackers that seed from depth (SDVL::SetDepthSeeding): depths is empty or
-  // has one entry per tracker, and single entries may be empty.  A depth image is read inside the step's ONE sdvl_depth_seed call only
+  // has one entry per tracker, and single entries may be empty (for a tracker that seeds from a stereo pair, SDVL::SetStereoSeeding, the
+  // entry is the pair's right image, DEPTH_RIGHT8, read inside the step's ONE sdvl_stereo_depth call).  A depth image is read inside the step's ONE sdvl_depth_seed call only
   // (FinishKeyframes); nothing is copied or kept, and the look-ahead does not need it.
   void HandleFrames(const std::vector<Image> &imgs, const std::vector<DepthImage> &depths, FrameStats *stats);
   // Round 4: a caller that already holds the images of the NEXT step (a sequence from disk, frames resident in HBM) names them before
@@ -72,6 +73,7 @@ class SDVLBatch {
   const DepthImage *DepthOf(int i) const;                  // tracker i's, null: none
   std::vector<double> depth_z_;                            // sdvl_depth_seed's results for the step's keyframes
   std::vector<uint8_t> depth_status_;
+  std::vector<double> stereo_disparity_;                   // sdvl_stereo_depth's disparities (stereo trackers: z and status lie in the two above)
   // ---- batch_tables.cc: the device-resident tracking tables.  The set and the rows on their way to it; besides the table functions
   // the tabled step (batch_tracked.cc) uses them, and batch.cc where it releases the set, appends a keyframe's seeds (FinishKeyframes)
   // and lets the mapper's depth filter patch the rows (RunMappers)

@@ -293,6 +293,15 @@ int sdvlh_batch_depth_stats(void *bp, int i, long long *out8) {
   out8[7] = s.no_depth;
   return 0;
 }
+// ---- stereo cameras (SDVL::SetStereoSeeding, TrackerGroup::SetStereo): the pointers the *_depth step calls take beside the images are
+// the pairs' rectified right images (8-bit gray, dense rows); the rule's fields as sdvl_stereo_params (0: the default)
+int sdvlh_batch_set_stereo(void *bp, int on, double baseline, double min_depth, double max_depth, int max_disparity, int max_sad, int uniqueness) {
+  if (!bp) return -1;
+  return Guarded([&] { AsGroup(bp)->SetStereo(on != 0, baseline, sdvl_stereo_params{0.0, min_depth, max_depth, max_disparity, max_sad, uniqueness, 0, nullptr}); });
+}
+// tracker i's stereo seeding so far: out8 = keyframes seeded, seeds, corners by status (OK, NOMATCH, AMBIGUOUS, EDGE, OUTSIDE), keyframes
+// or first frames that came without a right image — the counters of sdvlh_batch_depth_stats under the stereo producer's names
+int sdvlh_batch_stereo_stats(void *bp, int i, long long *out8) { return sdvlh_batch_depth_stats(bp, i, out8); }
 // Depth cameras inside the mappers of the batch (SDVL::SetDepthMapping): needs sdvlh_batch_set_depth and the reference's mapper; the
 // trackers share the noise parameters (0: the defaults)
 int sdvlh_batch_set_depth_mapping(void *bp, int on, double noise_abs, double noise_quad) {

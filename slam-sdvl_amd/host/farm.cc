@@ -62,7 +62,7 @@ void TrackerGroup::Step(Frames where, const void *const *imgs, int stride, const
   for (size_t i = 0; i < trackers_.size(); i++) out[i] = FrameStats();
   std::vector<DepthImage> d;
   if (depths) {
-    const int bps = depth_format_ == DEPTH_U16 ? 2 : 4;
+    const int bps = depth_format_ == DEPTH_RIGHT8 ? 1 : depth_format_ == DEPTH_U16 ? 2 : 4;
     for (size_t i = 0; i < trackers_.size(); i++)
       d.push_back(depths[i] ? DepthImage::Wrap(depths[i], w_, h_, w_ * bps, depth_format_, depth_scale_, where != Frames::kHost) : DepthImage());
   }
@@ -75,6 +75,16 @@ void TrackerGroup::SetDepth(bool on, int format, double scale, const sdvl_depth_
   for (auto &t : trackers_) t->SetDepthSeeding(on, rule);
   depth_format_ = format;
   depth_scale_ = scale;
+}
+
+void TrackerGroup::SetStereo(bool on, double baseline, const sdvl_stereo_params &rule) {
+  for (auto &t : trackers_) t->SetStereoSeeding(on, baseline, rule);
+  if (on) {
+    depth_format_ = DEPTH_RIGHT8;
+    depth_scale_ = 1.0;
+  } else if (depth_format_ == DEPTH_RIGHT8) {
+    depth_format_ = DEPTH_F32;
+  }
 }
 
 void TrackerGroup::SetNextImages(const void *const *dev_imgs, int stride) {

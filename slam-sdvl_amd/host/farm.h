@@ -62,6 +62,9 @@ class TrackerGroup {
   // `format` (DEPTH_F32 / DEPTH_U16) with `scale` metres per unit.  Throws what SDVL::SetDepthSeeding throws, and on an unknown format
   // or a scale <= 0 with DEPTH_U16.
   void SetDepth(bool on, int format, double scale, const sdvl_depth_seed_params &rule);
+  // Stereo cameras (SDVL::SetStereoSeeding for every tracker): the second images handed to Step are the pairs' rectified right images,
+  // 8-bit gray with dense rows.  Throws what SDVL::SetStereoSeeding throws.
+  void SetStereo(bool on, double baseline, const sdvl_stereo_params &rule);
 
   Device *device() const { return dev_; }
   int size() const { return static_cast<int>(trackers_.size()); }

@@ -256,6 +256,18 @@ class SDVL {
   // question — and with a map that is neither PlaneMap nor MapperMap; std::invalid_argument for a rule sdvl_depth_seed would refuse.
   void SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule = sdvl_depth_seed_params{0.0, 0.0, 0.0, 0, 0});
   bool DepthSeeding() const { return depth_seeding_; }
+  // Stereo cameras (an addition): depth seeding's keyframe path with another producer.  The second image handed over with a frame is the
+  // pair's rectified RIGHT image (a DepthImage of format DEPTH_RIGHT8: 8-bit gray, the camera image's size and intrinsics, the right camera
+  // `baseline` metres along the left camera's x axis); the filtered corners of the step's keyframes are matched in it by ONE
+  // sdvl_stereo_depth call, and z / status go where sdvl_depth_seed's go: every keyframe of a plane map, the bootstrap keyframe of the
+  // reference's mapper.  `rule`: sdvl_stereo_params, zero fields take the defaults (its baseline and dist are ignored); the trackers of
+  // one batch share baseline and rule.  First frames as with SetDepthSeeding: one without a right image, or with fewer OK corners than
+  // SDVL.min_init_corners, is not kept.  Throws std::runtime_error together with the two-frame initialisation, with depth seeding from a
+  // depth image, with depth mapping or depth edges (both look depths up at found pixels, which a matcher at the corners does not give),
+  // on a camera with a lens (rectified pairs only) and with a map that is neither PlaneMap nor MapperMap; std::invalid_argument for a
+  // baseline or a rule sdvl_stereo_depth would refuse.
+  void SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &rule = sdvl_stereo_params{0.0, 0.0, 0.0, 0, 0, 0, 0, nullptr});
+  bool StereoSeeding() const { return stereo_seeding_; }
   // Depth cameras inside the reference's mapper (an addition, MapperMap::SetDepthMapping): the depth image of every tracked frame feeds
   // the candidates' depth filter, and a new keyframe's corners become fixed points at their measured depth.  noise: the sensor's depth
   // noise tau = noise_abs + noise_quad z^2 (0: 0.001 m and 0.0015 per metre); the trackers of a batch share it.  Needs SetDepthSeeding and
@@ -281,7 +293,7 @@ class SDVL {
   void Stop() { map_->Stop(); }
   void Mapping();
   bool HandleFrame(const Image &img);
-  bool HandleFrame(const Image &img, const DepthImage &depth);  // SetDepthSeeding: the frame's registered depth image (empty: none)
+  bool HandleFrame(const Image &img, const DepthImage &depth);  // SetDepthSeeding: the frame's registered depth image; SetStereoSeeding: the pair's right image (empty: none)
   // Round 5, an addition for callers that READ a sequence (main.cc's Video.type 1: images from disk are there before they are needed):
   // name the image the NEXT HandleFrame call will be given (a device image, e.g. what Camera::UndistortImage returns, kept alive and
   // unchanged until that call).  Its pyramid and corner detection are queued behind the coming call's chain and run while the host
@@ -310,6 +322,8 @@ class SDVL {
   bool depth_seeding_ = false, first_frame_waiting_ = false;
   const Frame *step_frame_ = nullptr;  // the frame of the step in flight (BeginFrame): whose depth image the step's is
   sdvl_depth_seed_params depth_rule_ = {0.0, 0.0, 0.0, 0, 0};
+  bool stereo_seeding_ = false;  // depth_seeding_ with sdvl_stereo_depth as the producer (SetStereoSeeding)
+  sdvl_stereo_params stereo_rule_ = {0.0, 0.0, 0.0, 0, 0, 0, 0, nullptr};
   bool InitFirstFrame(FrameStats &st);                       // sdvl.cc:132-148 (two-frame initialisation)
   void SecondFrameDone(bool initialised, FrameStats &st);    // sdvl.cc:154-176 behind HomographyInit::InitSecondFrame
   bool two_frame_init_ = false, init_failed_ = false;

@@ -494,13 +494,36 @@ void SDVL::SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule) {
   if (on && !dynamic_cast<PlaneMap *>(map_)) throw std::runtime_error("SDVL::SetDepthSeeding needs a PlaneMap or the reference's mapper (MapperMap)");
   if (on && (rule.edge_ratio < 0.0 || rule.min_valid < 0 || rule.min_valid > 9))
     throw std::invalid_argument("SDVL::SetDepthSeeding: edge_ratio is negative or min_valid lies outside 1 .. 9");
+  if (on && stereo_seeding_) throw std::runtime_error("SDVL::SetDepthSeeding: the tracker seeds from a stereo pair (SetStereoSeeding); a frame brings one second image");
   depth_seeding_ = on;
   depth_rule_ = rule;
+  if (!on) stereo_seeding_ = false;
+}
+
+void SDVL::SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &rule) {
+  if (on && two_frame_init_) throw std::runtime_error("SDVL::SetStereoSeeding: the tracker takes the two-frame initialisation; the two answer the same question");
+  if (on && !dynamic_cast<PlaneMap *>(map_)) throw std::runtime_error("SDVL::SetStereoSeeding needs a PlaneMap or the reference's mapper (MapperMap)");
+  if (on && depth_seeding_ && !stereo_seeding_)
+    throw std::runtime_error("SDVL::SetStereoSeeding: the tracker seeds from a depth image (SetDepthSeeding); a frame brings one second image");
+  if (MapperMap *m = dynamic_cast<MapperMap *>(map_))
+    if (on && (m->DepthMapping() || m->DepthBundleOn()))
+      throw std::runtime_error("SDVL::SetStereoSeeding: depth mapping and depth edges look depths up at found pixels, which a matcher at the corners does not give");
+  if (on && camera_->HasDistortion()) throw std::runtime_error("SDVL::SetStereoSeeding: the camera has a lens; rectified pairs only");
+  if (on && !(baseline > 0.0 && std::isfinite(baseline))) throw std::invalid_argument("SDVL::SetStereoSeeding: the baseline is not a positive finite number");
+  if (on && (rule.max_disparity < 0 || rule.max_disparity > SDVL_STEREO_MAX_DISPARITY || rule.uniqueness < 0 || rule.uniqueness > 100 || rule.max_sad < 0 ||
+             rule.max_sad > 255 || !(rule.min_depth >= 0.0 && std::isfinite(rule.min_depth)) || !(rule.max_depth >= 0.0 && std::isfinite(rule.max_depth))))
+    throw std::invalid_argument("SDVL::SetStereoSeeding: max_disparity above 511, uniqueness outside 1 .. 100, max_sad outside 1 .. 255 or a negative depth");
+  depth_seeding_ = on;
+  stereo_seeding_ = on;
+  stereo_rule_ = rule;
+  stereo_rule_.baseline = baseline;
+  stereo_rule_.dist = nullptr;
 }
 
 void SDVL::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
   MapperMap *m = AsMapperMap(map_);
   if (on && !m) throw std::runtime_error("SDVL::SetDepthMapping needs the reference's mapper (MapperMap)");
+  if (on && stereo_seeding_) throw std::runtime_error("SDVL::SetDepthMapping: the tracker seeds from a stereo pair (SetStereoSeeding), which gives no depth at a found pixel");
   if (on && !depth_seeding_) throw std::runtime_error("SDVL::SetDepthMapping needs depth seeding (SetDepthSeeding): the bootstrap keyframe is seeded from depth too");
   if (m) m->SetDepthMapping(on, noise_abs, noise_quad);
 }
@@ -508,6 +531,7 @@ void SDVL::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
 void SDVL::SetDepthBundle(bool on, double bf) {
   MapperMap *m = dynamic_cast<MapperMap *>(map_);
   if (on && !m) throw std::runtime_error("SDVL::SetDepthBundle needs the reference's mapper (MapperMap)");
+  if (on && stereo_seeding_) throw std::runtime_error("SDVL::SetDepthBundle: the tracker seeds from a stereo pair (SetStereoSeeding), which gives no depth at a found pixel");
   if (on && !depth_seeding_) throw std::runtime_error("SDVL::SetDepthBundle needs depth seeding (SetDepthSeeding): without it no observation carries a depth");
   if (m) m->SetDepthBundle(on, bf);
 }

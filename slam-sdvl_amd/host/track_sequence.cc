@@ -17,7 +17,11 @@
 //                                                                frame's depth feeds the candidates' filter, new keyframes' corners become fixed points; beside --depth only
 //   track_sequence --list frames.txt --depth-list depth.txt --depth-scale S   the same from disk: one 16-bit binary PGM (P5, maxval above 255; netpbm's samples are
 //                                                                big-endian and are swapped here) per frame, S metres per unit (TUM: 0.0002)
-//   track_sequence ... --depth --depth-bundle [--depth-bf X]   depth edges in the local bundle adjustment (SDVL::SetDepthBundle; implies --bundle): X in
+//   track_sequence --synthetic N --scene shelf --stereo --baseline B   a stereo camera: every frame comes with the rendered right image — the right camera's centre is the
+//                                                                left one's plus B metres along the left camera's x axis, the same orientation — and the keyframes' points
+//                                                                are seeded from the pair (SDVL::SetStereoSeeding) — no plane; a --plane is ignored
+//   track_sequence --list frames.txt --right-list right.txt --baseline B   the same from disk: one 8-bit binary PGM, the rectified right image, per frame
+//   track_sequence ... --depth --depth-bundle [--depth-bf X]  depth edges in the local bundle adjustment (SDVL::SetDepthBundle; implies --bundle): X in
 //                                                                pixel x metres, default 1 / noise_quad of the depth mapping = 666.7
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
 //   round 5 (bench.py's latency legs):  [--texture plane|camera]  [--trackers N]  N cameras = N host threads, each with its own Device
@@ -114,7 +118,8 @@ int RawFormatByName(const std::string &name) {
 }
 
 const char kUsage[] =
-    "track_sequence --synthetic N [--seed S] [--scene NAME [--depth]] | --list frames.txt [--raw-format NAME] [--depth-list depth.txt --depth-scale S]\n"
+    "track_sequence --synthetic N [--seed S] [--scene NAME [--depth | --stereo --baseline B]] |\n"
+    "               --list frames.txt [--raw-format NAME] [--depth-list depth.txt --depth-scale S | --right-list right.txt --baseline B]\n"
     "  --list: one binary PGM (P5, 8 bit) or PPM (P6, 8 bit RGB) path per line\n"
     "  --raw-format NAME: the P5 files are raw camera frames, converted to gray on the device:\n"
     "      bayer_rggb | bayer_grbg | bayer_gbrg | bayer_bggr   a Bayer mosaic, named by the 2x2 tile at its top-left corner\n"
@@ -124,6 +129,10 @@ const char kUsage[] =
     "  --depth: with --synthetic N --scene NAME, the keyframes' points are seeded from the renderer's registered depth image (no plane)\n"
     "  --depth-bundle [--depth-bf X]: with --depth, observations that carry a measured depth are depth edges of the bundle adjustment (implies --bundle)\n"
     "  --depth-list FILE --depth-scale S: one 16-bit P5 depth image (big-endian samples, S metres per unit) per frame of --list\n"
+    "  --stereo --baseline B: with --synthetic N --scene NAME, a stereo camera: every frame comes with the rendered right image (the right camera's\n"
+    "      centre is the left one's plus B metres along the left camera's x axis, the same orientation) and the keyframes' points are seeded from the\n"
+    "      pair (no plane, no lens)\n"
+    "  --right-list FILE --baseline B: one 8-bit P5 rectified right image per frame of --list\n"
     "  common: [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle]\n"
     "          [--init plane|two-frame] [--trackers N] [--batch] [--lookahead] [--prerender] [--pageable] [--set SDVL.key value]\n"
     "          [--quiet] [--json] [--profile]\n";
@@ -152,6 +161,9 @@ int main(int argc, char **argv) {
   double depth_bf = 0.0;
   std::string depth_list;
   double depth_scale = 0.0;
+  bool stereo = false;
+  double baseline = 0.0;
+  std::string right_list;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
   unsigned texture = SDVL_TEXTURE_PLANE_NOISE;
   for (int i = 1; i < argc; i++) {
@@ -173,6 +185,9 @@ int main(int argc, char **argv) {
     else if (a == "--depth-bf") { need(1); depth_bf = std::atof(argv[++i]); }
     else if (a == "--depth-list") { need(1); depth_list = argv[++i]; depth = true; }
     else if (a == "--depth-scale") { need(1); depth_scale = std::atof(argv[++i]); }
+    else if (a == "--stereo") stereo = true;
+    else if (a == "--baseline") { need(1); baseline = std::atof(argv[++i]); }
+    else if (a == "--right-list") { need(1); right_list = argv[++i]; stereo = true; }
     else if (a == "--mapper") mapper = true;
     else if (a == "--bundle") { bundle = true; mapper = true; }  // local bundle adjustment of every new keyframe (SDVL::SetBundleAdjustment; implies --mapper)
     else if (a == "--init") { need(1); const std::string t = argv[++i]; if (t == "two-frame") { two_frame = true; mapper = true; } else if (t != "plane") { std::cerr << "unknown --init " << t << std::endl; return 2; } }
@@ -208,6 +223,15 @@ int main(int argc, char **argv) {
     if (batch || prerender || n_trackers > 1) { std::cerr << "--depth runs one camera on frames made inside the loop: not with --batch, --trackers or --prerender" << std::endl; return 2; }
     if (plane_given) std::cerr << "note: --plane is ignored, the keyframes' points are seeded from depth" << std::endl;
   }
+  if (stereo) {  // what SDVL::SetStereoSeeding would throw, said before any device is touched
+    if (right_list.empty() && !use_scene) { std::cerr << "--stereo tracks on the rendered right image: give --synthetic N --scene NAME, or --right-list FILE with --list" << std::endl; return 2; }
+    if (!right_list.empty() && list.empty()) { std::cerr << "--right-list goes with --list" << std::endl; return 2; }
+    if (!(baseline > 0.0) || baseline > 1e300) { std::cerr << "--stereo and --right-list need --baseline B (metres, above 0)" << std::endl; return 2; }
+    if (depth) { std::cerr << "--stereo and --depth / --depth-list both fill the frame's second image: give one" << std::endl; return 2; }
+    if (two_frame) { std::cerr << "--stereo and --init two-frame answer the same question: give one" << std::endl; return 2; }
+    if (batch || prerender || n_trackers > 1) { std::cerr << "--stereo runs one camera on frames made inside the loop: not with --batch, --trackers or --prerender" << std::endl; return 2; }
+    if (plane_given) std::cerr << "note: --plane is ignored, the keyframes' points are seeded from the stereo pair" << std::endl;
+  }
 
   // main.cc:60-75: configuration file, then the TUM overrides the reference's config_tum_f1.cfg carries
   Config &c = Config::GetInstance();
@@ -240,6 +264,14 @@ int main(int argc, char **argv) {
       if (!line.empty() && line[0] != '#') depth_files.push_back(line);
     if (depth_files.size() != files.size()) { std::cerr << depth_list << " names " << depth_files.size() << " depth images for " << files.size() << " frames" << std::endl; return 2; }
   }
+  std::vector<std::string> right_files;
+  if (!right_list.empty()) {
+    std::ifstream lf(right_list);
+    for (std::string line; std::getline(lf, line);)
+      if (!line.empty() && line[0] != '#') right_files.push_back(line);
+    if (right_files.size() != files.size()) { std::cerr << right_list << " names " << right_files.size() << " right images for " << files.size() << " frames" << std::endl; return 2; }
+  }
+  if (stereo && dist[0] != 0.0) { std::cerr << "--stereo takes rectified pairs: not with a lens (--dist, or the configuration file's Camera.d1)" << std::endl; return 2; }
   const int n_frames = n_synth > 0 ? n_synth : static_cast<int>(files.size());
 
   const double tw[6] = {0.004, 0.002, 0.001, 0.0008, -0.0012, 0.0005};
@@ -334,6 +366,8 @@ int main(int argc, char **argv) {
         if (depth) sdvl.SetDepthSeeding(true);
         if (depth_mapping) sdvl.SetDepthMapping(true);
         if (depth_bundle) sdvl.SetDepthBundle(true, depth_bf);
+        if (stereo) sdvl.SetStereoSeeding(true, baseline);
+        std::vector<uint8_t> right_px(stereo ? frame_bytes : 0);
         std::vector<float> depth_f32(depth && depth_list.empty() ? frame_bytes : 0);
         std::vector<uint16_t> depth_u16;
         std::vector<uint8_t> px(pool ? 0 : frame_bytes);
@@ -393,6 +427,19 @@ int main(int argc, char **argv) {
               return;
             }
             dimg = DepthImage::Wrap(depth_u16.data(), W, H, W * 2, DEPTH_U16, depth_scale, false);
+          } else if (stereo) {
+            if (right_list.empty()) {  // the same scene from the right camera: t_right = t_left - (B, 0, 0)
+              sdvl_synth_scene sc = scene_of(k);
+              sc.t[0] -= baseline;
+              sdvl_synth_render_scene_host(&sc, W, H, right_px.data(), W, nullptr, nullptr);
+            } else {
+              int w = 0, h = 0, fmt = PIX_GRAY8;
+              if (!ReadPNM(right_files[k], &w, &h, &right_px, &fmt) || fmt != PIX_GRAY8 || w != W || h != H) {
+                me.err = "cannot read " + right_files[k] + " as an 8-bit binary PGM of the configured size";
+                return;
+              }
+            }
+            dimg = DepthImage::Wrap(right_px.data(), W, H, W, DEPTH_RIGHT8, 1.0, false);
           }
           const auto t0 = std::chrono::steady_clock::now();
           sdvl.HandleFrame(imgu, dimg);                           // main.cc:136-138
@@ -404,7 +451,7 @@ int main(int argc, char **argv) {
             std::printf("%d %d %d %d %d %d  %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", k, st.state, st.quality, st.matches, st.attempts, st.inliers,
                         st.pose[0], st.pose[1], st.pose[2], st.pose[3], st.pose[4], st.pose[5], st.pose[6]);
         }
-        if (depth) me.depth = dynamic_cast<PlaneMap *>(map.get())->GetDepthStats();
+        if (depth || stereo) me.depth = dynamic_cast<PlaneMap *>(map.get())->GetDepthStats();
         if (depth_mapping) me.depth_map = dynamic_cast<MapperMap *>(map.get())->GetDepthMapStats();
         if (depth_bundle) me.depth_bundle = dynamic_cast<MapperMap *>(map.get())->GetDepthBundleStats();
         if (profile && id == 0) {
@@ -534,6 +581,11 @@ int main(int argc, char **argv) {
       const PlaneMap::DepthStats &d = per[0].depth;
       std::fprintf(stderr, "depth seeding: %ld keyframes, %ld seeds; corners OK %ld HOLE %ld FEW %ld EDGE %ld OUTSIDE %ld; %ld frames without depth\n", d.keyframes, d.seeds,
                    d.by_status[0], d.by_status[1], d.by_status[2], d.by_status[3], d.by_status[4], d.no_depth);
+    }
+    if (stereo) {
+      const PlaneMap::DepthStats &d = per[0].depth;
+      std::fprintf(stderr, "stereo seeding: %ld keyframes, %ld seeds; corners OK %ld NOMATCH %ld AMBIGUOUS %ld EDGE %ld OUTSIDE %ld; %ld frames without a right image\n",
+                   d.keyframes, d.seeds, d.by_status[0], d.by_status[1], d.by_status[2], d.by_status[3], d.by_status[4], d.no_depth);
     }
     char depth_map_json[256] = "";
     if (depth_mapping) {

@@ -189,7 +189,9 @@ struct Image {
 // (an addition) A depth image REGISTERED to the camera image as delivered (the raw pixel grid): a header over caller-owned samples, host or
 // HBM.  DEPTH_F32: metres; DEPTH_U16: units of `scale` metres (TUM 1 / 5000, millimetres 0.001) — enum sdvl_depth_format of
 // include/sdvl_hip.h.  Read only while a keyframe's points are seeded (sdvl_depth_seed), never copied or kept.  Empty means none.
-enum DepthFormat { DEPTH_F32 = 0, DEPTH_U16 = 1 };
+// DEPTH_RIGHT8 is no depth image: the rectified right image of a stereo pair travels in the same slot (SDVL::SetStereoSeeding) — 8-bit
+// gray, dense or strided rows, `scale` unused, host or HBM
+enum DepthFormat { DEPTH_F32 = 0, DEPTH_U16 = 1, DEPTH_RIGHT8 = 2 };
 struct DepthImage {
   const void *data = nullptr;
   int cols = 0, rows = 0, step = 0;  // step: bytes between rows

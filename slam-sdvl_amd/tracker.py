@@ -164,8 +164,17 @@ class TrackerBatch:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
 
-    def step_host(self, imgs, depths=None):
-        """depths (set_depth): per tracker the frame's registered depth image, numpy [h, w] float32 or uint16 as set_depth named it, or None"""
+    @staticmethod
+    def _second(depths, rights, names):
+        """the step calls' second images under either name: depths= / depth_ptrs= or rights= / right_ptrs= (set_stereo), never both"""
+        if depths is not None and rights is not None:
+            raise ValueError("%s and %s name the same argument: give one" % names)
+        return depths if rights is None else rights
+
+    def step_host(self, imgs, depths=None, rights=None):
+        """depths (set_depth): per tracker the frame's registered depth image, numpy [h, w] float32 or uint16 as set_depth named it, or None;
+        rights (set_stereo): another name for the same argument — per tracker the pair's rectified right image, numpy [h, w] uint8, or None"""
+        depths = self._second(depths, rights, ("depths", "rights"))
         # (16-bit gray frames go as their little-endian bytes)
         imgs = [np.ascontiguousarray(im, "<u2").view(np.uint8) if np.asarray(im).dtype == np.uint16 else np.ascontiguousarray(im, np.uint8) for im in imgs]
         ptrs = (C.c_void_p * self.B)(*[im.ctypes.data for im in imgs])
@@ -176,8 +185,10 @@ class TrackerBatch:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         return self._stats
 
-    def step_device(self, dev_ptrs, depth_ptrs=None):
-        """depth_ptrs (set_depth): per tracker the device pointer of the frame's registered depth image (dense rows), or None"""
+    def step_device(self, dev_ptrs, depth_ptrs=None, right_ptrs=None):
+        """depth_ptrs (set_depth): per tracker the device pointer of the frame's registered depth image (dense rows), or None; right_ptrs
+        (set_stereo): another name for the same argument — the device pointers of the pairs' right images"""
+        depth_ptrs = self._second(depth_ptrs, right_ptrs, ("depth_ptrs", "right_ptrs"))
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs])
         if depth_ptrs is not None:
             return self._step_depth("sdvlh_batch_step_device_depth", ptrs, depth_ptrs)
@@ -200,6 +211,30 @@ class TrackerBatch:
                                           float(max_depth)) != 0:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         self.depth_dtype = np.uint16 if code == 1 else np.float32
+
+    def set_stereo(self, baseline, on=True, min_depth=0.0, max_depth=0.0, max_disparity=0, max_sad=0, uniqueness=0):
+        """stereo cameras: depth seeding's keyframe path with a sparse stereo matcher as the producer (SDVL::SetStereoSeeding).  The second
+        image handed over with each frame (rights= / right_ptrs= of the step calls, or depths= / depth_ptrs=) is the pair's rectified right
+        image: 8-bit gray of the camera image's size and intrinsics, dense rows, the right camera `baseline` metres along the left camera's
+        x axis.  The filtered corners of the step's keyframes are matched in it by one sdvl_stereo_depth call — every keyframe on the plane
+        map, the bootstrap keyframe with the reference's mapper.  The rule's fields as sdvl_stereo_params (0: the default — min_depth 0.3 m,
+        no max_depth, max_disparity 192, max_sad 20 per sample, uniqueness 80); the trackers share baseline and rule.  A first frame
+        without a right image, or with fewer OK corners than SDVL.min_init_corners, is not kept (state 0) and the next frame starts over.
+        Raises together with set_two_frame_init(True), set_depth(True), set_depth_mapping, set_depth_bundle and on a camera with a lens"""
+        self.lib.sdvlh_batch_set_stereo.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]
+        if self.lib.sdvlh_batch_set_stereo(self.h, int(bool(on)), float(baseline), float(min_depth), float(max_depth), int(max_disparity),
+                                           int(max_sad), int(uniqueness)) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        self.depth_dtype = np.uint8 if on else np.float32
+
+    def stereo_stats(self, i):
+        """tracker i's stereo seeding so far: dict(keyframes, seeds, ok, nomatch, ambiguous, edge, outside, no_image) — keyframes seeded,
+        points seeded, the keyframes' filtered corners by status, keyframes or first frames that came without a right image"""
+        out = (C.c_longlong * 8)()
+        self.lib.sdvlh_batch_stereo_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        if self.lib.sdvlh_batch_stereo_stats(self.h, int(i), out) != 0:
+            raise RuntimeError("no tracker %d" % i)
+        return dict(zip(("keyframes", "seeds", "ok", "nomatch", "ambiguous", "edge", "outside", "no_image"), [int(v) for v in out]))
 
     def seeded_points(self, i):
         """the live points tracker i seeded from depth, oldest first: rows of x y z keyframe_id u v level (float64; u, v in level coordinates)"""
@@ -337,9 +372,10 @@ class TrackerBatch:
         n = self.lib.sdvlh_batch_keyframe_poses(self.h, int(i), n, poses.ctypes.data, ids.ctypes.data)
         return ids[:n].copy(), poses[:n].copy()
 
-    def step_device_transient(self, dev_ptrs, depth_ptrs=None):
+    def step_device_transient(self, dev_ptrs, depth_ptrs=None, right_ptrs=None):
         """frames in HBM that stay valid for THIS step only (a slot of an input ring): aliased while tracked, frames that become
-        keyframes take a copy at the end of the step.  depth_ptrs as for step_device: a depth image is read inside the step only"""
+        keyframes take a copy at the end of the step.  depth_ptrs / right_ptrs as for step_device: a second image is read inside the step only"""
+        depth_ptrs = self._second(depth_ptrs, right_ptrs, ("depth_ptrs", "right_ptrs"))
         ptrs = (C.c_void_p * self.B)(*[int(p) for p in dev_ptrs])
         if depth_ptrs is not None:
             return self._step_depth("sdvlh_batch_step_device_transient_depth", ptrs, depth_ptrs)

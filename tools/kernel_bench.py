@@ -160,6 +160,35 @@ for _ in range(reps):
     dz, dstatus, dok = ctx.depth_seed(djobs, W, H, dxyl, cam)
 print("depth_seed: %d corners of %d frames per call, %d OK; %.1f us per blocking call (host wall, push + launch + copy back + wait)" %
       (len(dxyl), n, int(dok.sum()), (time.perf_counter() - t0) / reps * 1e6))
+# stereo cameras: sdvl_stereo_depth for the filtered corners (~265) of n keyframes of `shelf`, one job per pair, both images in HBM, all n
+# jobs in ONE call (the default rule at baseline 0.11 m searches up to 190 disparities a corner); blocking like depth_seed, and the
+# kernel's own dispatch time appears as stereo_depth in the table below
+st_scenes = [sdvl.synth_scene(B.se3_exp(shard.sequence_twist(j) * 2), B.TUM_CAM, preset="shelf", seed=shard.sequence_seed(j), frame_id=2) for j in range(n)]
+st_right = []
+for s_ in st_scenes:
+    r_ = sdvl.SynthScene.from_buffer_copy(s_)
+    r_.t[0] -= 0.11
+    st_right.append(r_)
+st_buf = ctx.device_malloc(2 * n * W * H)
+ctx.synth_render_scene(st_scenes + st_right, W, H, st_buf)
+st_fr = [sdvl.Frame(ctx, W, H) for _ in range(n)]
+for j in range(n):
+    st_fr[j].set_image_device(st_buf + j * W * H)
+ctx.pyramid_build(st_fr)
+ctx.detect_corners(st_fr, dp, 1000)
+ctx.orb_describe(st_fr, want=False)
+st_xyl = [f[1] for f in ctx.filter_corners(st_fr, [[] for _ in range(n)])]
+st_jobs, at = [], 0
+for j in range(n):
+    st_jobs.append(sdvl.StereoJob(st_fr[j].h, st_buf + (n + j) * W * H, 1, W, at, at + len(st_xyl[j])))
+    at += len(st_xyl[j])
+st_all = np.concatenate(st_xyl).astype(np.int32)
+t0 = time.perf_counter()
+for _ in range(reps):
+    sz, sdisp, sstatus, sok = ctx.stereo_depth(st_jobs, st_all, cam, 0.11)
+print("stereo_depth: %d corners of %d pairs per call, %d OK; %.1f us per blocking call (host wall, push + launch + copy back + wait)" %
+      (len(st_all), n, int(sok.sum()), (time.perf_counter() - t0) / reps * 1e6))
+st_nc = len(st_all) / float(n)
 # the mapper's depth filter on the search's own results, triangulated (depth_filter) and with a measured depth (depth_filter_measured): the
 # requests of frame pair j are one job over frame j's float depth image in HBM; both kernels appear in the table below
 fstates = (sdvl.DepthState * nreq)()
@@ -214,7 +243,8 @@ P = [(W >> l) * (H >> l) for l in range(5)]
 alg = {"pyr_down": (sum(P[:4]) + sum(P[1:])) / 4.0, "fast_cells": sum(P[:3]) + 16 * nc, "select_cells": 4 * 10000 + 6 * nc + 1600, "select_pack": 1600 + 30 * nc,
        "orb_describe": 993 * nc, "image_align": 147 * nf + 25 * nf * i_ia, "pose_hypotheses": 48 * nf + 6400, "undistort": 2 * W * H,
        "search_points": 12 * nc + nf * (121 + 164 + lk * 81), "search_prepare": nf * (120 + 80),
-       "pose_refine": 52 * nf + 6480, "depth_seed": min(300.0, nc) * (9 * 4 + 12 + 9)}
+       "pose_refine": 52 * nf + 6480, "depth_seed": min(300.0, nc) * (9 * 4 + 12 + 9),
+       "stereo_depth": st_nc * (9 * (190 + 9) + 81 + 12 + 17)}
 print("n_frames=%d reps=%d corners/frame=%.0f GN evaluations/job=%.1f" % (n, reps, nc, i_ia))
 for k, (ms, launches) in sorted(t.items()):
     us = ms / launches * 1e3
