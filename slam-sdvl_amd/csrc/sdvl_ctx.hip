@@ -104,6 +104,19 @@ int sdvl_stage_alloc(sdvl_ctx *ctx, size_t bytes, void **h, void **d) {
   return SDVL_OK;
 }
 
+int sdvl_reserve_out_stage(sdvl_ctx *ctx, size_t out_bytes, size_t stage_bytes, void **h, void **d) {
+  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, out_bytes, false);
+  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, out_bytes, true);
+  if (!rc) rc = sdvl_stage_alloc(ctx, stage_bytes, h, d);
+  return rc;
+}
+
+int sdvl_collect_out(sdvl_ctx *ctx, size_t bytes) {
+  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
+  return SDVL_OK;
+}
+
 int sdvl_allow_dynamic_lds(sdvl_ctx *ctx, const void *kernel, size_t bytes, std::atomic<unsigned long long> *devices) {
   const unsigned long long bit = 1ull << (ctx->device & 63);
   if (!(devices->load(std::memory_order_acquire) & bit)) {

@@ -60,6 +60,79 @@ __global__ __launch_bounds__(256) void depth_lookup_kernel(const DepthJobDev *__
   out_status[i] = static_cast<uint8_t>(status);
 }
 
+// ---- sdvl_depth_seed and sdvl_depth_lookup: one body (depth_items_run) over what each states of its own — its inputs, their parts of the
+// staging block and how they are filled, the level of an item with the message of its check, and its launch (tail: the arguments the two
+// kernels share behind n)
+struct SeedStage {  // staging: jobs | corners | the job of every corner (-1: none)
+  static constexpr const char *who = "sdvl_depth_seed", *level_msg = "sdvl_depth_seed: corner level outside 0 .. SDVL_MAX_LEVELS - 1";
+  const int32_t *xyl;
+  sdvl_part<int32_t> st_xyl;
+  bool stated() const { return xyl != nullptr; }
+  int level(int i) const { return xyl[3 * i + 2]; }
+  void take(sdvl_layout &st, int n) { st_xyl = st.take<int32_t>(3 * static_cast<size_t>(n)); }
+  void fill(void *hs) const { memcpy(st_xyl.in(hs), xyl, st_xyl.bytes()); }
+  template <typename... Tail>
+  void launch(sdvl_ctx *ctx, const void *ds, const DepthJobDev *jobs, const int32_t *item_job, int n, Tail... tail) const {
+    SDVL_LAUNCH(ctx, "depth_seed", depth_seed, dim3((n + 255) / 256), dim3(256), jobs, st_xyl.cin(ds), item_job, n, tail...);
+  }
+};
+
+struct LookupStage {  // staging: jobs | positions | levels | the job of every position (-1: none)
+  static constexpr const char *who = "sdvl_depth_lookup", *level_msg = "sdvl_depth_lookup: level outside 0 .. SDVL_MAX_LEVELS - 1";
+  const double *px2;
+  const int32_t *lv;
+  sdvl_part<double> st_px;
+  sdvl_part<int32_t> st_level;
+  bool stated() const { return px2 != nullptr && lv != nullptr; }
+  int level(int i) const { return lv[i]; }
+  void take(sdvl_layout &st, int n) { st_px = st.take<double>(2 * static_cast<size_t>(n)), st_level = st.take<int32_t>(n); }
+  void fill(void *hs) const { memcpy(st_px.in(hs), px2, st_px.bytes()), memcpy(st_level.in(hs), lv, st_level.bytes()); }
+  template <typename... Tail>
+  void launch(sdvl_ctx *ctx, const void *ds, const DepthJobDev *jobs, const int32_t *item_job, int n, Tail... tail) const {
+    SDVL_LAUNCH(ctx, "depth_lookup", depth_lookup_kernel, dim3((n + 255) / 256), dim3(256), jobs, st_px.cin(ds), st_level.cin(ds), item_job, n, tail...);
+  }
+};
+
+// d_out and h_out: z | status
+template <typename Stage>
+int depth_items_run(sdvl_ctx *ctx, Stage &stage, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n, const sdvl_camera *cam,
+                    const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status, int32_t *out_ok_per_job) {
+  if (!ctx) return SDVL_ERR_INVALID;
+  const std::string w(Stage::who);
+  SDVL_REQUIRE(ctx, n_jobs >= 0 && n >= 0, w + ": negative count");
+  if (n_jobs == 0 || n == 0) {
+    for (int j = 0; j < n_jobs && out_ok_per_job; j++) out_ok_per_job[j] = 0;
+    return SDVL_OK;
+  }
+  SDVL_REQUIRE(ctx, jobs && stage.stated() && cam && out_z && out_status && out_ok_per_job, w + ": null pointer");
+  DepthRule rule;
+  int rc = sdvl_depth_rule_of(ctx, Stage::who, p, &rule);
+  if (!rc) rc = sdvl_depth_jobs_check(ctx, Stage::who, n_jobs, jobs, width, height, n);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) SDVL_REQUIRE(ctx, stage.level(i) >= 0 && stage.level(i) < SDVL_MAX_LEVELS, Stage::level_msg);
+  sdvl_layout st, o;
+  const sdvl_part<DepthJobDev> st_jobs = st.take<DepthJobDev>(n_jobs);
+  stage.take(st, n);
+  const sdvl_part<int32_t> st_item_job = st.take<int32_t>(n);
+  const sdvl_part<double> o_z = o.take<double>(n);
+  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
+  void *hs = nullptr, *ds = nullptr;
+  rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
+  if (!rc) rc = sdvl_depth_jobs_resolve(ctx, n_jobs, jobs, width, height, st_jobs.in(hs));
+  if (rc) return rc;
+  sdvl_item_jobs_fill(n, n_jobs, jobs, st_item_job.in(hs));  // (ranges that overlap: the later job's)
+  stage.fill(hs);
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  stage.launch(ctx, ds, st_jobs.cin(ds), st_item_job.cin(ds), n, width, height, sdvl_depth_lens_of(cam, dist), rule, o_z.in(ctx->d_out), o_status.in(ctx->d_out));
+  SDVL_HIP_CHECK(ctx, hipGetLastError());
+  rc = sdvl_collect_out(ctx, o.bytes());
+  if (rc) return rc;
+  memcpy(out_z, o_z.in(ctx->h_out), o_z.bytes());
+  memcpy(out_status, o_status.in(ctx->h_out), o_status.bytes());
+  sdvl_ok_per_job(n_jobs, jobs, out_status, SDVL_DEPTH_SEED_OK, out_ok_per_job);
+  return SDVL_OK;
+}
+
 }  // namespace
 
 // ---- what the entries that take depth jobs share (sdvl_depth_device.h)
@@ -105,9 +178,8 @@ DepthLens sdvl_depth_lens_of(const sdvl_camera *cam, const sdvl_distortion *dist
 // reads it.  A buffer keeps its allocation from call to call; `live` says that it holds `host` as staged since sdvl_depth_stage_begin
 // (outside a begin .. end pair: since the start of this call).
 int sdvl_depth_jobs_resolve(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, DepthJobDev *out) {
-  SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
-  if (!ctx->depth_stage_open)
-    for (sdvl_ctx::DepthStaged &e : ctx->depth_pool) e.live = 0;
+  const int scope = sdvl_depth_pool_scope(ctx);
+  if (scope) return scope;
   for (int j = 0; j < n_jobs; j++) {
     const sdvl_depth_job &jb = jobs[j];
     out[j] = DepthJobDev{static_cast<const uint8_t *>(jb.depth), jb.stride, jb.scale, jb.format, 0};
@@ -124,6 +196,13 @@ int sdvl_depth_jobs_resolve(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *job
     if (rc) return rc;
     out[j].stride = static_cast<long long>(row);
   }
+  return SDVL_OK;
+}
+
+int sdvl_depth_pool_scope(sdvl_ctx *ctx) {
+  SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
+  if (!ctx->depth_stage_open)
+    for (sdvl_ctx::DepthStaged &e : ctx->depth_pool) e.live = 0;
   return SDVL_OK;
 }
 
@@ -171,103 +250,15 @@ int sdvl_depth_stage_end(sdvl_ctx *ctx) {
 int sdvl_depth_seed(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n_corners, const int32_t *xyl,
                     const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
                     int32_t *out_ok_per_job) {
-  if (!ctx) return SDVL_ERR_INVALID;
-  SDVL_REQUIRE(ctx, n_jobs >= 0 && n_corners >= 0, "sdvl_depth_seed: negative count");
-  if (n_jobs == 0 || n_corners == 0) {
-    for (int j = 0; j < n_jobs && out_ok_per_job; j++) out_ok_per_job[j] = 0;
-    return SDVL_OK;
-  }
-  SDVL_REQUIRE(ctx, jobs && xyl && cam && out_z && out_status && out_ok_per_job, "sdvl_depth_seed: null pointer");
-  SDVL_REQUIRE(ctx, width >= 1 && height >= 1 && width <= 16384 && height <= 16384, "sdvl_depth_seed: image size out of range (1 .. 16384 a side)");
-  DepthRule rule;
-  int rc = sdvl_depth_rule_of(ctx, "sdvl_depth_seed", p, &rule);
-  if (!rc) rc = sdvl_depth_jobs_check(ctx, "sdvl_depth_seed", n_jobs, jobs, width, height, n_corners);
-  if (rc) return rc;
-  for (int i = 0; i < n_corners; i++)
-    SDVL_REQUIRE(ctx, xyl[3 * i + 2] >= 0 && xyl[3 * i + 2] < SDVL_MAX_LEVELS, "sdvl_depth_seed: corner level outside 0 .. SDVL_MAX_LEVELS - 1");
-  // staging: jobs | corners | the job of every corner (-1: none); d_out and h_out: z | status
-  sdvl_layout st, o;
-  const sdvl_part<DepthJobDev> st_jobs = st.take<DepthJobDev>(n_jobs);
-  const sdvl_part<int32_t> st_xyl = st.take<int32_t>(3 * static_cast<size_t>(n_corners)), st_cj = st.take<int32_t>(n_corners);
-  const sdvl_part<double> o_z = o.take<double>(n_corners);
-  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n_corners);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
-  if (!rc) rc = sdvl_depth_jobs_resolve(ctx, n_jobs, jobs, width, height, st_jobs.in(hs));
-  if (rc) return rc;
-  int32_t *hcj = st_cj.in(hs);
-  for (int i = 0; i < n_corners; i++) hcj[i] = -1;
-  for (int j = 0; j < n_jobs; j++)
-    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) hcj[i] = j;
-  memcpy(st_xyl.in(hs), xyl, st_xyl.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  const DepthLens lens = sdvl_depth_lens_of(cam, dist);
-  SDVL_LAUNCH(ctx, "depth_seed", depth_seed, dim3((n_corners + 255) / 256), dim3(256), st_jobs.cin(ds), st_xyl.cin(ds), st_cj.cin(ds), n_corners, width,
-              height, lens, rule, o_z.in(ctx->d_out), o_status.in(ctx->d_out));
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out_z, o_z.in(ctx->h_out), o_z.bytes());
-  memcpy(out_status, o_status.in(ctx->h_out), o_status.bytes());
-  for (int j = 0; j < n_jobs; j++) {
-    int ok = 0;
-    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) ok += out_status[i] == SDVL_DEPTH_SEED_OK ? 1 : 0;
-    out_ok_per_job[j] = ok;
-  }
-  return SDVL_OK;
+  SeedStage stage{xyl, {}};
+  return depth_items_run(ctx, stage, n_jobs, jobs, width, height, n_corners, cam, dist, p, out_z, out_status, out_ok_per_job);
 }
 
 int sdvl_depth_lookup(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *jobs, int width, int height, int n, const double *px2, const int32_t *level,
                       const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_depth_seed_params *p, double *out_z, uint8_t *out_status,
                       int32_t *out_ok_per_job) {
-  if (!ctx) return SDVL_ERR_INVALID;
-  SDVL_REQUIRE(ctx, n_jobs >= 0 && n >= 0, "sdvl_depth_lookup: negative count");
-  if (n_jobs == 0 || n == 0) {
-    for (int j = 0; j < n_jobs && out_ok_per_job; j++) out_ok_per_job[j] = 0;
-    return SDVL_OK;
-  }
-  SDVL_REQUIRE(ctx, jobs && px2 && level && cam && out_z && out_status && out_ok_per_job, "sdvl_depth_lookup: null pointer");
-  DepthRule rule;
-  int rc = sdvl_depth_rule_of(ctx, "sdvl_depth_lookup", p, &rule);
-  if (!rc) rc = sdvl_depth_jobs_check(ctx, "sdvl_depth_lookup", n_jobs, jobs, width, height, n);
-  if (rc) return rc;
-  for (int i = 0; i < n; i++) SDVL_REQUIRE(ctx, level[i] >= 0 && level[i] < SDVL_MAX_LEVELS, "sdvl_depth_lookup: level outside 0 .. SDVL_MAX_LEVELS - 1");
-  // staging: jobs | positions | levels | the job of every position (-1: none); d_out and h_out: z | status
-  sdvl_layout st, o;
-  const sdvl_part<DepthJobDev> st_jobs = st.take<DepthJobDev>(n_jobs);
-  const sdvl_part<double> st_px = st.take<double>(2 * static_cast<size_t>(n));
-  const sdvl_part<int32_t> st_level = st.take<int32_t>(n), st_pj = st.take<int32_t>(n);
-  const sdvl_part<double> o_z = o.take<double>(n);
-  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
-  if (!rc) rc = sdvl_depth_jobs_resolve(ctx, n_jobs, jobs, width, height, st_jobs.in(hs));
-  if (rc) return rc;
-  int32_t *hpj = st_pj.in(hs);
-  for (int i = 0; i < n; i++) hpj[i] = -1;
-  for (int j = 0; j < n_jobs; j++)
-    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) hpj[i] = j;
-  memcpy(st_px.in(hs), px2, st_px.bytes());
-  memcpy(st_level.in(hs), level, st_level.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  const DepthLens lens = sdvl_depth_lens_of(cam, dist);
-  SDVL_LAUNCH(ctx, "depth_lookup", depth_lookup_kernel, dim3((n + 255) / 256), dim3(256), st_jobs.cin(ds), st_px.cin(ds), st_level.cin(ds), st_pj.cin(ds), n,
-              width, height, lens, rule, o_z.in(ctx->d_out), o_status.in(ctx->d_out));
-  SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(out_z, o_z.in(ctx->h_out), o_z.bytes());
-  memcpy(out_status, o_status.in(ctx->h_out), o_status.bytes());
-  for (int j = 0; j < n_jobs; j++) {
-    int ok = 0;
-    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) ok += out_status[i] == SDVL_DEPTH_SEED_OK ? 1 : 0;
-    out_ok_per_job[j] = ok;
-  }
-  return SDVL_OK;
+  LookupStage stage{px2, level, {}, {}};
+  return depth_items_run(ctx, stage, n_jobs, jobs, width, height, n, cam, dist, p, out_z, out_status, out_ok_per_job);
 }
 
 }  // extern "C"

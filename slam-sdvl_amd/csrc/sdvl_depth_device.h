@@ -1,6 +1,6 @@
 // sdvl_depth_device.h — the depth lookup of include/sdvl_hip.h's "depth cameras" section, stated once for the two kernels that make it:
 // depth_seed (sdvl_depth.hip: a keyframe's corners) and depth_filter_measured_kernel (sdvl_depth_filter.hip: the pixel a candidate was found
-// at); and what their host entries share: the checks of a job list, the rule's defaults, where an image is read.
+// at); and what their host entries share: the checks of a job list, the rule's defaults, where an image is read, the job of every item.
 #ifndef SDVL_DEPTH_DEVICE_H_
 #define SDVL_DEPTH_DEVICE_H_
 
@@ -105,5 +105,29 @@ int sdvl_depth_jobs_resolve(sdvl_ctx *ctx, int n_jobs, const sdvl_depth_job *job
 // sdvl_stereo_depth stages a right image in host memory through it (format SDVL_DEPTH_RIGHT8)
 int sdvl_depth_stage_image(sdvl_ctx *ctx, const void *host, long long stride, int format, int width, int height, size_t row, const uint8_t **staged);
 sdvl_depth::DepthLens sdvl_depth_lens_of(const sdvl_camera *cam, const sdvl_distortion *dist);
+// a call's scope of those buffers: binds the device; outside a sdvl_depth_stage_begin .. _end pair nothing staged earlier stays live
+int sdvl_depth_pool_scope(sdvl_ctx *ctx);
+
+// ---- for every entry whose jobs name ranges [c_begin, c_end) of one item list (sdvl_depth_job, sdvl_stereo_job); ranges checked before
+// the job of every item of a list of n, -1 for none; where ranges overlap the later job's.  -> whether any did
+template <typename Job>
+bool sdvl_item_jobs_fill(int n, int n_jobs, const Job *jobs, int32_t *item_job) {
+  bool overlap = false;
+  for (int i = 0; i < n; i++) item_job[i] = -1;
+  for (int j = 0; j < n_jobs; j++)
+    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) {
+      overlap = overlap || item_job[i] >= 0;
+      item_job[i] = j;
+    }
+  return overlap;
+}
+// the items of every job whose status is `ok`
+template <typename Job>
+void sdvl_ok_per_job(int n_jobs, const Job *jobs, const uint8_t *status, int ok, int32_t *ok_per_job) {
+  for (int j = 0; j < n_jobs; j++) {
+    ok_per_job[j] = 0;
+    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) ok_per_job[j] += status[i] == ok ? 1 : 0;
+  }
+}
 
 #endif  // SDVL_DEPTH_DEVICE_H_

@@ -142,10 +142,7 @@ struct DepthMeasureStage {
   int fill(sdvl_ctx *ctx, void *hs, int n, int n_jobs, const sdvl_depth_job *in, int width, int height) const {
     const int rc = n_jobs > 0 ? sdvl_depth_jobs_resolve(ctx, n_jobs, in, width, height, jobs.in(hs)) : SDVL_OK;
     if (rc) return rc;
-    int32_t *rj = req_job.in(hs);
-    for (int i = 0; i < n; i++) rj[i] = -1;
-    for (int j = 0; j < n_jobs; j++)
-      for (int i = in[j].c_begin; i < in[j].c_end; i++) rj[i] = j;
+    sdvl_item_jobs_fill(n, n_jobs, in, req_job.in(hs));  // (ranges that overlap: the later job's)
     return SDVL_OK;
   }
 };
@@ -257,9 +254,7 @@ int sdvl_depth_filter(sdvl_ctx *ctx, int n, const double *cur_pose, const double
   const StatedStage stated(st, n);
   const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
   void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
+  rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
   if (rc) return rc;
   memset(hs, 0, st.bytes());
   stated.fill(hs, n, cur_pose, ref_pose, bearing, found, px, nullptr, state);
@@ -327,9 +322,7 @@ int sdvl_depth_filter_measured(sdvl_ctx *ctx, int n, const double *cur_pose, con
   const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
   const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
   void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
+  rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
   if (rc) return rc;
   memset(hs, 0, st.bytes());
   rc = st_depth.fill(ctx, hs, n, n_jobs, jobs, width, height);

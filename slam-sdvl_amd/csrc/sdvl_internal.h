@@ -210,6 +210,10 @@ int sdvl_ensure(sdvl_ctx *ctx, void **p, size_t *cur, size_t need, bool pinned);
 // last sdvl_stream_wait never overlap, so a call can fill its records while earlier copies are still in flight;
 // only when the ring is exhausted does this wait for the stream.
 int sdvl_stage_alloc(sdvl_ctx *ctx, size_t bytes, void **h, void **d);
+// what a blocking entry reserves: `out_bytes` of d_out and of the pinned h_out, `stage_bytes` of staging
+int sdvl_reserve_out_stage(sdvl_ctx *ctx, size_t out_bytes, size_t stage_bytes, void **h, void **d);
+// the first `bytes` of d_out -> h_out, and the wait for the stream
+int sdvl_collect_out(sdvl_ctx *ctx, size_t bytes);
 // Records staged in the context's pinned ring (sdvl_stage_alloc) -> device memory, queued on ctx->stream.  Round 3: a small KERNEL
 // pulls them over the bus instead of a hipMemcpyAsync: a DMA copy command waits in its engine's queue behind whatever that engine
 // is doing — with a farm's 79 MB image transfers under way every job-record copy (a few KB, in front of every kernel) queued up

@@ -192,32 +192,27 @@ extern "C" int sdvl_stereo_depth(sdvl_ctx *ctx, int n_jobs, const sdvl_stereo_jo
   const sdvl_part<double> o_z = o.take<double>(n_corners), o_disp = o.take<double>(n_corners);
   const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n_corners);
   void *hs = nullptr, *ds = nullptr;
-  int rc = sdvl_ensure(ctx, &ctx->d_out, &ctx->d_out_bytes, o.bytes(), false);
-  if (!rc) rc = sdvl_ensure(ctx, &ctx->h_out, &ctx->h_out_bytes, o.bytes(), true);
-  if (!rc) rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
+  int rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
   if (rc) return rc;
-  int32_t *hcj = st_cj.in(hs);
-  for (int i = 0; i < n_corners; i++) hcj[i] = -1;
-  int max_level = 0;
   for (int j = 0; j < n_jobs; j++) {
     const sdvl_stereo_job &jb = jobs[j];
     SDVL_REQUIRE(ctx, jb.left != nullptr && jb.right != nullptr, "sdvl_stereo_depth: null image");
     SDVL_REQUIRE(ctx, jb.left->home == ctx, "sdvl_stereo_depth: the left frame belongs to another context");
     SDVL_REQUIRE(ctx, jb.stride >= jb.left->width, "sdvl_stereo_depth: stride smaller than the width");
     SDVL_REQUIRE(ctx, jb.c_begin >= 0 && jb.c_begin <= jb.c_end && jb.c_end <= n_corners, "sdvl_stereo_depth: corner range outside the corner list");
-    for (int i = jb.c_begin; i < jb.c_end; i++) {
-      SDVL_REQUIRE(ctx, hcj[i] < 0, "sdvl_stereo_depth: corner ranges overlap");
-      const int l = xyl[3 * i + 2];
-      SDVL_REQUIRE(ctx, l >= 0 && l < jb.left->v.levels, "sdvl_stereo_depth: a corner's level lies outside the left frame's pyramid");
-      max_level = l > max_level ? l : max_level;
-      hcj[i] = j;
-    }
   }
+  SDVL_REQUIRE(ctx, !sdvl_item_jobs_fill(n_corners, n_jobs, jobs, st_cj.in(hs)), "sdvl_stereo_depth: corner ranges overlap");
+  int max_level = 0;
+  for (int j = 0; j < n_jobs; j++)
+    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) {
+      const int l = xyl[3 * i + 2];
+      SDVL_REQUIRE(ctx, l >= 0 && l < jobs[j].left->v.levels, "sdvl_stereo_depth: a corner's level lies outside the left frame's pyramid");
+      max_level = l > max_level ? l : max_level;
+    }
   // a right image in HBM is read where it lies; one in host memory is copied to HBM first (a keyframe's corners read its rows many times
   // over), through the buffers the context keeps for depth images
-  SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
-  if (!ctx->depth_stage_open)
-    for (sdvl_ctx::DepthStaged &e : ctx->depth_pool) e.live = 0;
+  rc = sdvl_depth_pool_scope(ctx);
+  if (rc) return rc;
   StereoJobDev *hj = st_jobs.in(hs);
   for (int j = 0; j < n_jobs; j++) {
     const sdvl_stereo_job &jb = jobs[j];
@@ -238,15 +233,11 @@ extern "C" int sdvl_stereo_depth(sdvl_ctx *ctx, int n_jobs, const sdvl_stereo_jo
   SDVL_LAUNCH_LDS(ctx, "stereo_depth", stereo_depth, dim3(n_corners), dim3(64), lds_bytes, st_jobs.cin(ds), st_xyl.cin(ds), st_cj.cin(ds), rule, sw_max,
                   o_z.in(ctx->d_out), o_disp.in(ctx->d_out), o_status.in(ctx->d_out));
   SDVL_HIP_CHECK(ctx, hipGetLastError());
-  SDVL_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_out, ctx->d_out, o.bytes(), hipMemcpyDeviceToHost, ctx->stream));
-  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
+  rc = sdvl_collect_out(ctx, o.bytes());
+  if (rc) return rc;
   memcpy(out_z, o_z.in(ctx->h_out), o_z.bytes());
   memcpy(out_disparity, o_disp.in(ctx->h_out), o_disp.bytes());
   memcpy(out_status, o_status.in(ctx->h_out), o_status.bytes());
-  for (int j = 0; j < n_jobs; j++) {
-    int ok = 0;
-    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++) ok += out_status[i] == SDVL_STEREO_OK ? 1 : 0;
-    out_ok_per_job[j] = ok;
-  }
+  sdvl_ok_per_job(n_jobs, jobs, out_status, SDVL_STEREO_OK, out_ok_per_job);
   return SDVL_OK;
 }

@@ -1,8 +1,9 @@
 // batch.cc — SDVLBatch, the batch driver (B trackers per submission): the worker pool and the process-wide switches; the pieces every
 // form of a step shares (BeginFrame, InitializeTrackers, DetectOnSideStream, FetchCornerCounts, CollectKeyframes); HandleFrames; what
-// follows the decisions (FinishKeyframes, EpilogueAndMapper, RunMappers).  The other jobs have files of their own: the tracking tables
-// (batch_tables.cc), relocalisation inside the tabled step (batch_reloc.cc), the step on the tables (batch_tracked.cc) and the
-// host-driven step (batch_host_step.cc).  Reference line numbers are cited at each function; device work goes through the C-ABI
+// follows the decisions (FinishKeyframes, EpilogueAndMapper).  The other jobs have files of their own: the tracking tables
+// (batch_tables.cc), relocalisation inside the tabled step (batch_reloc.cc), the step on the tables (batch_tracked.cc), the
+// host-driven step (batch_host_step.cc), the calls that read a frame's depth or right image (batch_depth.cc) and the sequential
+// mappers' stage (batch_mapper.cc).  Reference line numbers are cited at each function; device work goes through the C-ABI
 // (include/sdvl_hip.h) only.
 #include "batch_internal.h"
 #include "homography_init.h"
@@ -304,11 +305,6 @@ void SDVLBatch::CollectKeyframes(Step &s, bool fetch_counts) {
   s.filter_begun = true;
 }
 
-const DepthImage *SDVLBatch::DepthOf(int i) const {
-  if (!step_depths_ || step_depths_->empty() || (*step_depths_)[i].empty()) return nullptr;
-  return &(*step_depths_)[i];
-}
-
 void SDVLBatch::HandleFrames(const vector<Image> &imgs, FrameStats *stats) { HandleFrames(imgs, vector<DepthImage>(), stats); }
 
 // SDVL::HandleFrame (sdvl.cc:55-130) for B trackers
@@ -374,94 +370,6 @@ void SDVLBatch::HandleFrames(const vector<Image> &imgs, const vector<DepthImage>
 }
 
 // --------------------------------------------------------------------------------- SDVLBatch: what follows the decisions
-// Depth cameras: the filtered corners of the step's keyframes whose tracker seeds from depth (SDVL::SetDepthSeeding) are looked up in
-// their frames' depth images by ONE sdvl_depth_seed call.  (*z)[k] / (*status)[k]: keyframe k's results, null for a keyframe that is not
-// seeded from depth.  A keyframe that came without a depth image seeds nothing and is counted.  A first frame becomes the first keyframe
-// here if at least SDVL.min_init_corners of its corners have a depth; otherwise it is not kept (its entry of s.kfs becomes null).
-void SDVLBatch::SeedKeyframesFromDepth(Step &s, vector<const double *> *z, vector<const uint8_t *> *status) {
-  const size_t K = s.kfs.size();
-  z->assign(K, nullptr);
-  status->assign(K, nullptr);
-  bool any = false;
-  for (size_t k = 0; k < K; k++) any = any || trk_[s.kf_owner[k]]->depth_seeding_;
-  if (!any) return;
-  // (a stereo tracker's second image is the pair's right image, SDVL::SetStereoSeeding: the same jobs with sdvl_stereo_depth as the producer)
-  vector<sdvl_depth_job> jobs;
-  vector<sdvl_stereo_job> pairs;
-  vector<size_t> whose;
-  vector<int32_t> xyl;
-  const sdvl_depth_seed_params *rule = nullptr;
-  const sdvl_stereo_params *stereo = nullptr;
-  for (size_t k = 0; k < K; k++) {
-    SDVL &t = *trk_[s.kf_owner[k]];
-    if (!t.depth_seeding_) continue;
-    const DepthImage *d = DepthOf(s.kf_owner[k]);
-    if (!d) continue;  // (counted below)
-    if (t.stereo_seeding_) {
-      if (rule || (stereo && std::memcmp(stereo, &t.stereo_rule_, sizeof(*stereo)) != 0))
-        throw std::runtime_error("SDVLBatch: the trackers of a batch share the stereo baseline and rule");
-      if (d->format != DEPTH_RIGHT8) throw std::runtime_error("SDVLBatch: a tracker that seeds from a stereo pair takes a right image (DEPTH_RIGHT8), not a depth image");
-      stereo = &t.stereo_rule_;
-    } else {
-      if (stereo || (rule && std::memcmp(rule, &t.depth_rule_, sizeof(*rule)) != 0))
-        throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
-      rule = &t.depth_rule_;
-    }
-    const int begin = static_cast<int>(xyl.size() / 3), n = s.kfs[k]->NumFiltered();
-    for (int c = 0; c < n; c++) {
-      const Vector3i corner = s.kfs[k]->FilteredCorner(c);
-      xyl.insert(xyl.end(), {corner(0), corner(1), corner(2)});
-    }
-    jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, begin, begin + n});
-    pairs.push_back(sdvl_stereo_job{s.kfs[k]->device(), d->data, d->on_device ? 1 : 0, d->step, begin, begin + n});
-    whose.push_back(k);
-  }
-  const int n_corners = static_cast<int>(xyl.size() / 3);
-  depth_z_.assign(std::max(n_corners, 1), 0.0);
-  depth_status_.assign(std::max(n_corners, 1), 0);
-  vector<int32_t> ok(std::max<size_t>(jobs.size(), 1), 0);
-  if (!jobs.empty()) {
-    const Camera &camera = *trk_[0]->camera_;
-    const sdvl_camera cam = camera.abi();
-    const sdvl_distortion dist = camera.distortion();
-    if (stereo) {
-      sdvl_stereo_params sp = *stereo;
-      sp.dist = camera.HasDistortion() ? &dist : nullptr;  // (refused: rectified pairs only)
-      stereo_disparity_.assign(n_corners, 0.0);
-      dev_->Check(sdvl_stereo_depth(dev_->ctx(), static_cast<int>(pairs.size()), pairs.data(), n_corners, xyl.data(), &cam, &sp, depth_z_.data(),
-                                    stereo_disparity_.data(), depth_status_.data(), ok.data()),
-                  "sdvl_stereo_depth");
-    } else {
-      dev_->Check(sdvl_depth_seed(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), s.kfs[whose[0]]->GetWidth(), s.kfs[whose[0]]->GetHeight(), n_corners,
-                                  xyl.data(), &cam, camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
-                  "sdvl_depth_seed");
-    }
-  }
-  for (size_t j = 0; j < jobs.size(); j++) {
-    (*z)[whose[j]] = depth_z_.data() + jobs[j].c_begin;
-    (*status)[whose[j]] = depth_status_.data() + jobs[j].c_begin;
-  }
-  size_t j = 0;
-  for (size_t k = 0; k < K; k++) {
-    SDVL &t = *trk_[s.kf_owner[k]];
-    if (!t.depth_seeding_) continue;
-    const bool looked_up = j < whose.size() && whose[j] == k;
-    if (!looked_up)
-      if (PlaneMap *pm = dynamic_cast<PlaneMap *>(t.map_)) pm->CountNoDepth();
-    if (t.first_frame_waiting_) {
-      if (looked_up && ok[j] >= Config::MinInitCorners()) {
-        t.CommitFirstFrame(s.stats[s.kf_owner[k]]);
-      } else {  // too few corners with a depth: the frame is not kept, the next one starts over
-        t.first_frame_waiting_ = false;
-        t.init_failed_ = true;
-        t.pending_kf_ = nullptr;
-        s.kfs[k] = nullptr;
-      }
-    }
-    if (looked_up) j++;
-  }
-}
-
 // stage 4, the mapper stand-in for the step's keyframes (sequential mode, main.cc:148-149): the second half of their FilterCorners round
 // trip, the seeding from the scene plane or from the frames' depth images, and the seeds' rows behind the tables that stayed on the device
 void SDVLBatch::FinishKeyframes(Step &s) {
@@ -521,277 +429,6 @@ void SDVLBatch::EpilogueAndMapper(Step &s) {
   s.Stage(ST_MAPPER);
   RunMappers();
   s.clk.reset();
-}
-
-// Depth cameras inside the mapper: the filtered corners of all the step's new keyframes whose mapper measures, looked up in their frames'
-// depth images by ONE sdvl_depth_seed call (as SeedKeyframesFromDepth does for the keyframes the driver seeds) and handed to the mappers
-void SDVLBatch::MeasureKeyframeCorners(const vector<MapperMap *> &mm, const vector<int> &mm_trk, const vector<int> &kf_idx, const vector<char> &need,
-                                       const vector<const DepthImage *> &depth_of) {
-  vector<sdvl_depth_job> jobs;
-  vector<int> whose;
-  vector<int32_t> xyl;
-  const sdvl_depth_seed_params *rule = nullptr;
-  for (size_t q = 0; q < kf_idx.size(); q++) {
-    const int k = kf_idx[q];
-    if (!need[q] || !mm[k]->DepthMapping()) continue;
-    const DepthImage *d = depth_of[k];
-    if (!d) {
-      mm[k]->SetCornerDepths(nullptr, nullptr);
-      continue;
-    }
-    const sdvl_depth_seed_params *r = &trk_[mm_trk[k]]->depth_rule_;
-    if (rule && std::memcmp(rule, r, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
-    rule = r;
-    const shared_ptr<Frame> &kf = mm[k]->CurrentFrame();
-    const int first = static_cast<int>(xyl.size() / 3), n = kf->NumFiltered();
-    for (int c = 0; c < n; c++) {
-      const Vector3i corner = kf->FilteredCorner(c);
-      xyl.insert(xyl.end(), {corner(0), corner(1), corner(2)});
-    }
-    jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, first, first + n});
-    whose.push_back(k);
-  }
-  if (jobs.empty()) return;
-  const int n_corners = static_cast<int>(xyl.size() / 3);
-  depth_z_.assign(std::max(n_corners, 1), 0.0);
-  depth_status_.assign(std::max(n_corners, 1), 0);
-  vector<int32_t> ok(jobs.size(), 0);
-  const Camera &camera = *trk_[0]->camera_;
-  const sdvl_camera cam = camera.abi();
-  const sdvl_distortion dist = camera.distortion();
-  const shared_ptr<Frame> &kf0 = mm[whose[0]]->CurrentFrame();
-  dev_->Check(sdvl_depth_seed(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), kf0->GetWidth(), kf0->GetHeight(), n_corners, xyl.data(), &cam,
-                              camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
-              "sdvl_depth_seed");
-  for (size_t j = 0; j < jobs.size(); j++) mm[whose[j]]->SetCornerDepths(depth_z_.data() + jobs[j].c_begin, depth_status_.data() + jobs[j].c_begin);
-}
-
-// Depth edges in bundle adjustment (SDVL::SetDepthBundle): the features the step's new keyframes hold when their mapper takes them up —
-// the tracked matches, at their found pixel and level — are looked up in their frames' depth images by ONE sdvl_depth_lookup call, inside
-// the step's sdvl_depth_stage_begin / _end bracket like the sdvl_depth_seed calls beside it.  A keyframe that is not the step's own frame
-// (or came without an image) is not looked up: its image is gone.
-void SDVLBatch::LookupKeyframeFeatures(const vector<MapperMap *> &mm, const vector<int> &mm_trk, const vector<int> &kf_idx) {
-  vector<sdvl_depth_job> jobs;
-  vector<int> whose;
-  vector<double> px2;
-  vector<int32_t> level;
-  const sdvl_depth_seed_params *rule = nullptr;
-  int width = 0, height = 0;
-  for (int k : kf_idx) {
-    if (!mm[k]->DepthBundleOn() || mm[k]->CurrentFrame().get() != trk_[mm_trk[k]]->step_frame_) continue;
-    const DepthImage *d = DepthOf(mm_trk[k]);
-    if (!d) continue;
-    const sdvl_depth_seed_params *r = &trk_[mm_trk[k]]->depth_rule_;
-    if (rule && std::memcmp(rule, r, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
-    rule = r;
-    const int first = static_cast<int>(level.size());
-    const int n = mm[k]->EmitDepthLookups(&px2, &level);
-    if (n == 0) continue;
-    width = mm[k]->CurrentFrame()->GetWidth();
-    height = mm[k]->CurrentFrame()->GetHeight();
-    jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, first, first + n});
-    whose.push_back(k);
-  }
-  if (jobs.empty()) return;
-  const int n = static_cast<int>(level.size());
-  depth_z_.assign(n, 0.0);
-  depth_status_.assign(n, 0);
-  vector<int32_t> ok(jobs.size(), 0);
-  const Camera &camera = *trk_[0]->camera_;
-  const sdvl_camera cam = camera.abi();
-  const sdvl_distortion dist = camera.distortion();
-  dev_->Check(sdvl_depth_lookup(dev_->ctx(), static_cast<int>(jobs.size()), jobs.data(), width, height, n, px2.data(), level.data(), &cam,
-                                camera.HasDistortion() ? &dist : nullptr, rule, depth_z_.data(), depth_status_.data(), ok.data()),
-              "sdvl_depth_lookup");
-  for (size_t j = 0; j < jobs.size(); j++) mm[whose[j]]->ApplyDepthLookups(depth_z_.data() + jobs[j].c_begin, depth_status_.data() + jobs[j].c_begin);
-}
-
-// stage 5: SDVL::Mapping() of sequential mode (main.cc:148-149) for the trackers that own a real mapper: the phases of
-// Map::UpdateMap run in lock step, every phase's SearchPoint requests of ALL trackers in one K7 launch
-void SDVLBatch::RunMappers() {
-  vector<MapperMap *> mm;
-  vector<int> mm_trk;  // whose mapper mm[k] is
-  {
-    StageClock begin_clk(ST_MAP_BEGIN);
-    for (size_t i = 0; i < trk_.size(); i++) {
-      MapperMap *m = AsMapperMap(trk_[i]->map_);
-      if (m && !m->IsThreaded() && m->BeginUpdate()) {  // a started mapper thread does its own UpdateMap
-        mm.push_back(m);
-        mm_trk.push_back(static_cast<int>(i));
-      }
-    }
-  }
-  const int M = static_cast<int>(mm.size());
-  if (M == 0) return;
-  vector<vector<sdvl_search_req>> per(M);
-  vector<sdvl_search_res> res;
-  vector<size_t> begin(M + 1, 0);
-  // UpdateCandidates with the depth filter on the device: one filter state per request, outcomes beside the search results;
-  // the rows of the points the trackers follow are patched in the same submission (same context, same stream)
-  const bool dev_filter = MapperMap::DeviceFilter();
-  vector<vector<sdvl_depth_state>> per_st(M);
-  vector<sdvl_depth_state> states;
-  vector<sdvl_depth_out> fout;
-  const sdvl_depth_params fparams = mm[0]->FilterParams();
-  // Depth cameras (SDVL::SetDepthMapping): when a mapper of the step has the switch on, the candidate passes go through the measured
-  // filter — still one launch for all trackers.  depth_of[k]: the depth image of the step's frame, for a mapper with the switch on whose
-  // update works on that very frame; the requests of every other mapper are in no job and take the triangulated rule.
-  vector<const DepthImage *> depth_of(M, nullptr);
-  const MapperMap *measuring = nullptr;
-  for (int k = 0; k < M; k++) {
-    if (!mm[k]->DepthMapping()) continue;
-    if (!dev_filter) throw std::runtime_error("mapper: depth mapping (SDVL::SetDepthMapping) needs the depth filter on the device");
-    const sdvl_depth_measure_params a = mm[k]->DepthMeasureParams(trk_[mm_trk[k]]->depth_rule_);
-    if (measuring) {
-      const sdvl_depth_measure_params b = measuring->DepthMeasureParams(trk_[mm_trk[k]]->depth_rule_);
-      if (a.noise_abs != b.noise_abs || a.noise_quad != b.noise_quad) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth noise parameters");
-    }
-    measuring = mm[k];
-    if (mm[k]->CurrentFrame().get() == trk_[mm_trk[k]]->step_frame_) depth_of[k] = DepthOf(mm_trk[k]);
-  }
-  vector<uint8_t> depth_status;  // per candidate request, with `measuring`
-  auto launch = [&](bool filter = false) {  // search everything the maps emitted, leave the offsets in `begin`
-    // the requests go from the maps' lists straight into the context's pinned batch (device layout, frames by slot)
-    Concatenate(per, nullptr, &begin);
-    const size_t total = begin[M];
-    states.clear();
-    res.resize(std::max<size_t>(total, 1));   // every record is written by the call below (no clearing pass over MBs)
-    fout.resize(std::max<size_t>(filter ? total : 0, 1));
-    if (total == 0) return;
-    sdvl_ctx *ctx = dev_->ctx();
-    sdvl_search_req_packed *packed = nullptr;
-    dev_->Check(sdvl_search_begin(ctx, static_cast<int>(total), &packed), "sdvl_search_begin");
-    size_t o = 0;
-    for (int k = 0; k < M; k++) {
-      for (const sdvl_search_req &r : per[k]) {
-        sdvl_search_req_packed &d = packed[o++];
-        d.cur = sdvl_search_slot(ctx, r.cur, r.cur_pose);
-        d.ref = sdvl_search_slot(ctx, r.ref, r.ref_pose);
-        if (d.cur < 0 || d.ref < 0) dev_->Check(d.cur < 0 ? d.cur : d.ref, "sdvl_search_slot");
-        d.level = r.level; d.fixed = r.fixed;
-        d.px[0] = r.px[0]; d.px[1] = r.px[1];
-        d.bearing[0] = r.bearing[0]; d.bearing[1] = r.bearing[1]; d.bearing[2] = r.bearing[2];
-        d.idepth = r.idepth; d.idepth_std = r.idepth_std;
-        d.px0[0] = r.px0[0]; d.px0[1] = r.px0[1];
-        std::memcpy(d.desc, r.desc, 32);
-      }
-      per[k].clear();
-      if (filter) {
-        states.insert(states.end(), per_st[k].begin(), per_st[k].end());
-        per_st[k].clear();
-      }
-    }
-    const sdvl_camera c = trk_[0]->camera_->abi();
-    const sdvl_search_params sp = SearchParams();
-    if (filter && measuring) {
-      if (states.size() != total) throw std::runtime_error("mapper: one filter state per candidate request");
-      vector<sdvl_depth_job> jobs;
-      const sdvl_depth_seed_params *rule = nullptr;
-      int width = 0, height = 0;
-      for (int k = 0; k < M; k++) {
-        const DepthImage *d = depth_of[k];
-        if (!d || begin[k] == begin[k + 1]) continue;
-        const sdvl_depth_seed_params *r = &trk_[mm_trk[k]]->depth_rule_;
-        if (rule && std::memcmp(rule, r, sizeof(*rule)) != 0) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth seeding rule");
-        rule = r;
-        width = mm[k]->CurrentFrame()->GetWidth();
-        height = mm[k]->CurrentFrame()->GetHeight();
-        jobs.push_back(sdvl_depth_job{d->data, d->on_device ? 1 : 0, d->step, d->format, 0, d->scale, static_cast<int>(begin[k]), static_cast<int>(begin[k + 1])});
-      }
-      if (jobs.empty()) { width = 1; height = 1; }  // (no request has an image: nothing is looked up)
-      const sdvl_depth_measure_params mp = measuring->DepthMeasureParams(rule ? *rule : sdvl_depth_seed_params{0.0, 0.0, 0.0, 0, 0});
-      const Camera &camera = *trk_[0]->camera_;
-      const sdvl_distortion dist = camera.distortion();
-      depth_status.resize(total);
-      dev_->Check(sdvl_search_run_filter_measured(ctx, static_cast<int>(total), &c, &sp, states.data(), &fparams, tables_.set, static_cast<int>(jobs.size()),
-                                                  jobs.data(), width, height, camera.HasDistortion() ? &dist : nullptr, &mp, res.data(), fout.data(),
-                                                  depth_status.data()),
-                  "sdvl_search_run_filter_measured");
-    } else if (filter) {
-      if (states.size() != total) throw std::runtime_error("mapper: one filter state per candidate request");
-      dev_->Check(sdvl_search_run_filter(ctx, static_cast<int>(total), &c, &sp, states.data(), &fparams, tables_.set, res.data(), fout.data()),
-                  "sdvl_search_run_filter");
-    } else {
-      dev_->Check(sdvl_search_run(ctx, static_cast<int>(total), &c, &sp, res.data()), "sdvl_search_run");
-    }
-  };
-  std::unique_ptr<StageClock> sub(new StageClock(ST_MAP_CANDIDATES));
-  for (;;) {  // UpdateCandidates, one occurrence pass at a time
-    vector<char> more(M, 0);
-    {
-      StageClock c(ST_MAP_EMIT);
-      ParallelFor(M, [&](int k) { more[k] = mm[k]->EmitCandidates(&per[k], dev_filter ? &per_st[k] : nullptr) ? 1 : 0; });
-    }
-    if (std::find(more.begin(), more.end(), 1) == more.end()) break;
-    {
-      StageClock c(ST_MAP_SEARCH);
-      launch(dev_filter);
-    }
-    StageClock c(ST_MAP_APPLY);
-    ParallelFor(M, [&](int k) {
-      if (more[k]) mm[k]->ApplyCandidates(res.data() + begin[k], dev_filter ? fout.data() + begin[k] : nullptr,
-                                          measuring && !depth_status.empty() ? depth_status.data() + begin[k] : nullptr);
-    });
-  }
-  vector<int> kf_idx;
-  for (int k = 0; k < M; k++)
-    if (mm[k]->IsKeyframeUpdate()) kf_idx.push_back(k);
-  const int K = static_cast<int>(kf_idx.size());
-  sub.reset(new StageClock(ST_MAP_CONNECTIONS));
-  if (K > 0) LookupKeyframeFeatures(mm, mm_trk, kf_idx);  // (returns at once unless a mapper has depth edges on)
-  if (K > 0) {
-    ParallelFor(K, [&](int q) {
-      MapperMap *m = mm[kf_idx[q]];
-      m->CheckConnections();
-      m->EmitConnectionsPoints(&per[kf_idx[q]]);
-    });
-    launch();
-    vector<char> need(K, 0);
-    ParallelFor(K, [&](int q) {
-      MapperMap *m = mm[kf_idx[q]];
-      m->ApplyConnectionsPoints(res.data() + begin[kf_idx[q]]);
-      need[q] = m->PrepareInitCandidates() ? 1 : 0;
-    });
-    sub.reset(new StageClock(ST_MAP_INIT));
-    vector<shared_ptr<Frame>> to_filter;
-    for (int q = 0; q < K; q++)
-      if (need[q]) to_filter.push_back(mm[kf_idx[q]]->CurrentFrame());
-    if (!to_filter.empty()) {
-      Frame::FilterCornersBatch(to_filter);
-      if (measuring) MeasureKeyframeCorners(mm, mm_trk, kf_idx, need, depth_of);
-      ParallelFor(K, [&](int q) { if (need[q]) mm[kf_idx[q]]->EmitInitCandidates(&per[kf_idx[q]]); });
-      launch();
-      ParallelFor(K, [&](int q) { if (need[q]) mm[kf_idx[q]]->ApplyInitCandidates(res.data() + begin[kf_idx[q]]); });
-    }
-  }
-  sub.reset(new StageClock(ST_MAP_FINISH));
-  ParallelFor(M, [&](int k) { mm[k]->FinishUpdate(); });
-  // local bundle adjustment (map.cc:130-137): the windows of all the step's mappers in ONE sdvl_bundle_adjust call
-  bool any_bundle = false;
-  for (int k = 0; k < M; k++) any_bundle = any_bundle || mm[k]->BundleAdjustmentOn();
-  if (!any_bundle) return;
-  sub.reset(new StageClock(ST_MAP_BUNDLE));
-  vector<BundleProblem> windows(M);
-  vector<char> has(M, 0);
-  ParallelFor(M, [&](int k) { has[k] = mm[k]->PrepareBundle(&windows[k]) ? 1 : 0; });
-  vector<BundleProblem *> problems;
-  vector<int> whose;
-  for (int k = 0; k < M; k++)
-    if (has[k]) {
-      problems.push_back(&windows[k]);
-      whose.push_back(k);
-    }
-  if (problems.empty()) return;
-  vector<sdvl_bundle_result> results;
-  vector<vector<Frame *>> moved;
-  double bf = 0.0;  // depth edges: the windows of the mappers that have them on carry depths; the trackers of a batch share bf
-  for (int k : whose) {
-    if (!mm[k]->DepthBundleOn()) continue;
-    if (bf > 0.0 && bf != mm[k]->DepthBundleBf()) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth edges' bf");
-    bf = mm[k]->DepthBundleBf();
-  }
-  Bundle::Solve(dev_, *trk_[0]->camera_, problems, &results, &moved, bf);
-  for (size_t j = 0; j < problems.size(); j++) mm[whose[j]]->FinishBundle(windows[whose[j]], results[j], moved[j]);
 }
 
 }  // namespace sdvl

@@ -18,8 +18,8 @@ class SDVLBatch {
   void HandleFrames(const std::vector<Image> &imgs, FrameStats *stats);
   // the same with the frames' registered depth images for the trackers that seed from depth (SDVL::SetDepthSeeding): depths is empty or
   // has one entry per tracker, and single entries may be empty (for a tracker that seeds from a stereo pair, SDVL::SetStereoSeeding, the
-  // entry is the pair's right image, DEPTH_RIGHT8, read inside the step's ONE sdvl_stereo_depth call).  A depth image is read inside the step's ONE sdvl_depth_seed call only
-  // (FinishKeyframes); nothing is copied or kept, and the look-ahead does not need it.
+  // entry is the pair's right image, DEPTH_RIGHT8, read inside the step's ONE sdvl_stereo_depth call).  A depth image is read inside the
+  // step's ONE sdvl_depth_seed call only (FinishKeyframes); nothing is copied or kept, and the look-ahead does not need it.
   void HandleFrames(const std::vector<Image> &imgs, const std::vector<DepthImage> &depths, FrameStats *stats);
   // Round 4: a caller that already holds the images of the NEXT step (a sequence from disk, frames resident in HBM) names them before
   // the current step: their pyramids and corner detection — all that depends on the image alone, 45 % of a step's vector instructions —
@@ -64,19 +64,35 @@ class SDVLBatch {
   void CollectKeyframes(Step &s, bool fetch_counts);
   void EpilogueAndMapper(Step &s);
   void FinishKeyframes(Step &s);
+  // ---- batch_depth.cc: the calls of a step that read a frame's second image (depth image, right image), ONE call for all trackers each
+  struct MapStep;  // what the stages of the mappers' update hand to each other (defined in batch_internal.h)
   void SeedKeyframesFromDepth(Step &s, std::vector<const double *> *z, std::vector<const uint8_t *> *status);
-  void RunMappers();
-  void LookupKeyframeFeatures(const std::vector<MapperMap *> &mm, const std::vector<int> &mm_trk, const std::vector<int> &kf_idx);
-  void MeasureKeyframeCorners(const std::vector<MapperMap *> &mm, const std::vector<int> &mm_trk, const std::vector<int> &kf_idx, const std::vector<char> &need,
-                              const std::vector<const DepthImage *> &depth_of);
-  const std::vector<DepthImage> *step_depths_ = nullptr;  // the depth images of the step in flight (HandleFrames)
+  void MeasureKeyframeCorners(MapStep &m, const std::vector<char> &need);
+  void LookupKeyframeFeatures(MapStep &m);
+  void SearchFilterMeasured(MapStep &m, int total, const sdvl_camera &cam, const sdvl_search_params &sp);
+  const std::vector<DepthImage> *step_depths_ = nullptr;  // the depth images of the step in flight (HandleFrames, batch.cc)
   const DepthImage *DepthOf(int i) const;                  // tracker i's, null: none
-  std::vector<double> depth_z_;                            // sdvl_depth_seed's results for the step's keyframes
+  struct CameraAndLens {  // the camera of the batch as the device calls take it, and its lens if it has one
+    sdvl_camera cam;
+    sdvl_distortion dist;
+    bool has_lens;
+    const sdvl_distortion *lens() const { return has_lens ? &dist : nullptr; }
+  };
+  CameraAndLens BatchCamera() const;
+  std::vector<double> depth_z_;  // the results of the last of those calls; its owners' ranges are handed on as pointers into them
   std::vector<uint8_t> depth_status_;
-  std::vector<double> stereo_disparity_;                   // sdvl_stereo_depth's disparities (stereo trackers: z and status lie in the two above)
+  void SizeDepthResults(int n);
+  // ---- batch_mapper.cc: SDVL::Mapping() of sequential mode for the trackers that own a real mapper, in stages over a MapStep
+  void RunMappers();
+  bool CollectMappers(MapStep &m);
+  void SetUpMeasuring(MapStep &m);
+  void PackAndSearch(MapStep &m, bool filter);
+  void CandidatePasses(MapStep &m);
+  void KeyframePasses(MapStep &m);
+  void BundleWindows(MapStep &m);
   // ---- batch_tables.cc: the device-resident tracking tables.  The set and the rows on their way to it; besides the table functions
-  // the tabled step (batch_tracked.cc) uses them, and batch.cc where it releases the set, appends a keyframe's seeds (FinishKeyframes)
-  // and lets the mapper's depth filter patch the rows (RunMappers)
+  // the tabled step (batch_tracked.cc) uses them, batch.cc where it releases the set and appends a keyframe's seeds (FinishKeyframes),
+  // and the mappers' stage where it lets the depth filter patch the rows (PackAndSearch)
   struct Tables {
     sdvl_track_set *set = nullptr;
     int cells = 0, cap = 0;

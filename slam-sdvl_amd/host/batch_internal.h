@@ -1,6 +1,6 @@
 // batch_internal.h — what the translation units of SDVLBatch (batch.cc, batch_tables.cc, batch_reloc.cc, batch_tracked.cc,
-// batch_host_step.cc) share besides batch.h (not installed).  Helpers that run once per request or per tracker in a loop are inline
-// here: the build has no link-time optimisation.
+// batch_host_step.cc, batch_depth.cc, batch_mapper.cc) share besides batch.h (not installed).  Helpers that run once per request or per
+// tracker in a loop are inline here: the build has no link-time optimisation.
 #ifndef SDVL_BATCH_INTERNAL_H_
 #define SDVL_BATCH_INTERNAL_H_
 
@@ -34,6 +34,27 @@ struct SDVLBatch::Step {
   std::unique_ptr<StageClock> clk;   // the host stage the step is in
   void Stage(int id) { clk.reset(new StageClock(id)); }
   int R() const { return static_cast<int>(run.size()); }
+};
+
+// What the stages of the sequential mappers' update (batch_mapper.cc) hand to each other.  Indices k run over the mappers that began an
+// update this step.
+struct SDVLBatch::MapStep {
+  std::vector<MapperMap *> mm;
+  std::vector<int> trk;  // whose mapper mm[k] is
+  int M() const { return static_cast<int>(mm.size()); }
+  std::vector<std::vector<sdvl_search_req>> per;  // the requests each mapper emitted for the next search
+  std::vector<size_t> begin;                      // where those of mapper k lay in the last search, M + 1 entries
+  std::vector<sdvl_search_res> res;               // its results
+  bool dev_filter = false;                        // the candidate passes run the depth filter on the device:
+  std::vector<std::vector<sdvl_depth_state>> per_st;  // one filter state per request, as emitted
+  std::vector<sdvl_depth_state> states;               // ... of the last search
+  std::vector<sdvl_depth_out> fout;                   // its outcomes
+  sdvl_depth_params fparams;
+  const MapperMap *measuring = nullptr;        // a mapper with depth mapping on (SDVL::SetDepthMapping), if the step has one
+  std::vector<const DepthImage *> depth_of;    // the depth image mapper k's requests are measured in, null: none
+  std::vector<uint8_t> depth_status;           // per candidate request, with `measuring`
+  std::vector<int> kf_idx;                     // the mappers whose update takes a new keyframe
+  std::unique_ptr<StageClock> sub;             // the ST_MAP_* stage the update is in
 };
 
 // the requests of per.size() sources behind each other: (*begin)[k] = where those of source k start, the last entry = their number.
