@@ -11,7 +11,8 @@
  *
  * Depth cameras are an addition (the reference reads no depth image): sdvl_depth_seed / sdvl_depth_lookup read a registered depth image at
  * a keyframe's corners / at tracked features, sdvl_depth_filter_measured feeds the mapper's depth filter, and sdvl_bundle_adjust_depth
- * gives local bundle adjustment depth edges (g2o's EdgeStereoSE3ProjectXYZ).
+ * gives local bundle adjustment depth edges (g2o's EdgeStereoSE3ProjectXYZ).  Stereo cameras too: sdvl_stereo_depth / sdvl_stereo_lookup
+ * match a rectified right image at a keyframe's corners / at tracked features, sdvl_depth_filter_stereo feeds the mapper's depth filter.
  *
  * Poses are 7 doubles (qw,qx,qy,qz,tx,ty,tz) of Frame::pose_ (world -> camera), extra/se3.h:32-78.
  * Threading: one sdvl_ctx per host thread (tracker / mapper); frames may be shared read-only across contexts
@@ -620,6 +621,16 @@ typedef struct sdvl_stereo_params {
 
 int sdvl_stereo_depth(sdvl_ctx *ctx, int n_jobs, const sdvl_stereo_job *jobs, int n_corners, const int32_t *xyl, const sdvl_camera *cam,
                       const sdvl_stereo_params *p, double *out_z, double *out_disparity, uint8_t *out_status, int32_t *out_ok_per_job);
+/* The same rule at positions of the caller's own: px2[n][2] are LEVEL-0 positions of the left image (a tracked feature's found pixel,
+ * sub-pixel) and level[n] the pyramid level each was found on.  Per position the centre is (X, Y) = (floor(px + 0.5), floor(py + 0.5)) and
+ * the stride s = 1 << level; X need not be a multiple of s.  From there on window, range, cost, ties, status order, parabola and
+ * z = fx baseline / disparity are sdvl_stereo_depth's at (X, Y, s), word for word: a level-l corner (x, y) looked up anywhere within half
+ * a pixel of (x s, y s) gives sdvl_stereo_depth's bits.  A position that is not finite is OUTSIDE; a position no job names comes back
+ * NOMATCH.  Jobs (c_* indexing the positions), staging, refusals, the refusal of overlapping ranges and out_ok_per_job as for
+ * sdvl_stereo_depth; refused too: a level outside the left frame's pyramid.  One launch (stereo_lookup: one wave per position, lane per
+ * disparity).  tests/stereo_lookup_restatement.py is its specification. */
+int sdvl_stereo_lookup(sdvl_ctx *ctx, int n_jobs, const sdvl_stereo_job *jobs, int n, const double *px2, const int32_t *level, const sdvl_camera *cam,
+                       const sdvl_stereo_params *p, double *out_z, double *out_disparity, uint8_t *out_status, int32_t *out_ok_per_job);
 
 /* ---- the mapper's depth filter with a MEASURED depth (this project's rule; tests/depth_measure_restatement.py is its specification) -----
  * sdvl_depth_filter / sdvl_search_run_filter for a depth camera.  jobs[]: the depth image of the CURRENT frame of the requests
@@ -654,6 +665,36 @@ int sdvl_search_run_filter_measured(sdvl_ctx *ctx, int n, const sdvl_camera *cam
                                     const sdvl_depth_params *fp, struct sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width,
                                     int height, const sdvl_distortion *dist, const sdvl_depth_measure_params *mp, sdvl_search_res *out,
                                     sdvl_depth_out *fout, uint8_t *out_status);
+
+/* ---- the same with the depth a STEREO pair gives at the found pixel (tests/stereo_lookup_restatement.py is its specification) -----------
+ * sdvl_depth_filter / sdvl_search_run_filter for a stereo rig.  jobs[]: sdvl_stereo_job as above, `left` the CURRENT frame of the requests
+ * c_begin .. c_end and `right` its rectified right image (c_* indexing the requests); a request in no job has no pair.  Per request:
+ *   miss, or a hit in no job   as sdvl_depth_filter (a miss: Unpromote; a hit: the triangulated update, the same bits); out_status 255
+ *   hit at px on level l       sdvl_stereo_lookup's rule at (px, l), l clamped to 0 .. SDVL_MAX_LEVELS - 1
+ *   status not OK              the triangulated update of sdvl_depth_filter: the same bits
+ *   status OK, depth z_c       exactly the measured update above with noise_abs = 0 and noise_quad = disparity_sigma / (fx baseline): from
+ *                              z = fx b / d follows dz = z^2 / (fx b) dd, so tau = disparity_sigma z_c^2 / (fx b)
+ * out_status[n]: SDVL_STEREO_* of a request that was matched, 255 for one that was not.  disparity_sigma 0: 0.25 px, an order of
+ * magnitude that nobody has measured against a real pair (on the synthetic `shelf` scene the matcher's median error is 0.04 - 0.07 px).
+ * One submission and one wait: the search (the first entry), stereo_lookup over the search results where they lie in HBM (one wave per
+ * request; the wave of a miss or of a request in no job writes 255 and leaves), then the lane-per-request filter, which reads the z and
+ * status the lookup left.  The strip LDS is sized from the rule's range and the coarsest level of the jobs' left frames.  Right images are
+ * read or staged as for sdvl_stereo_depth.  Refused with a message: what sdvl_depth_filter and sdvl_stereo_depth refuse (null parameters,
+ * baseline, rule fields, a lens, stride, a left frame of another context, a range outside n, overlapping ranges), a disparity_sigma that
+ * is negative or not finite, a stated level outside 0 .. SDVL_MAX_LEVELS - 1 or (for a hit in a job) outside the left frame's pyramid. */
+typedef struct sdvl_stereo_measure_params {
+  sdvl_stereo_params rule;
+  double disparity_sigma; /* pixels */
+} sdvl_stereo_measure_params;
+#define SDVL_STEREO_DISPARITY_SIGMA 0.25 /* pixels: what disparity_sigma 0 stands for; not measured against a real pair */
+int sdvl_depth_filter_stereo(sdvl_ctx *ctx, int n, const double *cur_pose7, const double *ref_pose7, const double *bearing3, const int32_t *found,
+                             const double *px2, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state,
+                             const sdvl_depth_params *fp, struct sdvl_track_set *set, int n_jobs, const sdvl_stereo_job *jobs,
+                             const sdvl_stereo_measure_params *mp, sdvl_depth_out *fout, uint8_t *out_status);
+/* the same behind sdvl_search_begin / sdvl_search_slot: px and level are the search's own */
+int sdvl_search_run_filter_stereo(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
+                                  const sdvl_depth_params *fp, struct sdvl_track_set *set, int n_jobs, const sdvl_stereo_job *jobs,
+                                  const sdvl_stereo_measure_params *mp, sdvl_search_res *out, sdvl_depth_out *fout, uint8_t *out_status);
 
 /* ---- pose from matches: FeatureAlign::SelectInliers + OptimizePose (feature_align.cc:73-82,152-243,258-283,341-431) --
  * One job per frame.  obs[] are the frame's matched features in found order: ax, ay = feature bearing x/z, y/z

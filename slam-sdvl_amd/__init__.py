@@ -165,6 +165,11 @@ class StereoParams(C.Structure):
                 ("max_sad", C.c_int32), ("uniqueness", C.c_int32), ("pad_", C.c_int32), ("dist", C.c_void_p)]
 
 
+class StereoMeasureParams(C.Structure):
+    """sdvl_stereo_measure_params: the matcher's rule and the disparity noise in pixels (0: 0.25 px, not measured against a real pair)"""
+    _fields_ = [("rule", StereoParams), ("disparity_sigma", C.c_double)]
+
+
 class SynthView(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("u0", C.c_double), ("v0", C.c_double),
                 ("R", C.c_double * 9), ("t", C.c_double * 3), ("plane", C.c_double * 4),
@@ -200,7 +205,7 @@ ABI_SYMBOLS = [
     "sdvl_pyramid_build", "sdvl_frame_download_level", "sdvl_fast_num_cells", "sdvl_cell_kp_cap", "sdvl_fast_cells",
     "sdvl_detect_corners", "sdvl_frames_corner_counts", "sdvl_frame_download_corners", "sdvl_retain_best",
     "sdvl_frame_set_corners", "sdvl_frames_set_corners", "sdvl_frame_num_corners", "sdvl_shi_tomasi", "sdvl_orb_describe",
-    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_lookup", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_stereo_depth", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
+    "sdvl_frame_download_descriptors", "sdvl_filter_inputs", "sdvl_filter_inputs_begin", "sdvl_filter_inputs_end", "sdvl_filter_corners_begin", "sdvl_filter_corners_end", "sdvl_orb_describe_points", "sdvl_hamming_argmin", "sdvl_image_align", "sdvl_image_align_begin", "sdvl_image_align_end", "sdvl_align_store_create", "sdvl_align_store_destroy", "sdvl_align_store_write", "sdvl_image_align_begin_stored", "sdvl_search_points", "sdvl_search_begin", "sdvl_search_slot", "sdvl_search_run", "sdvl_align_patches", "sdvl_pose_from_matches", "sdvl_search_points_filter", "sdvl_search_run_filter", "sdvl_depth_filter", "sdvl_search_run_chain", "sdvl_search_chain_end", "sdvl_frame_footprint", "sdvl_undistort", "sdvl_frames_upload_undistorted", "sdvl_convert_gray", "sdvl_frames_upload_color", "sdvl_depth_seed", "sdvl_depth_lookup", "sdvl_depth_stage_begin", "sdvl_depth_stage_end", "sdvl_stereo_depth", "sdvl_stereo_lookup", "sdvl_depth_filter_measured", "sdvl_search_run_filter_measured", "sdvl_depth_filter_stereo", "sdvl_search_run_filter_stereo", "sdvl_ctx_set_wait_hook", "sdvl_ctx_wait_done", "sdvl_ctx_wait_block", "sdvl_ctx_health", "sdvl_ctx_counters",
     "sdvl_track_create", "sdvl_track_destroy", "sdvl_frame_register", "sdvl_frames_register", "sdvl_track_upload", "sdvl_track_append", "sdvl_track_align", "sdvl_track_search",
     "sdvl_track_collect", "sdvl_track_features", "sdvl_track_stats",
     "sdvl_synth_render", "sdvl_synth_render_scene", "sdvl_synth_scene_size", "sdvl_synth_scene_preset", "sdvl_synth_scene_preset_names",
@@ -810,6 +815,19 @@ class Context:
         (device pointers, pinned memory).  xyl [n][3] level coordinates and level; cam a Camera; baseline in metres; dist (k1, k2, p1, p2,
         k3) or None: a lens is refused; rule: min_depth, max_depth, max_disparity, max_sad, uniqueness (0: the default)
         -> (z float64 [n], disparity float64 [n], status uint8 [n], ok per job int32)"""
+        keep, arr, d5, p = self._stereo_args(jobs, baseline, dist, rule)
+        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3)
+        n = len(xyl)
+        z, disparity, status = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8)
+        ok = np.zeros(max(len(jobs), 1), np.int32)
+        self.lib.sdvl_stereo_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        self._check(self.lib.sdvl_stereo_depth(self.h, len(jobs), C.addressof(arr), n, xyl.ctypes.data, C.addressof(cam), C.addressof(p),
+                                               z.ctypes.data, disparity.ctypes.data, status.ctypes.data, ok.ctypes.data))
+        del keep
+        return z[:n], disparity[:n], status[:n], ok[:len(jobs)]
+
+    def _stereo_args(self, jobs, baseline, dist, rule):
+        """the stereo side of an entry -> (objects to keep alive, StereoJob array, distortion or None, StereoParams)"""
         keep, arr = [], (StereoJob * max(len(jobs), 1))()
         for j, job in enumerate(jobs):
             if isinstance(job, StereoJob):
@@ -823,13 +841,22 @@ class Context:
         p = StereoParams(float(baseline), float(rule.pop("min_depth", 0.0)), float(rule.pop("max_depth", 0.0)), int(rule.pop("max_disparity", 0)),
                          int(rule.pop("max_sad", 0)), int(rule.pop("uniqueness", 0)), 0, C.addressof(d5) if d5 is not None else None)
         assert not rule, "unknown rule field %s" % list(rule)
-        xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3)
-        n = len(xyl)
+        return keep, arr, d5, p
+
+    def stereo_lookup(self, jobs, px, levels, cam, baseline, dist=None, **rule):
+        """sdvl_stereo_lookup: stereo_depth's rule at level-0 positions px [n][2] of the left image (sub-pixel) with the window stride of
+        levels [n]; jobs, cam, baseline, dist and rule as for stereo_depth, the jobs' ranges indexing the positions
+        -> (z float64 [n], disparity float64 [n], status uint8 [n], ok per job int32)"""
+        keep, arr, d5, p = self._stereo_args(jobs, baseline, dist, rule)
+        px = np.ascontiguousarray(px, np.float64).reshape(-1, 2)
+        levels = np.ascontiguousarray(levels, np.int32).reshape(-1)
+        n = len(px)
+        assert len(levels) == n
         z, disparity, status = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8)
         ok = np.zeros(max(len(jobs), 1), np.int32)
-        self.lib.sdvl_stereo_depth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        self._check(self.lib.sdvl_stereo_depth(self.h, len(jobs), C.addressof(arr), n, xyl.ctypes.data, C.addressof(cam), C.addressof(p),
-                                               z.ctypes.data, disparity.ctypes.data, status.ctypes.data, ok.ctypes.data))
+        self.lib.sdvl_stereo_lookup.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        self._check(self.lib.sdvl_stereo_lookup(self.h, len(jobs), C.addressof(arr), n, px.ctypes.data, levels.ctypes.data, C.addressof(cam),
+                                                C.addressof(p), z.ctypes.data, disparity.ctypes.data, status.ctypes.data, ok.ctypes.data))
         del keep
         return z[:n], disparity[:n], status[:n], ok[:len(jobs)]
 
@@ -918,6 +945,65 @@ class Context:
             len(jobs), C.addressof(arr), width, height, C.addressof(d5) if d5 is not None else None, C.addressof(mp), C.addressof(res),
             C.addressof(fout), status.ctypes.data))
         del keep
+        return res, fout, status[:n]
+
+    def depth_filter_stereo(self, cur_poses, ref_poses, bearings, found, px, levels, cam, states, fparams, jobs, baseline, disparity_sigma=0.0,
+                            dist=None, track_set=None, **rule):
+        """sdvl_depth_filter_stereo: depth_filter's arguments and the found level of every item [n]; jobs as for stereo_depth, each the left
+        frame and right image of the current frame of the items c_begin .. c_end (an item in no job has no pair); disparity_sigma in pixels
+        (0: 0.25, not measured against a real pair) and rule: 0 takes the default
+        -> (DepthOut array, status uint8 [n]: stereo_depth's codes, 255 where nothing was matched)"""
+        n = len(states)
+        cp, rp, bv, fd, pp = self._stated_results(n, cur_poses, ref_poses, bearings, found, px)
+        lv = np.ascontiguousarray(levels, np.int32).reshape(n)
+        keep, arr, d5, p = self._stereo_args(jobs, baseline, dist, rule)
+        mp = StereoMeasureParams(p, float(disparity_sigma))
+        fout, status = (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
+        vp = C.c_void_p
+        self.lib.sdvl_depth_filter_stereo.argtypes = [vp, C.c_int] + [vp] * 10 + [C.c_int, vp, vp, vp, vp]
+        self._check(self.lib.sdvl_depth_filter_stereo(
+            self.h, n, cp.ctypes.data, rp.ctypes.data, bv.ctypes.data, fd.ctypes.data, pp.ctypes.data, lv.ctypes.data, C.addressof(cam),
+            C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None, len(jobs), C.addressof(arr),
+            C.addressof(mp), C.addressof(fout), status.ctypes.data))
+        del keep, d5
+        return fout, status[:n]
+
+    def _pack_search_requests(self, reqs):
+        """sdvl_search_begin / _slot: the requests (frames by handle) into the context's packed records"""
+        n = len(reqs)
+        lib = self.lib
+        lib.sdvl_search_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(SearchReqPacked))]
+        lib.sdvl_search_slot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        packed = C.POINTER(SearchReqPacked)()
+        self._check(lib.sdvl_search_begin(self.h, n, C.byref(packed)))
+        for i, r in enumerate(reqs):
+            d = packed[i]
+            d.cur = lib.sdvl_search_slot(self.h, r.cur, r.cur_pose)
+            d.ref = lib.sdvl_search_slot(self.h, r.ref, r.ref_pose)
+            assert d.cur >= 0 and d.ref >= 0
+            d.level, d.fixed = r.level, r.fixed
+            d.px[0], d.px[1] = r.px[0], r.px[1]
+            for k in range(3):
+                d.bearing[k] = r.bearing[k]
+            d.idepth, d.idepth_std = r.idepth, r.idepth_std
+            d.px0[0], d.px0[1] = r.px0[0], r.px0[1]
+            for k in range(32):
+                d.desc[k] = r.desc[k]
+
+    def search_points_filter_stereo(self, reqs, cam, sp, states, fparams, jobs, baseline, disparity_sigma=0.0, dist=None, track_set=None, **rule):
+        """sdvl_search_begin / _slot / sdvl_search_run_filter_stereo: search_points_filter's requests (frames by handle) with the stereo
+        side of depth_filter_stereo -> (SearchRes array, DepthOut array, status uint8 [n])"""
+        n = len(reqs)
+        self._pack_search_requests(reqs)
+        keep, arr, d5, p = self._stereo_args(jobs, baseline, dist, rule)
+        mp = StereoMeasureParams(p, float(disparity_sigma))
+        res, fout, status = (SearchRes * n)(), (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
+        vp = C.c_void_p
+        self.lib.sdvl_search_run_filter_stereo.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        self._check(self.lib.sdvl_search_run_filter_stereo(
+            self.h, n, C.addressof(cam), C.addressof(sp), C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None,
+            len(jobs), C.addressof(arr), C.addressof(mp), C.addressof(res), C.addressof(fout), status.ctypes.data))
+        del keep, d5
         return res, fout, status[:n]
 
     def track_points_download(self, track_set):

@@ -107,15 +107,17 @@ void SDVLBatch::SeedKeyframesFromDepth(Step &s, vector<const double *> *z, vecto
 }
 
 // Depth cameras inside the mapper: the filtered corners of all the step's new keyframes whose mapper measures, looked up in their frames'
-// depth images by ONE sdvl_depth_seed call (as SeedKeyframesFromDepth does for the keyframes the driver seeds) and handed to the mappers
+// depth images by ONE sdvl_depth_seed call (as SeedKeyframesFromDepth does for the keyframes the driver seeds) and handed to the mappers.
+// Stereo mapping: matched in their frames' right images by ONE sdvl_stereo_depth call, z / status handed over unchanged
 void SDVLBatch::MeasureKeyframeCorners(MapStep &m, const vector<char> &need) {
   DepthJobs jobs;
   vector<int32_t> xyl;
   for (size_t q = 0; q < m.kf_idx.size(); q++) {
     const int k = m.kf_idx[q];
-    if (!need[q] || !m.mm[k]->DepthMapping()) continue;
+    if (!need[q] || !m.mm[k]->Measuring()) continue;
     const Frame &kf = *m.mm[k]->CurrentFrame();
-    if (jobs.AddDepth(k, m.depth_of[k], trk_[m.trk[k]]->depth_rule_, kf.NumFiltered(), kf.GetWidth(), kf.GetHeight()))
+    if (m.mm[k]->StereoMapping() ? jobs.AddStereo(k, kf.device(), m.depth_of[k], trk_[m.trk[k]]->stereo_rule_, kf.NumFiltered(), kf.GetWidth(), kf.GetHeight())
+                                 : jobs.AddDepth(k, m.depth_of[k], trk_[m.trk[k]]->depth_rule_, kf.NumFiltered(), kf.GetWidth(), kf.GetHeight()))
       AppendFilteredCorners(kf, &xyl);
     else
       m.mm[k]->SetCornerDepths(nullptr, nullptr);
@@ -124,9 +126,18 @@ void SDVLBatch::MeasureKeyframeCorners(MapStep &m, const vector<char> &need) {
   SizeDepthResults(jobs.items());
   vector<int32_t> ok(jobs.size(), 0);
   const CameraAndLens c = BatchCamera();
-  dev_->Check(sdvl_depth_seed(dev_->ctx(), jobs.size(), jobs.depth_jobs(), jobs.width(), jobs.height(), jobs.items(), xyl.data(), &c.cam, c.lens(),
-                              jobs.rule(), depth_z_.data(), depth_status_.data(), ok.data()),
-              "sdvl_depth_seed");
+  if (jobs.stereo()) {
+    sdvl_stereo_params sp = *jobs.stereo_rule();
+    sp.dist = c.lens();  // (refused: rectified pairs only)
+    vector<double> disparity(jobs.items(), 0.0);
+    dev_->Check(sdvl_stereo_depth(dev_->ctx(), jobs.size(), jobs.stereo_jobs(), jobs.items(), xyl.data(), &c.cam, &sp, depth_z_.data(), disparity.data(),
+                                  depth_status_.data(), ok.data()),
+                "sdvl_stereo_depth");
+  } else {
+    dev_->Check(sdvl_depth_seed(dev_->ctx(), jobs.size(), jobs.depth_jobs(), jobs.width(), jobs.height(), jobs.items(), xyl.data(), &c.cam, c.lens(),
+                                jobs.rule(), depth_z_.data(), depth_status_.data(), ok.data()),
+                "sdvl_depth_seed");
+  }
   for (const DepthJobs::Range &r : jobs.ranges()) m.mm[r.owner]->SetCornerDepths(depth_z_.data() + r.begin, depth_status_.data() + r.begin);
 }
 
@@ -158,22 +169,37 @@ void SDVLBatch::LookupKeyframeFeatures(MapStep &m) {
 }
 
 // The measured form of PackAndSearch (batch_mapper.cc): the requests m.begin[k] .. m.begin[k + 1] of every mapper whose update works on
-// the step's frame are looked up in that frame's depth image; the requests of every other mapper are in no job
+// the step's frame are looked up in that frame's depth image; the requests of every other mapper are in no job.  Stereo mapping: matched
+// against that frame's right image (sdvl_search_run_filter_stereo), the frame being the jobs' left one
 void SDVLBatch::SearchFilterMeasured(MapStep &m, int total, const sdvl_camera &cam, const sdvl_search_params &sp) {
   DepthJobs jobs;
+  const bool stereo = m.measuring->StereoMapping();
   for (int k = 0; k < m.M(); k++) {
     const int n = static_cast<int>(m.begin[k + 1] - m.begin[k]);
     if (!m.depth_of[k] || n == 0) {
       jobs.Skip(n);
       continue;
     }
-    jobs.AddDepth(k, m.depth_of[k], trk_[m.trk[k]]->depth_rule_, n, m.mm[k]->CurrentFrame()->GetWidth(), m.mm[k]->CurrentFrame()->GetHeight());
+    if (stereo)
+      jobs.AddStereo(k, m.mm[k]->CurrentFrame()->device(), m.depth_of[k], trk_[m.trk[k]]->stereo_rule_, n, m.mm[k]->CurrentFrame()->GetWidth(),
+                     m.mm[k]->CurrentFrame()->GetHeight());
+    else
+      jobs.AddDepth(k, m.depth_of[k], trk_[m.trk[k]]->depth_rule_, n, m.mm[k]->CurrentFrame()->GetWidth(), m.mm[k]->CurrentFrame()->GetHeight());
+  }
+  m.depth_status.resize(total);
+  if (stereo) {  // (no request has a pair: nothing is matched; the rule is still checked, so it is the measuring tracker's)
+    sdvl_stereo_measure_params mp = {jobs.stereo_rule() ? *jobs.stereo_rule() : trk_[m.measuring_trk]->stereo_rule_, m.measuring->DisparitySigma()};
+    const CameraAndLens c = BatchCamera();
+    mp.rule.dist = c.lens();  // (refused: rectified pairs only)
+    dev_->Check(sdvl_search_run_filter_stereo(dev_->ctx(), total, &cam, &sp, m.states.data(), &m.fparams, tables_.set, jobs.size(), jobs.stereo_jobs(), &mp,
+                                              m.res.data(), m.fout.data(), m.depth_status.data()),
+                "sdvl_search_run_filter_stereo");
+    return;
   }
   // (no request has an image: nothing is looked up, and the call names an image of one pixel)
   const int width = jobs.empty() ? 1 : jobs.width(), height = jobs.empty() ? 1 : jobs.height();
   const sdvl_depth_measure_params mp = m.measuring->DepthMeasureParams(jobs.rule() ? *jobs.rule() : sdvl_depth_seed_params{0.0, 0.0, 0.0, 0, 0});
   const CameraAndLens c = BatchCamera();
-  m.depth_status.resize(total);
   dev_->Check(sdvl_search_run_filter_measured(dev_->ctx(), total, &cam, &sp, m.states.data(), &m.fparams, tables_.set, jobs.size(), jobs.depth_jobs(), width,
                                               height, c.lens(), &mp, m.res.data(), m.fout.data(), m.depth_status.data()),
               "sdvl_search_run_filter_measured");

@@ -50,8 +50,9 @@ struct SDVLBatch::MapStep {
   std::vector<sdvl_depth_state> states;               // ... of the last search
   std::vector<sdvl_depth_out> fout;                   // its outcomes
   sdvl_depth_params fparams;
-  const MapperMap *measuring = nullptr;        // a mapper with depth mapping on (SDVL::SetDepthMapping), if the step has one
-  std::vector<const DepthImage *> depth_of;    // the depth image mapper k's requests are measured in, null: none
+  const MapperMap *measuring = nullptr;        // a mapper with depth or stereo mapping on (SDVL::SetDepthMapping, SetStereoMapping), if the step has one
+  int measuring_trk = -1;                      // whose it is
+  std::vector<const DepthImage *> depth_of;    // the depth image (stereo mapping: the right image) mapper k's requests are measured in, null: none
   std::vector<uint8_t> depth_status;           // per candidate request, with `measuring`
   std::vector<int> kf_idx;                     // the mappers whose update takes a new keyframe
   std::unique_ptr<StageClock> sub;             // the ST_MAP_* stage the update is in

@@ -52,16 +52,28 @@ bool SDVLBatch::CollectMappers(MapStep &m) {
 // Depth cameras (SDVL::SetDepthMapping): when a mapper of the step has the switch on, the candidate passes go through the measured
 // filter — still one launch for all trackers.  depth_of[k]: the depth image of the step's frame, for a mapper with the switch on whose
 // update works on that very frame; the requests of every other mapper are in no job and take the triangulated rule.
+// Stereo cameras (SDVL::SetStereoMapping): the same with the step frame's right image in depth_of[k] and the matcher as the producer.
 void SDVLBatch::SetUpMeasuring(MapStep &m) {
   for (int k = 0; k < m.M(); k++) {
-    if (!m.mm[k]->DepthMapping()) continue;
-    if (!m.dev_filter) throw std::runtime_error("mapper: depth mapping (SDVL::SetDepthMapping) needs the depth filter on the device");
+    if (!m.mm[k]->Measuring()) continue;
+    if (!m.dev_filter) throw std::runtime_error("mapper: depth mapping (SDVL::SetDepthMapping, SetStereoMapping) needs the depth filter on the device");
+    if (m.measuring && m.measuring->StereoMapping() != m.mm[k]->StereoMapping())
+      throw std::runtime_error("SDVLBatch: a batch does not mix depth mapping and stereo mapping");
+    if (m.mm[k]->StereoMapping()) {
+      if (m.measuring && m.measuring->DisparitySigma() != m.mm[k]->DisparitySigma())
+        throw std::runtime_error("SDVLBatch: the trackers of a batch share the disparity noise");
+      m.measuring = m.mm[k];
+      m.measuring_trk = m.trk[k];
+      if (m.mm[k]->CurrentFrame().get() == trk_[m.trk[k]]->step_frame_) m.depth_of[k] = DepthOf(m.trk[k]);
+      continue;
+    }
     const sdvl_depth_measure_params a = m.mm[k]->DepthMeasureParams(trk_[m.trk[k]]->depth_rule_);
     if (m.measuring) {
       const sdvl_depth_measure_params b = m.measuring->DepthMeasureParams(trk_[m.trk[k]]->depth_rule_);
       if (a.noise_abs != b.noise_abs || a.noise_quad != b.noise_quad) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth noise parameters");
     }
     m.measuring = m.mm[k];
+    m.measuring_trk = m.trk[k];
     if (m.mm[k]->CurrentFrame().get() == trk_[m.trk[k]]->step_frame_) m.depth_of[k] = DepthOf(m.trk[k]);
   }
 }

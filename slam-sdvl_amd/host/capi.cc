@@ -323,6 +323,16 @@ int sdvlh_batch_depth_map_stats(void *bp, int i, long long *out9) {
   out9[5] = s.keyframes; out9[6] = s.fixed_matched; out9[7] = s.fixed_unmatched; out9[8] = s.linked;
   return 0;
 }
+// ---- stereo cameras inside the mappers of the batch (SDVL::SetStereoMapping): needs sdvlh_batch_set_stereo and the reference's mapper;
+// the trackers share disparity_sigma (pixels; 0: 0.25, not measured against a real pair)
+int sdvlh_batch_set_stereo_mapping(void *bp, int on, double disparity_sigma) {
+  if (!bp) return -1;
+  return Guarded([&] { AsGroup(bp)->SetStereoMapping(on != 0, disparity_sigma); });
+}
+// tracker i's stereo mapping so far: out9 = candidate updates measured, fallen back by status (NOMATCH, AMBIGUOUS, EDGE, OUTSIDE),
+// keyframes matched, corners fixed and matched, fixed and unmatched, linked — the counters of sdvlh_batch_depth_map_stats under the
+// stereo producer's names
+int sdvlh_batch_stereo_map_stats(void *bp, int i, long long *out9) { return sdvlh_batch_depth_map_stats(bp, i, out9); }
 
 // Depth edges in the mappers' bundle adjustment (SDVL::SetDepthBundle): needs sdvlh_batch_set_depth and sdvlh_batch_set_bundle_adjustment;
 // bf in pixel x metres, 0: the default; the trackers share it

@@ -1,5 +1,5 @@
 // depth_jobs.h — the job list of ONE device call that reads a second image per frame: a registered depth image (sdvl_depth_seed,
-// sdvl_depth_lookup, sdvl_search_run_filter_measured) or a stereo pair's right image (sdvl_stereo_depth).  The callers (batch_depth.cc)
+// sdvl_depth_lookup, sdvl_search_run_filter_measured) or a stereo pair's right image (sdvl_stereo_depth, sdvl_search_run_filter_stereo).  The callers (batch_depth.cc)
 // name the owners of a call — keyframes, mappers — in the order their items lie in the call's item list; the builder makes the jobs,
 // checks what the owners of one call must share, and hands each owner's range of the results back.  It includes nothing of the device
 // layer beyond the C-ABI's structs, so host/depth_jobs_check.cc drives it without a device.

@@ -77,6 +77,10 @@ void TrackerGroup::SetDepth(bool on, int format, double scale, const sdvl_depth_
   depth_scale_ = scale;
 }
 
+void TrackerGroup::SetStereoMapping(bool on, double disparity_sigma) {
+  for (auto &t : trackers_) t->SetStereoMapping(on, disparity_sigma);
+}
+
 void TrackerGroup::SetStereo(bool on, double baseline, const sdvl_stereo_params &rule) {
   for (auto &t : trackers_) t->SetStereoSeeding(on, baseline, rule);
   if (on) {

@@ -65,6 +65,8 @@ class TrackerGroup {
   // Stereo cameras (SDVL::SetStereoSeeding for every tracker): the second images handed to Step are the pairs' rectified right images,
   // 8-bit gray with dense rows.  Throws what SDVL::SetStereoSeeding throws.
   void SetStereo(bool on, double baseline, const sdvl_stereo_params &rule);
+  // Stereo cameras inside the mappers (SDVL::SetStereoMapping for every tracker; the trackers share disparity_sigma).  Throws what it throws.
+  void SetStereoMapping(bool on, double disparity_sigma = 0.0);
 
   Device *device() const { return dev_; }
   int size() const { return static_cast<int>(trackers_.size()); }

@@ -840,20 +840,45 @@ void MapperMap::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
   if (on && running_) throw std::runtime_error("MapperMap::SetDepthMapping: depth mapping runs in sequential mode only, the mapper thread is started");
   if (on && !DeviceFilter()) throw std::runtime_error("MapperMap::SetDepthMapping: the measured depth filter is a device kernel, the host depth filter is selected");
   if (on && !(noise_abs >= 0.0 && noise_quad >= 0.0)) throw std::invalid_argument("MapperMap::SetDepthMapping: noise_abs and noise_quad must not be negative");
+  if (on && stereo_mapping_) throw std::runtime_error("MapperMap::SetDepthMapping: stereo mapping is on (SetStereoMapping); a frame brings one second image");
   depth_mapping_ = on;
   noise_abs_ = noise_abs;
   noise_quad_ = noise_quad;
+  if (!stereo_mapping_) {
+    tau_abs_ = noise_abs != 0.0 ? noise_abs : SDVL_DEPTH_NOISE_ABS;
+    tau_quad_ = noise_quad != 0.0 ? noise_quad : SDVL_DEPTH_NOISE_QUAD;
+  }
 }
 
-// the tau_inverse of the measured depth filter (point.cc:69 with tau = noise_abs + noise_quad z^2) for a range and its sample z
+// ---- stereo cameras inside the mapper (sdvl_host.h)
+void MapperMap::SetStereoMapping(bool on, double disparity_sigma, double fb) {
+  if (on && running_) throw std::runtime_error("MapperMap::SetStereoMapping: stereo mapping runs in sequential mode only, the mapper thread is started");
+  if (on && !DeviceFilter()) throw std::runtime_error("MapperMap::SetStereoMapping: the measured depth filter is a device kernel, the host depth filter is selected");
+  if (on && depth_mapping_) throw std::runtime_error("MapperMap::SetStereoMapping: depth mapping is on (SetDepthMapping); a frame brings one second image");
+  if (on && !(disparity_sigma >= 0.0 && std::isfinite(disparity_sigma)))
+    throw std::invalid_argument("MapperMap::SetStereoMapping: disparity_sigma is negative or not finite");
+  if (on && !(fb > 0.0 && std::isfinite(fb))) throw std::invalid_argument("MapperMap::SetStereoMapping: fx x baseline is not a positive finite number");
+  stereo_mapping_ = on;
+  disparity_sigma_ = disparity_sigma;
+  if (on) {  // the pair sdvl_search_run_filter_stereo applies, in its expression
+    tau_abs_ = 0.0;
+    tau_quad_ = (disparity_sigma != 0.0 ? disparity_sigma : SDVL_STEREO_DISPARITY_SIGMA) / fb;
+  } else {
+    tau_abs_ = noise_abs_ != 0.0 ? noise_abs_ : SDVL_DEPTH_NOISE_ABS;
+    tau_quad_ = noise_quad_ != 0.0 ? noise_quad_ : SDVL_DEPTH_NOISE_QUAD;
+  }
+}
+
+// the tau_inverse of the measured depth filter (point.cc:69 with tau = noise_abs + noise_quad z^2) for a range and its sample z; the
+// pair is the resolved one: a stereo rig's noise_abs is exactly 0
 double MapperMap::MeasuredTauInverse(double range, double z) const {
-  const double tau = (noise_abs_ != 0.0 ? noise_abs_ : SDVL_DEPTH_NOISE_ABS) + (noise_quad_ != 0.0 ? noise_quad_ : SDVL_DEPTH_NOISE_QUAD) * (z * z);
+  const double tau = tau_abs_ + tau_quad_ * (z * z);
   return tau_inverse(range, tau);
 }
 
 void MapperMap::SetCornerDepths(const double *z, const uint8_t *status) {
   ic_range_.clear();
-  if (!depth_mapping_ || !cur_ || !z || !status) return;
+  if (!Measuring() || !cur_ || !z || !status) return;
   const int nc = cur_->NumFiltered();
   ic_range_.assign(nc, 0.0);
   ic_z_.assign(nc, 0.0);
@@ -929,6 +954,7 @@ void MapperMap::Start() {
   if (running_) return;
   if (bundle_on_) throw std::runtime_error("MapperMap::Start: bundle adjustment is on and runs in sequential mode only");
   if (depth_mapping_) throw std::runtime_error("MapperMap::Start: depth mapping is on and runs in sequential mode only");
+  if (stereo_mapping_) throw std::runtime_error("MapperMap::Start: stereo mapping is on and runs in sequential mode only");
   tracker_device_ = Device::CurrentOrNull();
   running_ = true;
   thread_ = std::thread(&MapperMap::Run, this);

@@ -117,6 +117,17 @@ class MapperMap : public PlaneMap {
   bool DepthMapping() const { return depth_mapping_; }
   sdvl_depth_measure_params DepthMeasureParams(const sdvl_depth_seed_params &rule) const { return sdvl_depth_measure_params{rule, noise_abs_, noise_quad_}; }
   void SetCornerDepths(const double *z, const uint8_t *status);
+  // ---- stereo cameras inside the mapper (an addition; SDVL::SetStereoMapping): the same machinery with the other producer.  The
+  // second image of the step's frame is the pair's right image; UpdateCandidates goes through sdvl_search_run_filter_stereo (the matcher
+  // at the found pixel), the new keyframe's filtered corners through sdvl_stereo_depth, whose z / status SetCornerDepths takes as it takes
+  // sdvl_depth_seed's (OK is 0 in both status families).  The depth noise is tau = disparity_sigma z^2 / fb, fb = fx x baseline in
+  // pixel x metres; disparity_sigma 0: SDVL_STEREO_DISPARITY_SIGMA (0.25 px, not measured against a real pair).  The counters are
+  // DepthMapStats, fallback[] by the matcher's status (NOMATCH, AMBIGUOUS, EDGE, OUTSIDE).  Throws as SetDepthMapping does, and
+  // std::invalid_argument for a disparity_sigma that is negative or not finite or an fb that is not positive.
+  void SetStereoMapping(bool on, double disparity_sigma, double fb);
+  bool StereoMapping() const { return stereo_mapping_; }
+  bool Measuring() const { return depth_mapping_ || stereo_mapping_; }
+  double DisparitySigma() const { return disparity_sigma_; }  // as given (0: the default)
   // candidate updates that took the measured depth and those that fell back by the lookup's status (HOLE, FEW, EDGE, OUTSIDE); keyframes
   // whose corners were looked up; corners fixed from depth and matched in a connected keyframe, fixed on the new keyframe alone, and
   // measured corners that were linked to an existing point
@@ -205,6 +216,11 @@ class MapperMap : public PlaneMap {
   std::vector<sdvl_search_req> ic_proto_;                  // InitCandidates: the request of filtered corner c without its keyframe
   bool depth_mapping_ = false;
   double noise_abs_ = 0.0, noise_quad_ = 0.0;              // SetDepthMapping: as given (0: sdvl_depth_measure_params' default)
+  bool stereo_mapping_ = false;
+  double disparity_sigma_ = 0.0;                           // SetStereoMapping: as given (0: SDVL_STEREO_DISPARITY_SIGMA)
+  // the noise MeasuredTauInverse applies, RESOLVED: a depth camera's pair with its defaults put in, a stereo rig's exactly 0 and
+  // disparity_sigma / fb (a 0 here is a 0, not "take the default")
+  double tau_abs_ = SDVL_DEPTH_NOISE_ABS, tau_quad_ = SDVL_DEPTH_NOISE_QUAD;
   std::vector<double> ic_range_;                           // SetCornerDepths: the measured range of filtered corner c, 0: not measured
   std::vector<double> ic_z_;                               // and the sample itself, for Feature::SetDepth
   bool depth_bundle_ = false;
@@ -274,6 +290,16 @@ class SDVL {
   // the reference's mapper in sequential mode with the depth filter on the device: throws std::runtime_error without depth seeding, with
   // any other map, while the mapper thread runs (and Start() throws while it is on), and with the host depth filter.
   void SetDepthMapping(bool on, double noise_abs = 0.0, double noise_quad = 0.0);
+  // Stereo cameras inside the reference's mapper (an addition, MapperMap::SetStereoMapping): the right image of every tracked frame feeds
+  // the candidates' depth filter through the matcher at the found pixel (sdvl_search_run_filter_stereo), and a new keyframe's corners
+  // become fixed points at the depth sdvl_stereo_depth gives them — what SetDepthMapping does for a depth camera.  Off by default; a
+  // frame that comes without a right image is mapped as before.  disparity_sigma: the matcher's disparity noise in pixels, depth noise
+  // tau = disparity_sigma z^2 / (fx baseline); 0: 0.25 px, an order of magnitude that nobody has measured against a real pair (on the
+  // synthetic `shelf` scene the matcher's median error is 0.04 - 0.07 px); the trackers of a batch share it.  Throws std::runtime_error
+  // without stereo seeding, with any map but the reference's mapper, while the mapper thread runs (and Start() throws while it is on)
+  // and with the host depth filter; std::invalid_argument for a negative or non-finite disparity_sigma.  While it is on,
+  // SetStereoSeeding(false) and SetDepthSeeding(false) throw.
+  void SetStereoMapping(bool on, double disparity_sigma = 0.0);
   // Map::BundleAdjustment after every keyframe update of a map with more than two keyframes (map.cc:130-137), on the device
   // (sdvl_bundle_adjust).  Off by default.  Needs the reference's mapper in sequential mode: throws std::runtime_error with any other map
   // and while the mapper thread runs.

@@ -495,6 +495,8 @@ void SDVL::SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule) {
   if (on && (rule.edge_ratio < 0.0 || rule.min_valid < 0 || rule.min_valid > 9))
     throw std::invalid_argument("SDVL::SetDepthSeeding: edge_ratio is negative or min_valid lies outside 1 .. 9");
   if (on && stereo_seeding_) throw std::runtime_error("SDVL::SetDepthSeeding: the tracker seeds from a stereo pair (SetStereoSeeding); a frame brings one second image");
+  if (MapperMap *m = dynamic_cast<MapperMap *>(map_))
+    if (!on && m->StereoMapping()) throw std::runtime_error("SDVL::SetDepthSeeding: stereo mapping is on (SetStereoMapping) and needs the stereo seeding this turns off");
   depth_seeding_ = on;
   depth_rule_ = rule;
   if (!on) stereo_seeding_ = false;
@@ -505,6 +507,8 @@ void SDVL::SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &
   if (on && !dynamic_cast<PlaneMap *>(map_)) throw std::runtime_error("SDVL::SetStereoSeeding needs a PlaneMap or the reference's mapper (MapperMap)");
   if (on && depth_seeding_ && !stereo_seeding_)
     throw std::runtime_error("SDVL::SetStereoSeeding: the tracker seeds from a depth image (SetDepthSeeding); a frame brings one second image");
+  if (MapperMap *m = dynamic_cast<MapperMap *>(map_))
+    if (!on && m->StereoMapping()) throw std::runtime_error("SDVL::SetStereoSeeding: stereo mapping is on (SetStereoMapping) and needs stereo seeding");
   if (MapperMap *m = dynamic_cast<MapperMap *>(map_))
     if (on && (m->DepthMapping() || m->DepthBundleOn()))
       throw std::runtime_error("SDVL::SetStereoSeeding: depth mapping and depth edges look depths up at found pixels, which a matcher at the corners does not give");
@@ -526,6 +530,13 @@ void SDVL::SetDepthMapping(bool on, double noise_abs, double noise_quad) {
   if (on && stereo_seeding_) throw std::runtime_error("SDVL::SetDepthMapping: the tracker seeds from a stereo pair (SetStereoSeeding), which gives no depth at a found pixel");
   if (on && !depth_seeding_) throw std::runtime_error("SDVL::SetDepthMapping needs depth seeding (SetDepthSeeding): the bootstrap keyframe is seeded from depth too");
   if (m) m->SetDepthMapping(on, noise_abs, noise_quad);
+}
+
+void SDVL::SetStereoMapping(bool on, double disparity_sigma) {
+  MapperMap *m = AsMapperMap(map_);
+  if (on && !m) throw std::runtime_error("SDVL::SetStereoMapping needs the reference's mapper (MapperMap)");
+  if (on && !stereo_seeding_) throw std::runtime_error("SDVL::SetStereoMapping needs stereo seeding (SetStereoSeeding): the baseline, the rule and the bootstrap keyframe are its");
+  if (m) m->SetStereoMapping(on, disparity_sigma, camera_->abi().fx * stereo_rule_.baseline);
 }
 
 void SDVL::SetDepthBundle(bool on, double bf) {

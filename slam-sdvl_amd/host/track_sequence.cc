@@ -20,6 +20,9 @@
 //   track_sequence --synthetic N --scene shelf --stereo --baseline B   a stereo camera: every frame comes with the rendered right image — the right camera's centre is the
 //                                                                left one's plus B metres along the left camera's x axis, the same orientation — and the keyframes' points
 //                                                                are seeded from the pair (SDVL::SetStereoSeeding) — no plane; a --plane is ignored
+//   ... --stereo --stereo-mapping [--disparity-sigma X]          the stereo pair inside the reference's mapper too (SDVL::SetStereoMapping; implies --mapper): every tracked
+//                                                                frame's right image feeds the candidates' filter through the matcher at the found pixel, new keyframes'
+//                                                                corners become fixed points; X: the disparity noise in pixels (default 0.25, not measured against a real pair)
 //   track_sequence --list frames.txt --right-list right.txt --baseline B   the same from disk: one 8-bit binary PGM, the rectified right image, per frame
 //   track_sequence ... --depth --depth-bundle [--depth-bf X]  depth edges in the local bundle adjustment (SDVL::SetDepthBundle; implies --bundle): X in
 //                                                                pixel x metres, default 1 / noise_quad of the depth mapping = 666.7
@@ -132,6 +135,8 @@ const char kUsage[] =
     "  --stereo --baseline B: with --synthetic N --scene NAME, a stereo camera: every frame comes with the rendered right image (the right camera's\n"
     "      centre is the left one's plus B metres along the left camera's x axis, the same orientation) and the keyframes' points are seeded from the\n"
     "      pair (no plane, no lens)\n"
+    "  --stereo-mapping [--disparity-sigma X]: with --stereo, the right image of every tracked frame feeds the mapper's depth filter and new\n"
+    "      keyframes' corners become fixed points (implies --mapper); X: disparity noise in pixels, default 0.25 (not measured against a real pair)\n"
     "  --right-list FILE --baseline B: one 8-bit P5 rectified right image per frame of --list\n"
     "  common: [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle]\n"
     "          [--init plane|two-frame] [--trackers N] [--batch] [--lookahead] [--prerender] [--pageable] [--set SDVL.key value]\n"
@@ -161,8 +166,8 @@ int main(int argc, char **argv) {
   double depth_bf = 0.0;
   std::string depth_list;
   double depth_scale = 0.0;
-  bool stereo = false;
-  double baseline = 0.0;
+  bool stereo = false, stereo_mapping = false;
+  double baseline = 0.0, disparity_sigma = 0.0;
   std::string right_list;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
   unsigned texture = SDVL_TEXTURE_PLANE_NOISE;
@@ -187,6 +192,8 @@ int main(int argc, char **argv) {
     else if (a == "--depth-scale") { need(1); depth_scale = std::atof(argv[++i]); }
     else if (a == "--stereo") stereo = true;
     else if (a == "--baseline") { need(1); baseline = std::atof(argv[++i]); }
+    else if (a == "--stereo-mapping") { stereo_mapping = true; mapper = true; }
+    else if (a == "--disparity-sigma") { need(1); disparity_sigma = std::atof(argv[++i]); }
     else if (a == "--right-list") { need(1); right_list = argv[++i]; stereo = true; }
     else if (a == "--mapper") mapper = true;
     else if (a == "--bundle") { bundle = true; mapper = true; }  // local bundle adjustment of every new keyframe (SDVL::SetBundleAdjustment; implies --mapper)
@@ -223,6 +230,9 @@ int main(int argc, char **argv) {
     if (batch || prerender || n_trackers > 1) { std::cerr << "--depth runs one camera on frames made inside the loop: not with --batch, --trackers or --prerender" << std::endl; return 2; }
     if (plane_given) std::cerr << "note: --plane is ignored, the keyframes' points are seeded from depth" << std::endl;
   }
+  if (stereo_mapping && !stereo) { std::cerr << "--stereo-mapping feeds the mapper from the frames' right images: give --stereo or --right-list too" << std::endl; return 2; }
+  if (!(disparity_sigma >= 0.0) || disparity_sigma > 1e300) { std::cerr << "--disparity-sigma X: pixels, not negative" << std::endl; return 2; }
+  if (disparity_sigma != 0.0 && !stereo_mapping) { std::cerr << "--disparity-sigma is the noise of --stereo-mapping: give that too" << std::endl; return 2; }
   if (stereo) {  // what SDVL::SetStereoSeeding would throw, said before any device is touched
     if (right_list.empty() && !use_scene) { std::cerr << "--stereo tracks on the rendered right image: give --synthetic N --scene NAME, or --right-list FILE with --list" << std::endl; return 2; }
     if (!right_list.empty() && list.empty()) { std::cerr << "--right-list goes with --list" << std::endl; return 2; }
@@ -367,6 +377,7 @@ int main(int argc, char **argv) {
         if (depth_mapping) sdvl.SetDepthMapping(true);
         if (depth_bundle) sdvl.SetDepthBundle(true, depth_bf);
         if (stereo) sdvl.SetStereoSeeding(true, baseline);
+        if (stereo_mapping) sdvl.SetStereoMapping(true, disparity_sigma);
         std::vector<uint8_t> right_px(stereo ? frame_bytes : 0);
         std::vector<float> depth_f32(depth && depth_list.empty() ? frame_bytes : 0);
         std::vector<uint16_t> depth_u16;
@@ -452,7 +463,7 @@ int main(int argc, char **argv) {
                         st.pose[0], st.pose[1], st.pose[2], st.pose[3], st.pose[4], st.pose[5], st.pose[6]);
         }
         if (depth || stereo) me.depth = dynamic_cast<PlaneMap *>(map.get())->GetDepthStats();
-        if (depth_mapping) me.depth_map = dynamic_cast<MapperMap *>(map.get())->GetDepthMapStats();
+        if (depth_mapping || stereo_mapping) me.depth_map = dynamic_cast<MapperMap *>(map.get())->GetDepthMapStats();
         if (depth_bundle) me.depth_bundle = dynamic_cast<MapperMap *>(map.get())->GetDepthBundleStats();
         if (profile && id == 0) {
           char names[32][32];
@@ -595,6 +606,15 @@ int main(int argc, char **argv) {
       std::snprintf(depth_map_json, sizeof(depth_map_json),
                     ", \"depth_mapping\": {\"measured\": %ld, \"hole\": %ld, \"few\": %ld, \"edge\": %ld, \"outside\": %ld, \"keyframes\": %ld, \"fixed_matched\": %ld, "
                     "\"fixed_unmatched\": %ld, \"linked\": %ld}",
+                    d.measured, d.fallback[0], d.fallback[1], d.fallback[2], d.fallback[3], d.keyframes, d.fixed_matched, d.fixed_unmatched, d.linked);
+    }
+    if (stereo_mapping) {
+      const MapperMap::DepthMapStats &d = per[0].depth_map;
+      std::fprintf(stderr, "stereo mapping: %ld measured updates, fallen back NOMATCH %ld AMBIGUOUS %ld EDGE %ld OUTSIDE %ld; %ld keyframes matched, corners fixed %ld matched + %ld unmatched, %ld linked\n",
+                   d.measured, d.fallback[0], d.fallback[1], d.fallback[2], d.fallback[3], d.keyframes, d.fixed_matched, d.fixed_unmatched, d.linked);
+      std::snprintf(depth_map_json, sizeof(depth_map_json),
+                    ", \"stereo_mapping\": {\"measured\": %ld, \"nomatch\": %ld, \"ambiguous\": %ld, \"edge\": %ld, \"outside\": %ld, \"keyframes\": %ld, "
+                    "\"fixed_matched\": %ld, \"fixed_unmatched\": %ld, \"linked\": %ld}",
                     d.measured, d.fallback[0], d.fallback[1], d.fallback[2], d.fallback[3], d.keyframes, d.fixed_matched, d.fixed_unmatched, d.linked);
     }
     char depth_bundle_json[320] = "";

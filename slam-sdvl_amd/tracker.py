@@ -276,6 +276,31 @@ class TrackerBatch:
             raise RuntimeError("no tracker %d, or not a mapper batch" % i)
         return dict(zip(("measured", "hole", "few", "edge", "outside", "keyframes", "fixed_matched", "fixed_unmatched", "linked"), [int(v) for v in out]))
 
+    def set_stereo_mapping(self, on=True, disparity_sigma=0.0):
+        """stereo cameras inside the reference's mapper (SDVL::SetStereoMapping; needs set_stereo and a mapper batch): the right image of
+        every tracked frame feeds the candidates' depth filter through the stereo matcher at the found pixel
+        (sdvl_search_run_filter_stereo), and the corners of a new keyframe become fixed points at the depth sdvl_stereo_depth gives them —
+        matched in a connected keyframe or on the new keyframe alone.  The depth noise is tau = disparity_sigma z^2 / (fx baseline);
+        disparity_sigma in pixels, 0: 0.25, an order of magnitude that nobody has measured against a real pair (on the synthetic `shelf`
+        scene the matcher's median error is 0.04 - 0.07 px); the trackers share it.  A frame without a right image is mapped as before.
+        The points fixed from the pair join seeded_points; stereo_stats keeps counting what the driver seeds.  Raises RuntimeError without
+        stereo seeding, without the mapper, with the mapper thread started, with the host depth filter and for a negative or non-finite
+        disparity_sigma; while it is on, set_stereo(on=False) raises."""
+        self.lib.sdvlh_batch_set_stereo_mapping.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        if self.lib.sdvlh_batch_set_stereo_mapping(self.h, int(bool(on)), float(disparity_sigma)) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+
+    def stereo_map_stats(self, i):
+        """tracker i's stereo mapping so far: dict(measured, nomatch, ambiguous, edge, outside, keyframes, fixed_matched, fixed_unmatched,
+        linked) — candidate updates that took the matcher's depth and those that fell back by its status, keyframes whose corners were
+        matched, corners fixed and matched in a connected keyframe, fixed on the new keyframe alone, and measured corners linked to a point"""
+        out = (C.c_longlong * 9)()
+        self.lib.sdvlh_batch_stereo_map_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        if self.lib.sdvlh_batch_stereo_map_stats(self.h, int(i), out) != 0:
+            raise RuntimeError("no tracker %d, or not a mapper batch" % i)
+        return dict(zip(("measured", "nomatch", "ambiguous", "edge", "outside", "keyframes", "fixed_matched", "fixed_unmatched", "linked"),
+                        [int(v) for v in out]))
+
     def set_next_device(self, dev_ptrs):
         """look-ahead: the device images the NEXT step_device call will be given (None: none); their pyramids and corner detection
         are queued behind the coming step's search / pose chain (SDVLBatch::SetNextImages).  The buffers must keep their CONTENT until that

@@ -189,6 +189,15 @@ for _ in range(reps):
 print("stereo_depth: %d corners of %d pairs per call, %d OK; %.1f us per blocking call (host wall, push + launch + copy back + wait)" %
       (len(st_all), n, int(sok.sum()), (time.perf_counter() - t0) / reps * 1e6))
 st_nc = len(st_all) / float(n)
+# the same matcher at positions of the caller's own (sdvl_stereo_lookup): the same corners displaced by a fixed sub-pixel offset, at their
+# levels — the found pixels of tracked features stand no further from a corner; the kernel appears as stereo_lookup in the table below
+st_s = (1 << st_all[:, 2]).astype(np.float64)
+st_px = np.stack([st_all[:, 0] * st_s, st_all[:, 1] * st_s], 1) + np.random.default_rng(7).uniform(-0.49, 0.49, (len(st_all), 2))
+t0 = time.perf_counter()
+for _ in range(reps):
+    lz, ldisp, lstatus, lok = ctx.stereo_lookup(st_jobs, st_px, st_all[:, 2], cam, 0.11)
+print("stereo_lookup: %d positions of %d pairs per call, %d OK (stereo_depth at the corners: %d); %.1f us per blocking call (host wall, push + launch + "
+      "copy back + wait)" % (len(st_px), n, int(lok.sum()), int(sok.sum()), (time.perf_counter() - t0) / reps * 1e6))
 # the mapper's depth filter on the search's own results, triangulated (depth_filter) and with a measured depth (depth_filter_measured): the
 # requests of frame pair j are one job over frame j's float depth image in HBM; both kernels appear in the table below
 fstates = (sdvl.DepthState * nreq)()
@@ -244,7 +253,7 @@ alg = {"pyr_down": (sum(P[:4]) + sum(P[1:])) / 4.0, "fast_cells": sum(P[:3]) + 1
        "orb_describe": 993 * nc, "image_align": 147 * nf + 25 * nf * i_ia, "pose_hypotheses": 48 * nf + 6400, "undistort": 2 * W * H,
        "search_points": 12 * nc + nf * (121 + 164 + lk * 81), "search_prepare": nf * (120 + 80),
        "pose_refine": 52 * nf + 6480, "depth_seed": min(300.0, nc) * (9 * 4 + 12 + 9),
-       "stereo_depth": st_nc * (9 * (190 + 9) + 81 + 12 + 17)}
+       "stereo_depth": st_nc * (9 * (190 + 9) + 81 + 12 + 17), "stereo_lookup": st_nc * (9 * (190 + 9) + 81 + 20 + 17)}
 print("n_frames=%d reps=%d corners/frame=%.0f GN evaluations/job=%.1f" % (n, reps, nc, i_ia))
 for k, (ms, launches) in sorted(t.items()):
     us = ms / launches * 1e3
