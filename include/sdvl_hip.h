@@ -285,7 +285,8 @@ int sdvl_filter_inputs_end(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, int 
  * TRUNCATED score stored for the cell), cells whose score stays <= min_feature_score are dropped, and the survivors come
  * back in cell order with their ORB descriptors (the reference computes descriptors for the filtered corners only).
  * locked_cells[i][mask_words]: bit c of frame i's mask = grid cell c already holds a feature (FastDetector::LockCell on the
- * frame's features, frame.cc:139-142); grid = ceil(width / cell_size) x ceil(height / cell_size), at most 4096 cells.
+ * frame's features, frame.cc:139-142); grid = ceil(width / cell_size) x ceil(height / cell_size), at most
+ * SDVL_MAX_LEVEL_CELLS (8192) cells.
  * _begin queues everything, _end waits and returns counts[n] and records out[n][cap] (cap >= the cell count is always enough). */
 typedef struct sdvl_filtered_corner {
   int32_t index;        /* position in the frame's corner list (Frame::GetFilteredCorners() holds these) */

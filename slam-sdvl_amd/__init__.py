@@ -699,6 +699,19 @@ class Context:
             out.append((r[:, 0].copy(), r[:, 1:4].copy(), r[:, 4].copy(), r[:, 6:].copy().view(np.uint8).reshape(-1, 32)))
         return out
 
+    def filter_inputs(self, frames, cap=MAX_CORNERS, with_desc=True):
+        """sdvl_filter_inputs: what Frame::FilterCorners needs from the frames in one round trip.  Returns per frame (xyl, scores,
+        descriptors or None)."""
+        n = len(frames)
+        xyl = np.zeros((n, cap, 3), np.int32)
+        scores = np.zeros((n, cap), np.float64)
+        desc = np.zeros((n, cap, 32), np.uint8) if with_desc else None
+        counts = np.zeros(n, np.int32)
+        arr = (C.c_void_p * n)(*[f.h for f in frames])
+        self._check(self.lib.sdvl_filter_inputs(self.h, n, arr, cap, _ptr(xyl, i32p), _ptr(scores, f64p),
+                                                _ptr(desc, u8p) if with_desc else None, _ptr(counts, i32p)))
+        return [(xyl[i, :c].copy(), scores[i, :c].copy(), desc[i, :c].copy() if with_desc else None) for i, c in enumerate(counts)]
+
     def orb_describe_points(self, frame, xyl):
         xyl = np.ascontiguousarray(xyl, np.int32).reshape(-1, 3)
         desc = np.zeros((len(xyl), 32), np.uint8)

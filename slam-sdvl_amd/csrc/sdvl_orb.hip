@@ -22,6 +22,7 @@ struct OrbJob {
   const int32_t *n_ptr;    // device-resident corner count (frame header); null -> use n
   int n;
   int levels;
+  int cap;                 // corners out_score has room for (shi_tomasi_kernel scores no more, whatever the device's count says)
 };
 
 // Blocks b and b + 8 share an XCD (observed placement, used for speed only): the `chunks` workgroups of frame f all run on XCD f % 8, so
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void shi_tomasi_kernel(const OrbJob *__restric
   if (!xcd_frame_block(n_jobs, chunks, &fj, &bx)) return;
   const OrbJob &job = jobs[fj];
   const int lane = threadIdx.x & 63, grp = lane >> 4, q = lane & 15;
-  const int n = job.n_ptr ? min(job.n_ptr[0], SDVL_MAX_CORNERS) : job.n;
+  const int n = job.n_ptr ? min(job.n_ptr[0], job.cap) : job.n;
   const int wpb = static_cast<int>(blockDim.x >> 6);
   for (int c0 = (bx * wpb + (threadIdx.x >> 6)) * kShiPerWave; c0 < n; c0 += chunks * wpb * kShiPerWave) {
     const int ci = c0 + grp;
@@ -386,6 +387,7 @@ int fill_jobs(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, int cap, uint8_t 
     hj[i].n_ptr = v.corner_hdr;
     hj[i].n = v.n_corners;
     hj[i].levels = v.levels;
+    hj[i].cap = cap < SDVL_MAX_CORNERS ? cap : SDVL_MAX_CORNERS;
     const int bound = v.n_corners >= 0 ? v.n_corners : 1280;  // device-only count: a typical grid; the kernels grid-stride
     if (bound > *max_n) *max_n = bound;
   }
