@@ -508,6 +508,83 @@ int sdvl_convert_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stri
 int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
                              int format, const sdvl_camera *cam, const sdvl_distortion *dist);
 
+/* ---- input stage, stereo rigs as calibrated: both cameras rectified on the device ---------------------------------------------------
+ * The stereo entries below (sdvl_stereo_depth, sdvl_stereo_lookup, the stereo depth filter) take a RECTIFIED pair.  A calibrated rig
+ * delivers K1, D1 (left), K2, D2 (right) and R, T with X_right = R X_left + T (OpenCV's convention; the ideal rig is R = I,
+ * T = (-B, 0, 0)).  The rule below is stated by this project (tests/rectify_restatement.py is its specification), not pinned to
+ * OpenCV.
+ *   rotations   Bouguet's construction, as cv::stereoRectify has it: om = rotation vector of R, r_r = exp(-om / 2), t = r_r T,
+ *               u = (sign(t_x), 0, 0), w = t x u scaled to the angle acos(|t.u| / |t|), R1 = exp(w) r_r^T, R2 = exp(w) r_r,
+ *               baseline = |T|.  A point X of the left camera's frame lies at R1 X in the rectified left frame.
+ *   intrinsics  ONE pinhole camera for both images (fx = fy = f, one u0, one v0: zero disparity at infinity).  Every pixel of the four
+ *               borders of each raw image is un-distorted (50 fixed-point iterations of the radial-tangential model, in the expression
+ *               order of sdvl_undistort's forward model), rotated by its camera's R_i and normalised; per camera the inner rectangle
+ *               is [max x of the left border, min x of the right] x [max y of the top border, min y of the bottom]; [x0, x1] x
+ *               [y0, y1] is the two rectangles' intersection; f = max((w - 1 + 4) / (x1 - x0), (h - 1 + 4) / (y1 - y0)),
+ *               u0 = (w - 1) / 2 - f (x0 + x1) / 2, v0 alike.  Two pixels of margin a side: all four bilinear taps of every
+ *               rectified pixel lie inside its raw image, so no black border exists for FAST or a SAD window to meet.
+ *               A non-null `override` (fx, fy, u0, v0) sets the rectified intrinsics instead; pixels without a source may then exist
+ *               (they read 0; sdvl_rectify_stats counts them).
+ * sdvl_stereo_rectify_plan is host code in FP64 and needs no context or device.  It returns 0, or one of the codes below, whose text
+ * sdvl_stereo_rectify_plan_message gives. */
+typedef struct sdvl_stereo_rig {
+  sdvl_camera left;          /* K1 (width, height are not read: the size is an argument of the plan) */
+  sdvl_distortion left_dist; /* D1 = (k1, k2, p1, p2, k3), used as given */
+  sdvl_camera right;         /* K2 */
+  sdvl_distortion right_dist;
+  double R[9], T[3];         /* row-major; X_right = R X_left + T */
+} sdvl_stereo_rig;
+
+typedef struct sdvl_rectification { /* one camera of a rectified pair: what its map is built from */
+  sdvl_camera raw;                  /* K_i */
+  sdvl_distortion dist;             /* D_i */
+  double R[9];                      /* R_i, row-major: raw camera frame -> rectified frame */
+  sdvl_camera rect;                 /* the rectified camera, the same for both sides of a pair */
+} sdvl_rectification;
+
+typedef struct sdvl_stereo_rectified {
+  sdvl_rectification left, right;
+  double baseline; /* |T|: u_left - u_right = rect.fx * baseline / z */
+} sdvl_stereo_rectified;
+
+enum sdvl_rectify_plan_error {
+  SDVL_RECTIFY_PLAN_NULL = 1,       /* a null rig or output */
+  SDVL_RECTIFY_PLAN_SIZE = 2,       /* a size outside 2 .. 4095 a side */
+  SDVL_RECTIFY_PLAN_T = 3,          /* T not finite or zero */
+  SDVL_RECTIFY_PLAN_R = 4,          /* R^T R differs from I by more than 1e-9, or R turns by more than 90 degrees */
+  SDVL_RECTIFY_PLAN_VERTICAL = 5,   /* |t_y| > |t_x| behind r_r: a vertical rig */
+  SDVL_RECTIFY_PLAN_ORDER = 6,      /* t_x > 0: the "right" camera stands left of the left one */
+  SDVL_RECTIFY_PLAN_EMPTY = 7,      /* the inner rectangle is empty (or not finite) */
+  SDVL_RECTIFY_PLAN_INTRINSICS = 8  /* a focal length of the rig or the override that is not finite and positive */
+};
+int sdvl_stereo_rectify_plan(const sdvl_stereo_rig *rig, int width, int height, const sdvl_camera *override_or_null,
+                             sdvl_stereo_rectified *out);
+const char *sdvl_stereo_rectify_plan_message(int code);
+
+/* The map of one camera: output pixel (j, i) -> (x, y, w) = M (j, i, 1) with M = R_i^T K_rect^-1 (host, FP64: M00 j + M01 i + M02,
+ * evaluated directly), x / w, y / w, the forward lens model with K_i, D_i in sdvl_undistort's expression order, cvRound(32 u),
+ * cvRound(32 v) and sdvl_undistort's packed words: the per-frame remap is sdvl_undistort's own kernel behind another map (bilinear,
+ * fixed-point weights, a tap outside the raw image reads 0; a ray with w <= 0 has no source at all).  R_i must be a rotation (R^T R
+ * within 1e-9 of I, as the plan requires of the rig's R) and every value finite, the focal lengths positive.  Maps are kept per context in a cache of four, keyed by K_i, D_i, R_i,
+ * K_rect, the size and the source stride: a rig that alternates left and right builds each map once.  sdvl_undistort's own map and
+ * its count (sdvl_ctx_counters) are not touched.
+ * n raw images of one camera: src[i] (host, or device if src_on_device) -> dst_dev[i] (device, distinct from src), sizes 2 .. 4095. */
+int sdvl_rectify(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int width, int height,
+                 const sdvl_rectification *r, void *const *dst_dev, int dst_stride);
+/* the fused form: raw images -> rectified level 0 of the frames, the sibling of sdvl_frames_upload_undistorted */
+int sdvl_frames_upload_rectified(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride,
+                                 int src_on_device, const sdvl_rectification *r);
+/* colour and raw formats: level 0 = rectify(gray(raw)), the conversion first, as sdvl_frames_upload_color has it with a lens */
+int sdvl_frames_upload_color_rectified(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride,
+                                       int src_on_device, int format, const sdvl_rectification *r);
+/* out2[0] = rectification maps built on this context, out2[1] = pixels of the last map built with one of their four taps outside the
+ * raw image (0 for a plan without an override) */
+int sdvl_rectify_stats(sdvl_ctx *ctx, int64_t *out2);
+/* the per-pixel words of a camera's map (built now unless cached), for checks: out_words[height][width], or [height][width][2] for
+ * the wide map (a side above 2044): a | b << 5 | (sx + 2) << 10 | (sy + 2) << 21, wide a | b << 5 then (sx + 2) | (sy + 2) << 16,
+ * with a, b the 5-bit fractions and sx, sy the integer source position clamped to [-2, size] */
+int sdvl_rectify_map_words(sdvl_ctx *ctx, int width, int height, int src_stride, const sdvl_rectification *r, uint32_t *out_words);
+
 /* ---- input stage, depth cameras: the depth of a keyframe's corners from a REGISTERED depth image --------------------------------------
  * Map::InitCandidates carries a branch that makes a candidate a fixed point at a known depth (`bool fixed`, map.cc:269,385-389) and
  * never takes it; a depth camera is what it is for.  The rule below is stated by this project (tests/depth_seed_restatement.py is its

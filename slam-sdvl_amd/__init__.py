@@ -212,6 +212,8 @@ ABI_SYMBOLS = [
     "sdvl_device_malloc", "sdvl_device_free", "sdvl_device_download",
     "sdvl_frames_own_images", "sdvl_feed_create", "sdvl_feed_destroy", "sdvl_feed_last_error", "sdvl_feed_slot_arrived", "sdvl_feed_images", "sdvl_ctx_feed_acquire", "sdvl_ctx_feed_release", "sdvl_frame_footprint_cap", "sdvl_ctx_set_corner_capacity", "sdvl_frame_corner_capacity", "sdvl_detect_scratch_bytes",
     "sdvl_klt_track", "sdvl_homography_ransac", "sdvl_bundle_adjust", "sdvl_bundle_adjust_depth",
+    "sdvl_stereo_rectify_plan", "sdvl_stereo_rectify_plan_message", "sdvl_rectify", "sdvl_frames_upload_rectified",
+    "sdvl_frames_upload_color_rectified", "sdvl_rectify_stats", "sdvl_rectify_map_words",
     "sdvl_ctx_set_wait_spin", "sdvl_ctx_fork_mark", "sdvl_ctx_fork_begin", "sdvl_ctx_fork_end", "sdvl_host_alloc_pinned", "sdvl_host_free_pinned", "sdvl_host_register", "sdvl_host_unregister",
 ]
 
@@ -351,6 +353,66 @@ class AlignStore:
 
 class Distortion(C.Structure):
     _fields_ = [("d", C.c_double * 5)]
+
+
+class StereoRig(C.Structure):
+    """sdvl_stereo_rig: K1, D1 (left), K2, D2 (right), R, T with X_right = R X_left + T"""
+    _fields_ = [("left", Camera), ("left_dist", Distortion), ("right", Camera), ("right_dist", Distortion), ("R", C.c_double * 9),
+                ("T", C.c_double * 3)]
+
+
+class Rectification(C.Structure):
+    """sdvl_rectification: one camera of a rectified pair (raw K and D, its rotation R_i, the rectified camera)"""
+    _fields_ = [("raw", Camera), ("dist", Distortion), ("R", C.c_double * 9), ("rect", Camera)]
+
+
+class StereoRectified(C.Structure):
+    """sdvl_stereo_rectified: the plan's output"""
+    _fields_ = [("left", Rectification), ("right", Rectification), ("baseline", C.c_double)]
+
+    def camera(self):
+        """the rectified camera (fx, fy, u0, v0), the same for both images"""
+        c = self.left.rect
+        return np.array([c.fx, c.fy, c.u0, c.v0])
+
+
+class RectifyPlanError(SdvlError):
+    """sdvl_stereo_rectify_plan refused the rig; `code` is its sdvl_rectify_plan_error"""
+
+    def __init__(self, code, message):
+        SdvlError.__init__(self, message)
+        self.code = code
+
+
+def rectification(raw, dist, R, rect, width=0, height=0):
+    """a Rectification from raw = (fx, fy, u0, v0), dist = (k1, k2, p1, p2, k3), R [3][3] and rect = (fx, fy, u0, v0)"""
+    r = Rectification()
+    r.raw = Camera(float(width), float(height), *[float(v) for v in raw])
+    r.dist = Distortion((C.c_double * 5)(*[float(v) for v in dist]))
+    r.R = (C.c_double * 9)(*[float(v) for v in np.asarray(R, np.float64).reshape(9)])
+    r.rect = Camera(float(width), float(height), *[float(v) for v in rect])
+    return r
+
+
+def stereo_rectify_plan(K1, D1, K2, D2, R, T, width, height, override=None):
+    """sdvl_stereo_rectify_plan (host code, no device): the calibrated rig K_i = (fx, fy, u0, v0), D_i = (k1, k2, p1, p2, k3), R [3][3],
+    T [3] with X_right = R X_left + T -> StereoRectified; `override` = (fx, fy, u0, v0) sets the rectified intrinsics.  Raises
+    RectifyPlanError for a rig the plan refuses."""
+    lib = load_library()
+    lib.sdvl_stereo_rectify_plan_message.restype = C.c_char_p
+    rig = StereoRig()
+    rig.left = Camera(float(width), float(height), *[float(v) for v in K1])
+    rig.right = Camera(float(width), float(height), *[float(v) for v in K2])
+    rig.left_dist = Distortion((C.c_double * 5)(*[float(v) for v in D1]))
+    rig.right_dist = Distortion((C.c_double * 5)(*[float(v) for v in D2]))
+    rig.R = (C.c_double * 9)(*[float(v) for v in np.asarray(R, np.float64).reshape(9)])
+    rig.T = (C.c_double * 3)(*[float(v) for v in np.asarray(T, np.float64).reshape(3)])
+    ov = Camera(float(width), float(height), *[float(v) for v in override]) if override is not None else None
+    out = StereoRectified()
+    rc = lib.sdvl_stereo_rectify_plan(C.byref(rig), int(width), int(height), C.byref(ov) if ov is not None else None, C.byref(out))
+    if rc != 0:
+        raise RectifyPlanError(rc, lib.sdvl_stereo_rectify_plan_message(rc).decode())
+    return out
 
 
 class PoseObs(C.Structure):
@@ -1313,6 +1375,71 @@ class Context:
                                                       C.byref(d) if d is not None else None))
 
     frames_upload_color = upload_color   # (the C entry's name)
+
+    # ---- stereo rigs as calibrated
+    stereo_rectify_plan = staticmethod(stereo_rectify_plan)
+
+    @staticmethod
+    def _image_sources(imgs, width=None):
+        """host images (numpy u8 [h, stride]) or device images (objects with data_ptr / stride / shape, e.g. torch tensors on the
+        context's GPU) -> (kept arrays, pointer array, h, w, stride, on_device); `width`: the columns that count, when rows are wider"""
+        on_device = hasattr(imgs[0], "data_ptr")
+        if on_device:
+            keep = list(imgs)
+            ptrs = [int(im.data_ptr()) for im in keep]
+            stride = int(keep[0].stride(0))
+        else:
+            keep = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+            ptrs = [im.ctypes.data for im in keep]
+            stride = keep[0].shape[1]
+        h = int(keep[0].shape[0])
+        w = int(width) if width is not None else int(keep[0].shape[1])
+        return keep, (C.c_void_p * len(ptrs))(*ptrs), h, w, stride, int(on_device)
+
+    def rectify(self, imgs, r, frames=None, width=None):
+        """sdvl_rectify for a batch of raw images of one camera (see _image_sources) behind the Rectification r.  With `frames` the
+        result becomes their level 0 (sdvl_frames_upload_rectified); otherwise it is returned as numpy arrays."""
+        keep, src, h, w, stride, on_device = self._image_sources(imgs, width)
+        n = len(keep)
+        if frames is not None:
+            arr = (C.c_void_p * n)(*[f.h for f in frames])
+            self.lib.sdvl_frames_upload_rectified.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            self._check(self.lib.sdvl_frames_upload_rectified(self.h, n, arr, src, stride, on_device, C.byref(r)))
+            return None
+        buf = self.device_malloc(n * w * h)
+        try:
+            dst = (C.c_void_p * n)(*[buf + i * w * h for i in range(n)])
+            self.lib.sdvl_rectify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+            self._check(self.lib.sdvl_rectify(self.h, n, src, stride, on_device, w, h, C.byref(r), dst, w))
+            out = self.device_download(buf, n * w * h).reshape(n, h, w)
+        finally:
+            self.device_free(buf)
+        return [out[i].copy() for i in range(n)]
+
+    def upload_color_rectified(self, frames, imgs, fmt, r):
+        """host colour or raw images (as for upload_color) -> level 0 of `frames` = rectify(gray(img))"""
+        n = len(imgs)
+        imgs = [_raw_bytes(im) for im in imgs]
+        h, w, ch = imgs[0].shape
+        src = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
+        arr = (C.c_void_p * n)(*[f.h for f in frames])
+        self.lib.sdvl_frames_upload_color_rectified.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self._check(self.lib.sdvl_frames_upload_color_rectified(self.h, n, arr, src, w * ch, 0, int(fmt), C.byref(r)))
+
+    def rectify_stats(self):
+        """(rectification maps built on this context, pixels of the last map built with a tap outside the raw image)"""
+        out = (C.c_int64 * 2)()
+        self.lib.sdvl_rectify_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_rectify_stats(self.h, out))
+        return int(out[0]), int(out[1])
+
+    def rectify_map_words(self, r, width, height, src_stride=None):
+        """the per-pixel words of the camera's map: uint32 [h][w], or [h][w][2] for the wide map (a side above 2044)"""
+        wide = width > 2044 or height > 2044
+        out = np.zeros((height, width, 2) if wide else (height, width), np.uint32)
+        self.lib.sdvl_rectify_map_words.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(self.lib.sdvl_rectify_map_words(self.h, int(width), int(height), int(src_stride or width), C.byref(r), out.ctypes.data))
+        return out
 
     # ---- synthetic frames in HBM
     def device_malloc(self, nbytes):

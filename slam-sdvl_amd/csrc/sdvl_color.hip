@@ -394,8 +394,10 @@ int sdvl_convert_gray(sdvl_ctx *ctx, int n, const void *const *src, int src_stri
   return run_to_gray(ctx, n, src, src_stride, src_on_device, width, height, format, reinterpret_cast<uint8_t *const *>(dst_dev), dst_stride, nullptr);
 }
 
-int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
-                             int format, const sdvl_camera *cam, const sdvl_distortion *dist) {
+// `rect` (a rectified camera, sdvl_frames_upload_color_rectified) takes the place of the lens: where the upload routes to the
+// undistorted upload it routes to the rectified one
+static int upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
+                        int format, const sdvl_camera *cam, const sdvl_distortion *dist, const sdvl_rectification *rect) {
   if (!ctx) return SDVL_ERR_INVALID;
   SDVL_REQUIRE(ctx, n >= 0 && (n == 0 || (frames && src)), "sdvl_frames_upload_color: null frame or image list");
   const int C = channels_of(format);
@@ -411,9 +413,13 @@ int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, co
   }
   SDVL_REQUIRE(ctx, !size_objection(format, w, h), std::string("sdvl_frames_upload_color: ") + size_objection(format, w, h));
   SDVL_REQUIRE(ctx, static_cast<long long>(src_stride) >= static_cast<long long>(w) * C, "sdvl_frames_upload_color: source stride smaller than width x bytes per pixel");
-  const bool lens = dist && dist->d[0] != 0.0;  // Camera::SetDistortions tests d0 only (camera.cc:46)
+  const bool lens = rect || (dist && dist->d[0] != 0.0);  // Camera::SetDistortions tests d0 only (camera.cc:46)
+  const auto remapped_upload = [&](const void *const *gray, int gray_stride, int gray_on_device) {
+    if (rect) return sdvl_frames_upload_rectified(ctx, n, frames, gray, gray_stride, gray_on_device, rect);
+    return sdvl_frames_upload_undistorted(ctx, n, frames, gray, gray_stride, gray_on_device, cam, dist);
+  };
   if (format == SDVL_GRAY8) {  // exactly the gray producers
-    if (lens) return sdvl_frames_upload_undistorted(ctx, n, frames, src, src_stride, src_on_device, cam, dist);
+    if (lens) return remapped_upload(src, src_stride, src_on_device);
     return sdvl_frames_upload(ctx, n, frames, reinterpret_cast<const uint8_t *const *>(src), src_stride);
   }
   SDVL_REQUIRE(ctx, w <= kMaxSide && h <= kMaxSide, "sdvl_frames_upload_color: image size out of range");
@@ -430,7 +436,19 @@ int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, co
   const int rc = run_to_gray(ctx, n, src, src_stride, src_on_device, w, h, format, nullptr, w, &gray);
   if (rc) return rc;
   std::vector<const void *> gsrc(gray.begin(), gray.end());
-  return sdvl_frames_upload_undistorted(ctx, n, frames, gsrc.data(), w, 1, cam, dist);
+  return remapped_upload(gsrc.data(), w, 1);
+}
+
+int sdvl_frames_upload_color(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, int src_on_device,
+                             int format, const sdvl_camera *cam, const sdvl_distortion *dist) {
+  return upload_color(ctx, n, frames, src, src_stride, src_on_device, format, cam, dist, nullptr);
+}
+
+int sdvl_frames_upload_color_rectified(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride,
+                                       int src_on_device, int format, const sdvl_rectification *r) {
+  if (!ctx) return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, r != nullptr, "sdvl_frames_upload_color_rectified: null rectification");
+  return upload_color(ctx, n, frames, src, src_stride, src_on_device, format, nullptr, nullptr, r);
 }
 
 }  // extern "C"

@@ -416,6 +416,8 @@ int sdvl_ctx_destroy(sdvl_ctx *ctx) {
   if (ctx->d_registry) (void)hipFree(ctx->d_registry);
   if (ctx->d_fast_table) (void)hipFree(ctx->d_fast_table);
   if (ctx->d_undist_map) (void)hipFree(ctx->d_undist_map);
+  for (const sdvl_ctx::RectMap &m : ctx->rect_maps)
+    if (m.d_map) (void)hipFree(m.d_map);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_search) (void)hipHostFree(ctx->h_search);
   if (ctx->d_search) (void)hipFree(ctx->d_search);

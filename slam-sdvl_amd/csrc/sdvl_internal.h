@@ -69,6 +69,20 @@ struct sdvl_ctx {
   double undist_key[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   void *undist_quads = nullptr;  // the per-quad records behind the per-pixel words, same allocation
   long long undist_maps_built = 0;
+  // the maps of rectified cameras (sdvl_rectify): a cache of their own, least recently used slot replaced, so that a rig alternating
+  // left and right builds each map once.  key = raw K, D, R_i, rectified K, size, source stride
+  struct RectMap {
+    void *d_map = nullptr;
+    size_t bytes = 0;
+    void *quads = nullptr;
+    double key[25] = {0};
+    unsigned long long used = 0;  // rect_tick of the last use; 0: empty
+  };
+  static constexpr int kRectMaps = 4;
+  RectMap rect_maps[kRectMaps];
+  unsigned long long rect_tick = 0;
+  long long rect_maps_built = 0, rect_no_source_last = 0;
+  uint32_t rect_count_host = 0;  // where a map build's count of pixels without a source lands
   // input ring (sdvl_ctx_prefetch_images / _fence): a second stream that carries the NEXT step's images while this one computes
   hipStream_t copy_stream = nullptr;
   hipEvent_t copy_event[4] = {nullptr, nullptr, nullptr, nullptr};  // one per prefetch in flight (ticket & 3)

@@ -13,6 +13,11 @@
 // four frames — map words decoded once, 15-bit weight table entry, 4 taps, (sum + 2^14) >> 15, one 32-bit store per frame.
 // HBM-bound: one u8 neighbourhood read and one u8 write per pixel (2 W H algorithmic bytes per frame).
 // Round 5's kernel recomputed the FP64 model for every pixel of every frame: 282 us per 256 frames of 640x480 (0.07 of HBM).
+//
+// Stereo rigs as calibrated (sdvl_rectify, sdvl_frames_upload_rectified): rectification is the same remap behind another map — where
+// cv::undistort passes the identity and K, a rectified camera has a rotation R_i and new intrinsics.  rectify_map_kernel writes that map
+// in the same words, undistort_quad_kernel and undistort_remap_kernel consume it unchanged, one launch per camera.  Those maps are kept in a
+// cache of their own (sdvl_ctx::rect_maps); the undistortion's single slot and its counter stay as they were.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -71,28 +76,57 @@ __device__ __forceinline__ void map_load4(const uint32_t *map, size_t px, uint32
   }
 }
 
+// the map entry of the ray (x, y, 1): the radial-tangential model in the library's expression order, fixed-point position, the word's
+// parts.  Returns whether one of the entry's four taps lies outside the image
+__device__ __forceinline__ bool map_entry(const UndistParams &P, double x, double y, uint32_t *fa, uint32_t *fb, uint32_t *sxc, uint32_t *syc) {
+  const double x2 = x * x, y2 = y * y;
+  const double r2 = x2 + y2, _2xy = 2 * x * y;
+  const double k4 = 0, k5 = 0, k6 = 0;
+  const double kr = (1 + ((P.k3 * r2 + P.k2) * r2 + P.k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+  const double u = P.fx * (x * kr + P.p1 * _2xy + P.p2 * (r2 + 2 * x2)) + P.u0;
+  const double v = P.fy * (y * kr + P.p1 * (r2 + 2 * y2) + P.p2 * _2xy) + P.v0;
+  const int iu = __double2int_rn(u * 32), iv = __double2int_rn(v * 32);  // cvRound = round half to even
+  const int sx = static_cast<short>(iu >> 5), sy = static_cast<short>(iv >> 5);
+  *fa = static_cast<uint32_t>(iu & 31);
+  *fb = static_cast<uint32_t>(iv & 31);
+  *sxc = static_cast<uint32_t>(min(max(sx, -2), P.w) + 2);
+  *syc = static_cast<uint32_t>(min(max(sy, -2), P.h) + 2);
+  return sx < 0 || sy < 0 || sx + 1 >= P.w || sy + 1 >= P.h;
+}
+
 template <bool kWideMap>
 __global__ __launch_bounds__(256) void undistort_map_kernel(const double *__restrict__ xw, const double *__restrict__ yw, UndistParams P, int pitch,
                                                             uint32_t *__restrict__ map) {
   const int j = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
   if (j >= pitch) return;
   uint32_t fa = 0, fb = 0, sxc = 0, syc = 0;  // sx = sy = -2: outside
-  if (j < P.w) {
-    const double x = xw[j], y = yw[r];
-    const double x2 = x * x, y2 = y * y;
-    const double r2 = x2 + y2, _2xy = 2 * x * y;
-    const double k4 = 0, k5 = 0, k6 = 0;
-    const double kr = (1 + ((P.k3 * r2 + P.k2) * r2 + P.k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
-    const double u = P.fx * (x * kr + P.p1 * _2xy + P.p2 * (r2 + 2 * x2)) + P.u0;
-    const double v = P.fy * (y * kr + P.p1 * (r2 + 2 * y2) + P.p2 * _2xy) + P.v0;
-    const int iu = __double2int_rn(u * 32), iv = __double2int_rn(v * 32);  // cvRound = round half to even
-    const int sx = static_cast<short>(iu >> 5), sy = static_cast<short>(iv >> 5);
-    fa = static_cast<uint32_t>(iu & 31);
-    fb = static_cast<uint32_t>(iv & 31);
-    sxc = static_cast<uint32_t>(min(max(sx, -2), P.w) + 2);
-    syc = static_cast<uint32_t>(min(max(sy, -2), P.h) + 2);
-  }
+  if (j < P.w) map_entry(P, xw[j], yw[r], &fa, &fb, &sxc, &syc);
   map_store<kWideMap>(map, static_cast<size_t>(r) * pitch + j, fa, fb, sxc, syc);
+}
+
+// The map of a RECTIFIED camera, the sibling of undistort_map_kernel: the ray of output pixel (j, r) is M (j, r, 1) with M = R_i^T
+// K_rect^-1 (host, FP64), evaluated directly — M is full, so the library's accumulation along a row (xw / yw above) has no per-row and
+// per-column table to live in — then the same entry.  A ray that does not point forward in the raw camera's frame (w <= 0, or not a
+// number: a large turn, a wide override) has no source: the entry says "outside", it is not left to what x / w converts to.  The kernel
+// also counts the pixels with a tap outside the raw image: one ballot and one atomic add per wave.
+struct RectifyRays {
+  double M[9];
+};
+
+template <bool kWideMap>
+__global__ __launch_bounds__(256) void rectify_map_kernel(RectifyRays rays, UndistParams P, int pitch, uint32_t *__restrict__ map,
+                                                          unsigned int *__restrict__ no_source) {
+  const int j = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+  uint32_t fa = 0, fb = 0, sxc = 0, syc = 0;  // sx = sy = -2: outside
+  bool outside = false;
+  if (j < P.w) {
+    const double *M = rays.M;
+    const double x = M[0] * j + M[1] * r + M[2], y = M[3] * j + M[4] * r + M[5], w = M[6] * j + M[7] * r + M[8];
+    outside = !(w > 0) || map_entry(P, x / w, y / w, &fa, &fb, &sxc, &syc);  // (w <= 0: the entry stays "outside")
+  }
+  if (j < pitch) map_store<kWideMap>(map, static_cast<size_t>(r) * pitch + j, fa, fb, sxc, syc);
+  const unsigned long long votes = __ballot(outside);  // (every lane of the wave arrives here)
+  if (votes != 0 && (threadIdx.x & 63) == 0) atomicAdd(no_source, static_cast<unsigned int>(__popcll(votes)));
 }
 
 // The remap proper works on QUADS of adjacent output pixels.  The map moves by about a pixel per pixel, so the source pixels of a quad
@@ -354,57 +388,73 @@ bool build_tables(int w, int h, const sdvl_camera *cam, double *xw, double *yw) 
   return true;
 }
 
-int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int w, int h, const sdvl_camera *cam,
-                  const sdvl_distortion *dist, uint8_t *const *dst, int dst_stride) {
-  const size_t img_bytes = static_cast<size_t>(w) * h;
-  const bool remap = dist->d[0] != 0.0;  // Camera::SetDistortions tests d0 only (camera.cc:46): otherwise out = in.clone()
-  const uint8_t *dev_src[1];
-  std::vector<const uint8_t *> srcs(n);
-  if (src_on_device) {
-    for (int i = 0; i < n; i++) srcs[i] = static_cast<const uint8_t *>(src[i]);
-  } else if (remap) {  // raw images go to a device scratch area first
-    int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, img_bytes * n, false);
-    if (rc) return rc;
-    for (int i = 0; i < n; i++) {
-      uint8_t *d = static_cast<uint8_t *>(ctx->d_work) + img_bytes * i;
-      SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(d, w, src[i], src_stride, w, h, hipMemcpyHostToDevice, ctx->stream));
-      srcs[i] = d;
-    }
-    src_stride = w;
+// ---- the two halves every route shares: "get the map" (the camera's, or a rectified camera's) and "remap with a map"
+struct MapRef {
+  const uint32_t *words;  // per-pixel words, row pitch `pitch`
+  const QuadRec *quads;   // per-quad records
+  int pitch;
+  bool wide;              // two words per pixel
+};
+
+int map_pitch(int w) { return (w + 3) / 4 * 4; }
+bool map_is_wide(int w, int h) { return w > kMapMax || h > kMapMax; }  // integer parts beyond the packed word's 11 bits: two words per pixel
+
+// a map's allocation: per-pixel words | per-quad records, and for a rectified camera's map | the count of pixels without a source
+struct MapLayout {
+  sdvl_part<uint32_t> px;
+  sdvl_part<QuadRec> quads;
+  sdvl_part<unsigned int> count;
+  size_t bytes;
+  MapLayout(int w, int h, bool with_count) {
+    sdvl_layout m;
+    const int pitch = map_pitch(w);
+    px = m.take<uint32_t>((map_is_wide(w, h) ? 2 : 1) * static_cast<size_t>(pitch) * h);
+    quads = m.take<QuadRec>(static_cast<size_t>(pitch / 4) * h);
+    if (with_count) count = m.take<unsigned int>(1);
+    bytes = m.bytes();
   }
-  (void)dev_src;
-  if (!remap) {
-    for (int i = 0; i < n; i++)
-      SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(dst[i], dst_stride, src[i], src_stride, w, h,
-                                           src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    return SDVL_OK;
+};
+
+// room for a map of `bytes` in *d_map (grown only)
+int map_storage(sdvl_ctx *ctx, void **d_map, size_t *have, size_t bytes) {
+  if (*have >= bytes) return SDVL_OK;
+  if (*d_map) {
+    SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));  // remaps that read the old map may still be queued
+    SDVL_HIP_CHECK(ctx, hipFree(*d_map));
+    *d_map = nullptr;
+    *have = 0;
   }
-  // ---- the camera's map: built once per (size, intrinsics, distortion) and context
-  const int pitch = (w + 3) / 4 * 4;
-  const bool wide_map = w > kMapMax || h > kMapMax;  // integer parts beyond the packed word's 11 bits: two words per pixel
-  UndistParams P{cam->fx, cam->fy, cam->u0, cam->v0, dist->d[0], dist->d[1], dist->d[2], dist->d[3], dist->d[4], w, h, src_stride, dst_stride};
-  double key[12] = {cam->fx, cam->fy, cam->u0, cam->v0, dist->d[0], dist->d[1], dist->d[2], dist->d[3], dist->d[4], static_cast<double>(w), static_cast<double>(h),
-                    static_cast<double>(src_stride)};  // (the quad records hold source offsets)
+  SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
+  SDVL_HIP_CHECK(ctx, hipMalloc(d_map, bytes));
+  *have = bytes;
+  return SDVL_OK;
+}
+
+// the per-quad records behind freshly written per-pixel words
+int build_quads(sdvl_ctx *ctx, const UndistParams &P, bool wide_map, const uint32_t *d_map, QuadRec *d_quads) {
+  const int pitch = map_pitch(P.w);
+  if (wide_map)
+    SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<true>, dim3((pitch / 4 + 255) / 256, P.h), dim3(256), d_map, pitch, P, d_quads);
+  else
+    SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<false>, dim3((pitch / 4 + 255) / 256, P.h), dim3(256), d_map, pitch, P, d_quads);
+  SDVL_HIP_CHECK(ctx, hipGetLastError());
+  return SDVL_OK;
+}
+
+// the camera's map: built once per (size, intrinsics, distortion, source stride) and context
+int undistort_map_of(sdvl_ctx *ctx, const UndistParams &P, const sdvl_camera *cam, MapRef *out) {
+  const int w = P.w, h = P.h, pitch = map_pitch(w);
+  const bool wide_map = map_is_wide(w, h);
+  double key[12] = {P.fx, P.fy, P.u0, P.v0, P.k1, P.k2, P.p1, P.p2, P.k3, static_cast<double>(w), static_cast<double>(h),
+                    static_cast<double>(P.sstride)};  // (the quad records hold source offsets)
+  const MapLayout m(w, h, false);
   if (!ctx->d_undist_map || memcmp(key, ctx->undist_key, sizeof(key)) != 0) {
-    sdvl_layout m;  // the map's allocation: per-pixel words | per-quad records
-    const sdvl_part<uint32_t> px = m.take<uint32_t>((wide_map ? 2 : 1) * static_cast<size_t>(pitch) * h);
-    const sdvl_part<QuadRec> quads = m.take<QuadRec>(static_cast<size_t>(pitch / 4) * h);
-    const size_t map_bytes = m.bytes();
-    if (ctx->undist_map_bytes < map_bytes) {
-      if (ctx->d_undist_map) {
-        SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));  // remaps that read the old map may still be queued
-        SDVL_HIP_CHECK(ctx, hipFree(ctx->d_undist_map));
-        ctx->d_undist_map = nullptr;
-        ctx->undist_map_bytes = 0;
-      }
-      SDVL_HIP_CHECK(ctx, sdvl_bind_device(ctx));
-      SDVL_HIP_CHECK(ctx, hipMalloc(&ctx->d_undist_map, map_bytes));
-      ctx->undist_map_bytes = map_bytes;
-    }
+    int rc = map_storage(ctx, &ctx->d_undist_map, &ctx->undist_map_bytes, m.bytes);
+    if (rc) return rc;
     sdvl_layout st;  // staging: the column table | the row table
     const sdvl_part<double> st_xw = st.take<double>(w), st_yw = st.take<double>(h);
     void *hs = nullptr, *dsx = nullptr;
-    int rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
+    rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
     if (rc) return rc;
     if (!build_tables(w, h, cam, st_xw.in(hs), st_yw.in(hs))) {
       ctx->err = "camera matrix is singular";
@@ -412,40 +462,179 @@ int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, 
     }
     SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
     const double *d_xw = st_xw.cin(dsx), *d_yw = st_yw.cin(dsx);
-    uint32_t *d_map = px.in(ctx->d_undist_map);
-    QuadRec *d_quads = quads.in(ctx->d_undist_map);
-    if (wide_map) {
+    uint32_t *d_map = m.px.in(ctx->d_undist_map);
+    if (wide_map)
       SDVL_LAUNCH(ctx, "undistort_map", undistort_map_kernel<true>, dim3((pitch + 255) / 256, h), dim3(256), d_xw, d_yw, P, pitch, d_map);
-      SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<true>, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(d_map), pitch, P, d_quads);
-    } else {
+    else
       SDVL_LAUNCH(ctx, "undistort_map", undistort_map_kernel<false>, dim3((pitch + 255) / 256, h), dim3(256), d_xw, d_yw, P, pitch, d_map);
-      SDVL_LAUNCH(ctx, "undistort_map", undistort_quad_kernel<false>, dim3((pitch / 4 + 255) / 256, h), dim3(256), static_cast<const uint32_t *>(d_map), pitch, P, d_quads);
-    }
-    SDVL_HIP_CHECK(ctx, hipGetLastError());
-    ctx->undist_quads = d_quads;
+    rc = build_quads(ctx, P, wide_map, d_map, m.quads.in(ctx->d_undist_map));
+    if (rc) return rc;
+    ctx->undist_quads = m.quads.in(ctx->d_undist_map);
     memcpy(ctx->undist_key, key, sizeof(key));
     ctx->undist_maps_built++;
   }
-  // ---- the remap
+  *out = MapRef{m.px.cin(ctx->d_undist_map), static_cast<const QuadRec *>(ctx->undist_quads), pitch, wide_map};
+  return SDVL_OK;
+}
+
+UndistParams rectify_params(const sdvl_rectification *r, int w, int h, int src_stride, int dst_stride) {
+  return UndistParams{r->raw.fx, r->raw.fy, r->raw.u0, r->raw.v0, r->dist.d[0], r->dist.d[1], r->dist.d[2], r->dist.d[3], r->dist.d[4], w, h, src_stride, dst_stride};
+}
+
+// a rectified camera's map: looked up in the context's cache, built into its least recently used slot
+int rectify_map_of(sdvl_ctx *ctx, const UndistParams &P, const sdvl_rectification *r, MapRef *out) {
+  const int w = P.w, h = P.h, pitch = map_pitch(w);
+  const bool wide_map = map_is_wide(w, h);
+  double key[25] = {P.fx, P.fy, P.u0, P.v0, P.k1, P.k2, P.p1, P.p2, P.k3};
+  for (int i = 0; i < 9; i++) key[9 + i] = r->R[i];
+  key[18] = r->rect.fx, key[19] = r->rect.fy, key[20] = r->rect.u0, key[21] = r->rect.v0;
+  key[22] = w, key[23] = h, key[24] = P.sstride;
+  const MapLayout m(w, h, true);
+  sdvl_ctx::RectMap *slot = nullptr;
+  for (sdvl_ctx::RectMap &s : ctx->rect_maps)
+    if (s.used && memcmp(key, s.key, sizeof(key)) == 0) slot = &s;
+  if (!slot) {
+    slot = &ctx->rect_maps[0];
+    for (sdvl_ctx::RectMap &s : ctx->rect_maps)
+      if (s.used < slot->used) slot = &s;
+    slot->used = 0;  // (not a map until the build below has been queued)
+    int rc = map_storage(ctx, &slot->d_map, &slot->bytes, m.bytes);
+    if (rc) return rc;
+    // M = R_i^T K_rect^-1, every entry as written here
+    const double ifx = 1.0 / r->rect.fx, ify = 1.0 / r->rect.fy, cx = -r->rect.u0 * ifx, cy = -r->rect.v0 * ify;
+    RectifyRays rays;
+    for (int k = 0; k < 3; k++) {
+      const double a = r->R[k], b = r->R[3 + k], c = r->R[6 + k];  // row k of R_i^T
+      rays.M[3 * k] = a * ifx;
+      rays.M[3 * k + 1] = b * ify;
+      rays.M[3 * k + 2] = a * cx + b * cy + c;
+    }
+    uint32_t *d_map = m.px.in(slot->d_map);
+    unsigned int *d_count = m.count.in(slot->d_map);
+    SDVL_HIP_CHECK(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
+    if (wide_map)
+      SDVL_LAUNCH(ctx, "rectify_map", rectify_map_kernel<true>, dim3((pitch + 255) / 256, h), dim3(256), rays, P, pitch, d_map, d_count);
+    else
+      SDVL_LAUNCH(ctx, "rectify_map", rectify_map_kernel<false>, dim3((pitch + 255) / 256, h), dim3(256), rays, P, pitch, d_map, d_count);
+    rc = build_quads(ctx, P, wide_map, d_map, m.quads.in(slot->d_map));
+    if (rc) return rc;
+    // the count comes back with the build: once per camera, so the wait is not on any frame's path
+    SDVL_HIP_CHECK(ctx, hipMemcpyAsync(&ctx->rect_count_host, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
+    ctx->rect_no_source_last = ctx->rect_count_host;
+    slot->quads = m.quads.in(slot->d_map);
+    memcpy(slot->key, key, sizeof(key));
+    ctx->rect_maps_built++;
+  }
+  slot->used = ++ctx->rect_tick;
+  *out = MapRef{m.px.cin(slot->d_map), static_cast<const QuadRec *>(slot->quads), pitch, wide_map};
+  return SDVL_OK;
+}
+
+// raw images in host memory go to a device scratch area first: srcs[i] and *src_stride name what the remap reads
+int stage_sources(sdvl_ctx *ctx, int n, const void *const *src, int *src_stride, int src_on_device, int w, int h, std::vector<const uint8_t *> *srcs) {
+  srcs->resize(n);
+  if (src_on_device) {
+    for (int i = 0; i < n; i++) (*srcs)[i] = static_cast<const uint8_t *>(src[i]);
+    return SDVL_OK;
+  }
+  const size_t img_bytes = static_cast<size_t>(w) * h;
+  int rc = sdvl_ensure(ctx, &ctx->d_work, &ctx->d_work_bytes, img_bytes * n, false);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) {
+    uint8_t *d = static_cast<uint8_t *>(ctx->d_work) + img_bytes * i;
+    SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(d, w, src[i], *src_stride, w, h, hipMemcpyHostToDevice, ctx->stream));
+    (*srcs)[i] = d;
+  }
+  *src_stride = w;
+  return SDVL_OK;
+}
+
+int remap_with_map(sdvl_ctx *ctx, int n, const std::vector<const uint8_t *> &srcs, uint8_t *const *dst, const UndistParams &P, const MapRef &map) {
   const size_t jb = sizeof(UndistJob) * n;
   void *hs = nullptr, *dsx = nullptr;
   int rc = sdvl_stage_alloc(ctx, jb, &hs, &dsx);
   if (rc) return rc;
   UndistJob *hj = static_cast<UndistJob *>(hs);
-  int wide = ((dst_stride | w) & 3) == 0 ? 1 : 0;
+  int wide = ((P.dstride | P.w) & 3) == 0 ? 1 : 0;
   for (int i = 0; i < n; i++) {
     hj[i] = UndistJob{srcs[i], dst[i]};
     if (reinterpret_cast<uintptr_t>(dst[i]) & 3u) wide = 0;
   }
   SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, jb));
-  const dim3 grid((n + kRemapFrames - 1) / kRemapFrames, (w + 127) / 128, (h + 7) / 8);
-  if (wide_map)
-    SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel<true>, grid, dim3(256), static_cast<const UndistJob *>(dsx), static_cast<const uint32_t *>(ctx->d_undist_map),
-                static_cast<const QuadRec *>(ctx->undist_quads), pitch, n, wide, P);
+  const dim3 grid((n + kRemapFrames - 1) / kRemapFrames, (P.w + 127) / 128, (P.h + 7) / 8);
+  if (map.wide)
+    SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel<true>, grid, dim3(256), static_cast<const UndistJob *>(dsx), map.words, map.quads, map.pitch, n, wide, P);
   else
-    SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel<false>, grid, dim3(256), static_cast<const UndistJob *>(dsx), static_cast<const uint32_t *>(ctx->d_undist_map),
-                static_cast<const QuadRec *>(ctx->undist_quads), pitch, n, wide, P);
+    SDVL_LAUNCH(ctx, "undistort", undistort_remap_kernel<false>, grid, dim3(256), static_cast<const UndistJob *>(dsx), map.words, map.quads, map.pitch, n, wide, P);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
+  return SDVL_OK;
+}
+
+int run_undistort(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int w, int h, const sdvl_camera *cam,
+                  const sdvl_distortion *dist, uint8_t *const *dst, int dst_stride) {
+  if (dist->d[0] == 0.0) {  // Camera::SetDistortions tests d0 only (camera.cc:46): otherwise out = in.clone()
+    for (int i = 0; i < n; i++)
+      SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(dst[i], dst_stride, src[i], src_stride, w, h,
+                                           src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    return SDVL_OK;
+  }
+  std::vector<const uint8_t *> srcs;
+  int rc = stage_sources(ctx, n, src, &src_stride, src_on_device, w, h, &srcs);
+  if (rc) return rc;
+  const UndistParams P{cam->fx, cam->fy, cam->u0, cam->v0, dist->d[0], dist->d[1], dist->d[2], dist->d[3], dist->d[4], w, h, src_stride, dst_stride};
+  MapRef map;
+  rc = undistort_map_of(ctx, P, cam, &map);
+  if (rc) return rc;
+  return remap_with_map(ctx, n, srcs, dst, P, map);
+}
+
+int check_rectification(sdvl_ctx *ctx, const sdvl_rectification *r) {
+  bool finite = true;
+  for (int i = 0; i < 9; i++) finite = finite && std::isfinite(r->R[i]);
+  for (int i = 0; i < 5; i++) finite = finite && std::isfinite(r->dist.d[i]);
+  for (const sdvl_camera *c : {&r->raw, &r->rect}) finite = finite && std::isfinite(c->fx) && std::isfinite(c->fy) && std::isfinite(c->u0) && std::isfinite(c->v0);
+  SDVL_REQUIRE(ctx, finite, "sdvl_rectify: a value of the rectification is not finite");
+  SDVL_REQUIRE(ctx, r->raw.fx > 0 && r->raw.fy > 0 && r->rect.fx > 0 && r->rect.fy > 0, "sdvl_rectify: a focal length is not positive");
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) {
+      const double dot = r->R[a] * r->R[b] + r->R[3 + a] * r->R[3 + b] + r->R[6 + a] * r->R[6 + b];
+      SDVL_REQUIRE(ctx, std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-9, "sdvl_rectify: R is not a rotation (R^T R differs from I by more than 1e-9)");
+    }
+  return SDVL_OK;
+}
+
+// the rectified route: always a remap — the rotation and the new intrinsics move every pixel, lens or not.  The remap launch is the
+// undistorted route's own
+int run_rectify(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int w, int h, const sdvl_rectification *r,
+                uint8_t *const *dst, int dst_stride) {
+  int rc = check_rectification(ctx, r);
+  if (rc) return rc;
+  std::vector<const uint8_t *> srcs;
+  rc = stage_sources(ctx, n, src, &src_stride, src_on_device, w, h, &srcs);
+  if (rc) return rc;
+  const UndistParams P = rectify_params(r, w, h, src_stride, dst_stride);
+  MapRef map;
+  rc = rectify_map_of(ctx, P, r, &map);
+  if (rc) return rc;
+  return remap_with_map(ctx, n, srcs, dst, P, map);
+}
+
+// the frames of a fused upload take a new level 0: their own storage, nothing of the old image's corners
+int frames_take_level0(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride, std::vector<uint8_t *> *dst) {
+  dst->resize(n);
+  for (int i = 0; i < n; i++) {
+    SDVL_REQUIRE(ctx, frames[i] && src[i], "null frame or image");
+    SDVL_REQUIRE(ctx, frames[i]->width == frames[0]->width && frames[i]->height == frames[0]->height, "frames of one call share a size");
+    SDVL_REQUIRE(ctx, src_stride >= frames[i]->width, "stride smaller than width");
+    SDVL_REQUIRE(ctx, frames[i]->width <= kMapMaxWide && frames[i]->height <= kMapMaxWide, "image size out of range (2 .. 4095 a side)");
+    frames[i]->v.level[0] = frames[i]->own_level0;
+    (*dst)[i] = frames[i]->own_level0;
+    frames[i]->hdr_stale = 1;
+    frames[i]->v.n_corners = 0;
+    frames[i]->desc_valid = 0;
+    frames[i]->bins_valid = 0;
+  }
   return SDVL_OK;
 }
 
@@ -467,20 +656,53 @@ int sdvl_frames_upload_undistorted(sdvl_ctx *ctx, int n, sdvl_frame *const *fram
                                    int src_on_device, const sdvl_camera *cam, const sdvl_distortion *dist) {
   if (!ctx || n < 0 || (n > 0 && (!frames || !src)) || !cam || !dist) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  std::vector<uint8_t *> dst(n);
-  for (int i = 0; i < n; i++) {
-    SDVL_REQUIRE(ctx, frames[i] && src[i], "null frame or image");
-    SDVL_REQUIRE(ctx, frames[i]->width == frames[0]->width && frames[i]->height == frames[0]->height, "frames of one call share a size");
-    SDVL_REQUIRE(ctx, src_stride >= frames[i]->width, "stride smaller than width");
-    SDVL_REQUIRE(ctx, frames[i]->width <= kMapMaxWide && frames[i]->height <= kMapMaxWide, "image size out of range (2 .. 4095 a side)");
-    frames[i]->v.level[0] = frames[i]->own_level0;
-    dst[i] = frames[i]->own_level0;
-    frames[i]->hdr_stale = 1;
-    frames[i]->v.n_corners = 0;
-    frames[i]->desc_valid = 0;
-    frames[i]->bins_valid = 0;
-  }
+  std::vector<uint8_t *> dst;
+  const int rc = frames_take_level0(ctx, n, frames, src, src_stride, &dst);
+  if (rc) return rc;
   return run_undistort(ctx, n, src, src_stride, src_on_device, frames[0]->width, frames[0]->height, cam, dist, dst.data(), frames[0]->width);
+}
+
+int sdvl_rectify(sdvl_ctx *ctx, int n, const void *const *src, int src_stride, int src_on_device, int width, int height,
+                 const sdvl_rectification *r, void *const *dst_dev, int dst_stride) {
+  if (!ctx || n < 0 || (n > 0 && (!src || !dst_dev)) || !r) return SDVL_ERR_INVALID;
+  if (n == 0) return SDVL_OK;
+  SDVL_REQUIRE(ctx, width >= 2 && height >= 2 && width <= kMapMaxWide && height <= kMapMaxWide, "image size out of range (2 .. 4095 a side)");
+  SDVL_REQUIRE(ctx, src_stride >= width && dst_stride >= width, "stride smaller than width");
+  for (int i = 0; i < n; i++) SDVL_REQUIRE(ctx, src[i] && dst_dev[i] && src[i] != dst_dev[i], "null image or in-place rectification");
+  return run_rectify(ctx, n, src, src_stride, src_on_device, width, height, r, reinterpret_cast<uint8_t *const *>(dst_dev), dst_stride);
+}
+
+int sdvl_frames_upload_rectified(sdvl_ctx *ctx, int n, sdvl_frame *const *frames, const void *const *src, int src_stride,
+                                 int src_on_device, const sdvl_rectification *r) {
+  if (!ctx || n < 0 || (n > 0 && (!frames || !src)) || !r) return SDVL_ERR_INVALID;
+  if (n == 0) return SDVL_OK;
+  SDVL_REQUIRE(ctx, frames[0] && frames[0]->width >= 2 && frames[0]->height >= 2, "null frame or image");
+  std::vector<uint8_t *> dst;
+  const int rc = frames_take_level0(ctx, n, frames, src, src_stride, &dst);
+  if (rc) return rc;
+  return run_rectify(ctx, n, src, src_stride, src_on_device, frames[0]->width, frames[0]->height, r, dst.data(), frames[0]->width);
+}
+
+int sdvl_rectify_stats(sdvl_ctx *ctx, int64_t *out2) {
+  if (!ctx || !out2) return SDVL_ERR_INVALID;
+  out2[0] = ctx->rect_maps_built;
+  out2[1] = ctx->rect_no_source_last;
+  return SDVL_OK;
+}
+
+int sdvl_rectify_map_words(sdvl_ctx *ctx, int width, int height, int src_stride, const sdvl_rectification *r, uint32_t *out_words) {
+  if (!ctx || !r || !out_words) return SDVL_ERR_INVALID;
+  SDVL_REQUIRE(ctx, width >= 2 && height >= 2 && width <= kMapMaxWide && height <= kMapMaxWide, "image size out of range (2 .. 4095 a side)");
+  SDVL_REQUIRE(ctx, src_stride >= width, "stride smaller than width");
+  int rc = check_rectification(ctx, r);
+  if (rc) return rc;
+  MapRef map;
+  rc = rectify_map_of(ctx, rectify_params(r, width, height, src_stride, width), r, &map);
+  if (rc) return rc;
+  const size_t word_bytes = (map.wide ? 2 : 1) * sizeof(uint32_t);
+  SDVL_HIP_CHECK(ctx, hipMemcpy2DAsync(out_words, width * word_bytes, map.words, map.pitch * word_bytes, width * word_bytes, height, hipMemcpyDeviceToHost, ctx->stream));
+  SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
+  return SDVL_OK;
 }
 
 }  // extern "C"

@@ -121,6 +121,7 @@ SDVLBatch::~SDVLBatch() {  // (the relocalisation store goes with its member, be
     Device::SetCurrent(dev_);
     sdvl_track_destroy(dev_->ctx(), tables_.set);
   }
+  if (d_rights_) (void)sdvl_device_free(dev_->ctx(), d_rights_);
 }
 
 // the calling thread's pool: made at its first ParallelFor, made again when a batch asks for another size, never joined at thread exit
@@ -320,10 +321,12 @@ void SDVLBatch::HandleFrames(const vector<Image> &imgs, const vector<DepthImage>
     bool staged;
     ~DepthScope() {
       b->step_depths_ = nullptr;
+      b->rights_rectified_ = false;
       if (staged) (void)sdvl_depth_stage_end(b->dev_->ctx());
     }
   } depth_scope{this, !depths.empty()};
   step_depths_ = &depths;
+  rights_rectified_ = false;
   Device::SetCurrent(dev_);
   // a pageable depth image is copied to the device once per step: the keyframes' lookup and the mapper's filter passes share the copy
   if (!depths.empty()) dev_->Check(sdvl_depth_stage_begin(dev_->ctx()), "sdvl_depth_stage_begin");

@@ -71,7 +71,14 @@ class SDVLBatch {
   void LookupKeyframeFeatures(MapStep &m);
   void SearchFilterMeasured(MapStep &m, int total, const sdvl_camera &cam, const sdvl_search_params &sp);
   const std::vector<DepthImage> *step_depths_ = nullptr;  // the depth images of the step in flight (HandleFrames, batch.cc)
-  const DepthImage *DepthOf(int i) const;                  // tracker i's, null: none
+  const DepthImage *DepthOf(int i);                        // tracker i's, null: none; of a tracker fed raw pairs, the rectified right image
+  // SDVL::SetStereoRectification: the raw right images of the step, rectified into HBM by ONE sdvl_rectify call the first time a consumer
+  // asks for one (a step without a consumer rectifies nothing)
+  void RectifyRights();
+  std::vector<DepthImage> rectified_rights_;
+  bool rights_rectified_ = false;
+  void *d_rights_ = nullptr;
+  size_t d_rights_bytes_ = 0;
   struct CameraAndLens {  // the camera of the batch as the device calls take it, and its lens if it has one
     sdvl_camera cam;
     sdvl_distortion dist;

@@ -7,6 +7,7 @@
 #include "depth_jobs.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace sdvl {
 
@@ -32,9 +33,54 @@ SDVLBatch::CameraAndLens SDVLBatch::BatchCamera() const {
   return CameraAndLens{camera.abi(), camera.distortion(), camera.HasDistortion()};
 }
 
-const DepthImage *SDVLBatch::DepthOf(int i) const {
+const DepthImage *SDVLBatch::DepthOf(int i) {
   if (!step_depths_ || step_depths_->empty() || (*step_depths_)[i].empty()) return nullptr;
-  return &(*step_depths_)[i];
+  if (!trk_[i]->StereoRectification()) return &(*step_depths_)[i];
+  if (!rights_rectified_) RectifyRights();
+  return &rectified_rights_[i];
+}
+
+// Stereo rigs as calibrated (SDVL::SetStereoRectification): the step's right images are RAW images of the right camera.  They are
+// rectified into HBM here, all trackers' in ONE sdvl_rectify call, when the step's first consumer asks for one (DepthOf), and every
+// consumer of the step — sdvl_stereo_depth, sdvl_search_run_filter_stereo — is handed the rectified image on the device.
+void SDVLBatch::RectifyRights() {
+  const int B = static_cast<int>(trk_.size());
+  rectified_rights_.assign(B, DepthImage());
+  vector<int> who;
+  vector<const void *> src;
+  for (int i = 0; i < B; i++) {
+    const DepthImage &d = (*step_depths_)[i];
+    if (d.empty() || !trk_[i]->StereoRectification()) continue;
+    if (d.format != DEPTH_RIGHT8)
+      throw std::runtime_error("SDVLBatch: a tracker that seeds from a stereo pair takes a right image (DEPTH_RIGHT8), not a depth image");
+    if (!who.empty()) {
+      const DepthImage &first = (*step_depths_)[who[0]];
+      if (d.cols != first.cols || d.rows != first.rows || d.step != first.step || d.on_device != first.on_device)
+        throw std::runtime_error("SDVLBatch: the raw right images of a step share size, row pitch and memory kind");
+      if (std::memcmp(&trk_[i]->camera_->rectified_pair()->right, &trk_[who[0]]->camera_->rectified_pair()->right, sizeof(sdvl_rectification)) != 0)
+        throw std::runtime_error("SDVLBatch: the trackers of a batch share the rectified pair");
+    }
+    who.push_back(i);
+    src.push_back(d.data);
+  }
+  rights_rectified_ = true;
+  if (who.empty()) return;
+  const DepthImage &first = (*step_depths_)[who[0]];
+  const size_t image_bytes = static_cast<size_t>(first.cols) * first.rows, need = image_bytes * B;
+  if (d_rights_bytes_ < need) {
+    if (d_rights_) dev_->Check(sdvl_device_free(dev_->ctx(), d_rights_), "sdvl_device_free");
+    d_rights_ = nullptr;
+    d_rights_bytes_ = 0;
+    dev_->Check(sdvl_device_malloc(dev_->ctx(), static_cast<int64_t>(need), &d_rights_), "sdvl_device_malloc");
+    d_rights_bytes_ = need;
+  }
+  vector<void *> dst;
+  for (int i : who) dst.push_back(static_cast<uint8_t *>(d_rights_) + image_bytes * i);
+  dev_->Check(sdvl_rectify(dev_->ctx(), static_cast<int>(who.size()), src.data(), first.step, first.on_device ? 1 : 0, first.cols, first.rows,
+                           &trk_[who[0]]->camera_->rectified_pair()->right, dst.data(), first.cols),
+              "sdvl_rectify");
+  for (size_t k = 0; k < who.size(); k++)
+    rectified_rights_[who[k]] = DepthImage::Wrap(dst[k], first.cols, first.rows, first.cols, DEPTH_RIGHT8, 1.0, true);
 }
 
 void SDVLBatch::SizeDepthResults(int n) {

@@ -329,6 +329,34 @@ int sdvlh_batch_set_stereo_mapping(void *bp, int on, double disparity_sigma) {
   if (!bp) return -1;
   return Guarded([&] { AsGroup(bp)->SetStereoMapping(on != 0, disparity_sigma); });
 }
+// ---- stereo rigs as calibrated (SDVL::SetStereoRectification): rig30 = K1[4] D1[5] K2[4] D2[5] R[9] T[3] with X_right = R X_left + T.
+// The rig is planned for the batch's image size (sdvl_stereo_rectify_plan) and the step calls then take the RAW images of both cameras.
+// out5 (if not null) = the rectified camera fx fy u0 v0 and the baseline: the batch must have been made with that camera, and
+// sdvlh_batch_set_stereo called with that baseline.  on = 0 turns the switch off.  plan_only = 1: out5 is filled and nothing is set
+int sdvlh_batch_set_stereo_rectification(void *bp, int on, const double *rig30, int plan_only, double *out5) {
+  if (!bp || (on && !rig30)) return -1;
+  return Guarded([&] {
+    TrackerGroup *g = AsGroup(bp);
+    if (!on) {
+      g->SetStereoRectification(RectifiedPair(), false);
+      return;
+    }
+    StereoRig rig;
+    const double *p = rig30;
+    for (int i = 0; i < 4; i++) rig.K1[i] = *p++;
+    for (int i = 0; i < 5; i++) rig.D1[i] = *p++;
+    for (int i = 0; i < 4; i++) rig.K2[i] = *p++;
+    for (int i = 0; i < 5; i++) rig.D2[i] = *p++;
+    for (int i = 0; i < 9; i++) rig.R[i] = *p++;
+    for (int i = 0; i < 3; i++) rig.T[i] = *p++;
+    const RectifiedPair pair = RectifiedPair::Plan(rig, g->width(), g->height());
+    if (out5) {
+      out5[0] = pair.camera().fx; out5[1] = pair.camera().fy; out5[2] = pair.camera().u0; out5[3] = pair.camera().v0;
+      out5[4] = pair.baseline;
+    }
+    if (!plan_only) g->SetStereoRectification(pair, true);
+  });
+}
 // tracker i's stereo mapping so far: out9 = candidate updates measured, fallen back by status (NOMATCH, AMBIGUOUS, EDGE, OUTSIDE),
 // keyframes matched, corners fixed and matched, fixed and unmatched, linked — the counters of sdvlh_batch_depth_map_stats under the
 // stereo producer's names

@@ -56,6 +56,10 @@ bool Config::SetParameter(const std::string &key, double v) {
 }
 
 bool Config::ReadParameters(const std::string &filename) {
+  return ReadKeyValues(filename, [this](const std::string &key, double v) { SetParameter(key, v); });
+}
+
+bool Config::ReadKeyValues(const std::string &filename, const std::function<void(const std::string &, double)> &each) {
   std::ifstream in(filename.c_str());
   if (!in.is_open()) {
     std::cerr << "[ERROR] Failed to open file: " << filename << std::endl;
@@ -77,7 +81,7 @@ bool Config::ReadParameters(const std::string &filename) {
     char *end = nullptr;
     const double v = std::strtod(val.c_str(), &end);
     if (end == val.c_str()) continue;
-    SetParameter(key, v);
+    each(key, v);
   }
   return true;
 }

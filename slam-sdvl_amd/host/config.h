@@ -4,6 +4,7 @@
 #ifndef SDVL_HOST_CONFIG_H_
 #define SDVL_HOST_CONFIG_H_
 
+#include <functional>
 #include <string>
 
 namespace sdvl {
@@ -21,6 +22,10 @@ class Config {
     return c;
   }
   bool ReadParameters(const std::string &filename);
+  // The form of those files, stated once: "key: value" lines, '#' starts a comment, lines that begin with '%' (the YAML header), lines
+  // without a colon and values that are strings or no numbers are skipped.  `each` gets every key with its number; false: the file
+  // cannot be opened.  (host/track_sequence's --rig FILE is read through it too.)
+  static bool ReadKeyValues(const std::string &filename, const std::function<void(const std::string &, double)> &each);
   bool SetParameter(const std::string &key, double value);  // "SDVL.max_matches" style keys
   void Reset() { *this = Config(); }
 

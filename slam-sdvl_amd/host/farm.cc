@@ -91,6 +91,10 @@ void TrackerGroup::SetStereo(bool on, double baseline, const sdvl_stereo_params 
   }
 }
 
+void TrackerGroup::SetStereoRectification(const RectifiedPair &pair, bool on) {
+  for (auto &t : trackers_) t->SetStereoRectification(pair, on);
+}
+
 void TrackerGroup::SetNextImages(const void *const *dev_imgs, int stride) {
   batch_->SetNextImages(dev_imgs ? Wrap(Frames::kResident, dev_imgs, stride) : std::vector<Image>());
 }

@@ -67,9 +67,14 @@ class TrackerGroup {
   void SetStereo(bool on, double baseline, const sdvl_stereo_params &rule);
   // Stereo cameras inside the mappers (SDVL::SetStereoMapping for every tracker; the trackers share disparity_sigma).  Throws what it throws.
   void SetStereoMapping(bool on, double disparity_sigma = 0.0);
+  // Stereo rigs as calibrated (SDVL::SetStereoRectification for every tracker): the images and the second images handed to Step are the
+  // RAW images of the rig's two cameras; the group's camera must be the pair's rectified camera.  Throws what it throws.
+  void SetStereoRectification(const RectifiedPair &pair, bool on = true);
 
   Device *device() const { return dev_; }
   int size() const { return static_cast<int>(trackers_.size()); }
+  int width() const { return w_; }
+  int height() const { return h_; }
   SDVL &tracker(int i) const { return *trackers_[i]; }
   PlaneMap &map(int i) const { return *maps_[i]; }
   SDVLBatch &batch() const { return *batch_; }

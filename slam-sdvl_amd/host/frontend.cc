@@ -419,7 +419,8 @@ void BuildFrames(const vector<Frame *> &frames, const vector<sdvl_frame *> &devs
     up_f.clear();
     up_i.clear();
   };
-  // RAW camera images (Image::raw) of a camera with a lens: level 0 = Camera::UndistortImage(image), one remap launch per source kind
+  // RAW camera images (Image::raw) of a camera with a lens: level 0 = Camera::UndistortImage(image), one remap launch per source kind.
+  // Every image of a rectified camera (Camera::rectification) is a raw image of the rig's left side and takes the same route
   vector<sdvl_frame *> un_f[2];
   vector<const void *> un_i[2];
   int un_step[2] = {0, 0};
@@ -428,8 +429,12 @@ void BuildFrames(const vector<Frame *> &frames, const vector<sdvl_frame *> &devs
     const Camera *cam = frames[0]->GetCamera();
     const sdvl_camera c = cam->abi();
     const sdvl_distortion d = cam->distortion();
-    dev->Check(sdvl_frames_upload_undistorted(dev->ctx(), static_cast<int>(un_f[kind].size()), un_f[kind].data(), un_i[kind].data(), un_step[kind], kind, &c, &d),
-               "sdvl_frames_upload_undistorted");
+    if (const sdvl_rectification *r = cam->rectification())  // the left camera of a calibrated stereo rig: the same remap behind its map
+      dev->Check(sdvl_frames_upload_rectified(dev->ctx(), static_cast<int>(un_f[kind].size()), un_f[kind].data(), un_i[kind].data(), un_step[kind], kind, r),
+                 "sdvl_frames_upload_rectified");
+    else
+      dev->Check(sdvl_frames_upload_undistorted(dev->ctx(), static_cast<int>(un_f[kind].size()), un_f[kind].data(), un_i[kind].data(), un_step[kind], kind, &c, &d),
+                 "sdvl_frames_upload_undistorted");
     un_f[kind].clear();
     un_i[kind].clear();
   };
@@ -445,9 +450,14 @@ void BuildFrames(const vector<Frame *> &frames, const vector<sdvl_frame *> &devs
     const Camera *cam = co_cam;
     const sdvl_camera c = cam->abi();
     const sdvl_distortion d = cam->distortion();
-    dev->Check(sdvl_frames_upload_color(dev->ctx(), static_cast<int>(co_f.size()), co_f.data(), co_i.data(), co_key[1], co_key[2], co_key[0],
-                                        co_key[3] ? &c : nullptr, co_key[3] ? &d : nullptr),
-               "sdvl_frames_upload_color");
+    if (cam->rectification())
+      dev->Check(sdvl_frames_upload_color_rectified(dev->ctx(), static_cast<int>(co_f.size()), co_f.data(), co_i.data(), co_key[1], co_key[2], co_key[0],
+                                                    cam->rectification()),
+                 "sdvl_frames_upload_color_rectified");
+    else
+      dev->Check(sdvl_frames_upload_color(dev->ctx(), static_cast<int>(co_f.size()), co_f.data(), co_i.data(), co_key[1], co_key[2], co_key[0],
+                                          co_key[3] ? &c : nullptr, co_key[3] ? &d : nullptr),
+                 "sdvl_frames_upload_color");
     co_f.clear();
     co_i.clear();
   };
@@ -464,7 +474,7 @@ void BuildFrames(const vector<Frame *> &frames, const vector<sdvl_frame *> &devs
       co_i.push_back(imgs[i].dev_src ? imgs[i].dev_src : static_cast<const void *>(imgs[i].data));
       continue;
     }
-    if (imgs[i].raw && frames[i]->GetCamera()->HasDistortion()) {
+    if ((imgs[i].raw && frames[i]->GetCamera()->HasDistortion()) || frames[i]->GetCamera()->rectification()) {
       const int kind = imgs[i].dev_src ? 1 : 0;
       if (!un_f[kind].empty() && (imgs[i].step != un_step[kind] || frames[i]->GetCamera() != frames[0]->GetCamera())) flush_raw(kind);
       un_step[kind] = imgs[i].step;

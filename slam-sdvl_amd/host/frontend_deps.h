@@ -61,11 +61,23 @@ class Camera {
   // camera.cc:100-105: cv::undistort on the device of the calling thread.  `in` may live on the host or in HBM; `out`
   // is an HBM image that owns its storage (hand it to SDVL::HandleFrame / Frame like any other image).
   void UndistortImage(const Image &in, Image *out) const;
+  // (an addition) the camera is the RECTIFIED camera of a calibrated stereo rig (SDVL::SetStereoRectification): every image a Frame of
+  // this camera is built from is a raw image of the rig's left side, rectified inside the frame's upload (sdvl_frames_upload_rectified),
+  // and the second image of a step is a raw image of its right side.  The switch is stated HERE and nowhere else: trackers that share a
+  // Camera share it, on or off, with one pair
+  void SetRectifiedPair(const RectifiedPair *pair) {
+    rectified_ = pair != nullptr;
+    pair_ = pair ? *pair : RectifiedPair();
+  }
+  const RectifiedPair *rectified_pair() const { return rectified_ ? &pair_ : nullptr; }
+  const sdvl_rectification *rectification() const { return rectified_ ? &pair_.left : nullptr; }  // the left side's, null: not rectified
 
  private:
   double width_, height_, fx_, fy_, u0_, v0_;
   double d_[5] = {0, 0, 0, 0, 0};
   bool has_distortion_ = false;
+  bool rectified_ = false;
+  RectifiedPair pair_ = RectifiedPair();
 };
 
 // point.h:37-147 — the part the front-end reads or updates (the depth filter itself is map state, out of scope)

@@ -955,6 +955,8 @@ void MapperMap::Start() {
   if (bundle_on_) throw std::runtime_error("MapperMap::Start: bundle adjustment is on and runs in sequential mode only");
   if (depth_mapping_) throw std::runtime_error("MapperMap::Start: depth mapping is on and runs in sequential mode only");
   if (stereo_mapping_) throw std::runtime_error("MapperMap::Start: stereo mapping is on and runs in sequential mode only");
+  if (camera_ && camera_->rectified_pair())
+    throw std::runtime_error("MapperMap::Start: the camera takes raw stereo pairs (SDVL::SetStereoRectification), which are rectified in sequential mode only");
   tracker_device_ = Device::CurrentOrNull();
   running_ = true;
   thread_ = std::thread(&MapperMap::Run, this);

@@ -280,10 +280,22 @@ class SDVL {
   // one batch share baseline and rule.  First frames as with SetDepthSeeding: one without a right image, or with fewer OK corners than
   // SDVL.min_init_corners, is not kept.  Throws std::runtime_error together with the two-frame initialisation, with depth seeding from a
   // depth image, with depth mapping or depth edges (both look depths up at found pixels, which a matcher at the corners does not give),
-  // on a camera with a lens (rectified pairs only) and with a map that is neither PlaneMap nor MapperMap; std::invalid_argument for a
+  // on a camera with a lens (rectified pairs only; a calibrated rig goes through SetStereoRectification) and with a map that is neither PlaneMap nor MapperMap; std::invalid_argument for a
   // baseline or a rule sdvl_stereo_depth would refuse.
   void SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &rule = sdvl_stereo_params{0.0, 0.0, 0.0, 0, 0, 0, 0, nullptr});
   bool StereoSeeding() const { return stereo_seeding_; }
+  // Stereo rigs as calibrated (an addition): the tracker's Camera is the RECTIFIED camera of `pair` (RectifiedPair::Plan of the rig; the
+  // camera built from pair.camera(), no lens), and HandleFrame(img, right) takes the RAW images of both cameras.  The left one is
+  // rectified inside its frame's upload (sdvl_frames_upload_rectified, where a lens takes sdvl_frames_upload_undistorted); the right
+  // one into HBM, once per step for all trackers of a batch in ONE sdvl_rectify call, and only in a step that has a consumer for it (a
+  // keyframe to seed, stereo mapping).  Everything behind sees a rectified pair; poses are the rectified left camera's (R1 of the
+  // pair's left side takes the raw left camera's frame to it).  The trackers of one batch share the pair.  Throws std::runtime_error
+  // without stereo seeding, on a camera with a lens of its own, when the camera's intrinsics or size differ from the pair's, when the
+  // baseline of SetStereoSeeding differs from the pair's by more than 1e-12 relative, and with the mapper thread started;
+  // Start() throws while it is on.  The switch and the pair are kept on the Camera (Camera::rectified_pair): trackers that share a Camera
+  // share them.  SetStereoSeeding(false) and SetDepthSeeding(false) turn it off too.
+  void SetStereoRectification(const RectifiedPair &pair, bool on = true);
+  bool StereoRectification() const { return camera_->rectified_pair() != nullptr; }
   // Depth cameras inside the reference's mapper (an addition, MapperMap::SetDepthMapping): the depth image of every tracked frame feeds
   // the candidates' depth filter, and a new keyframe's corners become fixed points at their measured depth.  noise: the sensor's depth
   // noise tau = noise_abs + noise_quad z^2 (0: 0.001 m and 0.0015 per metre); the trackers of a batch share it.  Needs SetDepthSeeding and

@@ -499,7 +499,10 @@ void SDVL::SetDepthSeeding(bool on, const sdvl_depth_seed_params &rule) {
     if (!on && m->StereoMapping()) throw std::runtime_error("SDVL::SetDepthSeeding: stereo mapping is on (SetStereoMapping) and needs the stereo seeding this turns off");
   depth_seeding_ = on;
   depth_rule_ = rule;
-  if (!on) stereo_seeding_ = false;
+  if (!on) {
+    stereo_seeding_ = false;
+    camera_->SetRectifiedPair(nullptr);  // the raw pairs go with the switch that reads them
+  }
 }
 
 void SDVL::SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &rule) {
@@ -512,7 +515,9 @@ void SDVL::SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &
   if (MapperMap *m = dynamic_cast<MapperMap *>(map_))
     if (on && (m->DepthMapping() || m->DepthBundleOn()))
       throw std::runtime_error("SDVL::SetStereoSeeding: depth mapping and depth edges look depths up at found pixels, which a matcher at the corners does not give");
-  if (on && camera_->HasDistortion()) throw std::runtime_error("SDVL::SetStereoSeeding: the camera has a lens; rectified pairs only");
+  if (on && camera_->HasDistortion())
+    throw std::runtime_error("SDVL::SetStereoSeeding: the camera has a lens; rectified pairs only (for a calibrated rig build the camera from "
+                             "RectifiedPair::camera() and call SetStereoRectification)");
   if (on && !(baseline > 0.0 && std::isfinite(baseline))) throw std::invalid_argument("SDVL::SetStereoSeeding: the baseline is not a positive finite number");
   if (on && (rule.max_disparity < 0 || rule.max_disparity > SDVL_STEREO_MAX_DISPARITY || rule.uniqueness < 0 || rule.uniqueness > 100 || rule.max_sad < 0 ||
              rule.max_sad > 255 || !(rule.min_depth >= 0.0 && std::isfinite(rule.min_depth)) || !(rule.max_depth >= 0.0 && std::isfinite(rule.max_depth))))
@@ -522,6 +527,25 @@ void SDVL::SetStereoSeeding(bool on, double baseline, const sdvl_stereo_params &
   stereo_rule_ = rule;
   stereo_rule_.baseline = baseline;
   stereo_rule_.dist = nullptr;
+  if (!on) camera_->SetRectifiedPair(nullptr);  // the raw pairs go with the switch that reads them
+}
+
+void SDVL::SetStereoRectification(const RectifiedPair &pair, bool on) {
+  if (!on) {
+    camera_->SetRectifiedPair(nullptr);
+    return;
+  }
+  if (!stereo_seeding_) throw std::runtime_error("SDVL::SetStereoRectification needs stereo seeding (SetStereoSeeding): the right image is its");
+  if (camera_->HasDistortion())
+    throw std::runtime_error("SDVL::SetStereoRectification: the camera has a lens of its own; the tracker's camera is the pair's rectified camera, the lenses are the pair's");
+  const sdvl_camera have = camera_->abi(), &want = pair.camera();
+  if (have.fx != want.fx || have.fy != want.fy || have.u0 != want.u0 || have.v0 != want.v0 || have.width != pair.width || have.height != pair.height)
+    throw std::runtime_error("SDVL::SetStereoRectification: the camera's intrinsics or size differ from the pair's; build the camera from RectifiedPair::camera()");
+  if (!(std::fabs(stereo_rule_.baseline - pair.baseline) <= 1e-12 * pair.baseline))
+    throw std::runtime_error("SDVL::SetStereoRectification: the baseline of SetStereoSeeding differs from the pair's");
+  if (MapperMap *m = dynamic_cast<MapperMap *>(map_))
+    if (m->IsThreaded()) throw std::runtime_error("SDVL::SetStereoRectification: the mapper thread is started; raw pairs are rectified in sequential mode only");
+  camera_->SetRectifiedPair(&pair);
 }
 
 void SDVL::SetDepthMapping(bool on, double noise_abs, double noise_quad) {

@@ -24,6 +24,13 @@
 //                                                                frame's right image feeds the candidates' filter through the matcher at the found pixel, new keyframes'
 //                                                                corners become fixed points; X: the disparity noise in pixels (default 0.25, not measured against a real pair)
 //   track_sequence --list frames.txt --right-list right.txt --baseline B   the same from disk: one 8-bit binary PGM, the rectified right image, per frame
+//   ... --stereo --rig FILE                                      a stereo rig as calibrated (SDVL::SetStereoRectification): FILE is a settings file in the configuration
+//                                                                file's form with the RIGHT camera's Camera.fx fy u0 v0 d1..d5 and Rig.r11 .. Rig.r33, Rig.tx ty tz
+//                                                                (X_right = R X_left + T; R defaults to the identity); the left camera and its lens are the main
+//                                                                configuration's (--cam, --dist).  The rig is planned, the tracker's camera is the plan's rectified
+//                                                                camera, and the frames of both cameras are RAW: with --synthetic N --scene NAME both views are rendered
+//                                                                through their lenses, the right one at R, T; with --list / --right-list they are the files'.  The
+//                                                                baseline is the plan's |T| (--baseline is not needed); poses are the rectified left camera's
 //   track_sequence ... --depth --depth-bundle [--depth-bf X]  depth edges in the local bundle adjustment (SDVL::SetDepthBundle; implies --bundle): X in
 //                                                                pixel x metres, default 1 / noise_quad of the depth mapping = 666.7
 //   common:  [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle] [--init plane|two-frame]
@@ -112,6 +119,31 @@ bool ReadDepthPGM(const std::string &path, int *w, int *h, std::vector<uint16_t>
   return true;
 }
 
+// --rig FILE: the right camera and the rig's R, T in the configuration file's form (Config::ReadKeyValues)
+bool ReadRig(const std::string &path, StereoRig *rig, std::string *err) {
+  static const char *const cam_keys[9] = {"Camera.fx", "Camera.fy", "Camera.u0", "Camera.v0", "Camera.d1", "Camera.d2", "Camera.d3", "Camera.d4", "Camera.d5"};
+  static const char *const r_keys[9] = {"Rig.r11", "Rig.r12", "Rig.r13", "Rig.r21", "Rig.r22", "Rig.r23", "Rig.r31", "Rig.r32", "Rig.r33"};
+  static const char *const t_keys[3] = {"Rig.tx", "Rig.ty", "Rig.tz"};
+  bool have_cam[4] = {false, false, false, false}, have_t[3] = {false, false, false};
+  const bool opened = Config::ReadKeyValues(path, [&](const std::string &key, double v) {
+    bool known = false;
+    for (int i = 0; i < 9; i++) {
+      if (key == cam_keys[i]) { (i < 4 ? rig->K2[i] : rig->D2[i - 4]) = v; if (i < 4) have_cam[i] = true; known = true; }
+      if (key == r_keys[i]) { rig->R[i] = v; known = true; }
+    }
+    for (int i = 0; i < 3; i++)
+      if (key == t_keys[i]) { rig->T[i] = v; have_t[i] = true; known = true; }
+    if (!known && err->empty()) *err = path + ": unknown key " + key;
+  });
+  if (!opened) { *err = "cannot read " + path; return false; }
+  if (!err->empty()) return false;
+  for (int i = 0; i < 4; i++)
+    if (!have_cam[i]) { *err = path + ": the right camera needs Camera.fx, Camera.fy, Camera.u0 and Camera.v0"; return false; }
+  for (int i = 0; i < 3; i++)
+    if (!have_t[i]) { *err = path + ": the rig needs Rig.tx, Rig.ty and Rig.tz"; return false; }
+  return true;
+}
+
 // --raw-format NAME -> PIX_* (0: no such name)
 int RawFormatByName(const std::string &name) {
   static const char *const names[] = {"bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr", "yuyv", "uyvy", "gray10", "gray12", "gray16"};
@@ -138,6 +170,9 @@ const char kUsage[] =
     "  --stereo-mapping [--disparity-sigma X]: with --stereo, the right image of every tracked frame feeds the mapper's depth filter and new\n"
     "      keyframes' corners become fixed points (implies --mapper); X: disparity noise in pixels, default 0.25 (not measured against a real pair)\n"
     "  --right-list FILE --baseline B: one 8-bit P5 rectified right image per frame of --list\n"
+    "  --rig FILE: with --stereo, a rig as calibrated: FILE holds the right camera's Camera.fx fy u0 v0 d1..d5 and Rig.r11 .. r33, Rig.tx ty tz\n"
+    "      (X_right = R X_left + T) in the configuration file's form; the left camera is --cam / --dist.  Both cameras' frames are raw and are\n"
+    "      rectified on the device; the baseline is the rig's\n"
     "  common: [--config file.cfg] [--size W H] [--cam fx fy u0 v0] [--dist d0 d1 d2 d3 d4] [--plane nx ny nz d] [--mapper] [--bundle]\n"
     "          [--init plane|two-frame] [--trackers N] [--batch] [--lookahead] [--prerender] [--pageable] [--set SDVL.key value]\n"
     "          [--quiet] [--json] [--profile]\n";
@@ -168,7 +203,7 @@ int main(int argc, char **argv) {
   double depth_scale = 0.0;
   bool stereo = false, stereo_mapping = false;
   double baseline = 0.0, disparity_sigma = 0.0;
-  std::string right_list;
+  std::string right_list, rig_file;
   std::vector<std::pair<std::string, double>> sets;  // --set SDVL.key value, applied after the configuration file
   unsigned texture = SDVL_TEXTURE_PLANE_NOISE;
   for (int i = 1; i < argc; i++) {
@@ -195,6 +230,7 @@ int main(int argc, char **argv) {
     else if (a == "--stereo-mapping") { stereo_mapping = true; mapper = true; }
     else if (a == "--disparity-sigma") { need(1); disparity_sigma = std::atof(argv[++i]); }
     else if (a == "--right-list") { need(1); right_list = argv[++i]; stereo = true; }
+    else if (a == "--rig") { need(1); rig_file = argv[++i]; }
     else if (a == "--mapper") mapper = true;
     else if (a == "--bundle") { bundle = true; mapper = true; }  // local bundle adjustment of every new keyframe (SDVL::SetBundleAdjustment; implies --mapper)
     else if (a == "--init") { need(1); const std::string t = argv[++i]; if (t == "two-frame") { two_frame = true; mapper = true; } else if (t != "plane") { std::cerr << "unknown --init " << t << std::endl; return 2; } }
@@ -233,10 +269,11 @@ int main(int argc, char **argv) {
   if (stereo_mapping && !stereo) { std::cerr << "--stereo-mapping feeds the mapper from the frames' right images: give --stereo or --right-list too" << std::endl; return 2; }
   if (!(disparity_sigma >= 0.0) || disparity_sigma > 1e300) { std::cerr << "--disparity-sigma X: pixels, not negative" << std::endl; return 2; }
   if (disparity_sigma != 0.0 && !stereo_mapping) { std::cerr << "--disparity-sigma is the noise of --stereo-mapping: give that too" << std::endl; return 2; }
+  if (!rig_file.empty() && !stereo) { std::cerr << "--rig FILE describes the rig of --stereo / --right-list: give one of them too" << std::endl; return 2; }
   if (stereo) {  // what SDVL::SetStereoSeeding would throw, said before any device is touched
     if (right_list.empty() && !use_scene) { std::cerr << "--stereo tracks on the rendered right image: give --synthetic N --scene NAME, or --right-list FILE with --list" << std::endl; return 2; }
     if (!right_list.empty() && list.empty()) { std::cerr << "--right-list goes with --list" << std::endl; return 2; }
-    if (!(baseline > 0.0) || baseline > 1e300) { std::cerr << "--stereo and --right-list need --baseline B (metres, above 0)" << std::endl; return 2; }
+    if (rig_file.empty() && (!(baseline > 0.0) || baseline > 1e300)) { std::cerr << "--stereo and --right-list need --baseline B (metres, above 0)" << std::endl; return 2; }
     if (depth) { std::cerr << "--stereo and --depth / --depth-list both fill the frame's second image: give one" << std::endl; return 2; }
     if (two_frame) { std::cerr << "--stereo and --init two-frame answer the same question: give one" << std::endl; return 2; }
     if (batch || prerender || n_trackers > 1) { std::cerr << "--stereo runs one camera on frames made inside the loop: not with --batch, --trackers or --prerender" << std::endl; return 2; }
@@ -281,7 +318,29 @@ int main(int argc, char **argv) {
       if (!line.empty() && line[0] != '#') right_files.push_back(line);
     if (right_files.size() != files.size()) { std::cerr << right_list << " names " << right_files.size() << " right images for " << files.size() << " frames" << std::endl; return 2; }
   }
-  if (stereo && dist[0] != 0.0) { std::cerr << "--stereo takes rectified pairs: not with a lens (--dist, or the configuration file's Camera.d1)" << std::endl; return 2; }
+  if (stereo && rig_file.empty() && dist[0] != 0.0) {
+    std::cerr << "--stereo takes rectified pairs: not with a lens (--dist, or the configuration file's Camera.d1); a rig as calibrated goes through --rig FILE" << std::endl;
+    return 2;
+  }
+  // --rig: the plan of the rig (host code, no device); the tracker's camera is its rectified camera, the frames stay raw
+  StereoRig rig;
+  RectifiedPair pair;
+  const bool rectify = !rig_file.empty();
+  if (rectify) {
+    std::string err;
+    if (!ReadRig(rig_file, &rig, &err)) { std::cerr << err << std::endl; return 2; }
+    for (int q = 0; q < 4; q++) rig.K1[q] = cam4[q];
+    for (int q = 0; q < 5; q++) rig.D1[q] = dist[q];
+    try {
+      pair = RectifiedPair::Plan(rig, W, H);
+    } catch (const std::exception &e) {
+      std::cerr << "--rig " << rig_file << ": " << e.what() << std::endl;
+      return 2;
+    }
+    baseline = pair.baseline;
+    std::fprintf(stderr, "rectified camera: fx %.6f fy %.6f u0 %.6f v0 %.6f, baseline %.6f m\n", pair.camera().fx, pair.camera().fy, pair.camera().u0,
+                 pair.camera().v0, pair.baseline);
+  }
   const int n_frames = n_synth > 0 ? n_synth : static_cast<int>(files.size());
 
   const double tw[6] = {0.004, 0.002, 0.001, 0.0008, -0.0012, 0.0005};
@@ -365,8 +424,9 @@ int main(int argc, char **argv) {
       try {
         Device dev(0);             // one per thread that enters the path; fails loudly without an MI355X
         Device::SetCurrent(&dev);
-        Camera camera(W, H, cam4[0], cam4[1], cam4[2], cam4[3]);
-        camera.SetDistortions(dist[0], dist[1], dist[2], dist[3], dist[4]);  // camera.cc:39-67
+        Camera camera(W, H, rectify ? pair.camera().fx : cam4[0], rectify ? pair.camera().fy : cam4[1], rectify ? pair.camera().u0 : cam4[2],
+                      rectify ? pair.camera().v0 : cam4[3]);
+        if (!rectify) camera.SetDistortions(dist[0], dist[1], dist[2], dist[3], dist[4]);  // camera.cc:39-67 (--rig: the lenses are the pair's)
         std::unique_ptr<Map> map;
         if (mapper) map.reset(new MapperMap(Vector3d(plane[0], plane[1], plane[2]), plane[3], &camera));
         else map.reset(new PlaneMap(Vector3d(plane[0], plane[1], plane[2]), plane[3]));
@@ -377,6 +437,7 @@ int main(int argc, char **argv) {
         if (depth_mapping) sdvl.SetDepthMapping(true);
         if (depth_bundle) sdvl.SetDepthBundle(true, depth_bf);
         if (stereo) sdvl.SetStereoSeeding(true, baseline);
+        if (rectify) sdvl.SetStereoRectification(pair);
         if (stereo_mapping) sdvl.SetStereoMapping(true, disparity_sigma);
         std::vector<uint8_t> right_px(stereo ? frame_bytes : 0);
         std::vector<float> depth_f32(depth && depth_list.empty() ? frame_bytes : 0);
@@ -441,7 +502,17 @@ int main(int argc, char **argv) {
           } else if (stereo) {
             if (right_list.empty()) {  // the same scene from the right camera: t_right = t_left - (B, 0, 0)
               sdvl_synth_scene sc = scene_of(k);
-              sc.t[0] -= baseline;
+              if (rectify) {  // the right camera as calibrated: pose (R R_l, R t_l + T), its own intrinsics and lens
+                const sdvl_synth_scene l = sc;
+                for (int r = 0; r < 3; r++) {
+                  for (int q = 0; q < 3; q++) sc.R[3 * r + q] = rig.R[3 * r] * l.R[q] + rig.R[3 * r + 1] * l.R[3 + q] + rig.R[3 * r + 2] * l.R[6 + q];
+                  sc.t[r] = rig.R[3 * r] * l.t[0] + rig.R[3 * r + 1] * l.t[1] + rig.R[3 * r + 2] * l.t[2] + rig.T[r];
+                }
+                sc.fx = rig.K2[0]; sc.fy = rig.K2[1]; sc.u0 = rig.K2[2]; sc.v0 = rig.K2[3];
+                for (int q = 0; q < 5; q++) sc.dist[q] = rig.D2[q];
+              } else {
+                sc.t[0] -= baseline;
+              }
               sdvl_synth_render_scene_host(&sc, W, H, right_px.data(), W, nullptr, nullptr);
             } else {
               int w = 0, h = 0, fmt = PIX_GRAY8;

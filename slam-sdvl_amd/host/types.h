@@ -9,7 +9,10 @@
 #include <stdint.h>
 
 #include <memory>
+#include <stdexcept>
 #include <vector>
+
+#include "../../include/sdvl_hip.h"
 
 // Real Eigen / OpenCV, when the build has them (this image has neither): the look-alikes below then convert to and from the real
 // types, so callers written against the reference's headers (sdvl.cc, map.cc, ui/: cv::Mat frames in, Eigen vectors out) pass and
@@ -203,6 +206,38 @@ struct DepthImage {
     DepthImage r;
     r.data = p; r.cols = w; r.rows = h; r.step = stride; r.format = depth_format; r.scale = metres_per_unit; r.on_device = device;
     return r;
+  }
+};
+
+// (an addition) A stereo rig as calibrated: K_i = fx fy u0 v0, D_i = k1 k2 p1 p2 k3 (Camera.d1..d5), R (row-major) and T with
+// X_right = R X_left + T — OpenCV's convention; the ideal rig is R = I, T = (-baseline, 0, 0).
+struct StereoRig {
+  double K1[4] = {0, 0, 0, 0}, D1[5] = {0, 0, 0, 0, 0};
+  double K2[4] = {0, 0, 0, 0}, D2[5] = {0, 0, 0, 0, 0};
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0};
+};
+
+// (an addition) The plan of a rig's rectification (sdvl_stereo_rectify_plan, include/sdvl_hip.h): what each camera's map is built from,
+// the one rectified pinhole camera of both images and the baseline.  SDVL::SetStereoRectification takes it.
+struct RectifiedPair {
+  sdvl_rectification left = {}, right = {};
+  double baseline = 0.0;
+  int width = 0, height = 0;
+  const sdvl_camera &camera() const { return left.rect; }  // fx fy u0 v0 (and the size) of the rectified images
+  // throws std::invalid_argument with the plan's message for a rig it refuses; `intrinsics`: the rectified camera's, instead of the plan's
+  static RectifiedPair Plan(const StereoRig &rig, int width, int height, const sdvl_camera *intrinsics = nullptr) {
+    sdvl_stereo_rig r;
+    r.left = sdvl_camera{static_cast<double>(width), static_cast<double>(height), rig.K1[0], rig.K1[1], rig.K1[2], rig.K1[3]};
+    r.right = sdvl_camera{static_cast<double>(width), static_cast<double>(height), rig.K2[0], rig.K2[1], rig.K2[2], rig.K2[3]};
+    for (int i = 0; i < 5; i++) { r.left_dist.d[i] = rig.D1[i]; r.right_dist.d[i] = rig.D2[i]; }
+    for (int i = 0; i < 9; i++) r.R[i] = rig.R[i];
+    for (int i = 0; i < 3; i++) r.T[i] = rig.T[i];
+    sdvl_stereo_rectified out;
+    const int rc = sdvl_stereo_rectify_plan(&r, width, height, intrinsics, &out);
+    if (rc != 0) throw std::invalid_argument(sdvl_stereo_rectify_plan_message(rc));
+    RectifiedPair p;
+    p.left = out.left; p.right = out.right; p.baseline = out.baseline; p.width = width; p.height = height;
+    return p;
   }
 };
 

@@ -227,6 +227,28 @@ class TrackerBatch:
             raise RuntimeError(self.lib.sdvlh_last_error().decode())
         self.depth_dtype = np.uint8 if on else np.float32
 
+    def set_stereo_rectification(self, rig=None, on=True, plan_only=False):
+        """stereo rigs as calibrated (SDVL::SetStereoRectification; needs set_stereo): rig = (K1, D1, K2, D2, R, T) with K_i = fx fy u0 v0,
+        D_i = k1 k2 p1 p2 k3, R [3][3] and T [3] such that X_right = R X_left + T.  The rig is planned for the batch's image size and the
+        step calls then take the RAW images of both cameras (imgs and rights=): the left one is rectified inside its frame's upload, the
+        right ones into HBM in one launch per step, and only in a step that reads them.  Returns (rectified camera fx fy u0 v0, baseline):
+        the batch must have been made with that camera and set_stereo called with that baseline — plan_only=True returns them without
+        setting anything, on any batch of the image size.  Poses are the rectified left camera's.  Raises RuntimeError for a rig the plan
+        refuses, without set_stereo, on a camera with a lens of its own, when camera or baseline differ from the plan's and with the
+        mapper thread started."""
+        self.lib.sdvlh_batch_set_stereo_rectification.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        if not on:
+            if self.lib.sdvlh_batch_set_stereo_rectification(self.h, 0, None, 0, None) != 0:
+                raise RuntimeError(self.lib.sdvlh_last_error().decode())
+            return None
+        K1, D1, K2, D2, R, T = rig
+        rig30 = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).ravel() for v in (K1, D1, K2, D2, R, T)]))
+        assert rig30.shape == (30,), "rig = (K1[4], D1[5], K2[4], D2[5], R[3][3], T[3])"
+        out = np.zeros(5)
+        if self.lib.sdvlh_batch_set_stereo_rectification(self.h, 1, rig30.ctypes.data, int(bool(plan_only)), out.ctypes.data) != 0:
+            raise RuntimeError(self.lib.sdvlh_last_error().decode())
+        return out[:4].copy(), float(out[4])
+
     def stereo_stats(self, i):
         """tracker i's stereo seeding so far: dict(keyframes, seeds, ok, nomatch, ambiguous, edge, outside, no_image) — keyframes seeded,
         points seeded, the keyframes' filtered corners by status, keyframes or first frames that came without a right image"""

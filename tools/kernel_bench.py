@@ -260,3 +260,22 @@ for k, (ms, launches) in sorted(t.items()):
     a = alg.get(k)
     gbs = (a * n / (us * 1e-6) / 1e9) if a else float("nan")
     print("  %-16s %8.1f us/launch  %7.2f us/frame  %8.1f GB/s algorithmic  (%.4f of 8 TB/s)" % (k, us, us / n, gbs, gbs / 8000))
+# Stereo rigs as calibrated, in a timing window of its own (its launches carry the remap's and the map build's names, so the table above
+# is printed first and the timers are reset): the remap behind a RECTIFIED camera's map (sdvl_frames_upload_rectified) — the right
+# camera of a rig with the lens above on both sides, turned by (0.009, -0.017, 0.005) rad — and the map's one-off build
+und_us = t["undistort"][0] / t["undistort"][1] * 1e3
+ctx.timing_reset()
+_w = np.array([0.009, -0.017, 0.005])
+_th = float(np.linalg.norm(_w))
+_K = np.array([[0, -_w[2], _w[1]], [_w[2], 0, -_w[0]], [-_w[1], _w[0], 0]]) / _th
+_lens = [0.2624, -0.9531, -0.0054, 0.0026, 1.1633]
+rig = sdvl.stereo_rectify_plan(B.TUM_CAM, _lens, B.TUM_CAM, _lens, np.eye(3) + np.sin(_th) * _K + (1 - np.cos(_th)) * _K @ _K, (-0.11, 0.002, -0.001), W, H)
+lib.sdvl_frames_upload_rectified.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+for _ in range(reps):
+    ctx._check(lib.sdvl_frames_upload_rectified(ctx.h, n, arru, raw, W, 1, C.byref(rig.right)))
+ctx.synchronize()
+t = ctx.timing_get()
+rect_us = t["undistort"][0] / t["undistort"][1] * 1e3
+print("rectify: %.1f us/launch of %d frames (%.1f GB/s algorithmic) beside undistort %.1f us/launch; once per camera: rectify_map %.1f us + its quad records "
+      "%.1f us; %d pixels without a source" % (rect_us, n, 2 * W * H * n / (rect_us * 1e-6) / 1e9, und_us, t["rectify_map"][0] * 1e3,
+                                              t["undistort_map"][0] * 1e3, ctx.rectify_stats()[1]))
