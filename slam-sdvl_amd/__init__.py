@@ -839,33 +839,41 @@ class Context:
         im = (C.c_void_p * n)(*[int(a) for a in addresses])
         self._check(self.lib.sdvl_frames_upload(self.h, n, fr, im, int(stride)))
 
+    @staticmethod
+    def _stated_results(n, cur_poses, ref_poses, bearings, found, px, levels=None):
+        """what the stated depth_filter entries take in a search's place, as contiguous arrays [n][7], [n][7], [n][3], [n], [n][2] and,
+        for the entries that look a depth up, the found levels [n]"""
+        arrs = [np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7), np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7),
+                np.ascontiguousarray(bearings, np.float64).reshape(n, 3), np.ascontiguousarray(found, np.int32).reshape(n),
+                np.ascontiguousarray(px, np.float64).reshape(n, 2)]
+        return arrs + ([np.ascontiguousarray(levels, np.int32).reshape(n)] if levels is not None else [])
+
+    def _filter_entry(self, name, n, head, track_set, tail=(), searched=False, status=False):
+        """One of the depth filter's entries through _check: (context, n, head..., the track set's handle or null, tail..., results...).
+        An int goes as it is, None as null, an array or a ctypes object by its address.  -> the results: the SearchRes array of a
+        searched entry, the DepthOut array, the status bytes (uint8 [n], 255 where no depth was looked up) of an entry that writes them"""
+        out = ([(SearchRes * n)()] if searched else []) + [(DepthOut * n)()] + ([np.full(max(n, 1), 255, np.uint8)] if status else [])
+        args = [*head, track_set.h if track_set is not None else None, *tail, *out]
+        fn = getattr(self.lib, name)
+        if fn.argtypes is None:  # (an entry's ints stand at the same places in every call)
+            fn.argtypes = [C.c_void_p, C.c_int] + [C.c_int if type(a) is int else C.c_void_p for a in args]
+        self._check(fn(self.h, n, *[a.ctypes.data if type(a) is np.ndarray else a if a is None or type(a) in (int, C.c_void_p) else C.addressof(a)
+                                    for a in args]))
+        if status:
+            out[-1] = out[-1][:n]
+        return out[0] if len(out) == 1 else tuple(out)
+
     def search_points_filter(self, reqs, cam, sp, states, fparams, track_set=None):
         """sdvl_search_points_filter: (search results, depth-filter outcomes); with track_set (a TrackSet) the rows the states name
         are patched in its tables"""
-        n = len(reqs)
-        res = (SearchRes * n)()
-        fout = (DepthOut * n)()
-        self._check(self.lib.sdvl_search_points_filter(self.h, n, reqs, C.byref(cam), C.byref(sp), states, C.byref(fparams),
-                                                       track_set.h if track_set is not None else None, res, fout))
-        return res, fout
-
-    @staticmethod
-    def _stated_results(n, cur_poses, ref_poses, bearings, found, px):
-        """what the two depth_filter entries take in a search's place, as contiguous arrays [n][7], [n][7], [n][3], [n], [n][2]"""
-        return (np.ascontiguousarray(cur_poses, np.float64).reshape(n, 7), np.ascontiguousarray(ref_poses, np.float64).reshape(n, 7),
-                np.ascontiguousarray(bearings, np.float64).reshape(n, 3), np.ascontiguousarray(found, np.int32).reshape(n),
-                np.ascontiguousarray(px, np.float64).reshape(n, 2))
+        return self._filter_entry("sdvl_search_points_filter", len(reqs), [reqs, cam, sp, states, fparams], track_set, searched=True)
 
     def depth_filter(self, cur_poses, ref_poses, bearings, found, px, cam, states, fparams, track_set=None):
         """sdvl_depth_filter: the mapper's depth filter alone.  cur_poses / ref_poses [n][7], bearings [n][3], found [n], px [n][2];
         states: DepthState array -> DepthOut array"""
         n = len(states)
-        cp, rp, bv, fd, pp = self._stated_results(n, cur_poses, ref_poses, bearings, found, px)
-        fout = (DepthOut * n)()
-        dp = C.POINTER(C.c_double)
-        self._check(self.lib.sdvl_depth_filter(self.h, n, _ptr(cp, dp), _ptr(rp, dp), _ptr(bv, dp), _ptr(fd, i32p), _ptr(pp, dp), C.byref(cam),
-                                               states, C.byref(fparams), track_set.h if track_set is not None else None, fout))
-        return fout
+        return self._filter_entry("sdvl_depth_filter", n, self._stated_results(n, cur_poses, ref_poses, bearings, found, px) + [cam, states, fparams],
+                                  track_set)
 
     def depth_seed(self, jobs, width, height, xyl, cam, dist=None, **rule):
         """sdvl_depth_seed: the depth of corners from registered depth images.  jobs: (depth, c_begin, c_end) or (depth, c_begin, c_end,
@@ -975,52 +983,19 @@ class Context:
         image of the current frame of the items c_begin .. c_end (an item in no job has no image); noise_abs / noise_quad and rule: 0 takes
         the default -> (DepthOut array, status uint8 [n]: depth_seed's codes, 255 where no depth was looked up)"""
         n = len(states)
-        cp, rp, bv, fd, pp = self._stated_results(n, cur_poses, ref_poses, bearings, found, px)
-        lv = np.ascontiguousarray(levels, np.int32).reshape(n)
+        stated = self._stated_results(n, cur_poses, ref_poses, bearings, found, px, levels)
         keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, noise_abs, noise_quad, rule)
-        fout, status = (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
-        vp = C.c_void_p
-        self.lib.sdvl_depth_filter_measured.argtypes = [vp, C.c_int] + [vp] * 10 + [C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-        self._check(self.lib.sdvl_depth_filter_measured(
-            self.h, n, cp.ctypes.data, rp.ctypes.data, bv.ctypes.data, fd.ctypes.data, pp.ctypes.data, lv.ctypes.data, C.addressof(cam),
-            C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None, len(jobs), C.addressof(arr), width, height,
-            C.addressof(d5) if d5 is not None else None, C.addressof(mp), C.addressof(fout), status.ctypes.data))
-        del keep
-        return fout, status[:n]
+        return self._filter_entry("sdvl_depth_filter_measured", n, stated + [cam, states, fparams], track_set,
+                                  [len(jobs), arr, int(width), int(height), d5, mp], status=True)
 
     def search_points_filter_measured(self, reqs, cam, sp, states, fparams, jobs, width, height, dist=None, noise_abs=0.0, noise_quad=0.0,
                                       track_set=None, **rule):
         """sdvl_search_begin / _slot / sdvl_search_run_filter_measured: search_points_filter's requests (frames by handle) with the depth
         side of depth_filter_measured -> (SearchRes array, DepthOut array, status uint8 [n])"""
-        n = len(reqs)
-        lib = self.lib
-        lib.sdvl_search_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(SearchReqPacked))]
-        lib.sdvl_search_slot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
-        packed = C.POINTER(SearchReqPacked)()
-        self._check(lib.sdvl_search_begin(self.h, n, C.byref(packed)))
-        for i, r in enumerate(reqs):
-            d = packed[i]
-            d.cur = lib.sdvl_search_slot(self.h, r.cur, r.cur_pose)
-            d.ref = lib.sdvl_search_slot(self.h, r.ref, r.ref_pose)
-            assert d.cur >= 0 and d.ref >= 0
-            d.level, d.fixed = r.level, r.fixed
-            d.px[0], d.px[1] = r.px[0], r.px[1]
-            for k in range(3):
-                d.bearing[k] = r.bearing[k]
-            d.idepth, d.idepth_std = r.idepth, r.idepth_std
-            d.px0[0], d.px0[1] = r.px0[0], r.px0[1]
-            for k in range(32):
-                d.desc[k] = r.desc[k]
+        self._pack_search_requests(reqs)
         keep, arr, d5, mp = self._depth_measure_args(jobs, width, height, dist, noise_abs, noise_quad, rule)
-        res, fout, status = (SearchRes * n)(), (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
-        vp = C.c_void_p
-        lib.sdvl_search_run_filter_measured.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        self._check(lib.sdvl_search_run_filter_measured(
-            self.h, n, C.addressof(cam), C.addressof(sp), C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None,
-            len(jobs), C.addressof(arr), width, height, C.addressof(d5) if d5 is not None else None, C.addressof(mp), C.addressof(res),
-            C.addressof(fout), status.ctypes.data))
-        del keep
-        return res, fout, status[:n]
+        return self._filter_entry("sdvl_search_run_filter_measured", len(reqs), [cam, sp, states, fparams], track_set,
+                                  [len(jobs), arr, int(width), int(height), d5, mp], searched=True, status=True)
 
     def depth_filter_stereo(self, cur_poses, ref_poses, bearings, found, px, levels, cam, states, fparams, jobs, baseline, disparity_sigma=0.0,
                             dist=None, track_set=None, **rule):
@@ -1029,19 +1004,10 @@ class Context:
         (0: 0.25, not measured against a real pair) and rule: 0 takes the default
         -> (DepthOut array, status uint8 [n]: stereo_depth's codes, 255 where nothing was matched)"""
         n = len(states)
-        cp, rp, bv, fd, pp = self._stated_results(n, cur_poses, ref_poses, bearings, found, px)
-        lv = np.ascontiguousarray(levels, np.int32).reshape(n)
+        stated = self._stated_results(n, cur_poses, ref_poses, bearings, found, px, levels)
         keep, arr, d5, p = self._stereo_args(jobs, baseline, dist, rule)
         mp = StereoMeasureParams(p, float(disparity_sigma))
-        fout, status = (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
-        vp = C.c_void_p
-        self.lib.sdvl_depth_filter_stereo.argtypes = [vp, C.c_int] + [vp] * 10 + [C.c_int, vp, vp, vp, vp]
-        self._check(self.lib.sdvl_depth_filter_stereo(
-            self.h, n, cp.ctypes.data, rp.ctypes.data, bv.ctypes.data, fd.ctypes.data, pp.ctypes.data, lv.ctypes.data, C.addressof(cam),
-            C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None, len(jobs), C.addressof(arr),
-            C.addressof(mp), C.addressof(fout), status.ctypes.data))
-        del keep, d5
-        return fout, status[:n]
+        return self._filter_entry("sdvl_depth_filter_stereo", n, stated + [cam, states, fparams], track_set, [len(jobs), arr, mp], status=True)
 
     def _pack_search_requests(self, reqs):
         """sdvl_search_begin / _slot: the requests (frames by handle) into the context's packed records"""
@@ -1068,18 +1034,11 @@ class Context:
     def search_points_filter_stereo(self, reqs, cam, sp, states, fparams, jobs, baseline, disparity_sigma=0.0, dist=None, track_set=None, **rule):
         """sdvl_search_begin / _slot / sdvl_search_run_filter_stereo: search_points_filter's requests (frames by handle) with the stereo
         side of depth_filter_stereo -> (SearchRes array, DepthOut array, status uint8 [n])"""
-        n = len(reqs)
         self._pack_search_requests(reqs)
         keep, arr, d5, p = self._stereo_args(jobs, baseline, dist, rule)
         mp = StereoMeasureParams(p, float(disparity_sigma))
-        res, fout, status = (SearchRes * n)(), (DepthOut * n)(), np.full(max(n, 1), 255, np.uint8)
-        vp = C.c_void_p
-        self.lib.sdvl_search_run_filter_stereo.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
-        self._check(self.lib.sdvl_search_run_filter_stereo(
-            self.h, n, C.addressof(cam), C.addressof(sp), C.addressof(states), C.addressof(fparams), track_set.h if track_set is not None else None,
-            len(jobs), C.addressof(arr), C.addressof(mp), C.addressof(res), C.addressof(fout), status.ctypes.data))
-        del keep, d5
-        return res, fout, status[:n]
+        return self._filter_entry("sdvl_search_run_filter_stereo", len(reqs), [cam, sp, states, fparams], track_set, [len(jobs), arr, mp],
+                                  searched=True, status=True)
 
     def track_points_download(self, track_set):
         """the point rows of every tracker of a TrackSet as the device holds them: uint8 [n_trackers * max_points][144]"""
@@ -1097,23 +1056,7 @@ class Context:
         req_points[n][3].  Returns (search results, per tracker dict(pose, n_draws, refined, n_obs, inliers, outliers))."""
         n = len(reqs)
         lib = self.lib
-        lib.sdvl_search_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(SearchReqPacked))]
-        lib.sdvl_search_slot.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
-        packed = C.POINTER(SearchReqPacked)()
-        self._check(lib.sdvl_search_begin(self.h, n, C.byref(packed)))
-        for i, r in enumerate(reqs):
-            d = packed[i]
-            d.cur = lib.sdvl_search_slot(self.h, r.cur, r.cur_pose)
-            d.ref = lib.sdvl_search_slot(self.h, r.ref, r.ref_pose)
-            assert d.cur >= 0 and d.ref >= 0
-            d.level, d.fixed = r.level, r.fixed
-            d.px[0], d.px[1] = r.px[0], r.px[1]
-            for k in range(3):
-                d.bearing[k] = r.bearing[k]
-            d.idepth, d.idepth_std = r.idepth, r.idepth_std
-            d.px0[0], d.px0[1] = r.px0[0], r.px0[1]
-            for k in range(32):
-                d.desc[k] = r.desc[k]
+        self._pack_search_requests(reqs)
         nf = len(trackers)
         cf = (ChainFrame * nf)()
         cand_req, cand_first, rand_raw = [], [], []

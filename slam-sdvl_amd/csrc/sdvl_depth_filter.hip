@@ -3,7 +3,8 @@
 // states (sdvl_depth_filter), and the same for a depth camera (the *_measured entries).  The arithmetic is sdvl_depth_filter.h's, shared
 // with the host path; the search itself is sdvl_search.hip's.  A stereo rig has the same two entries (the *_stereo entries): the depth
 // at the found pixel is the matcher's (stereo_lookup, sdvl_stereo.hip: one wave per request), launched between the search and the filter,
-// whose third form reads what it left.  Compiled with -ffp-contract=off.
+// whose third form reads what it left.  The host side is two bodies, searched and stated, over the three sources of depth.  Compiled with
+// -ffp-contract=off.
 #include "sdvl_internal.h"
 #include "sdvl_math.h"
 #include "sdvl_search_types.h"
@@ -121,8 +122,7 @@ __global__ __launch_bounds__(128) void depth_filter_stereo_kernel(const SearchRe
   depth_filter_lane<kStereo, StereoMeasureArgs>(reqs, table, res, state, n, cam, fp, rows, n_rows, out, out_host, &m);
 }
 
-// ---- what the seven entries share
-// what every entry requires of the states; -> the rows the kernel may patch (none without a set)
+// ---- what every entry requires of the states; -> the rows the kernel may patch (none without a set)
 int depth_filter_check(sdvl_ctx *ctx, int n, const sdvl_depth_state *state, sdvl_track_set *set, TrackPoint **rows_out, int *n_rows_out) {
   TrackPoint *rows = nullptr;
   int n_rows = 0;
@@ -178,28 +178,104 @@ int stereo_measure_check(sdvl_ctx *ctx, const char *who, int n, int n_jobs, cons
   return sdvl_stereo_lds(ctx, who, max_level, rule, lds_bytes);
 }
 
-// jobs | the job of every request (-1: none) as one staged record
-struct StereoMeasureStage {
-  sdvl_part<sdvl_stereo::StereoJobDev> jobs;
-  sdvl_part<int32_t> req_job;
-  StereoMeasureStage(sdvl_layout &st, int n, int n_jobs) : jobs(st.take<sdvl_stereo::StereoJobDev>(n_jobs > 0 ? n_jobs : 1)), req_job(st.take<int32_t>(n)) {}
-  int fill(sdvl_ctx *ctx, const char *who, void *hs, int n, int n_jobs, const sdvl_stereo_job *in) const {
-    SDVL_REQUIRE(ctx, !sdvl_item_jobs_fill(n, n_jobs, in, req_job.in(hs)), std::string(who) + ": request ranges overlap");
-    return n_jobs > 0 ? sdvl_stereo_jobs_resolve(ctx, n_jobs, in, jobs.in(hs)) : sdvl_depth_pool_scope(ctx);
+// what the stated entries with a level per item require of it
+int found_levels_check(sdvl_ctx *ctx, const char *who, int n, const int32_t *level) {
+  for (int i = 0; i < n; i++)
+    SDVL_REQUIRE(ctx, level[i] >= 0 && level[i] < SDVL_MAX_LEVELS, std::string(who) + ": found level outside 0 .. SDVL_MAX_LEVELS - 1");
+  return SDVL_OK;
+}
+
+// ---- the three sources of the depth at a found pixel.  The six entries are two bodies (filter_searched, filter_stated) over a source,
+// which states only what is its own: its entry's name for the messages (who), its check, the check of the levels a caller states, its
+// parts of the result buffers (d: d_out, h: the pinned h_out, both behind the outcomes) and of the staging block (behind the body's
+// own) with their fill, what it queues between the search results and the filter, its launch of the filter (head: the arguments the
+// three kernels share) and what it copies out besides the outcomes.
+struct Triangulated {
+  int check(sdvl_ctx *, int, const sdvl_camera *) { return SDVL_OK; }
+  int levels_check(sdvl_ctx *, int, const int32_t *, const int32_t *) const { return SDVL_OK; }
+  void take_out(sdvl_layout &, sdvl_layout &, int) {}
+  void take_stage(sdvl_layout &, int) {}
+  int fill(sdvl_ctx *, void *, int) const { return SDVL_OK; }
+  int enqueue(sdvl_ctx *, int, const void *, const sdvl_search_res *) const { return SDVL_OK; }
+  template <typename... Head>
+  void launch(sdvl_ctx *ctx, int n, const void *, Head... head) const {
+    SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), head...);
   }
+  void collect(const sdvl_ctx *, int) const {}
 };
 
-// jobs | the job of every request (-1: none) as one staged record
-struct DepthMeasureStage {
-  sdvl_part<sdvl_depth::DepthJobDev> jobs;
-  sdvl_part<int32_t> req_job;
-  DepthMeasureStage(sdvl_layout &st, int n, int n_jobs) : jobs(st.take<sdvl_depth::DepthJobDev>(n_jobs > 0 ? n_jobs : 1)), req_job(st.take<int32_t>(n)) {}
-  int fill(sdvl_ctx *ctx, void *hs, int n, int n_jobs, const sdvl_depth_job *in, int width, int height) const {
-    const int rc = n_jobs > 0 ? sdvl_depth_jobs_resolve(ctx, n_jobs, in, width, height, jobs.in(hs)) : SDVL_OK;
+// a registered depth image per job.  d and h: the status bytes (the kernel writes both); staged: jobs | the job of every request (-1: none)
+struct FromDepthImage {
+  const char *who;
+  int n_jobs;
+  const sdvl_depth_job *jobs;
+  int width, height;
+  const sdvl_distortion *dist;
+  const sdvl_depth_measure_params *mp;
+  uint8_t *out_status;
+  DepthMeasure dm;
+  sdvl_part<uint8_t> d_status, h_status;
+  sdvl_part<sdvl_depth::DepthJobDev> st_jobs;
+  sdvl_part<int32_t> st_req_job;
+  int check(sdvl_ctx *ctx, int n, const sdvl_camera *cam) { return depth_measure_check(ctx, who, n, n_jobs, jobs, width, height, cam, dist, mp, &dm); }
+  int levels_check(sdvl_ctx *ctx, int n, const int32_t *, const int32_t *level) const { return found_levels_check(ctx, who, n, level); }
+  void take_out(sdvl_layout &d, sdvl_layout &h, int n) { d_status = d.take<uint8_t>(n), h_status = h.take<uint8_t>(n); }
+  void take_stage(sdvl_layout &st, int n) { st_jobs = st.take<sdvl_depth::DepthJobDev>(n_jobs > 0 ? n_jobs : 1), st_req_job = st.take<int32_t>(n); }
+  int fill(sdvl_ctx *ctx, void *hs, int n) const {
+    const int rc = n_jobs > 0 ? sdvl_depth_jobs_resolve(ctx, n_jobs, jobs, width, height, st_jobs.in(hs)) : SDVL_OK;
     if (rc) return rc;
-    sdvl_item_jobs_fill(n, n_jobs, in, req_job.in(hs));  // (ranges that overlap: the later job's)
+    sdvl_item_jobs_fill(n, n_jobs, jobs, st_req_job.in(hs));  // (ranges that overlap: the later job's)
     return SDVL_OK;
   }
+  int enqueue(sdvl_ctx *, int, const void *, const sdvl_search_res *) const { return SDVL_OK; }
+  template <typename... Head>
+  void launch(sdvl_ctx *ctx, int n, const void *ds, Head... head) const {
+    const DepthMeasureArgs m = {st_jobs.cin(ds), st_req_job.cin(ds), dm, d_status.in(ctx->d_out), h_status.in(ctx->h_out)};
+    SDVL_LAUNCH(ctx, "depth_filter_measured", depth_filter_measured_kernel, dim3((n + 127) / 128), dim3(128), head..., m);
+  }
+  void collect(const sdvl_ctx *ctx, int n) const { memcpy(out_status, h_status.in(ctx->h_out), static_cast<size_t>(n)); }
+};
+
+// a rectified pair per job: stereo_lookup (sdvl_stereo.hip: one wave per request) over the search results where they lie, the filter's
+// third form on what it left.  d: z | the status bytes, h: the status bytes (the filter writes them); staged: as FromDepthImage's
+struct FromStereoPair {
+  const char *who;
+  int n_jobs;
+  const sdvl_stereo_job *jobs;
+  const sdvl_stereo_measure_params *mp;
+  uint8_t *out_status;
+  sdvl_stereo::StereoRule rule;
+  size_t lds_bytes;
+  double noise_quad;
+  sdvl_part<double> d_z;
+  sdvl_part<uint8_t> d_status, h_status;
+  sdvl_part<sdvl_stereo::StereoJobDev> st_jobs;
+  sdvl_part<int32_t> st_req_job;
+  int check(sdvl_ctx *ctx, int n, const sdvl_camera *cam) { return stereo_measure_check(ctx, who, n, n_jobs, jobs, cam, mp, &rule, &lds_bytes, &noise_quad); }
+  // the matcher reads the left frame's pyramid on a hit's level (a miss's level is not looked at)
+  int levels_check(sdvl_ctx *ctx, int n, const int32_t *found, const int32_t *level) const {
+    const int rc = found_levels_check(ctx, who, n, level);
+    if (rc) return rc;
+    for (int j = 0; j < n_jobs; j++)
+      for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++)
+        SDVL_REQUIRE(ctx, !found[i] || level[i] < jobs[j].left->v.levels, std::string(who) + ": a hit's level lies outside the left frame's pyramid");
+    return SDVL_OK;
+  }
+  void take_out(sdvl_layout &d, sdvl_layout &h, int n) { d_z = d.take<double>(n), d_status = d.take<uint8_t>(n), h_status = h.take<uint8_t>(n); }
+  void take_stage(sdvl_layout &st, int n) { st_jobs = st.take<sdvl_stereo::StereoJobDev>(n_jobs > 0 ? n_jobs : 1), st_req_job = st.take<int32_t>(n); }
+  int fill(sdvl_ctx *ctx, void *hs, int n) const {
+    SDVL_REQUIRE(ctx, !sdvl_item_jobs_fill(n, n_jobs, jobs, st_req_job.in(hs)), std::string(who) + ": request ranges overlap");
+    return n_jobs > 0 ? sdvl_stereo_jobs_resolve(ctx, n_jobs, jobs, st_jobs.in(hs)) : sdvl_depth_pool_scope(ctx);
+  }
+  int enqueue(sdvl_ctx *ctx, int n, const void *ds, const sdvl_search_res *d_res) const {
+    return sdvl_stereo_lookup_enqueue(ctx, n, st_jobs.cin(ds), d_res, st_req_job.cin(ds), rule, lds_bytes, d_z.in(ctx->d_out), d_status.in(ctx->d_out));
+  }
+  template <typename... Head>
+  void launch(sdvl_ctx *ctx, int n, const void *, Head... head) const {
+    const StereoMeasureArgs m = {d_z.cin(ctx->d_out), d_status.cin(ctx->d_out), noise_quad, h_status.in(ctx->h_out)};
+    SDVL_LAUNCH(ctx, "depth_filter_stereo", depth_filter_stereo_kernel, dim3((n + 127) / 128), dim3(128), head..., m);
+  }
+  void collect(const sdvl_ctx *ctx, int n) const { memcpy(out_status, h_status.in(ctx->h_out), static_cast<size_t>(n)); }
 };
 
 // Search results the caller states, as the records a search leaves: requests | frame table (entry 2i: item i's current pose, 2i + 1:
@@ -234,59 +310,101 @@ struct StatedStage {
   }
 };
 
-// One launch over records that lie in HBM, the wait, and the outcomes (with a measured part m: and the status bytes) into the caller's
-// arrays.  d_fout / h_fout, m->status / m->status_host: their places in d_out and in the pinned h_out, which the kernel writes itself
-int filter_launch_collect(sdvl_ctx *ctx, int n, const SearchReqDev *d_reqs, const SearchFramePose *d_table, const sdvl_search_res *d_res,
-                          const sdvl_depth_state *d_state, const sdvl_camera *cam, const sdvl_depth_params *fp, TrackPoint *rows, int n_rows,
-                          sdvl_depth_out *d_fout, sdvl_depth_out *h_fout, sdvl_depth_out *fout, const DepthMeasureArgs *m = nullptr,
-                          uint8_t *out_status = nullptr, const StereoMeasureArgs *sm = nullptr) {
-  if (sm)
-    SDVL_LAUNCH(ctx, "depth_filter_stereo", depth_filter_stereo_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table, d_res, d_state, n, cam_of(*cam),
-                *fp, rows, n_rows, d_fout, h_fout, *sm);
-  else if (m)
-    SDVL_LAUNCH(ctx, "depth_filter_measured", depth_filter_measured_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table, d_res, d_state, n, cam_of(*cam),
-                *fp, rows, n_rows, d_fout, h_fout, *m);
-  else
-    SDVL_LAUNCH(ctx, "depth_filter", depth_filter_kernel, dim3((n + 127) / 128), dim3(128), d_reqs, d_table, d_res, d_state, n, cam_of(*cam), *fp, rows, n_rows,
-                d_fout, h_fout);
+// Behind the one push of a body's staging block ds: what the source queues first, its launch over records that lie in HBM, the wait, and
+// the outcomes with what the source adds into the caller's arrays.  out / out_host: the outcomes' places in d_out and in the pinned
+// h_out, which the kernel writes itself
+struct FilterRecords {
+  const SearchReqDev *reqs;
+  const SearchFramePose *table;
+  const sdvl_search_res *res;
+  const sdvl_depth_state *state;
+  sdvl_depth_out *out, *out_host;
+};
+template <typename Source>
+int filter_launch_collect(sdvl_ctx *ctx, const Source &src, int n, const void *ds, const FilterRecords &r, const sdvl_camera *cam,
+                          const sdvl_depth_params *fp, TrackPoint *rows, int n_rows, sdvl_depth_out *fout) {
+  const int rc = src.enqueue(ctx, n, ds, r.res);
+  if (rc) return rc;
+  src.launch(ctx, n, ds, r.reqs, r.table, r.res, r.state, n, cam_of(*cam), *fp, rows, n_rows, r.out, r.out_host);
   SDVL_HIP_CHECK(ctx, hipGetLastError());
   SDVL_HIP_CHECK(ctx, sdvl_stream_wait(ctx));
-  memcpy(fout, h_fout, sizeof(sdvl_depth_out) * static_cast<size_t>(n));
-  if (m) memcpy(out_status, m->status_host, static_cast<size_t>(n));
-  if (sm) memcpy(out_status, sm->status_host, static_cast<size_t>(n));
+  memcpy(fout, r.out_host, sizeof(sdvl_depth_out) * static_cast<size_t>(n));
+  src.collect(ctx, n);
   return SDVL_OK;
+}
+
+// search + depth filter (Map::UpdateCandidates, map.cc:402-498) over the batch the context holds: one submission, one wait.  d_out:
+// the search's | the outcomes | the source's; h_out: the search results | the outcomes | the source's; staged: the states | the source's
+template <typename Source>
+int filter_searched(sdvl_ctx *ctx, Source &src, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
+                    const sdvl_depth_params *fp, sdvl_track_set *set, sdvl_search_res *out, sdvl_depth_out *fout) {
+  TrackPoint *rows = nullptr;
+  int n_rows = 0;
+  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
+  if (!rc) rc = src.check(ctx, n, cam);
+  if (rc) return rc;
+  SearchOut so(n);
+  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
+  src.take_out(so.d, so.h, n);
+  FilterRecords r = {};
+  rc = sdvl_search_enqueue(ctx, n, cam, p, so, &r.reqs, &r.table);
+  if (rc) return rc;
+  sdvl_layout st;
+  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
+  src.take_stage(st, n);
+  void *hs = nullptr, *ds = nullptr;
+  rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &ds);
+  if (!rc) rc = src.fill(ctx, hs, n);
+  if (rc) return rc;
+  memcpy(st_state.in(hs), state, st_state.bytes());
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  r.res = so.res.cin(ctx->d_out), r.state = st_state.cin(ds), r.out = d_fout.in(ctx->d_out), r.out_host = h_fout.in(ctx->h_out);
+  rc = filter_launch_collect(ctx, src, n, ds, r, cam, fp, rows, n_rows, fout);
+  if (rc) return rc;
+  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
+  return SDVL_OK;
+}
+
+// the depth filter alone, on search results the caller states (level: null where the source reads none).  d_out and h_out: the outcomes |
+// the source's; staged: StatedStage | the source's, zeroed
+template <typename Source>
+int filter_stated(sdvl_ctx *ctx, Source &src, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
+                  const double *px, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state, const sdvl_depth_params *fp,
+                  sdvl_track_set *set, sdvl_depth_out *fout) {
+  TrackPoint *rows = nullptr;
+  int n_rows = 0;
+  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
+  if (!rc) rc = src.check(ctx, n, cam);
+  if (!rc) rc = src.levels_check(ctx, n, found, level);
+  if (rc) return rc;
+  sdvl_layout st, d, h;
+  const StatedStage stated(st, n);
+  src.take_stage(st, n);
+  const sdvl_part<sdvl_depth_out> d_fout = d.take<sdvl_depth_out>(n), h_fout = h.take<sdvl_depth_out>(n);
+  src.take_out(d, h, n);
+  void *hs = nullptr, *ds = nullptr;
+  rc = sdvl_reserve_out_stage(ctx, d.bytes() > h.bytes() ? d.bytes() : h.bytes(), st.bytes(), &hs, &ds);
+  if (rc) return rc;
+  memset(hs, 0, st.bytes());
+  rc = src.fill(ctx, hs, n);
+  if (rc) return rc;
+  stated.fill(hs, n, cur_pose, ref_pose, bearing, found, px, level, state);
+  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
+  const FilterRecords r = {stated.reqs.cin(ds), stated.tab.cin(ds), stated.res.cin(ds), stated.state.cin(ds), d_fout.in(ctx->d_out), h_fout.in(ctx->h_out)};
+  return filter_launch_collect(ctx, src, n, ds, r, cam, fp, rows, n_rows, fout);
 }
 
 }  // namespace
 
 extern "C" {
 
-// ---- search + depth filter (Map::UpdateCandidates, map.cc:402-498): one submission, one wait
+// ---- each entry: its null arguments, the empty call, its source, one of the two bodies
 int sdvl_search_run_filter(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
                            const sdvl_depth_params *fp, sdvl_track_set *set, sdvl_search_res *out, sdvl_depth_out *fout) {
   if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (rc) return rc;
-  SearchOut so(n);
-  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
-  const SearchReqDev *d_reqs = nullptr;
-  const SearchFramePose *d_table = nullptr;
-  rc = sdvl_search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
-  if (rc) return rc;
-  const size_t state_bytes = sizeof(sdvl_depth_state) * static_cast<size_t>(n);  // staged: the states alone
-  void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, state_bytes, &hs, &dsx);
-  if (rc) return rc;
-  memcpy(hs, state, state_bytes);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, state_bytes));
-  rc = filter_launch_collect(ctx, n, d_reqs, d_table, so.res.cin(ctx->d_out), static_cast<const sdvl_depth_state *>(dsx), cam, fp, rows, n_rows,
-                             d_fout.in(ctx->d_out), h_fout.in(ctx->h_out), fout);
-  if (rc) return rc;
-  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
-  return SDVL_OK;
+  Triangulated src;
+  return filter_searched(ctx, src, n, cam, p, state, fp, set, out, fout);
 }
 
 int sdvl_search_points_filter(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs, const sdvl_camera *cam, const sdvl_search_params *p,
@@ -299,27 +417,13 @@ int sdvl_search_points_filter(sdvl_ctx *ctx, int n, const sdvl_search_req *reqs,
   return sdvl_search_run_filter(ctx, n, cam, p, state, fp, set, out, fout);
 }
 
-// ---- the depth filter alone: on search results the caller states.  d_out and h_out: the outcomes
 int sdvl_depth_filter(sdvl_ctx *ctx, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
                       const double *px, const sdvl_camera *cam, const sdvl_depth_state *state, const sdvl_depth_params *fp,
                       sdvl_track_set *set, sdvl_depth_out *fout) {
   if (!ctx || !cam || !fp || n < 0 || (n > 0 && (!cur_pose || !ref_pose || !bearing || !found || !px || !state || !fout))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (rc) return rc;
-  sdvl_layout st, o;
-  const StatedStage stated(st, n);
-  const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
-  if (rc) return rc;
-  memset(hs, 0, st.bytes());
-  stated.fill(hs, n, cur_pose, ref_pose, bearing, found, px, nullptr, state);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  return filter_launch_collect(ctx, n, stated.reqs.cin(ds), stated.tab.cin(ds), stated.res.cin(ds), stated.state.cin(ds), cam, fp, rows, n_rows,
-                               o_fout.in(ctx->d_out), o_fout.in(ctx->h_out), fout);
+  Triangulated src;
+  return filter_stated(ctx, src, n, cur_pose, ref_pose, bearing, found, px, nullptr, cam, state, fp, set, fout);
 }
 
 // ---- the same two entries for a depth camera
@@ -329,37 +433,10 @@ int sdvl_search_run_filter_measured(sdvl_ctx *ctx, int n, const sdvl_camera *cam
                                     uint8_t *out_status) {
   if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout || !out_status))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  DepthMeasure dm;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (!rc) rc = depth_measure_check(ctx, "sdvl_search_run_filter_measured", n, n_jobs, jobs, width, height, cam, dist, mp, &dm);
-  if (rc) return rc;
-  SearchOut so(n);
-  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
-  const sdvl_part<uint8_t> d_status = so.d.take<uint8_t>(n), h_status = so.h.take<uint8_t>(n);
-  const SearchReqDev *d_reqs = nullptr;
-  const SearchFramePose *d_table = nullptr;
-  rc = sdvl_search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
-  if (rc) return rc;
-  sdvl_layout st;  // staged: states | jobs | the job of every request
-  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
-  const DepthMeasureStage st_depth(st, n, n_jobs);
-  void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
-  if (!rc) rc = st_depth.fill(ctx, hs, n, n_jobs, jobs, width, height);
-  if (rc) return rc;
-  memcpy(st_state.in(hs), state, st_state.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
-  const DepthMeasureArgs m = {st_depth.jobs.cin(dsx), st_depth.req_job.cin(dsx), dm, d_status.in(ctx->d_out), h_status.in(ctx->h_out)};
-  rc = filter_launch_collect(ctx, n, d_reqs, d_table, so.res.cin(ctx->d_out), st_state.cin(dsx), cam, fp, rows, n_rows, d_fout.in(ctx->d_out),
-                             h_fout.in(ctx->h_out), fout, &m, out_status);
-  if (rc) return rc;
-  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
-  return SDVL_OK;
+  FromDepthImage src = {"sdvl_search_run_filter_measured", n_jobs, jobs, width, height, dist, mp, out_status};
+  return filter_searched(ctx, src, n, cam, p, state, fp, set, out, fout);
 }
 
-// staging as sdvl_depth_filter's, then jobs | the job of every request; d_out and h_out: the outcomes | the status bytes
 int sdvl_depth_filter_measured(sdvl_ctx *ctx, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
                                const double *px, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state,
                                const sdvl_depth_params *fp, sdvl_track_set *set, int n_jobs, const sdvl_depth_job *jobs, int width, int height,
@@ -367,77 +444,20 @@ int sdvl_depth_filter_measured(sdvl_ctx *ctx, int n, const double *cur_pose, con
   if (!ctx || !cam || !fp || n < 0 || (n > 0 && (!cur_pose || !ref_pose || !bearing || !found || !px || !level || !state || !fout || !out_status)))
     return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  DepthMeasure dm;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (!rc) rc = depth_measure_check(ctx, "sdvl_depth_filter_measured", n, n_jobs, jobs, width, height, cam, dist, mp, &dm);
-  if (rc) return rc;
-  for (int i = 0; i < n; i++)
-    SDVL_REQUIRE(ctx, level[i] >= 0 && level[i] < SDVL_MAX_LEVELS, "sdvl_depth_filter_measured: found level outside 0 .. SDVL_MAX_LEVELS - 1");
-  sdvl_layout st, o;
-  const StatedStage stated(st, n);
-  const DepthMeasureStage st_depth(st, n, n_jobs);
-  const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
-  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
-  if (rc) return rc;
-  memset(hs, 0, st.bytes());
-  rc = st_depth.fill(ctx, hs, n, n_jobs, jobs, width, height);
-  if (rc) return rc;
-  stated.fill(hs, n, cur_pose, ref_pose, bearing, found, px, level, state);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  const DepthMeasureArgs m = {st_depth.jobs.cin(ds), st_depth.req_job.cin(ds), dm, o_status.in(ctx->d_out), o_status.in(ctx->h_out)};
-  return filter_launch_collect(ctx, n, stated.reqs.cin(ds), stated.tab.cin(ds), stated.res.cin(ds), stated.state.cin(ds), cam, fp, rows, n_rows,
-                               o_fout.in(ctx->d_out), o_fout.in(ctx->h_out), fout, &m, out_status);
+  FromDepthImage src = {"sdvl_depth_filter_measured", n_jobs, jobs, width, height, dist, mp, out_status};
+  return filter_stated(ctx, src, n, cur_pose, ref_pose, bearing, found, px, level, cam, state, fp, set, fout);
 }
 
-// ---- the same two entries for a stereo rig: the search, stereo_lookup over its results where they lie, the filter's third form — one
-// submission, one wait
+// ---- and for a stereo rig
 int sdvl_search_run_filter_stereo(sdvl_ctx *ctx, int n, const sdvl_camera *cam, const sdvl_search_params *p, const sdvl_depth_state *state,
                                   const sdvl_depth_params *fp, sdvl_track_set *set, int n_jobs, const sdvl_stereo_job *jobs,
                                   const sdvl_stereo_measure_params *mp, sdvl_search_res *out, sdvl_depth_out *fout, uint8_t *out_status) {
   if (!ctx || !cam || !p || !fp || n < 0 || (n > 0 && (!state || !out || !fout || !out_status))) return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  sdvl_stereo::StereoRule rule;
-  size_t lds_bytes = 0;
-  double noise_quad = 0.0;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (!rc) rc = stereo_measure_check(ctx, "sdvl_search_run_filter_stereo", n, n_jobs, jobs, cam, mp, &rule, &lds_bytes, &noise_quad);
-  if (rc) return rc;
-  SearchOut so(n);
-  const sdvl_part<sdvl_depth_out> d_fout = so.d.take<sdvl_depth_out>(n), h_fout = so.h.take<sdvl_depth_out>(n);
-  const sdvl_part<double> d_z = so.d.take<double>(n);
-  const sdvl_part<uint8_t> d_status = so.d.take<uint8_t>(n), h_status = so.h.take<uint8_t>(n);
-  const SearchReqDev *d_reqs = nullptr;
-  const SearchFramePose *d_table = nullptr;
-  rc = sdvl_search_enqueue(ctx, n, cam, p, so, &d_reqs, &d_table);
-  if (rc) return rc;
-  sdvl_layout st;  // staged: states | jobs | the job of every request
-  const sdvl_part<sdvl_depth_state> st_state = st.take<sdvl_depth_state>(n);
-  const StereoMeasureStage st_stereo(st, n, n_jobs);
-  void *hs = nullptr, *dsx = nullptr;
-  rc = sdvl_stage_alloc(ctx, st.bytes(), &hs, &dsx);
-  if (!rc) rc = st_stereo.fill(ctx, "sdvl_search_run_filter_stereo", hs, n, n_jobs, jobs);
-  if (rc) return rc;
-  memcpy(st_state.in(hs), state, st_state.bytes());
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, dsx, hs, st.bytes()));
-  rc = sdvl_stereo_lookup_enqueue(ctx, n, st_stereo.jobs.cin(dsx), so.res.cin(ctx->d_out), st_stereo.req_job.cin(dsx), rule, lds_bytes, d_z.in(ctx->d_out),
-                                  d_status.in(ctx->d_out));
-  if (rc) return rc;
-  const StereoMeasureArgs sm = {d_z.cin(ctx->d_out), d_status.cin(ctx->d_out), noise_quad, h_status.in(ctx->h_out)};
-  rc = filter_launch_collect(ctx, n, d_reqs, d_table, so.res.cin(ctx->d_out), st_state.cin(dsx), cam, fp, rows, n_rows, d_fout.in(ctx->d_out),
-                             h_fout.in(ctx->h_out), fout, nullptr, out_status, &sm);
-  if (rc) return rc;
-  memcpy(out, so.h_res.in(ctx->h_out), so.h_res.bytes());
-  return SDVL_OK;
+  FromStereoPair src = {"sdvl_search_run_filter_stereo", n_jobs, jobs, mp, out_status};
+  return filter_searched(ctx, src, n, cam, p, state, fp, set, out, fout);
 }
 
-// staging as sdvl_depth_filter's, then jobs | the job of every request; d_out: the outcomes | z | the status bytes, h_out: the outcomes |
-// the status bytes
 int sdvl_depth_filter_stereo(sdvl_ctx *ctx, int n, const double *cur_pose, const double *ref_pose, const double *bearing, const int32_t *found,
                              const double *px, const int32_t *level, const sdvl_camera *cam, const sdvl_depth_state *state,
                              const sdvl_depth_params *fp, sdvl_track_set *set, int n_jobs, const sdvl_stereo_job *jobs,
@@ -445,39 +465,8 @@ int sdvl_depth_filter_stereo(sdvl_ctx *ctx, int n, const double *cur_pose, const
   if (!ctx || !cam || !fp || n < 0 || (n > 0 && (!cur_pose || !ref_pose || !bearing || !found || !px || !level || !state || !fout || !out_status)))
     return SDVL_ERR_INVALID;
   if (n == 0) return SDVL_OK;
-  TrackPoint *rows = nullptr;
-  int n_rows = 0;
-  sdvl_stereo::StereoRule rule;
-  size_t lds_bytes = 0;
-  double noise_quad = 0.0;
-  int rc = depth_filter_check(ctx, n, state, set, &rows, &n_rows);
-  if (!rc) rc = stereo_measure_check(ctx, "sdvl_depth_filter_stereo", n, n_jobs, jobs, cam, mp, &rule, &lds_bytes, &noise_quad);
-  if (rc) return rc;
-  for (int i = 0; i < n; i++)
-    SDVL_REQUIRE(ctx, level[i] >= 0 && level[i] < SDVL_MAX_LEVELS, "sdvl_depth_filter_stereo: found level outside 0 .. SDVL_MAX_LEVELS - 1");
-  for (int j = 0; j < n_jobs; j++)
-    for (int i = jobs[j].c_begin; i < jobs[j].c_end; i++)
-      SDVL_REQUIRE(ctx, !found[i] || level[i] < jobs[j].left->v.levels, "sdvl_depth_filter_stereo: a hit's level lies outside the left frame's pyramid");
-  sdvl_layout st, o;
-  const StatedStage stated(st, n);
-  const StereoMeasureStage st_stereo(st, n, n_jobs);
-  const sdvl_part<sdvl_depth_out> o_fout = o.take<sdvl_depth_out>(n);
-  const sdvl_part<uint8_t> o_status = o.take<uint8_t>(n);
-  const sdvl_part<double> o_z = o.take<double>(n);
-  void *hs = nullptr, *ds = nullptr;
-  rc = sdvl_reserve_out_stage(ctx, o.bytes(), st.bytes(), &hs, &ds);
-  if (rc) return rc;
-  memset(hs, 0, st.bytes());
-  rc = st_stereo.fill(ctx, "sdvl_depth_filter_stereo", hs, n, n_jobs, jobs);
-  if (rc) return rc;
-  stated.fill(hs, n, cur_pose, ref_pose, bearing, found, px, level, state);
-  SDVL_HIP_CHECK(ctx, sdvl_push(ctx, ds, hs, st.bytes()));
-  rc = sdvl_stereo_lookup_enqueue(ctx, n, st_stereo.jobs.cin(ds), stated.res.cin(ds), st_stereo.req_job.cin(ds), rule, lds_bytes, o_z.in(ctx->d_out),
-                                  o_status.in(ctx->d_out));
-  if (rc) return rc;
-  const StereoMeasureArgs sm = {o_z.cin(ctx->d_out), o_status.cin(ctx->d_out), noise_quad, o_status.in(ctx->h_out)};
-  return filter_launch_collect(ctx, n, stated.reqs.cin(ds), stated.tab.cin(ds), stated.res.cin(ds), stated.state.cin(ds), cam, fp, rows, n_rows,
-                               o_fout.in(ctx->d_out), o_fout.in(ctx->h_out), fout, nullptr, out_status, &sm);
+  FromStereoPair src = {"sdvl_depth_filter_stereo", n_jobs, jobs, mp, out_status};
+  return filter_stated(ctx, src, n, cur_pose, ref_pose, bearing, found, px, level, cam, state, fp, set, fout);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@
 
 namespace sdvl {
 
+class DepthJobs;  // depth_jobs.h
+
 // B independent trackers stepping together, one launch per kernel per stage (MI355X-first driver)
 class SDVLBatch {
  public:
@@ -70,6 +72,7 @@ class SDVLBatch {
   void MeasureKeyframeCorners(MapStep &m, const std::vector<char> &need);
   void LookupKeyframeFeatures(MapStep &m);
   void SearchFilterMeasured(MapStep &m, int total, const sdvl_camera &cam, const sdvl_search_params &sp);
+  std::vector<int32_t> MeasureCorners(const DepthJobs &jobs, const std::vector<int32_t> &xyl);  // sdvl_stereo_depth or sdvl_depth_seed over filled jobs
   const std::vector<DepthImage> *step_depths_ = nullptr;  // the depth images of the step in flight (HandleFrames, batch.cc)
   const DepthImage *DepthOf(int i);                        // tracker i's, null: none; of a tracker fed raw pairs, the rectified right image
   // SDVL::SetStereoRectification: the raw right images of the step, rectified into HBM by ONE sdvl_rectify call the first time a consumer

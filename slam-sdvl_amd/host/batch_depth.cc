@@ -88,6 +88,29 @@ void SDVLBatch::SizeDepthResults(int n) {
   depth_status_.assign(std::max(n, 1), 0);
 }
 
+// The corners xyl (x, y, level each) that `jobs` lists, through the jobs' producer — sdvl_stereo_depth for pairs, sdvl_depth_seed for depth
+// images, ONE call — into depth_z_ / depth_status_; -> the corners with a depth per job.  No job: no call
+vector<int32_t> SDVLBatch::MeasureCorners(const DepthJobs &jobs, const vector<int32_t> &xyl) {
+  const int n_corners = jobs.items();
+  SizeDepthResults(n_corners);
+  vector<int32_t> ok(std::max(jobs.size(), 1), 0);
+  if (jobs.empty()) return ok;
+  const CameraAndLens c = BatchCamera();
+  if (jobs.stereo()) {
+    sdvl_stereo_params sp = *jobs.stereo_rule();
+    sp.dist = c.lens();  // (refused: rectified pairs only)
+    vector<double> disparity(n_corners, 0.0);
+    dev_->Check(sdvl_stereo_depth(dev_->ctx(), jobs.size(), jobs.stereo_jobs(), n_corners, xyl.data(), &c.cam, &sp, depth_z_.data(), disparity.data(),
+                                  depth_status_.data(), ok.data()),
+                "sdvl_stereo_depth");
+  } else {
+    dev_->Check(sdvl_depth_seed(dev_->ctx(), jobs.size(), jobs.depth_jobs(), jobs.width(), jobs.height(), n_corners, xyl.data(), &c.cam, c.lens(),
+                                jobs.rule(), depth_z_.data(), depth_status_.data(), ok.data()),
+                "sdvl_depth_seed");
+  }
+  return ok;
+}
+
 // Depth cameras: the filtered corners of the step's keyframes whose tracker seeds from depth (SDVL::SetDepthSeeding) are looked up in
 // their frames' depth images by ONE sdvl_depth_seed call.  (*z)[k] / (*status)[k]: keyframe k's results, null for a keyframe that is not
 // seeded from depth.  A keyframe that came without a depth image seeds nothing and is counted.  A first frame becomes the first keyframe
@@ -112,24 +135,7 @@ void SDVLBatch::SeedKeyframesFromDepth(Step &s, vector<const double *> *z, vecto
                           : jobs.AddDepth(owner, d, t.depth_rule_, n, kf.GetWidth(), kf.GetHeight()))
       AppendFilteredCorners(kf, &xyl);
   }
-  const int n_corners = jobs.items();
-  SizeDepthResults(n_corners);
-  vector<int32_t> ok(std::max(jobs.size(), 1), 0);
-  if (!jobs.empty()) {
-    const CameraAndLens c = BatchCamera();
-    if (jobs.stereo()) {
-      sdvl_stereo_params sp = *jobs.stereo_rule();
-      sp.dist = c.lens();  // (refused: rectified pairs only)
-      vector<double> disparity(n_corners, 0.0);
-      dev_->Check(sdvl_stereo_depth(dev_->ctx(), jobs.size(), jobs.stereo_jobs(), n_corners, xyl.data(), &c.cam, &sp, depth_z_.data(), disparity.data(),
-                                    depth_status_.data(), ok.data()),
-                  "sdvl_stereo_depth");
-    } else {
-      dev_->Check(sdvl_depth_seed(dev_->ctx(), jobs.size(), jobs.depth_jobs(), jobs.width(), jobs.height(), n_corners, xyl.data(), &c.cam, c.lens(),
-                                  jobs.rule(), depth_z_.data(), depth_status_.data(), ok.data()),
-                  "sdvl_depth_seed");
-    }
-  }
+  const vector<int32_t> ok = MeasureCorners(jobs, xyl);
   for (const DepthJobs::Range &r : jobs.ranges()) {
     (*z)[r.owner] = depth_z_.data() + r.begin;
     (*status)[r.owner] = depth_status_.data() + r.begin;
@@ -169,21 +175,7 @@ void SDVLBatch::MeasureKeyframeCorners(MapStep &m, const vector<char> &need) {
       m.mm[k]->SetCornerDepths(nullptr, nullptr);
   }
   if (jobs.empty()) return;
-  SizeDepthResults(jobs.items());
-  vector<int32_t> ok(jobs.size(), 0);
-  const CameraAndLens c = BatchCamera();
-  if (jobs.stereo()) {
-    sdvl_stereo_params sp = *jobs.stereo_rule();
-    sp.dist = c.lens();  // (refused: rectified pairs only)
-    vector<double> disparity(jobs.items(), 0.0);
-    dev_->Check(sdvl_stereo_depth(dev_->ctx(), jobs.size(), jobs.stereo_jobs(), jobs.items(), xyl.data(), &c.cam, &sp, depth_z_.data(), disparity.data(),
-                                  depth_status_.data(), ok.data()),
-                "sdvl_stereo_depth");
-  } else {
-    dev_->Check(sdvl_depth_seed(dev_->ctx(), jobs.size(), jobs.depth_jobs(), jobs.width(), jobs.height(), jobs.items(), xyl.data(), &c.cam, c.lens(),
-                                jobs.rule(), depth_z_.data(), depth_status_.data(), ok.data()),
-                "sdvl_depth_seed");
-  }
+  MeasureCorners(jobs, xyl);
   for (const DepthJobs::Range &r : jobs.ranges()) m.mm[r.owner]->SetCornerDepths(depth_z_.data() + r.begin, depth_status_.data() + r.begin);
 }
 

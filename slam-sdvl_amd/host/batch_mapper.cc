@@ -62,13 +62,8 @@ void SDVLBatch::SetUpMeasuring(MapStep &m) {
     if (m.mm[k]->StereoMapping()) {
       if (m.measuring && m.measuring->DisparitySigma() != m.mm[k]->DisparitySigma())
         throw std::runtime_error("SDVLBatch: the trackers of a batch share the disparity noise");
-      m.measuring = m.mm[k];
-      m.measuring_trk = m.trk[k];
-      if (m.mm[k]->CurrentFrame().get() == trk_[m.trk[k]]->step_frame_) m.depth_of[k] = DepthOf(m.trk[k]);
-      continue;
-    }
-    const sdvl_depth_measure_params a = m.mm[k]->DepthMeasureParams(trk_[m.trk[k]]->depth_rule_);
-    if (m.measuring) {
+    } else if (m.measuring) {
+      const sdvl_depth_measure_params a = m.mm[k]->DepthMeasureParams(trk_[m.trk[k]]->depth_rule_);
       const sdvl_depth_measure_params b = m.measuring->DepthMeasureParams(trk_[m.trk[k]]->depth_rule_);
       if (a.noise_abs != b.noise_abs || a.noise_quad != b.noise_quad) throw std::runtime_error("SDVLBatch: the trackers of a batch share the depth noise parameters");
     }

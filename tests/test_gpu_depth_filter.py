@@ -318,6 +318,63 @@ def test_search_plus_filter_alone_equals_search_points_filter(ctx, sdvl, orc, sy
     f_ref.close(); f_cur.close()
 
 
+@pytest.mark.parametrize("n", [1, 129])
+def test_entries_launch_what_they_did_before(ctx, sdvl, orc, synth, n):
+    """the kernels each of the six entries launches, by the context's own launch counts: the stated entries one filter kernel (the stereo
+    one behind one stereo_lookup), the searched entries what sdvl_search_points launches for the same requests and then the same.
+    n = 129: the first size with a second 128-lane workgroup, one request repeated; only launches are counted here, the values are
+    the business of the tests above and of test_gpu_depth_measure.py / test_gpu_stereo_lookup.py"""
+    from oraclelib import TUM_CAM, fill_search_reqs, search_request_meta, trajectory_pose
+    if "launch_pair" not in _w:
+        T_ref, T_cur = trajectory_pose(orc, 0), trajectory_pose(orc, 30)
+        img_ref, img_cur = (synth.render(T, TUM_CAM, 640, 480, frame_id=k) for T, k in ((T_ref, 0), (T_cur, 30)))
+        meta, ccur = search_request_meta(orc, img_ref, img_cur, T_ref, T_cur, TUM_CAM, 1, 47, False, 0.05)
+        _w["launch_pair"] = (T_ref, T_cur, img_ref, np.array(img_cur), ccur, meta[0])
+    T_ref, T_cur, img_ref, img_cur, ccur, m = _w["launch_pair"]
+    f_ref, f_cur = ctx.frame(img_ref), ctx.frame(img_cur)
+    f_cur.set_corners(ccur)
+    reqs = fill_search_reqs(sdvl, [m] * n, f_ref, f_cur, T_ref, T_cur, False)
+    states = (sdvl.DepthState * n)()
+    for st in states:
+        st.rho, st.sigma2, st.a, st.b, st.z_range = m["idepth"], m["istd"] ** 2, 10.0, 10.0, 6.0
+        st.cos_alpha, st.last_distance, st.depth_mean = 1.0, 1.0 / m["idepth"], 2.0
+        st.position[:] = (0.1, 0.2, 2.0)
+        st.fixed, st.n_failed, st.track_row = 0, 0, -1
+    cam, fp, sp = camera(sdvl), filter_params(sdvl), sdvl.default_search_params()
+    depth_jobs = [(np.full((480, 640), 2.0, np.float32), 0, n)]
+    stereo_jobs = [(f_cur, img_cur, 0, n)]                                 # (the left image as its own right one: a pair all the same)
+
+    def counted(call):
+        ctx.timing_reset()
+        out = call()
+        return out, {k: launches for k, (_, launches) in ctx.timing_get().items() if launches > 0}
+
+    ctx.timing_enable(True)
+    try:
+        plain, search = counted(lambda: ctx.search_points(reqs, cam, sp))
+        assert search and not {"depth_filter", "depth_filter_measured", "depth_filter_stereo", "stereo_lookup"} & set(search), search
+        stated = ([T_cur] * n, [T_ref] * n, [m["bearing"]] * n, [r.found for r in plain], [tuple(r.px) for r in plain])
+        levels = [r.level if r.found else 0 for r in plain]
+        got = {
+            "stated, triangulated": counted(lambda: ctx.depth_filter(*stated, cam, states, fp))[1],
+            "stated, measured": counted(lambda: ctx.depth_filter_measured(*stated, levels, cam, states, fp, depth_jobs, 640, 480))[1],
+            "stated, stereo": counted(lambda: ctx.depth_filter_stereo(*stated, levels, cam, states, fp, stereo_jobs, 0.11))[1],
+            "searched, triangulated": counted(lambda: ctx.search_points_filter(reqs, cam, sp, states, fp))[1],
+            "searched, measured": counted(lambda: ctx.search_points_filter_measured(reqs, cam, sp, states, fp, depth_jobs, 640, 480))[1],
+            "searched, stereo": counted(lambda: ctx.search_points_filter_stereo(reqs, cam, sp, states, fp, stereo_jobs, 0.11))[1],
+        }
+    finally:
+        ctx.timing_enable(False)
+        f_ref.close(); f_cur.close()
+    own = {"triangulated": {"depth_filter": 1}, "measured": {"depth_filter_measured": 1}, "stereo": {"stereo_lookup": 1, "depth_filter_stereo": 1}}
+    print("n = %d, sdvl_search_points: %s" % (n, search))
+    for entry, launches in got.items():
+        print("n = %d, %s: %s" % (n, entry, launches))
+    for entry, launches in got.items():
+        form, source = entry.split(", ")
+        assert launches == dict(search if form == "searched" else {}, **own[source]), (n, entry, launches)
+
+
 def test_largest_ratios():
     """not a check of its own: prints, per output, the largest |device - restatement| / bound the tests above met (all are <= 1, or a
     test above has failed)"""
